@@ -129,6 +129,37 @@ def log(msg):
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
 
+# ---------------------------------------------------------------------------------------------- --dump-outputs
+DUMP_MAX_PARAMS = 12 * 2 ** 20      # float32 elements (48 MiB): the flagship model's 11.2 M parameters fit whole
+DUMP_MAX_GRADS = 2 ** 20            # float32 elements (4 MiB); together with the losses well under 64 MB
+
+
+def seeded_sample(flat, limit, seed):
+    """`flat` itself if it has at most `limit` elements, else the same `limit` of them (sorted indices from `seed`) on
+    every run, so that two builds are compared element for element."""
+    if flat.size <= limit:
+        return flat
+    return flat[np.sort(np.random.default_rng(seed).choice(flat.size, limit, replace=False))]
+
+
+def dump_outputs(out_dir, model, loss, full):
+    """What the last timed step handed its caller, as float32 .npy files: loss.npy and full_loss.npy
+    (harness.train_step's return values), params.npy (every parameter after the optimizer step, flattened and
+    concatenated in named_parameters() order) and grads.npy (the gradients that step applied, same order, zeros for
+    a parameter that has none; a fixed seeded sample of DUMP_MAX_GRADS elements)."""
+    os.makedirs(out_dir, exist_ok=True)
+    ps = [p for _, p in model.named_parameters()]
+    with torch.no_grad():
+        flat_p = torch.cat([p.detach().reshape(-1).float() for p in ps]).cpu().numpy()
+        flat_g = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float()
+                            for p in ps]).cpu().numpy()
+    arrays = {"loss": loss.detach().float().cpu().numpy(), "full_loss": full.detach().float().cpu().numpy(),
+              "params": seeded_sample(flat_p, DUMP_MAX_PARAMS, seed=1), "grads": seeded_sample(flat_g, DUMP_MAX_GRADS, seed=2)}
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(arr, dtype=np.float32))
+    return {name: list(arr.shape) for name, arr in arrays.items()}
+
+
 # ---------------------------------------------------------------------------------------------- CPU baseline
 def cpu_info():
     model = "unknown"
@@ -388,7 +419,7 @@ def darcy_leg(rk, pool, engine, batch, steps):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=3, help="timed steps of the flagship workload (ms_per_step is their mean)")
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--batch-per-gpu", type=int, default=32)
     ap.add_argument("--engine", default=None, choices=[None, "f32", "split", "bf16", "bf16s"],
@@ -415,7 +446,12 @@ def main():
     ap.add_argument("--torch-optim", action="store_true", help="torch.optim.AdamW + torch rel-L2 instead of the fused kernels")
     ap.add_argument("--bf16-grad-wire", action="store_true",
                     help="all-reduce a bf16 copy of the gradient bucket (22.5 MB instead of 45 MB; accumulation stays fp32)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (losses, parameters, gradients) as "
+                         "DIR/<name>.npy (rank 0; seeded inputs, so runs with the same arguments compare output for output)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: this process has not touched the GPU (no torch.cuda call,
         # libpa2d not loaded) and never will — it starts N fresh ranks and relays their output.
@@ -479,6 +515,10 @@ def main():
     ar_ms = sync.drain_allreduce_ms() if world > 1 else []
     sync.timing = False
     log(f"{args.steps} timed steps in {dt:.2f} s")
+    if args.dump_outputs and rank == 0:
+        # before any secondary leg: the folded leg below keeps training this model
+        shapes = dump_outputs(args.dump_outputs, model, loss, full)
+        log(f"outputs of the last timed step written to {args.dump_outputs}: {shapes}")
 
     traffic = None
     pmc = os.path.join(ROOT, "profiles", "conv_pmc_traffic.json")

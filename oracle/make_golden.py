@@ -79,6 +79,21 @@ def check(name, got, want, tol):
     assert e <= tol, name
 
 
+def g0_unified_grids(Model):
+    """The reference's own float32 unified-position grids (Model.pos from get_grid) for the geometries of the fp64
+    fixtures (TINY 6x5 ref 3; NS 64x64 ref 8).  torch's float32 sqrt on the CPU is not correctly rounded and its last
+    bit depends on the host CPU; one ulp in the grid moves the fp64 outputs by ~1e-8, so the fp64 golden tests feed the
+    oracle these bits instead of recomputing them."""
+    out = {}
+    for cfg in (synth.TINY_CONFIG, synth.NS_CONFIG):
+        H, W, ref = cfg["H"], cfg["W"], cfg["ref"]
+        m = ref_model(Model, cfg, synth.synth_state_dict(cfg, seed=0), torch.float32)
+        pos = m.pos.detach().reshape(1, H * W, ref * ref).numpy()
+        assert pos.dtype == np.float32 and np.array_equal(pos, orc.unified_pos(H, W, ref).numpy())
+        out[f"pos_{H}x{W}_ref{ref}"] = pos
+    np.savez_compressed(os.path.join(GOLD, "G0_unified_pos.npz"), **out)
+
+
 def g1_tiny(Model, TestLoss):
     """Tiny full-model case: fp64 + fp32 reference outputs, loss and all gradients.  Includes
     temperatures outside [0.1, 5] so the clamp mask is pinned."""
@@ -359,7 +374,8 @@ def main():
     os.makedirs(GOLD, exist_ok=True)
     torch.manual_seed(0)
     Model, Attn, SOL, TestLoss = import_reference()
-    for name, fn in (("G1", lambda: g1_tiny(Model, TestLoss)), ("G1b", lambda: g1b_tiny_branches(Model)),
+    for name, fn in (("G0", lambda: g0_unified_grids(Model)), ("G1", lambda: g1_tiny(Model, TestLoss)),
+                     ("G1b", lambda: g1b_tiny_branches(Model)),
                      ("G2", lambda: g2_attn(Attn)), ("G3", lambda: g3_shipped_rollout(Model)),
                      ("G4", lambda: g4_train_iteration(Model, TestLoss)),
                      ("G5", lambda: g5_full_ns(Model, TestLoss)), ("G6", g6_irregular),
