@@ -132,6 +132,26 @@ int pa2d_conv3x3x2_bwd(const float* dout, const float* xn, const float* wx, cons
                        void* ws, size_t ws_bytes, int B, int H, int W, int C, int accumulate, int engine,
                        pa2d_stream_t stream, void* ev_start, void* ev_stop);
 
+/* ---- in_project_x / in_project_fx of the structured 3-D mesh: two Conv3d(C, C, 3, 1, 1) on the same input,
+ * reference model/Physics_Attention.py (Physics_Attention_Structured_Mesh_3D.forward), as ONE implicit GEMM
+ * [B*H*W*D, 27C] x [27C, 2C] on the [B,N,C] tensor with N = H*W*D and point n = (h*W + w)*D + d (D fastest, the
+ * reference's reshape to [B,H,W,D,C]).  Weights [C_out, C_in, 3, 3, 3] (kernel axes on H, W, D), zero padding on all
+ * six faces.  Same contract as the 3x3 pair above (engines, C % 16 == 0, accumulate, B <= 0, prepacked packs:
+ * direction 1 mirrors the taps 26 - t), with the depth D after W; B*H*W*D must fit an int. */
+size_t pa2d_conv3x3x3x2_workspace(int B, int H, int W, int D, int C, int engine);      /* backward */
+size_t pa2d_conv3x3x3x2_fwd_workspace(int B, int H, int W, int D, int C, int engine);  /* forward  */
+size_t pa2d_conv3x3x3x2_pack_bytes(int C);
+int pa2d_conv3x3x3x2_pack(const float* wx, const float* wf, void* pack, size_t pack_bytes, int B, int H, int W, int D,
+                          int C, int direction, int engine, pa2d_stream_t stream);
+int pa2d_conv3x3x3x2_fwd(const float* xn, const float* wx, const float* bx, const float* wf, const float* bf,
+                         float* out, const void* prepacked /* NULL = pack here */, void* ws, size_t ws_bytes, int B,
+                         int H, int W, int D, int C, int engine, pa2d_stream_t stream, void* ev_start, void* ev_stop);
+/* dxn may be NULL (input needs no gradient); dwx/dbx/dwf/dbf (+)= per `accumulate` */
+int pa2d_conv3x3x3x2_bwd(const float* dout, const float* xn, const float* wx, const float* wf, float* dxn,
+                         float* dwx, float* dbx, float* dwf, float* dbf, const void* prepacked /* NULL = pack here */,
+                         void* ws, size_t ws_bytes, int B, int H, int W, int D, int C, int accumulate, int engine,
+                         pa2d_stream_t stream, void* ev_start, void* ev_stop);
+
 /* ---- slice: softmax((x_mid . Ws^T + bs) / clamp(temperature, .1, 5)) and the weighted scatter of
  * N points into M tokens, Physics_Attention.py:98-101.  Emits per-chunk partial sums
  * spart [B,heads,nchunk,M,D] and npart [B,heads,nchunk,M] (npart NULL = skip), nchunk =

@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """Per-stage micro-benchmark at the bench shapes (B=32, N=4096, C=256, 8 heads, M=64): times each
 libpa2d stage alone with events on the launch stream and prints achieved TFLOP/s or GB/s.
+The conv3d_* stages time the 3x3x3 conv of the structured 3-D mesh on a --B3 x --S3^3 mesh (default 1 x 32^3).
 Usage: python tools/kbench.py [--only conv_fwd,linear_fwd,...] [--iters 10] [--B 32]"""
 import argparse
 import os
@@ -35,6 +36,8 @@ def main():
     ap.add_argument("--H", type=int, default=64)
     ap.add_argument("--W", type=int, default=64)
     ap.add_argument("--heads", type=int, default=8)
+    ap.add_argument("--B3", type=int, default=1, help="batch of the conv3d_* stages (3x3x3 conv, S3^3 mesh, C channels)")
+    ap.add_argument("--S3", type=int, default=32, help="edge of the cubic mesh of the conv3d_* stages")
     args = ap.parse_args()
     E = ops.resolve_engine(args.engine)
     print(f"engine {E}  B={args.B} H={args.H} W={args.W} C={args.C} M={args.M}", flush=True)
@@ -64,6 +67,15 @@ def main():
     tests["conv_fwd"] = (lambda: ops.conv3x3x2_fwd(xn, wx, bx, wf, bf, H, W, engine=E), conv_flops, "TF")
     tests["conv_bwd"] = (lambda: ops.conv3x3x2_bwd(dout2, xn, wx, wf, H, W, engine=E), 2 * conv_flops, "TF")
     tests["conv_bwd_wonly"] = (lambda: ops.conv3x3x2_bwd(dout2, xn, wx, wf, H, W, need_dx=False, engine=E), conv_flops, "TF")
+    # 3x3x3 conv of the structured 3-D mesh (pa2d_conv3x3x3x2_*): [B3*S3^3, 27C] x [27C, 2C]
+    S3 = args.S3
+    xn3, dout3 = rn(args.B3, S3 ** 3, C), rn(args.B3, S3 ** 3, 2 * C)
+    wx3, wf3 = rn(C, C, 3, 3, 3) * 0.02, rn(C, C, 3, 3, 3) * 0.02
+    conv3_flops = 2.0 * args.B3 * S3 ** 3 * 27 * C * 2 * C
+    tests["conv3d_fwd"] = (lambda: ops.conv3x3x3x2_fwd(xn3, wx3, bx, wf3, bf, S3, S3, S3, engine=E), conv3_flops, "TF")
+    tests["conv3d_bwd"] = (lambda: ops.conv3x3x3x2_bwd(dout3, xn3, wx3, wf3, S3, S3, S3, engine=E), 2 * conv3_flops, "TF")
+    tests["conv3d_bwd_wonly"] = (lambda: ops.conv3x3x3x2_bwd(dout3, xn3, wx3, wf3, S3, S3, S3, need_dx=False, engine=E),
+                                 conv3_flops, "TF")
     tests["linear_fwd"] = (lambda: ops.linear_fwd(x2d, w, bias, act="gelu", want_pre=True, engine=E), lin_flops, "TF")   # MLP1
     tests["linear_plain"] = (lambda: ops.linear_fwd(x2d, w, engine=E), lin_flops, "TF")
     tests["linear_bias_res"] = (lambda: ops.linear_fwd(x2d, w, bias, res=res, engine=E), lin_flops, "TF")

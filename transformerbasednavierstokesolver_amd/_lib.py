@@ -40,6 +40,13 @@ SIGNATURES = {
     "pa2d_conv3x3x2_fwd": (_i, [_f, _f, _f, _f, _f, _f, _f, _f, _sz, _i, _i, _i, _i, _i, _st, _st, _st]),
     "pa2d_conv3x3x2_bwd": (_i, [_f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _sz, _i, _i, _i, _i, _i, _i, _st, _st,
                                 _st]),
+    "pa2d_conv3x3x3x2_workspace": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "pa2d_conv3x3x3x2_fwd_workspace": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "pa2d_conv3x3x3x2_pack_bytes": (_sz, [_i]),
+    "pa2d_conv3x3x3x2_pack": (_i, [_f, _f, _f, _sz, _i, _i, _i, _i, _i, _i, _i, _st]),
+    "pa2d_conv3x3x3x2_fwd": (_i, [_f, _f, _f, _f, _f, _f, _f, _f, _sz, _i, _i, _i, _i, _i, _i, _st, _st, _st]),
+    "pa2d_conv3x3x3x2_bwd": (_i, [_f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _sz, _i, _i, _i, _i, _i, _i, _i, _st,
+                                  _st, _st]),
     "pa2d_slice_nchunk": (_i, [_i, _i, _i]),
     "pa2d_slice_scatter": (_i, [_f, _ll, _f, _ll, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _st, _st, _st]),
     "pa2d_token_attn_lds_bytes": (_sz, [_i, _i, _i]),

@@ -348,6 +348,7 @@ static int halo_policy() { return pa2d_env().conv_halo; }
 
 bool conv_halo_applies(const KCParams& p) {
     const int pol = halo_policy();
+    if (p.taps == 27) return false;      // 3x3 halo only: the 3x3x3 conv never comes here
     if (pol == 0 || !p.apre || (p.Cin % 32) != 0 || p.H <= 0 || p.W <= 0 || (p.M % (p.H * p.W)) != 0) return false;
     const long long tiles = (long long)(p.M / (p.H * p.W)) * ceil_div(p.H, TH) * ceil_div(p.W, TW) * ceil_div(p.N, BN);
     return pol == 2 || tiles >= 512;

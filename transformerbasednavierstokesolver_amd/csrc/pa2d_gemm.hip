@@ -82,7 +82,7 @@ static int launch_kc(const KCParams& p_in, bool im2col, hipStream_t st, hipEvent
         p.c_bytes = (unsigned)cb; p.res_bytes = (unsigned)rb; p.aux_bytes = (unsigned)xb;
     }
     if ((p.K & 3) || (p.lda & 3) || (p.ldb & 3)) return PA2D_ERR_ARG;
-    if (im2col && ((p.Cin & 15) || p.K != 9 * p.Cin)) return PA2D_ERR_UNSUPPORTED;
+    if (im2col && ((p.Cin & 15) || p.K != (p.taps == 27 ? 27 : 9) * p.Cin)) return PA2D_ERR_UNSUPPORTED;
     if (im2col && (p.epi != 0 || p.res)) return PA2D_ERR_ARG;      // conv kernels carry the bias-only epilogue
     if (ev0 && hipEventRecord(ev0, st) != hipSuccess) return PA2D_ERR_ARG;
     int rc;
@@ -134,6 +134,8 @@ static int launch_kc(const KCParams& p_in, bool im2col, hipStream_t st, hipEvent
 // mode 1: conv fwd pack    dst[co'][cic][tap][c16] = W_{co'<C ? x : f}[co][cic*16+c16][tap]       ([2C][9*Cin])
 // mode 2: conv bwd pack    dst[ci][cic'][tap'][c16] = W_{..}[co = cic'*16+c16][ci][8 - tap']        ([Cin][9*2C])
 //         (K order of gemm_kc's implicit GEMM: 16-channel chunk outer, tap inner)
+// TAPS = 27: modes 1 / 2 for the [C,C,3,3,3] kernels of the 3x3x3 conv (taps flipped as 26 - tap)
+template <int TAPS>
 __global__ void repack_kernel(const float* __restrict__ w0, const float* __restrict__ w1, float* __restrict__ dst,
                               int mode, int N, int K, int C, int Cin) {
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -142,33 +144,36 @@ __global__ void repack_kernel(const float* __restrict__ w0, const float* __restr
         const int n = (int)(idx % N), k = (int)(idx / N);
         dst[idx] = w0[(size_t)n * K + k];
     } else if (mode == 1) {
-        if (idx >= (long long)2 * C * 9 * Cin) return;
+        if (idx >= (long long)2 * C * TAPS * Cin) return;
         const int CH = K;      // channels per K-step (16 for the f32 engine, 32 for the split engine)
         const int c16 = (int)(idx % CH);
-        const int tap = (int)((idx / CH) % 9);
-        const int cic = (int)((idx / (9 * CH)) % (Cin / CH));
-        const int co = (int)(idx / ((long long)Cin * 9));
+        const int tap = (int)((idx / CH) % TAPS);
+        const int cic = (int)((idx / (TAPS * CH)) % (Cin / CH));
+        const int co = (int)(idx / ((long long)Cin * TAPS));
         const int ci = cic * CH + c16;
         const float* src = co < C ? w0 : w1;
-        dst[idx] = src[((size_t)(co % C) * Cin + ci) * 9 + tap];
+        dst[idx] = src[((size_t)(co % C) * Cin + ci) * TAPS + tap];
     } else {
-        if (idx >= (long long)2 * C * 9 * Cin) return;
+        if (idx >= (long long)2 * C * TAPS * Cin) return;
         const int CH = K;
         const int c16 = (int)(idx % CH);
-        const int tap = (int)((idx / CH) % 9);
-        const int cic = (int)((idx / (9 * CH)) % (2 * C / CH));
-        const int ci = (int)(idx / ((long long)2 * C * 9));
+        const int tap = (int)((idx / CH) % TAPS);
+        const int cic = (int)((idx / (TAPS * CH)) % (2 * C / CH));
+        const int ci = (int)(idx / ((long long)2 * C * TAPS));
         const int co = cic * CH + c16;
         const float* src = co < C ? w0 : w1;
-        dst[idx] = src[((size_t)(co % C) * Cin + ci) * 9 + (8 - tap)];
+        dst[idx] = src[((size_t)(co % C) * Cin + ci) * TAPS + (TAPS - 1 - tap)];
     }
 }
 
 static int launch_repack(const float* w0, const float* w1, float* dst, int mode, int N, int K, int C, int Cin,
-                         hipStream_t st) {
-    const long long count = mode == 0 ? (long long)N * K : (long long)2 * C * 9 * Cin;
-    hipLaunchKernelGGL(repack_kernel, dim3((unsigned)ceil_div_ll(count, 256)), dim3(256), 0, st, w0, w1, dst, mode,
-                       N, K, C, Cin);
+                         hipStream_t st, int taps = 9) {
+    const long long count = mode == 0 ? (long long)N * K : (long long)2 * C * taps * Cin;
+    const dim3 grid((unsigned)ceil_div_ll(count, 256));
+    if (taps == 27)
+        hipLaunchKernelGGL(repack_kernel<27>, grid, dim3(256), 0, st, w0, w1, dst, mode, N, K, C, Cin);
+    else
+        hipLaunchKernelGGL(repack_kernel<9>, grid, dim3(256), 0, st, w0, w1, dst, mode, N, K, C, Cin);
     PA2D_CHECK_LAUNCH();
     return PA2D_OK;
 }
@@ -289,53 +294,148 @@ static size_t conv_planes_bytes(int engine, int M, int N, int Cin) {
 }
 
 // bf16 engines: the weight gradient also runs from pre-split planes (of dOut and of X) when the tile shapes allow
-// 0 = fp32 operands (gather kernel), 1 = planes, 128 x 128 tiles, 2 = planes, 256 x 256 tiles (one round of workgroups)
-static int conv_dw_kind(int engine, int M, int C) {
-    if (conv_planes_bytes(engine, M, C, 2 * C) == 0) return 0;
+// 0 = fp32 operands (gather kernel), 1 = planes, 128 x 128 tiles, 2 = planes, 256 x 256 tiles (one round of workgroups).
+// The planes kernels are 3x3 only: the 3x3x3 conv (taps = 27) always takes the gather kernel.
+static int conv_dw_kind(int engine, int M, int C, int taps = 9) {
+    if (taps != 9 || conv_planes_bytes(engine, M, C, 2 * C) == 0) return 0;
     if (mc_planes_big_applies(C, C, M)) return 2;
     return (mc_planes_supported(C, C) && plan_mc(2 * C, 9 * C, M).big) ? 1 : 0;
 }
-static MCPlan conv_dw_plan(int engine, int M, int C) {
-    return conv_dw_kind(engine, M, C) == 2 ? plan_mc_planes_big(2 * C, 9 * C, M) : plan_mc(2 * C, 9 * C, M);
+static MCPlan conv_dw_plan(int engine, int M, int C, int taps = 9) {
+    return conv_dw_kind(engine, M, C, taps) == 2 ? plan_mc_planes_big(2 * C, 9 * C, M) : plan_mc(2 * C, taps * C, M);
 }
-static size_t conv_xplanes_bytes(int engine, int M, int C) {
-    return conv_dw_kind(engine, M, C) ? ((planes_bytes(M, C, engine == 2 ? 1 : 3) + 255) & ~(size_t)255) : 0;
+static size_t conv_xplanes_bytes(int engine, int M, int C, int taps = 9) {
+    return conv_dw_kind(engine, M, C, taps) ? ((planes_bytes(M, C, engine == 2 ? 1 : 3) + 255) & ~(size_t)255) : 0;
 }
+// weight pack: fp32 pack (2C * taps*C floats) or 3 bf16 planes (1.5x)
+static size_t conv_pack_floats(int C, int taps) { return (size_t)3 * C * taps * C; }
 
 // backward workspace: [weight pack | slabs or column-sum partials | dOut planes | X planes]  (planes: bf16 engines)
-size_t pa2d_conv3x3x2_workspace(int B, int H, int W, int C, int engine) {
-    const size_t pack = (size_t)3 * C * 9 * C;      // fp32 pack (2C*9C floats) or 3 bf16 planes (1.5x)
-    const MCPlan pl = conv_dw_plan(engine, B * H * W, C);
-    size_t sl = pl.slab_floats, cs = (size_t)colsum_blocks(B * H * W) * 2 * C;
-    return (pack + (sl > cs ? sl : cs)) * sizeof(float) + conv_planes_bytes(engine, B * H * W, C, 2 * C) +
-           conv_xplanes_bytes(engine, B * H * W, C);
+static size_t conv_bwd_workspace(int M, int C, int engine, int taps) {
+    const MCPlan pl = conv_dw_plan(engine, M, C, taps);
+    size_t sl = pl.slab_floats, cs = (size_t)colsum_blocks(M) * 2 * C;
+    return (conv_pack_floats(C, taps) + (sl > cs ? sl : cs)) * sizeof(float) + conv_planes_bytes(engine, M, C, 2 * C) +
+           conv_xplanes_bytes(engine, M, C, taps);
+}
+// forward workspace: [weight pack (unused if prepacked) | activation planes (bf16 engines)]
+static size_t conv_fwd_workspace(int M, int C, int engine, int taps) {
+    return conv_pack_floats(C, taps) * sizeof(float) + conv_planes_bytes(engine, M, 2 * C, C);
 }
 
-// forward workspace: [weight pack (unused if prepacked) | activation planes (bf16 engines)]
+size_t pa2d_conv3x3x2_workspace(int B, int H, int W, int C, int engine) { return conv_bwd_workspace(B * H * W, C, engine, 9); }
 size_t pa2d_conv3x3x2_fwd_workspace(int B, int H, int W, int C, int engine) {
-    return (size_t)3 * C * 9 * C * sizeof(float) + conv_planes_bytes(engine, B * H * W, 2 * C, C);
+    return conv_fwd_workspace(B * H * W, C, engine, 9);
 }
 
 // Packed conv weights in the layout the engine selected for these dims wants (channel chunk = K-step of the
-// tile, fp32 or bf16 planes by GEMM mode).  direction 0: forward pack ([2C][9C]); 1: data-gradient pack
-// ([C][9*2C], taps flipped).  pack: pa2d_conv3x3x2_pack_bytes(C) bytes.  A pack stays valid while the weights,
+// tile, fp32 or bf16 planes by GEMM mode).  direction 0: forward pack ([2C][taps*C]); 1: data-gradient pack
+// ([C][taps*2C], taps flipped).  pack: conv_pack_floats(C, taps) floats.  A pack stays valid while the weights,
 // the dims and the GEMM mode do not change.
 static int conv_pack(const float* wx, const float* wf, float* pack, int M, int C, int direction, int engine,
-                     hipStream_t st) {
+                     hipStream_t st, int taps = 9) {
     const int N = direction ? C : 2 * C, Cin = direction ? 2 * C : C;
     if (use_split(engine, N, true, Cin)) {
-        return launch_repack_split(wx, wf, pack, direction, engine == 2 ? 1 : 3, C, C, st);
+        return launch_repack_split(wx, wf, pack, direction, engine == 2 ? 1 : 3, C, C, st, taps);
     }
-    return launch_repack(wx, wf, pack, direction ? 2 : 1, 0, kc_tile(M, N, true, Cin).bk, C, C, st);
+    return launch_repack(wx, wf, pack, direction ? 2 : 1, 0, kc_tile(M, N, true, Cin).bk, C, C, st, taps);
 }
 
-size_t pa2d_conv3x3x2_pack_bytes(int C) { return (size_t)3 * C * 9 * C * sizeof(float); }
+size_t pa2d_conv3x3x2_pack_bytes(int C) { return conv_pack_floats(C, 9) * sizeof(float); }
 
 int pa2d_conv3x3x2_pack(const float* wx, const float* wf, void* pack, size_t pack_bytes, int B, int H, int W, int C,
                         int direction, int engine, hipStream_t st) {
     if (!engine_ok(engine)) return PA2D_ERR_ARG;
     if (pack_bytes < pa2d_conv3x3x2_pack_bytes(C)) return PA2D_ERR_WORKSPACE;
     return conv_pack(wx, wf, (float*)pack, B * H * W, C, direction ? 1 : 0, engine, st);
+}
+
+// Forward of the fused pair on M = B*H*W*depth rows: taps = 9 (depth 1) is the 3x3 conv of pa2d_conv3x3x2_fwd, taps = 27
+// the 3x3x3 conv of pa2d_conv3x3x3x2_fwd.  One implicit GEMM [M, taps*C] x [taps*C, 2C].
+static int conv_fwd(const float* xn, const float* wx, const float* bx, const float* wf, const float* bf, float* out,
+                    const void* prepacked, void* ws, size_t ws_bytes, int B, int H, int W, int depth, int taps, int C,
+                    int engine, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop) {
+    if (!engine_ok(engine)) return PA2D_ERR_ARG;
+    if (B <= 0) return PA2D_OK;
+    const int M = B * H * W * depth;
+    if (ws_bytes < conv_fwd_workspace(M, C, engine, taps)) return PA2D_ERR_WORKSPACE;
+    const float* pack = (const float*)prepacked;
+    if (!pack) {
+        const int rc = conv_pack(wx, wf, (float*)ws, M, C, 0, engine, st, taps);
+        if (rc) return rc;
+        pack = (const float*)ws;
+    }
+    const size_t apl = conv_planes_bytes(engine, M, 2 * C, C);
+    void* const planes = (char*)ws + conv_pack_floats(C, taps) * sizeof(float);
+    if (apl) {
+        const int rc = launch_split_planes(xn, C, planes, (long long)M, C, engine == 2 ? 1 : 3, st);
+        if (rc) return rc;
+    }
+    KCParams p = {};
+    p.engine = engine;
+    p.A = apl ? (const float*)planes : xn; p.apre = apl ? 1 : 0;
+    p.lda = C; p.B = pack; p.ldb = taps * C; p.C = out; p.ldc = 2 * C;
+    p.bias = bx; p.bias2 = bf; p.bias_split = C;
+    p.M = M; p.N = 2 * C; p.K = taps * C; p.H = H; p.W = W; p.Cin = C;
+    p.taps = taps; p.depth = depth;
+    return launch_kc(p, true, st, ev_start, ev_stop);
+}
+
+// Backward of the fused pair (taps / depth as in conv_fwd): dxn (plain store, may be NULL), dwx / dwf, dbx / dbf
+static int conv_bwd(const float* dout, const float* xn, const float* wx, const float* wf, float* dxn, float* dwx,
+                    float* dbx, float* dwf, float* dbf, const void* prepacked, void* ws, size_t ws_bytes, int B, int H,
+                    int W, int depth, int taps, int C, int accumulate, int engine, hipStream_t st, hipEvent_t ev_start,
+                    hipEvent_t ev_stop) {
+    if (!engine_ok(engine)) return PA2D_ERR_ARG;
+    if (B <= 0) {
+        if (accumulate) return PA2D_OK;
+        const size_t wb = sizeof(float) * (size_t)C * C * taps, bb = sizeof(float) * C;
+        int rz = pa2d_zero(dwx, wb, st);
+        if (!rz) rz = pa2d_zero(dwf, wb, st);
+        if (!rz) rz = pa2d_zero(dbx, bb, st);
+        return rz ? rz : pa2d_zero(dbf, bb, st);
+    }
+    const int M = B * H * W * depth;
+    const size_t need = conv_bwd_workspace(M, C, engine, taps);
+    if (ws_bytes < need) return PA2D_ERR_WORKSPACE;
+    float* scratch = (float*)ws + conv_pack_floats(C, taps);
+    int rc;
+    const int NT = engine == 2 ? 1 : 3;
+    const size_t apl = conv_planes_bytes(engine, M, C, 2 * C), xpl = conv_xplanes_bytes(engine, M, C, taps);
+    void* const planes = (char*)ws + need - apl - xpl;                                       // dOut planes
+    void* const xplanes = (char*)planes + apl;                                               // X planes
+    if (apl && (dxn || xpl)) {
+        rc = launch_split_planes(dout, 2 * C, planes, M, 2 * C, NT, st);
+        if (rc) return rc;
+    }
+    if (dxn) {
+        const float* pack = (const float*)prepacked;
+        if (!pack) {
+            rc = conv_pack(wx, wf, (float*)ws, M, C, 1, engine, st, taps);
+            if (rc) return rc;
+            pack = (const float*)ws;
+        }
+        KCParams p = {};
+        p.engine = engine;
+        p.A = apl ? (const float*)planes : dout; p.apre = apl ? 1 : 0;
+        p.lda = 2 * C; p.B = pack; p.ldb = taps * 2 * C; p.C = dxn; p.ldc = C;
+        p.M = M; p.N = C; p.K = taps * 2 * C; p.H = H; p.W = W; p.Cin = 2 * C;
+        p.taps = taps; p.depth = depth;
+        rc = launch_kc(p, true, st, ev_start, ev_stop);
+        if (rc) return rc;
+    }
+    const MCPlan pl = conv_dw_plan(engine, M, C, taps);
+    if (xpl) {      // bf16 engines: both operands as pre-split planes, transposed LDS reads, no conversion in the GEMM
+        rc = launch_split_planes(xn, C, xplanes, M, C, NT, st);
+        if (rc) return rc;
+        rc = pl.big == 2 ? launch_mc_planes_big(planes, xplanes, C, C, M, H, W, scratch, pl, NT, st)
+                         : launch_mc_planes(planes, xplanes, C, C, M, H, W, scratch, pl, NT, st);
+    } else {
+        rc = launch_mc(dout, 2 * C, 2 * C, xn, C, taps * C, M, true, H, W, C, scratch, pl, engine, st, nullptr, taps, depth);
+    }
+    if (rc) return rc;
+    rc = launch_reduce(scratch, pl.splits, (long long)2 * C * taps * C, dwx, dwf, 1, C, C, st, accumulate, taps);
+    if (rc) return rc;
+    return launch_colsum(dout, 2 * C, M, 2 * C, dbx, scratch, st, dbf, C, accumulate);
 }
 
 // out[B*H*W, 2C] = [conv3x3(xn, wx) + bx | conv3x3(xn, wf) + bf]   (zero padding 1, NHWC)
@@ -345,28 +445,7 @@ int pa2d_conv3x3x2_pack(const float* wx, const float* wf, void* pack, size_t pac
 int pa2d_conv3x3x2_fwd(const float* xn, const float* wx, const float* bx, const float* wf, const float* bf,
                        float* out, const void* prepacked, void* ws, size_t ws_bytes, int B, int H, int W, int C,
                        int engine, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop) {
-    if (!engine_ok(engine)) return PA2D_ERR_ARG;
-    if (B <= 0) return PA2D_OK;
-    if (ws_bytes < pa2d_conv3x3x2_fwd_workspace(B, H, W, C, engine)) return PA2D_ERR_WORKSPACE;
-    const float* pack = (const float*)prepacked;
-    if (!pack) {
-        const int rc = conv_pack(wx, wf, (float*)ws, B * H * W, C, 0, engine, st);
-        if (rc) return rc;
-        pack = (const float*)ws;
-    }
-    const size_t apl = conv_planes_bytes(engine, B * H * W, 2 * C, C);
-    void* const planes = (char*)ws + pa2d_conv3x3x2_pack_bytes(C);
-    if (apl) {
-        const int rc = launch_split_planes(xn, C, planes, (long long)B * H * W, C, engine == 2 ? 1 : 3, st);
-        if (rc) return rc;
-    }
-    KCParams p = {};
-    p.engine = engine;
-    p.A = apl ? (const float*)planes : xn; p.apre = apl ? 1 : 0;
-    p.lda = C; p.B = pack; p.ldb = 9 * C; p.C = out; p.ldc = 2 * C;
-    p.bias = bx; p.bias2 = bf; p.bias_split = C;
-    p.M = B * H * W; p.N = 2 * C; p.K = 9 * C; p.H = H; p.W = W; p.Cin = C;
-    return launch_kc(p, true, st, ev_start, ev_stop);
+    return conv_fwd(xn, wx, bx, wf, bf, out, prepacked, ws, ws_bytes, B, H, W, 1, 9, C, engine, st, ev_start, ev_stop);
 }
 
 // dxn[B*N, C] (plain store), dwx/dwf [C,C,3,3], dbx/dbf [C] (accumulate != 0: added to) from dout[B*N, 2C]
@@ -374,57 +453,65 @@ int pa2d_conv3x3x2_bwd(const float* dout, const float* xn, const float* wx, cons
                        float* dbx, float* dwf, float* dbf, const void* prepacked, void* ws, size_t ws_bytes, int B,
                        int H, int W, int C, int accumulate, int engine, hipStream_t st, hipEvent_t ev_start,
                        hipEvent_t ev_stop) {
-    if (!engine_ok(engine)) return PA2D_ERR_ARG;
-    if (B <= 0) {
-        if (accumulate) return PA2D_OK;
-        const size_t wb = sizeof(float) * (size_t)C * C * 9, bb = sizeof(float) * C;
-        int rz = pa2d_zero(dwx, wb, st);
-        if (!rz) rz = pa2d_zero(dwf, wb, st);
-        if (!rz) rz = pa2d_zero(dbx, bb, st);
-        return rz ? rz : pa2d_zero(dbf, bb, st);
-    }
-    if (ws_bytes < pa2d_conv3x3x2_workspace(B, H, W, C, engine)) return PA2D_ERR_WORKSPACE;
-    float* scratch = (float*)ws + (size_t)3 * C * 9 * C;
-    const int M = B * H * W;
-    int rc;
-    const int NT = engine == 2 ? 1 : 3;
-    const size_t apl = conv_planes_bytes(engine, M, C, 2 * C), xpl = conv_xplanes_bytes(engine, M, C);
-    void* const planes = (char*)ws + pa2d_conv3x3x2_workspace(B, H, W, C, engine) - apl - xpl;     // dOut planes
-    void* const xplanes = (char*)planes + apl;                                               // X planes
-    if (apl && (dxn || xpl)) {
-        rc = launch_split_planes(dout, 2 * C, planes, M, 2 * C, NT, st);
-        if (rc) return rc;
-    }
-    if (dxn) {
-        const float* pack = (const float*)prepacked;
-        if (!pack) {
-            rc = conv_pack(wx, wf, (float*)ws, M, C, 1, engine, st);
-            if (rc) return rc;
-            pack = (const float*)ws;
-        }
-        KCParams p = {};
-        p.engine = engine;
-        p.A = apl ? (const float*)planes : dout; p.apre = apl ? 1 : 0;
-        p.lda = 2 * C; p.B = pack; p.ldb = 9 * 2 * C; p.C = dxn; p.ldc = C;
-        p.M = M; p.N = C; p.K = 9 * 2 * C; p.H = H; p.W = W; p.Cin = 2 * C;
-        rc = launch_kc(p, true, st, ev_start, ev_stop);
-        if (rc) return rc;
-    }
-    const MCPlan pl = conv_dw_plan(engine, M, C);
-    if (xpl) {      // bf16 engines: both operands as pre-split planes, transposed LDS reads, no conversion in the GEMM
-        rc = launch_split_planes(xn, C, xplanes, M, C, NT, st);
-        if (rc) return rc;
-        rc = pl.big == 2 ? launch_mc_planes_big(planes, xplanes, C, C, M, H, W, scratch, pl, NT, st)
-                         : launch_mc_planes(planes, xplanes, C, C, M, H, W, scratch, pl, NT, st);
-    } else {
-        rc = launch_mc(dout, 2 * C, 2 * C, xn, C, 9 * C, M, true, H, W, C, scratch, pl, engine, st);
-    }
-    if (rc) return rc;
-    rc = launch_reduce(scratch, pl.splits, (long long)2 * C * 9 * C, dwx, dwf, 1, C, C, st, accumulate);
-    if (rc) return rc;
-    return launch_colsum(dout, 2 * C, M, 2 * C, dbx, scratch, st, dbf, C, accumulate);
+    return conv_bwd(dout, xn, wx, wf, dxn, dwx, dbx, dwf, dbf, prepacked, ws, ws_bytes, B, H, W, 1, 9, C, accumulate, engine,
+                    st, ev_start, ev_stop);
 }
 
+// ---- 3x3x3 conv (Physics_Attention_Structured_Mesh_3D: two Conv3d(C, C, 3, 1, 1) on [B, H, W, D, C]).
+// Point n = (h*W + w)*D + d; weights [C_out, C_in, 3, 3, 3], tap t = kh*9 + kw*3 + kd.  The same kernels as the 3x3
+// conv with 27 taps selected explicitly (KCParams::taps); never the halo-in-LDS conv or the planes weight gradient.
+// Rows of the GEMMs (B*H*W*D) must fit an int: larger problems return PA2D_ERR_UNSUPPORTED.
+static long long conv3d_rows(int B, int H, int W, int D) {
+    if (B <= 0 || H <= 0 || W <= 0 || D <= 0) return 0;
+    return (long long)B * H * W * D;
+}
+static int conv3d_check(int B, int H, int W, int D, int C) {
+    if (C <= 0 || (C & 15)) return PA2D_ERR_UNSUPPORTED;
+    if (B <= 0) return PA2D_OK;
+    if (H <= 0 || W <= 0 || D <= 0) return PA2D_ERR_ARG;
+    return conv3d_rows(B, H, W, D) > 0x7fffffffLL ? PA2D_ERR_UNSUPPORTED : PA2D_OK;
+}
+static int conv3d_ws_rows(int B, int H, int W, int D) {
+    const long long r = conv3d_rows(B, H, W, D);
+    return r > 0x7fffffffLL ? 0 : (int)r;      // oversized: the call itself refuses
+}
+
+size_t pa2d_conv3x3x3x2_workspace(int B, int H, int W, int D, int C, int engine) {
+    return conv_bwd_workspace(conv3d_ws_rows(B, H, W, D), C, engine, 27);
+}
+size_t pa2d_conv3x3x3x2_fwd_workspace(int B, int H, int W, int D, int C, int engine) {
+    return conv_fwd_workspace(conv3d_ws_rows(B, H, W, D), C, engine, 27);
+}
+size_t pa2d_conv3x3x3x2_pack_bytes(int C) { return conv_pack_floats(C, 27) * sizeof(float); }
+
+int pa2d_conv3x3x3x2_pack(const float* wx, const float* wf, void* pack, size_t pack_bytes, int B, int H, int W, int D,
+                          int C, int direction, int engine, hipStream_t st) {
+    if (!engine_ok(engine)) return PA2D_ERR_ARG;
+    const int rc = conv3d_check(B, H, W, D, C);
+    if (rc) return rc;
+    if (pack_bytes < pa2d_conv3x3x3x2_pack_bytes(C)) return PA2D_ERR_WORKSPACE;
+    return conv_pack(wx, wf, (float*)pack, conv3d_ws_rows(B, H, W, D), C, direction ? 1 : 0, engine, st, 27);
+}
+
+int pa2d_conv3x3x3x2_fwd(const float* xn, const float* wx, const float* bx, const float* wf, const float* bf, float* out,
+                         const void* prepacked, void* ws, size_t ws_bytes, int B, int H, int W, int D, int C, int engine,
+                         hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop) {
+    if (!engine_ok(engine)) return PA2D_ERR_ARG;
+    const int rc = conv3d_check(B, H, W, D, C);
+    if (rc) return rc;
+    return conv_fwd(xn, wx, bx, wf, bf, out, prepacked, ws, ws_bytes, B, H, W, D, 27, C, engine, st, ev_start, ev_stop);
+}
+
+int pa2d_conv3x3x3x2_bwd(const float* dout, const float* xn, const float* wx, const float* wf, float* dxn, float* dwx,
+                         float* dbx, float* dwf, float* dbf, const void* prepacked, void* ws, size_t ws_bytes, int B, int H,
+                         int W, int D, int C, int accumulate, int engine, hipStream_t st, hipEvent_t ev_start,
+                         hipEvent_t ev_stop) {
+    if (!engine_ok(engine)) return PA2D_ERR_ARG;
+    const int rc = conv3d_check(B, H, W, D, C);
+    if (rc) return rc;
+    return conv_bwd(dout, xn, wx, wf, dxn, dwx, dbx, dwf, dbf, prepacked, ws, ws_bytes, B, H, W, D, 27, C, accumulate, engine,
+                    st, ev_start, ev_stop);
+}
 
 // =============================================================================================
 // Operand-planes interface of the bf16 engines (fp32 storage): the producers of the conv operands (LayerNorm forward,

@@ -16,6 +16,8 @@ struct KCParams {
     float* C; long long ldc;
     const float* bias;
     const float* bias2; int bias_split;   // columns >= bias_split take bias2[col - bias_split] (two stacked projections)
+    int depth;   // taps == 27: the image's third extent (fastest spatial axis: point n = (h*W + w)*depth + d)
+                 // (depth and taps sit in alignment holes: the kernel-argument layout of the other kernels is unchanged)
     const float* res; long long ldres;
     float* aux; long long ldaux;
     int M, N, K;
@@ -30,7 +32,23 @@ struct KCParams {
     const float* wsrc; long long wsn, wsk;   // the image's source: B[n][k] = wsrc[n * wsn + k * wsk]
     int io_bf16; // bf16-storage entry points: A (row-major [M][K] or the NHWC image), C, res and aux hold bf16; lda / ldc /
                  // ldres / ldaux stay in ELEMENTS; a bf16 A is read as pre-made 1-plane "planes" (apre = 1)
+    int taps;    // im2col view: 27 = 3x3x3 conv on an image [B,H,W,depth,Cin] (K = 27*Cin; set only by the
+                 // pa2d_conv3x3x3x2_* entry points, which select the 27-tap kernels with it); anything else = 3x3, K = 9*Cin
 };
+
+// 27-tap geometry of the 3x3x3 implicit GEMMs: tap t = kh*9 + kw*3 + kd has offset (kh-1, kw-1, kd-1) on (H, W, depth);
+// point n = (h*W + w)*depth + d, so the neighbour at that offset is row n + ((kh-1)*W + (kw-1))*depth + (kd-1).
+__device__ __forceinline__ void conv3d_point(int n, int W, int depth, int& y, int& x, int& z) {
+    const int t = n / depth;
+    z = n - t * depth;
+    y = t / W;
+    x = t - y * W;
+}
+__device__ __forceinline__ void conv3d_tap(int tap, int& dy, int& dx, int& dz) {
+    dy = tap / 9 - 1;
+    dx = (tap / 3) % 3 - 1;
+    dz = tap % 3 - 1;
+}
 
 __device__ __forceinline__ float gelu_f(float x) { return gelu_exact(x); }
 __device__ __forceinline__ float dgelu_f(float x) { return dgelu_exact(x); }
@@ -129,6 +147,8 @@ __device__ __forceinline__ void split3(const float4 v, bf16x4& hi, bf16x4& mid, 
 
 struct MCParams {
     const float* A; long long lda; int Mi;
+    int depth;       // 27-tap kernels (TAPS = 27): image [B,H,W,depth,Cin], j = tap*Cin + ci with tap < 27 (an alignment
+                     // hole: the kernel-argument layout of the other kernels is unchanged)
     const float* B; long long ldb; int Nj;
     float* slab;
     int Mk, chunks_per_split, splits;
@@ -151,7 +171,9 @@ bool kc_split_small_applies(const KCParams& p, bool im2col);
 int launch_kc_split_small(const KCParams& p, hipStream_t st);
 size_t planes_bytes(long long rows, int C, int NT);
 int launch_split_planes(const float* src, long long ld, void* dst, long long rows, int C, int NT, hipStream_t st);
-int launch_repack_split(const float* w0, const float* w1, void* dst, int bwd, int NT, int C, int Cin, hipStream_t st);
+// taps = 27: pack of the two [C, Cin, 3, 3, 3] kernels of the 3x3x3 conv (same row image, K-step kc = cic*27 + tap)
+int launch_repack_split(const float* w0, const float* w1, void* dst, int bwd, int NT, int C, int Cin, hipStream_t st,
+                        int taps = 9);
 // persistent row-panel kernel for large-M plain GEMMs of the bf16 engines (pa2d_gemm_panel.hip)
 bool panel_applies(const KCParams& p, bool im2col);
 int launch_kc_panel(const KCParams& p, hipStream_t st);
@@ -165,11 +187,14 @@ bool conv_halo_applies(const KCParams& p);
 int launch_conv_halo(const KCParams& p, hipStream_t st);
 // weight-gradient engine and reductions (pa2d_gemm_mc.hip)
 MCPlan plan_mc(int Mi, int Nj, int Mk);
+// taps = 27 (im2col): the 3x3x3 view of an image [B,H,W,depth,Cin], Nj = 27*Cin
 int launch_mc(const float* A, long long lda, int Mi, const float* B, long long ldb, int Nj, int Mk, bool im2col,
-              int H, int W, int Cin, float* slab, const MCPlan& pl, int engine, hipStream_t st, float* colsum = nullptr);
-// accumulate != 0: out += sum of slabs (gradient accumulation straight into the caller's buffer)
+              int H, int W, int Cin, float* slab, const MCPlan& pl, int engine, hipStream_t st, float* colsum = nullptr,
+              int taps = 9, int depth = 1);
+// accumulate != 0: out += sum of slabs (gradient accumulation straight into the caller's buffer); mode 1 with taps = 27
+// un-packs [2C][27][Cin] into two [C][Cin][3][3][3] gradients
 int launch_reduce(const float* slab, int nslab, long long count, float* out, float* out2, int mode, int C, int Cin,
-                  hipStream_t st, int accumulate = 0);
+                  hipStream_t st, int accumulate = 0, int taps = 9);
 int pa2d_launch_reduce(const float* slab, int nslab, long long count, float* out, hipStream_t st);
 // weight gradient from pre-split planes (pa2d_gemm_mc_planes.hip)
 bool mc_planes_supported(int C, int Cin);

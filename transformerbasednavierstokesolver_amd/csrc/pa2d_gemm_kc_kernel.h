@@ -2,7 +2,8 @@
 #pragma once
 #include "pa2d_gemm_common.h"
 
-template <int BM, int BN, int WAVES_M, int WAVES_N, bool IM2COL, int BK = 16>
+// TAPS (IM2COL only): 9 = 3x3 conv on [B,H,W,Cin]; 27 = 3x3x3 conv on [B,H,W,depth,Cin] (KCParams::taps / depth)
+template <int BM, int BN, int WAVES_M, int WAVES_N, bool IM2COL, int BK = 16, int TAPS = 9>
 __global__ __launch_bounds__(256, 2) void gemm_kc_kernel(const KCParams p) {
     constexpr int PITCH = BK + 4;              // 20 or 36 floats: an odd number of 16-byte slots
     constexpr int QPR = BK / 4;                // float4 per tile row
@@ -32,12 +33,14 @@ __global__ __launch_bounds__(256, 2) void gemm_kc_kernel(const KCParams p) {
     const __amdgpu_buffer_rsrc_t ra_rsrc = make_rsrc(p.A, p.a_bytes);
     const __amdgpu_buffer_rsrc_t rb_rsrc = make_rsrc(p.B, p.b_bytes);
     unsigned a_off[A_IT], b_off[B_IT];
-    int a_y[A_IT], a_x[A_IT];
+    int a_y[A_IT], a_x[A_IT], a_z[A_IT];
 #pragma unroll
     for (int s = 0; s < A_IT; ++s) {
         const int gm = tile_m * BM + lr + RPP * s;
         a_off[s] = gm < p.M ? (unsigned)gm * (unsigned)p.lda * 4u + lq * 16u : OOB_OFF;
-        if (IM2COL) {
+        if (IM2COL && TAPS == 27) {
+            conv3d_point(gm % (p.H * p.W * p.depth), p.W, p.depth, a_y[s], a_x[s], a_z[s]);
+        } else if (IM2COL) {
             const int n = gm % (p.H * p.W);
             a_y[s] = n / p.W;
             a_x[s] = n - a_y[s] * p.W;
@@ -64,11 +67,23 @@ __global__ __launch_bounds__(256, 2) void gemm_kc_kernel(const KCParams p) {
     // K order of the implicit-GEMM conv: k = (ci_chunk*9 + tap)*16 + c, i.e. the 9 taps of one
     // 16-channel chunk are consecutive K-steps: they re-touch the same 64-B segments of the same
     // image rows (shifted by one pixel), which are then L1/L2 hits instead of fresh misses.
+    // TAPS = 27: k = (ci_chunk*27 + tap)*BK + c, with the border test on all three axes.
 #define KC_LOAD(kc_)                                                                                   \
     {                                                                                                  \
         const int k0_ = (kc_) * BK;                                                                    \
         const bool kin_ = k0_ + lq * 4 < p.K;                                                          \
-        if (IM2COL) {                                                                                  \
+        if (IM2COL && TAPS == 27) {                                                                    \
+            const int cic_ = (kc_) / 27;                                                               \
+            int dy_, dx_, dz_;                                                                         \
+            conv3d_tap((kc_) - cic_ * 27, dy_, dx_, dz_);                                              \
+            const int sh_ = (((dy_ * p.W + dx_) * p.depth + dz_) * (int)p.lda + cic_ * BK) * 4;        \
+            _Pragma("unroll") for (int s = 0; s < A_IT; ++s) {                                         \
+                const bool ok_ = (unsigned)(a_y[s] + dy_) < (unsigned)p.H &&                           \
+                                 (unsigned)(a_x[s] + dx_) < (unsigned)p.W &&                           \
+                                 (unsigned)(a_z[s] + dz_) < (unsigned)p.depth && a_off[s] != OOB_OFF;  \
+                ra[s] = buf_load4(ra_rsrc, ok_ ? a_off[s] + (unsigned)sh_ : OOB_OFF);                  \
+            }                                                                                          \
+        } else if (IM2COL) {                                                                           \
             const int cic_ = (kc_) / 9, tap_ = (kc_) - cic_ * 9;                                       \
             const int dy_ = tap_ / 3 - 1, dx_ = tap_ - (tap_ / 3) * 3 - 1;                             \
             const int sh_ = ((dy_ * p.W + dx_) * (int)p.lda + cic_ * BK) * 4;                          \

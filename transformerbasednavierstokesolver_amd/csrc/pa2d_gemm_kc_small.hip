@@ -2,10 +2,13 @@
 // with 128x128 tiles (batch-1 rollout, small-batch training).  Separate translation unit for build parallelism.
 #include "pa2d_gemm_kc_kernel.h"
 
-// K-step 32 whenever the operand layout allows it (plain GEMMs always; conv when Cin % 32 == 0), else 16
+// K-step 32 whenever the operand layout allows it (plain GEMMs always; conv when Cin % 32 == 0), else 16;
+// p.taps == 27: the 3x3x3 conv (pa2d_conv3x3x3x2_*)
 #define KC_GO(BM_, BN_, WM_, WN_)                                                                            \
     {                                                                                                      \
         if (!im2col) hipLaunchKernelGGL((gemm_kc_kernel<BM_, BN_, WM_, WN_, false, 32>), grid, dim3(256), 0, st, p); \
+        else if (p.taps == 27 && t.bk == 32) hipLaunchKernelGGL((gemm_kc_kernel<BM_, BN_, WM_, WN_, true, 32, 27>), grid, dim3(256), 0, st, p); \
+        else if (p.taps == 27) hipLaunchKernelGGL((gemm_kc_kernel<BM_, BN_, WM_, WN_, true, 16, 27>), grid, dim3(256), 0, st, p); \
         else if (t.bk == 32) hipLaunchKernelGGL((gemm_kc_kernel<BM_, BN_, WM_, WN_, true, 32>), grid, dim3(256), 0, st, p); \
         else hipLaunchKernelGGL((gemm_kc_kernel<BM_, BN_, WM_, WN_, true, 16>), grid, dim3(256), 0, st, p);  \
     }

@@ -19,7 +19,8 @@ __device__ __forceinline__ void mc_split_elem(float v, bf16x8 (&pl)[NT], int e) 
         pl[2][e] = (__bf16)(r1 - (float)m);
     }
 }
-template <int BM, int BN, bool IM2COL, int NT, int BK = 16>
+// TAPS (IM2COL only): 9 = 3x3 view of B, 27 = 3x3x3 view of an image [B,H,W,depth,Cin] (MCParams::depth)
+template <int BM, int BN, bool IM2COL, int NT, int BK = 16, int TAPS = 9>
 __global__ __launch_bounds__(256, 2) void gemm_mc_kernel(const MCParams p) {
     constexpr int WM = BM / 2, WN = BN / 2, TM = WM / 32, TN = WN / 32;
     constexpr int A_TPR = BM / 4, A_RPP = 256 / A_TPR, A_IT = BK / A_RPP;
@@ -62,20 +63,25 @@ __global__ __launch_bounds__(256, 2) void gemm_mc_kernel(const MCParams p) {
     const int gi = ti * BM + a_c;
     const int gj = tj * BN + b_c;
     const bool a_col_ok = gi < p.Mi, b_col_ok = gj < p.Nj;
-    int tap_dy = 0, tap_dx = 0, ci = 0;
-    if (IM2COL && b_col_ok) {
+    int tap_dy = 0, tap_dx = 0, tap_dz = 0, ci = 0;
+    if (IM2COL && TAPS == 27 && b_col_ok) {
+        const int tap = gj / p.Cin;
+        ci = gj - tap * p.Cin;
+        conv3d_tap(tap, tap_dy, tap_dx, tap_dz);
+    } else if (IM2COL && b_col_ok) {
         const int tap = gj / p.Cin;
         ci = gj - tap * p.Cin;
         tap_dy = tap / 3 - 1;
         tap_dx = tap - (tap / 3) * 3 - 1;
     }
     const int HW = p.H * p.W;
+    const int HWD = TAPS == 27 ? HW * p.depth : HW;
 
     const __amdgpu_buffer_rsrc_t ra_rsrc = make_rsrc(p.A, p.a_bytes);
     const __amdgpu_buffer_rsrc_t rb_rsrc = make_rsrc(p.B, p.b_bytes);
     const unsigned a_col = a_col_ok ? (unsigned)gi * 4u : OOB_OFF;
     const unsigned b_col = b_col_ok ? (unsigned)(IM2COL ? ci : gj) * 4u : OOB_OFF;
-    const int tap_shift = tap_dy * p.W + tap_dx;
+    const int tap_shift = TAPS == 27 ? (tap_dy * p.W + tap_dx) * p.depth + tap_dz : tap_dy * p.W + tap_dx;
     float4 ra[A_IT], rb[B_IT];
 #define MC_LOAD(c_)                                                                                       \
     {                                                                                                     \
@@ -87,7 +93,13 @@ __global__ __launch_bounds__(256, 2) void gemm_mc_kernel(const MCParams p) {
         _Pragma("unroll") for (int s = 0; s < B_IT; ++s) {                                                \
             const int m_ = m0_ + b_r + s * B_RPP;                                                         \
             bool ok_ = b_col != OOB_OFF && m_ < p.Mk;                                                     \
-            if (IM2COL) {                                                                                 \
+            if (IM2COL && TAPS == 27) {                                                                   \
+                int y_, x_, z_;                                                                           \
+                conv3d_point(m_ % HWD, p.W, p.depth, y_, x_, z_);                                         \
+                ok_ = ok_ && (unsigned)(y_ + tap_dy) < (unsigned)p.H && (unsigned)(x_ + tap_dx) < (unsigned)p.W && \
+                      (unsigned)(z_ + tap_dz) < (unsigned)p.depth;                                        \
+                rb[s] = buf_load4(rb_rsrc, ok_ ? (unsigned)(m_ + tap_shift) * (unsigned)p.ldb * 4u + b_col : OOB_OFF); \
+            } else if (IM2COL) {                                                                          \
                 const int n_ = m_ % HW;                                                                   \
                 const int y_ = n_ / p.W, x_ = n_ - y_ * p.W;                                              \
                 ok_ = ok_ && (unsigned)(y_ + tap_dy) < (unsigned)p.H && (unsigned)(x_ + tap_dx) < (unsigned)p.W; \
@@ -253,9 +265,11 @@ MCPlan plan_mc(int Mi, int Nj, int Mk) {
 }
 
 // out[idx] = sum_s slab[s][idx]; mode 1 additionally un-packs the conv weight gradient:
-// slab row-major [2C][9][Cin] -> dWx / dWf in the reference's [C_out][C_in][3][3] layout.
+// slab row-major [2C][TAPS][Cin] -> dWx / dWf in the reference's [C_out][C_in][3][3] (TAPS = 9) or [C_out][C_in][3][3][3]
+// (TAPS = 27) layout.
 // 64 consecutive idx x 4 slab lanes per workgroup: each lane sums slabs s = lane, lane+4, ... with
 // 4 independent loads in flight; the 4 lane sums are added in fixed order (deterministic).
+template <int TAPS>
 __global__ __launch_bounds__(256) void reduce_slabs_kernel(const float* __restrict__ slab, int nslab, long long count,
                                                            float* __restrict__ out, float* __restrict__ out2,
                                                            int mode, int C, int Cin, int accumulate) {
@@ -285,22 +299,23 @@ __global__ __launch_bounds__(256) void reduce_slabs_kernel(const float* __restri
         dst = idx < C ? out + idx : out2 + (idx - C);
     } else {
         const int ci = (int)(idx % Cin);
-        const int tap = (int)((idx / Cin) % 9);
-        const int co = (int)(idx / ((long long)Cin * 9));
-        dst = (co < C ? out : out2) + ((size_t)(co % C) * Cin + ci) * 9 + tap;
+        const int tap = (int)((idx / Cin) % TAPS);
+        const int co = (int)(idx / ((long long)Cin * TAPS));
+        dst = (co < C ? out : out2) + ((size_t)(co % C) * Cin + ci) * TAPS + tap;
     }
     *dst = accumulate ? *dst + s : s;
 }
 
 int launch_mc(const float* A, long long lda, int Mi, const float* B, long long ldb, int Nj, int Mk,
                      bool im2col, int H, int W, int Cin, float* slab, const MCPlan& pl, int engine, hipStream_t st,
-                     float* colsum) {
+                     float* colsum, int taps, int depth) {
     if ((Mi & 3) || (Nj & 3) || (lda & 3) || (ldb & 3)) return PA2D_ERR_ARG;
     if (im2col && (Cin & 3)) return PA2D_ERR_UNSUPPORTED;
     MCParams p;
     p.A = A; p.lda = lda; p.Mi = Mi; p.B = B; p.ldb = ldb; p.Nj = Nj; p.slab = slab; p.Mk = Mk;
     p.chunks_per_split = pl.chunks_per_split; p.splits = pl.splits; p.H = H; p.W = W; p.Cin = Cin;
     p.colsum = colsum;
+    p.depth = depth;
     {
         const unsigned long long ab = ((unsigned long long)(Mk - 1) * lda + Mi) * 4ull;
         const unsigned long long bb = ((unsigned long long)(Mk - 1) * ldb + (im2col ? Cin : Nj)) * 4ull;
@@ -312,6 +327,20 @@ int launch_mc(const float* A, long long lda, int Mi, const float* B, long long l
     const dim3 grid(ceil_div(Mi, bm) * ceil_div(Nj, bm) * pl.splits);
     const bool bf = engine == 2;
     const int mc_bk = pa2d_env().mc_bk;
+    if (im2col && taps == 27) {      // 3x3x3 conv weight gradient: the same variant choice on the 27-tap view
+        if (pl.big && !bf && mc_bk == 32 && (pl.chunks_per_split % 2) == 0)
+            hipLaunchKernelGGL((gemm_mc_kernel<128, 128, true, 0, 32, 27>), grid, dim3(256), 0, st, p);
+        else if (pl.big && engine == 1 && (Cin % 32) == 0)
+            hipLaunchKernelGGL((gemm_mc_kernel<128, 128, true, 3, 16, 27>), grid, dim3(256), 0, st, p);
+        else if (pl.big && bf)
+            hipLaunchKernelGGL((gemm_mc_kernel<128, 128, true, 1, 16, 27>), grid, dim3(256), 0, st, p);
+        else if (pl.big)
+            hipLaunchKernelGGL((gemm_mc_kernel<128, 128, true, 0, 16, 27>), grid, dim3(256), 0, st, p);
+        else
+            hipLaunchKernelGGL((gemm_mc_kernel<64, 64, true, 0, 16, 27>), grid, dim3(256), 0, st, p);
+        PA2D_CHECK_LAUNCH();
+        return PA2D_OK;
+    }
     if (pl.big && !bf && mc_bk == 32 && (pl.chunks_per_split % 2) == 0) {
         if (im2col) hipLaunchKernelGGL((gemm_mc_kernel<128, 128, true, 0, 32>), grid, dim3(256), 0, st, p);
         else hipLaunchKernelGGL((gemm_mc_kernel<128, 128, false, 0, 32>), grid, dim3(256), 0, st, p);
@@ -333,10 +362,14 @@ int launch_mc(const float* A, long long lda, int Mi, const float* B, long long l
 }
 
 int launch_reduce(const float* slab, int nslab, long long count, float* out, float* out2, int mode,
-                         int C, int Cin, hipStream_t st, int accumulate) {
+                         int C, int Cin, hipStream_t st, int accumulate, int taps) {
     const dim3 grid((unsigned)ceil_div_ll(count, 64));
-    hipLaunchKernelGGL(reduce_slabs_kernel, grid, dim3(256), 0, st, slab, nslab, count, out, out2, mode, C, Cin,
-                       accumulate);
+    if (taps == 27)
+        hipLaunchKernelGGL(reduce_slabs_kernel<27>, grid, dim3(256), 0, st, slab, nslab, count, out, out2, mode, C, Cin,
+                           accumulate);
+    else
+        hipLaunchKernelGGL(reduce_slabs_kernel<9>, grid, dim3(256), 0, st, slab, nslab, count, out, out2, mode, C, Cin,
+                           accumulate);
     PA2D_CHECK_LAUNCH();
     return PA2D_OK;
 }

@@ -27,7 +27,8 @@
 // each activation element is converted once instead of once per (tap, column tile) = 36 times.
 // TO: storage type of C / res / aux (float, or bf16 for the bf16-storage entry points).  APRE without IM2COL: A is a
 // row-major bf16 matrix [M][K] (K % 32 == 0), i.e. already the 1-plane image of every 32-wide K-step.
-template <int BM, int BN, bool IM2COL, int NT, bool APRE = false, typename TO = float>
+// TAPS (IM2COL only): 9 = 3x3 conv, 27 = 3x3x3 conv on [B,H,W,depth,Cin] (K-step kc = cic*27 + tap).
+template <int BM, int BN, bool IM2COL, int NT, bool APRE = false, typename TO = float, int TAPS = 9>
 __global__ __launch_bounds__(512, (BM + BN > 256) ? 1 : 2) void gemm_kc_split_kernel(const KCParams p) {
     constexpr int BK = 32, PITCHB = NT * 64 + 16;        // bytes per LDS row (NT planes x 64 B + 16): 208 / 80
     constexpr int WM = BM / 2, WN = BN / 2, TM = WM / 32, TN = WN / 32;
@@ -58,9 +59,9 @@ __global__ __launch_bounds__(512, (BM + BN > 256) ? 1 : 2) void gemm_kc_split_ke
         constexpr int BP_IT = (BN * PIECES) / 256;                // pieces per producer thread
         constexpr int AP_IT = (BM * PIECES) / 256;                // A pieces per producer thread (APRE)
         unsigned a_off[A_IT], b_off[B_IT], bp_off[BP_IT], bp_lds[BP_IT];
-        int a_y[A_IT], a_x[A_IT];
+        int a_y[A_IT], a_x[A_IT], a_z[A_IT];
         unsigned ap_off[AP_IT], ap_lds[AP_IT];
-        int ap_y[AP_IT], ap_x[AP_IT];
+        int ap_y[AP_IT], ap_x[AP_IT], ap_z[AP_IT];
         const int nch_in = p.Cin / 32;                            // 32-channel chunks per pixel (APRE)
 #pragma unroll
         for (int s = 0; s < AP_IT; ++s) {
@@ -69,15 +70,21 @@ __global__ __launch_bounds__(512, (BM + BN > 256) ? 1 : 2) void gemm_kc_split_ke
             ap_off[s] = (APRE && gm < p.M) ? (IM2COL ? ((unsigned)gm * (unsigned)(nch_in * PIECES) + piece) * 16u
                                                      : (unsigned)gm * (unsigned)p.lda * 2u + piece * 16u) : OOB_OFF;
             ap_lds[s] = row * PITCHB + piece * 16;
-            const int n = (APRE && IM2COL) ? gm % (p.H * p.W) : 0;
-            ap_y[s] = n / p.W;
-            ap_x[s] = n - ap_y[s] * p.W;
+            if (APRE && IM2COL && TAPS == 27) {
+                conv3d_point(gm % (p.H * p.W * p.depth), p.W, p.depth, ap_y[s], ap_x[s], ap_z[s]);
+            } else {
+                const int n = (APRE && IM2COL) ? gm % (p.H * p.W) : 0;
+                ap_y[s] = n / p.W;
+                ap_x[s] = n - ap_y[s] * p.W;
+            }
         }
 #pragma unroll
         for (int s = 0; s < A_IT; ++s) {
             const int gm = tile_m * BM + lr + 32 * s;
             a_off[s] = gm < p.M ? (unsigned)gm * (unsigned)p.lda * 4u + lq * 16u : OOB_OFF;
-            if (IM2COL) {
+            if (IM2COL && TAPS == 27) {
+                conv3d_point(gm % (p.H * p.W * p.depth), p.W, p.depth, a_y[s], a_x[s], a_z[s]);
+            } else if (IM2COL) {
                 const int n = gm % (p.H * p.W);
                 a_y[s] = n / p.W;
                 a_x[s] = n - a_y[s] * p.W;
@@ -108,6 +115,17 @@ __global__ __launch_bounds__(512, (BM + BN > 256) ? 1 : 2) void gemm_kc_split_ke
             _Pragma("unroll") for (int s = 0; s < AP_IT; ++s)                                          \
                 RQ[s] = __builtin_amdgcn_raw_buffer_load_b128(                                         \
                     ra_rsrc, ap_off[s] != OOB_OFF ? ap_off[s] + (unsigned)(kc_) * (PIECES * 16u) : OOB_OFF, 0, 0); \
+        } else if (APRE && TAPS == 27) {                                                               \
+            const int cic_ = (kc_) / 27;                                                               \
+            int dy_, dx_, dz_;                                                                         \
+            conv3d_tap((kc_) - cic_ * 27, dy_, dx_, dz_);                                              \
+            const int sh_ = (((dy_ * p.W + dx_) * p.depth + dz_) * nch_in + cic_) * (PIECES * 16);     \
+            _Pragma("unroll") for (int s = 0; s < AP_IT; ++s) {                                        \
+                const bool ok_ = (unsigned)(ap_y[s] + dy_) < (unsigned)p.H &&                          \
+                                 (unsigned)(ap_x[s] + dx_) < (unsigned)p.W &&                          \
+                                 (unsigned)(ap_z[s] + dz_) < (unsigned)p.depth && ap_off[s] != OOB_OFF; \
+                RQ[s] = __builtin_amdgcn_raw_buffer_load_b128(ra_rsrc, ok_ ? ap_off[s] + (unsigned)sh_ : OOB_OFF, 0, 0); \
+            }                                                                                          \
         } else if (APRE) {                                                                             \
             const int cic_ = (kc_) / 9, tap_ = (kc_) - cic_ * 9;                                       \
             const int dy_ = tap_ / 3 - 1, dx_ = tap_ - (tap_ / 3) * 3 - 1;                             \
@@ -116,6 +134,17 @@ __global__ __launch_bounds__(512, (BM + BN > 256) ? 1 : 2) void gemm_kc_split_ke
                 const bool ok_ = (unsigned)(ap_y[s] + dy_) < (unsigned)p.H &&                          \
                                  (unsigned)(ap_x[s] + dx_) < (unsigned)p.W && ap_off[s] != OOB_OFF;    \
                 RQ[s] = __builtin_amdgcn_raw_buffer_load_b128(ra_rsrc, ok_ ? ap_off[s] + (unsigned)sh_ : OOB_OFF, 0, 0); \
+            }                                                                                          \
+        } else if (IM2COL && TAPS == 27) {                                                             \
+            const int cic_ = (kc_) / 27;                                                               \
+            int dy_, dx_, dz_;                                                                         \
+            conv3d_tap((kc_) - cic_ * 27, dy_, dx_, dz_);                                              \
+            const int sh_ = (((dy_ * p.W + dx_) * p.depth + dz_) * (int)p.lda + cic_ * BK) * 4;        \
+            _Pragma("unroll") for (int s = 0; s < A_IT; ++s) {                                         \
+                const bool ok_ = (unsigned)(a_y[s] + dy_) < (unsigned)p.H &&                           \
+                                 (unsigned)(a_x[s] + dx_) < (unsigned)p.W &&                           \
+                                 (unsigned)(a_z[s] + dz_) < (unsigned)p.depth && a_off[s] != OOB_OFF;  \
+                RA[s] = buf_load4(ra_rsrc, ok_ ? a_off[s] + (unsigned)sh_ : OOB_OFF);                  \
             }                                                                                          \
         } else if (IM2COL) {                                                                                  \
             const int cic_ = (kc_) / 9, tap_ = (kc_) - cic_ * 9;                                       \
@@ -273,6 +302,29 @@ int launch_kc_split_small(const KCParams& p, hipStream_t st) {
     return PA2D_OK;
 }
 
+// 27-tap (3x3x3) conv on pre-split activation planes: the tile choice of the 9-tap conv below (256x128 where M % 256 == 0
+// and >= 512 tiles, 64x128 for small launches, else 128x128); the halo-in-LDS kernel is 2-D only and is never used here.
+template <int BM, int BN, int NT>
+static int launch_split27(const KCParams& p, int rows_per_tile, int tiles_n, hipStream_t st) {
+    const int smem = 2 * (BM + BN) * (NT * 64 + 16);
+    if (smem > 65536) {      // every launch: the attribute is per device, and the call is cheap
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_kc_split_kernel<BM, BN, true, NT, true, float, 27>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+        if (e != hipSuccess) return (int)e;
+    }
+    const dim3 grid(ceil_div(ceil_div(p.M, rows_per_tile), 8) * 8 * tiles_n);
+    hipLaunchKernelGGL((gemm_kc_split_kernel<BM, BN, true, NT, true, float, 27>), grid, dim3(512), smem, st, p);
+    PA2D_CHECK_LAUNCH();
+    return PA2D_OK;
+}
+static int launch_conv3d_split(const KCParams& p, int tiles_m, int tiles_n, hipStream_t st) {
+    if (p.engine == 2) return launch_split27<128, 128, 1>(p, 128, tiles_n, st);
+    if (pa2d_env().split_big && (p.M % 256) == 0 && (long long)(p.M / 256) * tiles_n >= 512)
+        return launch_split27<256, 128, 3>(p, 256, tiles_n, st);
+    if ((long long)tiles_m * tiles_n < 256) return launch_split27<64, 128, 3>(p, 64, tiles_n, st);
+    return launch_split27<128, 128, 3>(p, 128, tiles_n, st);
+}
+
 int launch_kc_split(KCParams& p, bool im2col, hipStream_t st) {
     const int tiles_m = ceil_div(p.M, 128), tiles_n = ceil_div(p.N, 128);
     const bool bf = p.engine == 2;
@@ -287,6 +339,7 @@ int launch_kc_split(KCParams& p, bool im2col, hipStream_t st) {
         return PA2D_ERR_ARG;
     }
     if (p.io_bf16) {          // bf16-storage entry points: A is the bf16 tensor itself, outputs are bf16
+        if (p.taps == 27) return PA2D_ERR_UNSUPPORTED;      // no bf16-storage 3x3x3 conv
         if (!bf || (!im2col && (p.K % 32) != 0)) return PA2D_ERR_UNSUPPORTED;
         if (!im2col) {
             const unsigned long long ab = ((unsigned long long)(p.M - 1) * p.lda + p.K) * 2ull;
@@ -300,6 +353,7 @@ int launch_kc_split(KCParams& p, bool im2col, hipStream_t st) {
         PA2D_CHECK_LAUNCH();
         return PA2D_OK;
     }
+    if (im2col && p.taps == 27) return launch_conv3d_split(p, tiles_m, tiles_n, st);
     if (im2col && conv_halo_applies(p)) return launch_conv_halo(p, st);
     const dim3 grid(ceil_div(tiles_m, 8) * 8 * tiles_n);
     const int smem = 2 * (128 + 128) * (bf ? 80 : 208);
@@ -368,31 +422,33 @@ int launch_split_planes(const float* src, long long ld, void* dst, long long row
 // conv weight pack for the bf16 engines: dst row n = [K-step kc = cic*9+tap][plane][32 channels] bf16,
 // i.e. the LDS row image of gemm_kc_split_kernel (NT planes: hi | mid | lo).  bwd != 0: data-gradient
 // layout (rows = input channels, contraction over the 2C output channels, taps mirrored).
+// TAPS = 27: the same for the [C, Cin, 3, 3, 3] kernels of the 3x3x3 conv (data gradient: taps mirrored as 26 - tap).
+template <int TAPS>
 __global__ void repack_split_kernel(const float* __restrict__ w0, const float* __restrict__ w1,
                                     __bf16* __restrict__ dst, int bwd, int NT, int C, int Cin) {
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (long long)2 * C * 9 * Cin) return;
+    if (idx >= (long long)2 * C * TAPS * Cin) return;
     float v;
     int n, kc, c32;
-    if (!bwd) {          // rows n = output channel co' in [0,2C), K = 9*Cin
+    if (!bwd) {          // rows n = output channel co' in [0,2C), K = TAPS*Cin
         c32 = (int)(idx % 32);
-        const int tap = (int)((idx / 32) % 9);
-        const int cic = (int)((idx / 288) % (Cin / 32));
-        n = (int)(idx / ((long long)Cin * 9));
-        kc = cic * 9 + tap;
+        const int tap = (int)((idx / 32) % TAPS);
+        const int cic = (int)((idx / (32 * TAPS)) % (Cin / 32));
+        n = (int)(idx / ((long long)Cin * TAPS));
+        kc = cic * TAPS + tap;
         const float* src = n < C ? w0 : w1;
-        v = src[((size_t)(n % C) * Cin + cic * 32 + c32) * 9 + tap];
-    } else {             // rows n = input channel ci in [0,Cin), K = 9*2C
+        v = src[((size_t)(n % C) * Cin + cic * 32 + c32) * TAPS + tap];
+    } else {             // rows n = input channel ci in [0,Cin), K = TAPS*2C
         c32 = (int)(idx % 32);
-        const int tap = (int)((idx / 32) % 9);
-        const int cic = (int)((idx / 288) % (2 * C / 32));
-        n = (int)(idx / ((long long)2 * C * 9));
-        kc = cic * 9 + tap;
+        const int tap = (int)((idx / 32) % TAPS);
+        const int cic = (int)((idx / (32 * TAPS)) % (2 * C / 32));
+        n = (int)(idx / ((long long)2 * C * TAPS));
+        kc = cic * TAPS + tap;
         const int co = cic * 32 + c32;
         const float* src = co < C ? w0 : w1;
-        v = src[((size_t)(co % C) * Cin + n) * 9 + (8 - tap)];
+        v = src[((size_t)(co % C) * Cin + n) * TAPS + (TAPS - 1 - tap)];
     }
-    const int nk = bwd ? (2 * C / 32) * 9 : (Cin / 32) * 9;
+    const int nk = bwd ? (2 * C / 32) * TAPS : (Cin / 32) * TAPS;
     __bf16* d = dst + ((size_t)n * nk + kc) * NT * 32 + c32;
     const __bf16 h = (__bf16)v;
     d[0] = h;
@@ -404,9 +460,13 @@ __global__ void repack_split_kernel(const float* __restrict__ w0, const float* _
     }
 }
 
-int launch_repack_split(const float* w0, const float* w1, void* dst, int bwd, int NT, int C, int Cin, hipStream_t st) {
-    hipLaunchKernelGGL(repack_split_kernel, dim3((unsigned)ceil_div_ll((long long)2 * C * 9 * Cin, 256)), dim3(256), 0, st, w0,
-                       w1, (__bf16*)dst, bwd, NT, C, Cin);
+int launch_repack_split(const float* w0, const float* w1, void* dst, int bwd, int NT, int C, int Cin, hipStream_t st,
+                        int taps) {
+    const dim3 grid((unsigned)ceil_div_ll((long long)2 * C * taps * Cin, 256));
+    if (taps == 27)
+        hipLaunchKernelGGL(repack_split_kernel<27>, grid, dim3(256), 0, st, w0, w1, (__bf16*)dst, bwd, NT, C, Cin);
+    else
+        hipLaunchKernelGGL(repack_split_kernel<9>, grid, dim3(256), 0, st, w0, w1, (__bf16*)dst, bwd, NT, C, Cin);
     PA2D_CHECK_LAUNCH();
     return PA2D_OK;
 }

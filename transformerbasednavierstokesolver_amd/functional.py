@@ -30,10 +30,18 @@ def _ret(targets, grads):
 
 
 # ------------------------------------------------------------------------------ Physics-Attention
+def mesh_extent(W):
+    """(width, depth) of a structured mesh: the geometry argument `W` of the functions below is the width of a 2-D mesh
+    (depth None: 3x3 conv projections) or the pair (width, depth) of a 3-D mesh [H, W, depth] (3x3x3 conv projections,
+    Physics_Attention_Structured_Mesh_3D)."""
+    return (W[0], W[1]) if isinstance(W, tuple) else (W, None)
+
+
 def attn_forward(xn, P, res, H, W, heads, engine=None, xn_planes=None, shape=None):
     """xn [B,N,C] (already layer-normed).  P: dict of parameter tensors.  Returns (out, saved).
     H is None -> irregular-mesh variant (Physics_Attention.py:6-57): Linear projections, no
-    temperature clamp; otherwise the structured-mesh variant (3x3 conv projections, clamp).
+    temperature clamp; otherwise the structured-mesh variant (3x3 conv projections, clamp; W = (width, depth):
+    the 3-D structured mesh, 3x3x3 conv projections, clamp).
     xn_planes (structured, bf16 engines): the LayerNorm output exists only as the conv's bf16 plane image
     (ops.layernorm_fwd_planes); `xn` is then None and `shape` = (B, N, C)."""
     B, N, C = xn.shape if xn is not None else shape
@@ -41,8 +49,13 @@ def attn_forward(xn, P, res, H, W, heads, engine=None, xn_planes=None, shape=Non
     M = P["ws"].shape[0]
     temp = P["temperature"].reshape(heads).contiguous()
     structured = H is not None
+    Wm, depth = mesh_extent(W)
     if xn_planes is not None:
+        if depth is not None:
+            raise ValueError("the operand-planes route is 3x3 only; the 3-D mesh takes the fp32 operand")
         xf = ops.conv3x3x2_fwd_planes(xn_planes, P["wx"], P["bx"], P["wf"], P["bf"], B, H, W, engine)
+    elif structured and depth is not None:
+        xf = ops.conv3x3x3x2_fwd(xn, P["wx"], P["bx"], P["wf"], P["bf"], H, Wm, depth, engine=engine)    # [B,N,2C]
     elif structured:
         xf = ops.conv3x3x2_fwd(xn, P["wx"], P["bx"], P["wf"], P["bf"], H, W, engine=engine)    # [B,N,2C]
     else:   # both Linear(C, C) projections as ONE GEMM with the weights stacked along the output dim
@@ -68,6 +81,9 @@ def attn_backward(saved, P, dout, H, W, heads, need_dx=True, engine=None, target
     M = P["ws"].shape[0]
     d2 = dout.reshape(B * N, C)
     structured = H is not None
+    Wm, depth = mesh_extent(W)
+    if planes and depth is not None:
+        raise ValueError("the operand-planes route is 3x3 only; the 3-D mesh takes the fp32 operand")
     T = targets if structured else None
     t = (lambda *ks: tuple(T[k] for k in ks)) if T is not None else (lambda *ks: None)
     dy = ops.linear_bwd_data(d2, P["wo"], engine=engine)                                      # [B*N,C]
@@ -87,7 +103,10 @@ def attn_backward(saved, P, dout, H, W, heads, need_dx=True, engine=None, target
                          wq=dwq, wk=dwk, wv=dwv, wo=dwo, bo=dbo)
     dxf, dws, dbs, dtemp = ops.slice_bwd_points(xf, dy, P["ws"], P["bs"], temp, o, ds, dn, B, N, heads, D, M,
                                                 clamp=structured, into=t("ws", "bs", "temperature"), engine=engine)
-    if structured:
+    if structured and depth is not None:
+        dxn, dwx, dbx, dwf, dbf = ops.conv3x3x3x2_bwd(dxf, xn, P["wx"], P["wf"], H, Wm, depth, need_dx=need_dx,
+                                                      engine=engine, into=t("wx", "bx", "wf", "bf"))
+    elif structured:
         dxn, dwx, dbx, dwf, dbf = ops.conv3x3x2_bwd(dxf, xn, P["wx"], P["wf"], H, W, need_dx=need_dx, engine=engine,
                                                     into=t("wx", "bx", "wf", "bf"))
     else:
@@ -117,7 +136,7 @@ ATTN_KEYS = ("temperature", "wx", "bx", "wf", "bf", "ws", "bs", "wq", "wk", "wv"
 
 
 class PhysicsAttentionFn(Function):
-    """out = to_out(deslice(attn(slice(conv(xn))))) (+ res)."""
+    """out = to_out(deslice(attn(slice(conv(xn))))) (+ res).  H / W: mesh geometry as for attn_forward."""
 
     @staticmethod
     def forward(ctx, xn, res, H, W, heads, engine, *params):
@@ -224,7 +243,8 @@ class HeadFn(Function):
 
 class AttnBranchFn(Function):
     """fx + Attn(LayerNorm(fx)) as ONE autograd node (Transolver_block.forward, …_2D.py:70): the residual
-    gradient is folded into the LayerNorm backward kernel (`dres`), so no separate elementwise add runs."""
+    gradient is folded into the LayerNorm backward kernel (`dres`), so no separate elementwise add runs.
+    H / W: mesh geometry as for attn_forward (W = (width, depth) on the 3-D structured mesh)."""
 
     @staticmethod
     def forward(ctx, fx, ln_w, ln_b, H, W, heads, engine, *params):
@@ -234,7 +254,7 @@ class AttnBranchFn(Function):
         ln_w, ln_b = ln_w.detach().contiguous(), ln_b.detach().contiguous()
         P = dict(zip(ATTN_KEYS, (p.detach().contiguous() for p in params)))
         # bf16 engines on fp32 storage: LayerNorm writes the conv's operand planes directly (no fp32 xn, no pre-pass)
-        ctx.planes = (H is not None and fx2d.dtype == torch.float32 and len(shp) == 3
+        ctx.planes = (H is not None and mesh_extent(W)[1] is None and fx2d.dtype == torch.float32 and len(shp) == 3
                       and ops.conv_planes_mask(shp[0], H, W, shp[2], engine) == 7)
         if ctx.planes:
             xnp, mean, rstd = ops.layernorm_fwd_planes(fx2d, ln_w, ln_b, engine)

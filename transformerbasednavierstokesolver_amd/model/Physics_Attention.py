@@ -56,3 +56,58 @@ class Physics_Attention_Structured_Mesh_2D(nn.Module):
             raise RuntimeError(f"shape '[{B}, {self.H}, {self.W}, {C}]' is invalid for input of size {x.numel()}")
         return Fn.physics_attention(x, residual, self.H, self.W, self.heads, self.attention_parameters(),
                                     engine=self.engine)
+
+
+class Physics_Attention_Structured_Mesh_3D(nn.Module):
+    """Physics-Attention for structured 3-D meshes: the reference class of the same name (model/Physics_Attention.py,
+    Physics_Attention_Structured_Mesh_3D) with the same constructor, parameter names and shapes (`in_project_x.weight`
+    [C, C, 3, 3, 3]) and `forward(x[B,N,C]) -> [B,N,C]`, N = H*W*D with point n = (h*W + w)*D + d.  Both Conv3d
+    projections run as one 27-tap implicit GEMM of libpa2d (pa2d_conv3x3x3x2_*); slice, token attention, de-slice and
+    to_out are the kernels of the 2-D class.  The nn.Conv3d / nn.Linear sub-modules are parameter containers only."""
+
+    def __init__(self, dim, heads=8, dim_head=64, dropout=0., slice_num=32, H=32, W=32, D=32, kernel=3):
+        super().__init__()
+        inner_dim = dim_head * heads
+        if kernel != 3:
+            raise NotImplementedError("the HIP path implements the 3x3x3 projection of the reference")
+        if inner_dim != dim:
+            raise NotImplementedError("HIP path needs heads*dim_head == dim (true for every reference model)")
+        self.dim_head = dim_head
+        self.heads = heads
+        self.scale = dim_head ** -0.5
+        self.softmax = nn.Softmax(dim=-1)
+        self.dropout = nn.Dropout(dropout)
+        self.temperature = nn.Parameter(torch.ones([1, heads, 1, 1]) * 0.5)
+        self.H = H
+        self.W = W
+        self.D = D
+        self.engine = None      # GEMM engine (None = pa2d_default_engine()); TransolverBase.set_engine sets it
+
+        self.in_project_x = nn.Conv3d(dim, inner_dim, kernel, 1, kernel // 2)
+        self.in_project_fx = nn.Conv3d(dim, inner_dim, kernel, 1, kernel // 2)
+        self.in_project_slice = nn.Linear(dim_head, slice_num)
+        torch.nn.init.orthogonal_(self.in_project_slice.weight)
+        self.to_q = nn.Linear(dim_head, dim_head, bias=False)
+        self.to_k = nn.Linear(dim_head, dim_head, bias=False)
+        self.to_v = nn.Linear(dim_head, dim_head, bias=False)
+        self.to_out = nn.Sequential(nn.Linear(inner_dim, dim), nn.Dropout(dropout))
+
+    @property
+    def mesh_w(self):
+        """The geometry argument `W` of the functional layer: (width, depth) selects the 3x3x3 conv."""
+        return (self.W, self.D)
+
+    def attention_parameters(self):
+        return (self.temperature, self.in_project_x.weight, self.in_project_x.bias, self.in_project_fx.weight,
+                self.in_project_fx.bias, self.in_project_slice.weight, self.in_project_slice.bias,
+                self.to_q.weight, self.to_k.weight, self.to_v.weight, self.to_out[0].weight, self.to_out[0].bias)
+
+    def forward(self, x, residual=None):
+        """x: [B, N=H*W*D, C].  `residual` (extension): added in the to_out epilogue (block uses it)."""
+        if self.training and self.dropout.p > 0:
+            raise NotImplementedError("dropout > 0 is not implemented in the HIP path; refusing to silently ignore it")
+        B, N, C = x.shape
+        if N != self.H * self.W * self.D:
+            raise RuntimeError(f"shape '[{B}, {self.H}, {self.W}, {self.D}, {C}]' is invalid for input of size {x.numel()}")
+        return Fn.physics_attention(x, residual, self.H, self.mesh_w, self.heads, self.attention_parameters(),
+                                    engine=self.engine)

@@ -75,8 +75,10 @@ class BlockBase(nn.Module):
         if attn.training and attn.dropout.p > 0:
             raise NotImplementedError("dropout > 0 is not implemented in the HIP path; refusing to ignore it")
         # each residual branch (LayerNorm -> sub-layer -> + fx) is one autograd node
-        fx = Fn.attn_branch(fx, self.ln_1.weight, self.ln_1.bias, getattr(attn, "H", None), getattr(attn, "W", None),
-                            attn.heads, attn.attention_parameters(), engine=self.engine)
+        # mesh geometry: H, and W (2-D) or (W, D) (3-D attention's `mesh_w`); the irregular mesh has neither
+        fx = Fn.attn_branch(fx, self.ln_1.weight, self.ln_1.bias, getattr(attn, "H", None),
+                            getattr(attn, "mesh_w", getattr(attn, "W", None)), attn.heads, attn.attention_parameters(),
+                            engine=self.engine)
         pre, post = mlp.linear_pre[0], mlp.linear_post
         if mlp.linears or pre.weight.shape[1] % 4:      # generic MLP shapes keep the unfused route
             fx = mlp(Fn.layer_norm(fx, self.ln_2.weight, self.ln_2.bias), residual=fx)

@@ -1,6 +1,7 @@
 """Model registry — the reference's plug-in boundary: `get_model(args)` maps `args.model` to a MODULE
 exposing `Model` (reference model_dict.py).  The structured-mesh-2D family is the hot path;
-the irregular-mesh family is its §8(f)-2 widening; the other two reference families are not built."""
+the irregular-mesh family is its §8(f)-2 widening.  The structured-mesh-3D family is built
+(model/Transolver_Structured_Mesh_3D.py) but not registered yet; the encoder family is not built."""
 from .model import Transolver_Irregular_Mesh, Transolver_Structured_Mesh_2D
 
 REGISTRY = {
@@ -12,6 +13,9 @@ NOT_BUILT = ("Transolver_Structured_Mesh_3D", "Transolver_Structured_Mesh2D_Enco
 
 def get_model(args):
     name = args.model
+    if name == "Transolver_Structured_Mesh_3D":
+        raise KeyError(f"{name}: not registered yet; import it as "
+                       "transformerbasednavierstokesolver_amd.model.Transolver_Structured_Mesh_3D (INTEGRATION.md)")
     if name in NOT_BUILT:
         raise KeyError(f"{name}: not part of the MI355X-native build (DESIGN.md §7)")
     return REGISTRY[name]     # KeyError for unknown names, like the reference's dict lookup

@@ -237,7 +237,8 @@ def linear_bwd_weight(dy, x2d, want_bias=True, engine=None, into=None):
 class _FrozenScope:
     """Book-keeping of one `weights_frozen()` scope: packs made inside it, keyed by (weights, dims, direction,
     engine) — the pack layout depends on the engine, which is part of the key, so models on different engines
-    can share a scope."""
+    can share a scope.  The dims include the depth of a 3-D mesh (None for the 3x3 conv): a 2-D and a 3-D model in
+    one scope never share a pack."""
 
     def __init__(self):
         self.packs = {}
@@ -246,8 +247,8 @@ class _FrozenScope:
     def refresh(self):
         """Re-pack every entry in place (same device pointers): called before replaying a hipGraph that was captured
         inside this scope, so the graph's conv launches always see the current weights."""
-        for (_, _, B, H, W, Cc, direction, eng), (wx, wf, pack) in self.packs.items():
-            _make_pack(wx, wf, pack, B, H, W, Cc, direction, eng)
+        for (_, _, B, H, W, depth, Cc, direction, eng), (wx, wf, pack) in self.packs.items():
+            _make_pack(wx, wf, pack, B, H, W, Cc, direction, eng, depth)
         for (_, transposed, N, K, eng), (w, img) in self.images.items():
             _make_image(w, transposed, img, N, K, eng)
 
@@ -290,9 +291,13 @@ def _lin_image(w, transposed, N, K, eng, nbytes):
     return hit[1].data_ptr()
 
 
-def _make_pack(wx, wf, pack, B, H, W, Cc, direction, eng):
-    """eng = ENGINE_BF16S: the pack of the bf16-storage conv entry points (always the bf16 kernels' layout)."""
-    if eng == ENGINE_BF16S:
+def _make_pack(wx, wf, pack, B, H, W, Cc, direction, eng, depth=None):
+    """eng = ENGINE_BF16S: the pack of the bf16-storage conv entry points (always the bf16 kernels' layout);
+    depth (not None): the 3x3x3 conv of a [B, H, W, depth] mesh."""
+    if depth is not None:
+        _lib.check(_L().pa2d_conv3x3x3x2_pack(_p(wx), _p(wf), pack.data_ptr(), pack.numel(), B, H, W, depth, Cc, direction,
+                                              eng, _stream()), "conv3x3x3x2_pack")
+    elif eng == ENGINE_BF16S:
         _lib.check(_L().pa2d_conv3x3x2_pack_bf16(_p(wx), _p(wf), pack.data_ptr(), pack.numel(), Cc, direction, _stream()),
                    "conv3x3x2_pack_bf16")
     else:
@@ -300,17 +305,17 @@ def _make_pack(wx, wf, pack, B, H, W, Cc, direction, eng):
                                             _stream()), "conv3x3x2_pack")
 
 
-def _conv_pack(wx, wf, B, H, W, Cc, direction, eng):
+def _conv_pack(wx, wf, B, H, W, Cc, direction, eng, depth=None):
     """Pack pointer for the active scope (0 = let the conv call pack into its workspace)."""
     if not _frozen:
         return 0
     scope = _frozen[-1]
-    key = (wx.data_ptr(), wf.data_ptr(), B, H, W, Cc, direction, eng)
+    key = (wx.data_ptr(), wf.data_ptr(), B, H, W, depth, Cc, direction, eng)
     hit = scope.packs.get(key)
     if hit is None:
-        nb = _L().pa2d_conv3x3x2_pack_bytes(Cc)
+        nb = _L().pa2d_conv3x3x2_pack_bytes(Cc) if depth is None else _L().pa2d_conv3x3x3x2_pack_bytes(Cc)
         pack = torch.empty(nb, dtype=torch.uint8, device=wx.device)
-        _make_pack(wx, wf, pack, B, H, W, Cc, direction, eng)
+        _make_pack(wx, wf, pack, B, H, W, Cc, direction, eng, depth)
         hit = scope.packs[key] = (wx, wf, pack)
     return hit[2].data_ptr()
 
@@ -359,6 +364,51 @@ def conv3x3x2_bwd(dout, xn, wx, wf, H, W, need_dx=True, engine=None, into=None):
     _lib.check(_L().pa2d_conv3x3x2_bwd(_p(dout), _p(xn), _p(wx), _p(wf), _p(dxn), _p(dwx), _p(dbx), _p(dwf), _p(dbf),
                                        pre, ws.data_ptr(), nb, B, H, W, Cc, acc, eng, _stream(), e0, e1),
                "conv3x3x2_bwd")
+    return dxn, dwx, dbx, dwf, dbf
+
+
+def _conv3d_engine(engine, *acts):
+    """fp32-I/O ABI engine of the 3x3x3 conv; bf16 storage has no 3-D kernels and is refused, never converted."""
+    if _chk_act(*acts) or resolve_engine(engine) == ENGINE_BF16S:
+        raise NotImplementedError("bf16 storage (engine 'bf16s') is not implemented for the 3-D structured mesh")
+    return _abi_engine(engine)
+
+
+def conv3x3x3x2_fwd(xn, wx, bx, wf, bf, H, W, depth, engine=None):
+    """The two Conv3d(C, C, 3, 1, 1) projections of the 3-D structured mesh: xn [B, N = H*W*depth, C] (point
+    n = (h*W + w)*depth + d) -> [B, N, 2C] = [x_mid | fx_mid]; weights [C, C, 3, 3, 3]."""
+    _chk(wx, bx, wf, bf)
+    eng = _conv3d_engine(engine, xn)
+    B, N, Cc = xn.shape
+    if N != H * W * depth:
+        raise ValueError(f"conv3x3x3x2_fwd: N = {N} is not H*W*depth = {H}*{W}*{depth}")
+    out = torch.empty(B, N, 2 * Cc, dtype=xn.dtype, device=xn.device)
+    pre = _conv_pack(wx, wf, B, H, W, Cc, 0, eng, depth)
+    e0, e1 = _events("conv")
+    nb = _L().pa2d_conv3x3x3x2_fwd_workspace(B, H, W, depth, Cc, eng)
+    ws = _ws(nb, xn)
+    _lib.check(_L().pa2d_conv3x3x3x2_fwd(_p(xn), _p(wx), _p(bx), _p(wf), _p(bf), _p(out), pre, ws.data_ptr(), nb,
+                                         B, H, W, depth, Cc, eng, _stream(), e0, e1), "conv3x3x3x2_fwd")
+    return out
+
+
+def conv3x3x3x2_bwd(dout, xn, wx, wf, H, W, depth, need_dx=True, engine=None, into=None):
+    """Backward of conv3x3x3x2_fwd: returns (dxn, dwx, dbx, dwf, dbf); `into` = (dwx, dbx, dwf, dbf) buffers to
+    accumulate into."""
+    _chk(wx, wf)
+    eng = _conv3d_engine(engine, dout, xn)
+    B, N, Cc = xn.shape
+    if N != H * W * depth:
+        raise ValueError(f"conv3x3x3x2_bwd: N = {N} is not H*W*depth = {H}*{W}*{depth}")
+    dxn = torch.empty_like(xn) if need_dx else None
+    (dwx, dbx, dwf, dbf), acc = _grad_outputs(into, (wx.shape, (Cc,), wf.shape, (Cc,)), xn)
+    pre = _conv_pack(wx, wf, B, H, W, Cc, 1, eng, depth) if need_dx else 0
+    e0, e1 = _events("conv") if need_dx else (0, 0)
+    nb = _L().pa2d_conv3x3x3x2_workspace(B, H, W, depth, Cc, eng)
+    ws = _ws(nb, xn)
+    _lib.check(_L().pa2d_conv3x3x3x2_bwd(_p(dout), _p(xn), _p(wx), _p(wf), _p(dxn), _p(dwx), _p(dbx), _p(dwf), _p(dbf),
+                                         pre, ws.data_ptr(), nb, B, H, W, depth, Cc, acc, eng, _stream(), e0, e1),
+               "conv3x3x3x2_bwd")
     return dxn, dwx, dbx, dwf, dbf
 
 

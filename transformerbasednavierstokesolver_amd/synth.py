@@ -12,7 +12,8 @@ from __future__ import annotations
 
 import numpy as np
 
-__all__ = ["darcy_batch", "DARCY_CONFIG", "make_config", "state_dict_spec", "synth_state_dict", "synth_ns_fields", "ns_batch",
+__all__ = ["darcy_batch", "DARCY_CONFIG", "make_config", "state_dict_spec", "synth_state_dict", "synth_state_dict_from_spec",
+           "synth_ns_fields", "ns_batch",
            "meshgrid_pos", "NS_CONFIG", "NS_SMALL_CONFIG", "TINY_CONFIG"]
 
 
@@ -143,6 +144,55 @@ def synth_state_dict(cfg, seed=0, wild_temperature=False):
             v = rng.uniform(0.0, 1.0, size=shape) / shape[0]
         else:  # pragma: no cover
             raise KeyError(kind)
+        out[key] = np.ascontiguousarray(v, dtype=np.float32)
+    return out
+
+
+def spec_kind(key, shape):
+    """Kind (as in state_dict_spec) of a state_dict entry of any Transolver family, from its name and shape."""
+    if key.endswith("temperature"):
+        return "temperature"
+    if key == "placeholder":
+        return "placeholder"
+    if key.endswith(".bias"):
+        return "bias"
+    if ".ln_" in key:
+        return "ln_w"
+    if key.endswith(("to_q.weight", "to_k.weight")):
+        return "qk_w"
+    if key.endswith("in_project_slice.weight"):
+        return "slice_w"
+    return "conv_w" if len(shape) > 2 else "lin_w"
+
+
+def synth_state_dict_from_spec(spec, seed=0, wild_temperature=False):
+    """synth_state_dict for an explicit [(key, shape), ...] list (e.g. a model's state_dict order): the same kinds and
+    scales, a conv weight [C_out, C_in, k...] scaled by 1/sqrt(C_in * taps) whatever its number of kernel axes."""
+    rng = np.random.default_rng(seed)
+    out = {}
+    for key, shape in spec:
+        shape = tuple(int(s) for s in shape)
+        kind = spec_kind(key, shape)
+        if kind == "lin_w":
+            v = rng.standard_normal(shape) / np.sqrt(shape[1])
+        elif kind == "qk_w":
+            v = rng.standard_normal(shape) * (1.5 / np.sqrt(shape[1]))
+        elif kind == "slice_w":
+            v = rng.standard_normal(shape) * (1.0 / np.sqrt(shape[1]))
+        elif kind == "conv_w":
+            v = rng.standard_normal(shape) / np.sqrt(float(np.prod(shape[1:])))
+        elif kind == "bias":
+            v = 0.1 * rng.standard_normal(shape)
+        elif kind == "ln_w":
+            v = 1.0 + 0.1 * rng.standard_normal(shape)
+        elif kind == "temperature":
+            if wild_temperature:
+                pool = np.array([0.03, 0.5, 7.0, 0.25, 1.5, 0.1, 5.0, 0.8])
+                v = np.resize(pool, shape[1]).reshape(shape)
+            else:
+                v = rng.uniform(0.3, 1.2, size=shape)
+        else:
+            v = rng.uniform(0.0, 1.0, size=shape) / shape[0]
         out[key] = np.ascontiguousarray(v, dtype=np.float32)
     return out
 
