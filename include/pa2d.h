@@ -198,6 +198,35 @@ int pa2d_slice_bwd_points(const float* xm, long long ldx, const float* fm, long 
                           size_t ws_bytes, int B, int N, int heads, int D, int M, int clamp_temperature,
                           int accumulate, int engine, pa2d_stream_t stream, void* ev_start, void* ev_stop);
 
+/* ---- auto-encoder attention (reference Physics_Attention_Structured_Mesh_2D_Auto_Encoder: encode caches the softmax
+ * slice weights, reconstruct_fx / decode project them with a Linear(M, M) and de-slice with the projected tensor).
+ * Exact fp32 (VALU FMA) whatever engine the rest of the model uses; no engine argument.  D in {8,16,32,64}, 1 <= M <= 128,
+ * N >= 1; B = 0 is a no-op (reductions zero-filled when accumulate = 0); an operand past 4 GiB returns
+ * PA2D_ERR_UNSUPPORTED before any launch.  ev_start / ev_stop as for the slice stages.
+ * slice weights: sw[B,heads,N,M] = softmax_m((x_mid[b,n,h*D:(h+1)*D] . ws[m,:] + bs[m]) / t_h), t_h = temperature[h]
+ * (clamped to [0.1, 5] with clamp_temperature = 1); x_mid rows of pitch ldx (ldx % 4 == 0, 16-byte aligned: the column view
+ * [x_mid | fx_mid] of the conv output has ldx = 2C). */
+int pa2d_slice_weights_fwd(const float* xm, long long ldx, const float* ws, const float* bs, const float* temperature,
+                           float* sw, int B, int N, int heads, int D, int M, int clamp_temperature, pa2d_stream_t stream,
+                           void* ev_start, void* ev_stop);
+/* backward from dsw [B,heads,N,M] (the weights are recomputed from x_mid): dxm (may be NULL) a plain store of rows of pitch
+ * lddx; dws [M,D], dbs [M], dtemperature [heads] reduced over (b, h, n), (+)= per `accumulate` (clamp mask applied) */
+size_t pa2d_slice_weights_bwd_workspace(int B, int N, int heads, int D, int M);
+int pa2d_slice_weights_bwd(const float* xm, long long ldx, const float* ws, const float* bs, const float* temperature,
+                           const float* dsw, float* dxm, long long lddx, float* dws, float* dbs, float* dtemperature,
+                           void* ws_buf, size_t ws_bytes, int B, int N, int heads, int D, int M, int clamp_temperature,
+                           int accumulate, pa2d_stream_t stream, void* ev_start, void* ev_stop);
+/* de-slice with explicit weights: y[b, n, h*D + d] = sum_g w[b,h,n,g] code[b,h,g,d] (einsum "bhgc,bhng->bhnc" and the
+ * rearrange to [B,N,(h d)]); code [B,heads,M,D], w [B,heads,N,M] contiguous, y rows of pitch ldy */
+int pa2d_deslice_weights_fwd(const float* code, const float* w, float* y, long long ldy, int B, int N, int heads, int D,
+                             int M, pa2d_stream_t stream, void* ev_start, void* ev_stop);
+/* dcode [B,heads,M,D] (reduced over n; overwritten) and dw [B,heads,N,M]; either may be NULL (a frozen encoder's weights,
+ * a code that needs no gradient); the workspace is needed for dcode only */
+size_t pa2d_deslice_weights_bwd_workspace(int B, int N, int heads, int D, int M);
+int pa2d_deslice_weights_bwd(const float* code, const float* w, const float* dy, long long lddy, float* dcode, float* dw,
+                             void* ws_buf, size_t ws_bytes, int B, int N, int heads, int D, int M, pa2d_stream_t stream,
+                             void* ev_start, void* ev_stop);
+
 /* ---- output head mlp2 = nn.Linear(C, out_dim), out_dim <= 8 (…_2D.py:66,73) */
 int pa2d_head_fwd(const float* xn, const float* w, const float* b, float* y, int rows, int C, int out_dim,
                   pa2d_stream_t stream);

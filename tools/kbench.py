@@ -2,6 +2,9 @@
 """Per-stage micro-benchmark at the bench shapes (B=32, N=4096, C=256, 8 heads, M=64): times each
 libpa2d stage alone with events on the launch stream and prints achieved TFLOP/s or GB/s.
 The conv3d_* stages time the 3x3x3 conv of the structured 3-D mesh on a --B3 x --S3^3 mesh (default 1 x 32^3).
+The ae_* stages run at auto_encoder.py's shape (--AB x 64 x 64, C=64, 4 heads, M=--AM, 3 layers): the four kernels of the
+auto-encoder attention (slice weights forward / backward, de-slice with explicit weights forward / backward; GB/s and the
+fraction of the 8 TB/s HBM peak) and one whole auto-encoder training iteration (autoencoder_train_step, FusedAdamW).
 Usage: python tools/kbench.py [--only conv_fwd,linear_fwd,...] [--iters 10] [--B 32]"""
 import argparse
 import os
@@ -38,6 +41,8 @@ def main():
     ap.add_argument("--heads", type=int, default=8)
     ap.add_argument("--B3", type=int, default=1, help="batch of the conv3d_* stages (3x3x3 conv, S3^3 mesh, C channels)")
     ap.add_argument("--S3", type=int, default=32, help="edge of the cubic mesh of the conv3d_* stages")
+    ap.add_argument("--AB", type=int, default=8, help="batch of the ae_* stages (auto_encoder.py's shape)")
+    ap.add_argument("--AM", type=int, default=32, help="slices of the ae_* stages")
     args = ap.parse_args()
     E = ops.resolve_engine(args.engine)
     print(f"engine {E}  B={args.B} H={args.H} W={args.W} C={args.C} M={args.M}", flush=True)
@@ -104,12 +109,38 @@ def main():
         tests["ln_fwd_planes"] = (lambda: ops.layernorm_fwd_planes(x2d, gamma, beta, E), (1.0 + nt * 0.5) * R * C * 4, "GB")
         tests["slice_bwd_planes"] = (lambda: ops.slice_bwd_points_planes(xf, dy3, ws, bs, temp, o, ds, dn, nrm, B, N, heads, D, M, E),
                                      (3.0 + nt * 1.0) * R * C * 4, "GB")
+    # auto-encoder attention at auto_encoder.py's shape: [AB, 4096, 64], 4 heads (D = 16), AM slices
+    AB, AN, AC, AH, AM = args.AB, 64 * 64, 64, 4, args.AM
+    AD = AC // AH
+    axf = rn(AB, AN, 2 * AC)
+    axm = axf[:, :, :AC]
+    aws, abs_, atemp = rn(AM, AD) * 0.25, rn(AM) * 0.1, torch.full((AH,), 0.5, device=dev)
+    asw = ops.slice_weights_fwd(axm, aws, abs_, atemp, AH)
+    adsw, acode, ady = rn(AB, AH, AN, AM), rn(AB, AH, AM, AD), rn(AB, AN, AC)
+    swb, actb = 4.0 * AB * AH * AN * AM, 4.0 * AB * AN * AC          # bytes of one [B,h,N,M] / one [B,N,C] tensor
+    tests["ae_sw_fwd"] = (lambda: ops.slice_weights_fwd(axm, aws, abs_, atemp, AH), actb + swb, "HBM")
+    tests["ae_sw_bwd"] = (lambda: ops.slice_weights_bwd(axm, aws, abs_, atemp, adsw), 2 * actb + swb, "HBM")
+    tests["ae_dsw_fwd"] = (lambda: ops.deslice_weights_fwd(acode, asw), actb + swb, "HBM")
+    tests["ae_dsw_bwd"] = (lambda: ops.deslice_weights_bwd(acode, asw, ady), actb + 2 * swb, "HBM")
+    if only & {"ae_iter"}:
+        from transformerbasednavierstokesolver_amd import harness
+        from transformerbasednavierstokesolver_amd.model.Transolver_Structured_Mesh2D_Encoder import Model as AEModel
+        from transformerbasednavierstokesolver_amd.optim import FusedAdamW
+        torch.manual_seed(0)
+        ae = AEModel(space_dim=2, n_layers=3, n_hidden=AC, n_head=AH, fun_dim=1, out_dim=1, slice_num=AM, H=64, W=64)
+        ae = ae.to(dev).set_engine(E)
+        aopt = FusedAdamW(ae.parameters(), lr=1e-3, weight_decay=1e-5, max_grad_norm=1.0)
+        apos, afx = torch.rand(AB, AN, 2, device=dev), rn(AB, AN, 1)
+        tests["ae_iter"] = (lambda: harness.autoencoder_train_step(ae, aopt, None, apos, afx, grad_sync=aopt.sync), 0, "us")
     for name, (fn, work, unit) in tests.items():
         if only and name not in only:
             continue
         ms = timeit(fn, args.iters)
         if unit == "TF":
             print(f"{name:20s} {ms:9.3f} ms  {work / ms / 1e9:8.1f} TFLOP/s  ({work / ms / 1e9 / 157.3:.3f} of fp32 MFMA peak)", flush=True)
+        elif unit == "HBM":
+            print(f"{name:20s} {ms * 1e3:9.1f} us  {work / ms / 1e6:8.0f} GB/s  ({work / ms / 1e9 / 8.0:.3f} of 8 TB/s HBM)",
+                  flush=True)
         elif unit == "GB":
             print(f"{name:20s} {ms:9.3f} ms  {work / ms / 1e6:8.0f} GB/s algorithmic", flush=True)
         else:

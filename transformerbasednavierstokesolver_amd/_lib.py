@@ -57,6 +57,13 @@ SIGNATURES = {
     "pa2d_slice_bwd_workspace": (_sz, [_i, _i, _i, _i, _i]),
     "pa2d_slice_bwd_points": (_i, [_f, _ll, _f, _ll, _f, _ll, _f, _f, _f, _f, _f, _f, _f, _ll, _f, _ll, _f, _f, _f,
                                    _f, _sz, _i, _i, _i, _i, _i, _i, _i, _i, _st, _st, _st]),
+    "pa2d_slice_weights_fwd": (_i, [_f, _ll, _f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _st, _st, _st]),
+    "pa2d_slice_weights_bwd_workspace": (_sz, [_i, _i, _i, _i, _i]),
+    "pa2d_slice_weights_bwd": (_i, [_f, _ll, _f, _f, _f, _f, _f, _ll, _f, _f, _f, _f, _sz, _i, _i, _i, _i, _i, _i, _i, _st,
+                                    _st, _st]),
+    "pa2d_deslice_weights_fwd": (_i, [_f, _f, _f, _ll, _i, _i, _i, _i, _i, _st, _st, _st]),
+    "pa2d_deslice_weights_bwd_workspace": (_sz, [_i, _i, _i, _i, _i]),
+    "pa2d_deslice_weights_bwd": (_i, [_f, _f, _f, _ll, _f, _f, _f, _sz, _i, _i, _i, _i, _i, _st, _st, _st]),
     "pa2d_head_fwd": (_i, [_f, _f, _f, _f, _i, _i, _i, _st]),
     "pa2d_head_bwd_workspace": (_sz, [_i, _i, _i]),
     "pa2d_head_bwd": (_i, [_f, _f, _f, _f, _f, _f, _f, _sz, _i, _i, _i, _i, _st]),

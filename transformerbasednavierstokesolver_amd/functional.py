@@ -376,3 +376,145 @@ class RelL2Fn(Function):
 
 def rel_l2(pred, y):
     return RelL2Fn.apply(pred, y)
+
+
+# ------------------------------------------------------------------------------ auto-encoder attention
+# Physics_Attention_Structured_Mesh_2D_Auto_Encoder (reference model/Physics_Attention.py): `encode` returns the slice
+# tokens after token attention (the code) and caches the softmax slice weights; `reconstruct_fx` / `decode` project the
+# cached weights with Linear(M, M) and de-slice the code with them.  The pieces are separate autograd nodes because the
+# cached weights are module state that the caller may read, replace or project again between the calls.
+ENC_KEYS = ("temperature", "wx", "bx", "wf", "bf", "ws", "bs", "wq", "wk", "wv")
+
+
+class EncodeFn(Function):
+    """xn [B,N,C] (already layer-normed) -> (code [B,heads,M,D], x_mid [B,N,C]): the 3x3 conv pair, slice scatter and
+    token attention of the 2-D structured attention.  x_mid is the column view of the conv output (row pitch 2C) that the
+    slice-weight node reads.  Backward: token attention backward from dcode, the slice backward with a zero de-slice
+    gradient, the x_mid gradient of the slice-weight node added to its x_mid half, then the conv backward."""
+
+    @staticmethod
+    def forward(ctx, xn, H, W, heads, engine, *params):
+        P = dict(zip(ENC_KEYS, (p.detach().contiguous() for p in params)))
+        xn = xn.detach().contiguous()
+        B, N, C = xn.shape
+        D = C // heads
+        M = P["ws"].shape[0]
+        temp = P["temperature"].reshape(heads).contiguous()
+        xf = ops.conv3x3x2_fwd(xn, P["wx"], P["bx"], P["wf"], P["bf"], H, W, engine=engine)       # [B,N,2C]
+        spart, npart = ops.slice_scatter(xf, 2 * C, 0, xf, 2 * C, C, P["ws"], P["bs"], temp, B, N, heads, D, M,
+                                         clamp=True, engine=engine)
+        s, nrm, o = ops.token_attn_fwd(spart, npart, P["wq"], P["wk"], P["wv"])
+        ctx.P, ctx.saved, ctx.geom, ctx.params = P, (xn, xf, s, nrm, o, temp), (H, W, heads, engine), params
+        return o.view(B, heads, M, D), xf[:, :, :C]
+
+    @staticmethod
+    def backward(ctx, dcode, dxm):
+        H, W, heads, engine = ctx.geom
+        P = ctx.P
+        xn, xf, s, nrm, o, temp = ctx.saved
+        B, N, C = xn.shape
+        D = C // heads
+        M = P["ws"].shape[0]
+        tg = grad_targets(ctx.params)
+        T = None if tg is None else dict(zip(ENC_KEYS, tg))
+        t = (lambda *ks: tuple(T[k] for k in ks)) if T is not None else (lambda *ks: None)
+        dop = (dcode.contiguous() if dcode is not None else torch.zeros_like(o)).view(B * heads, 1, M, D)
+        ds, dn, dwq, dwk, dwv = ops.token_attn_bwd(s, nrm, P["wq"], P["wk"], P["wv"], dop, into=t("wq", "wk", "wv"))
+        dy0 = torch.zeros(B, N, C, dtype=torch.float32, device=xn.device)
+        dxf, dws, dbs, dtemp = ops.slice_bwd_points(xf, dy0, P["ws"], P["bs"], temp, o, ds, dn, B, N, heads, D, M,
+                                                    clamp=True, into=t("ws", "bs", "temperature"), engine=engine)
+        if dxm is not None:
+            dxf[:, :, :C] += dxm
+        dxn, dwx, dbx, dwf, dbf = ops.conv3x3x2_bwd(dxf, xn, P["wx"], P["wf"], H, W, need_dx=ctx.needs_input_grad[0],
+                                                    engine=engine, into=t("wx", "bx", "wf", "bf"))
+        if T is not None:
+            return (dxn, None, None, None, None) + tuple(None for _ in ENC_KEYS)
+        g = dict(temperature=dtemp.view(1, heads, 1, 1), wx=dwx, bx=dbx, wf=dwf, bf=dbf, ws=dws, bs=dbs, wq=dwq, wk=dwk,
+                 wv=dwv)
+        return (dxn, None, None, None, None) + tuple(g[k] for k in ENC_KEYS)
+
+
+class SliceWeightsFn(Function):
+    """sw [B,heads,N,M] = softmax((x_mid . Ws^T + bs) / clamp(temperature, 0.1, 5)) per head (pa2d_slice_weights_*)."""
+
+    @staticmethod
+    def forward(ctx, xm, temperature, ws, bs):
+        heads = temperature.numel()
+        ctx.params = (temperature, ws, bs)
+        temp = temperature.detach().reshape(heads).contiguous()
+        ws, bs = ws.detach().contiguous(), bs.detach().contiguous()
+        xm = xm.detach()
+        ctx.saved = (xm, temp, ws, bs)
+        return ops.slice_weights_fwd(xm, ws, bs, temp, heads)
+
+    @staticmethod
+    def backward(ctx, dsw):
+        xm, temp, ws, bs = ctx.saved
+        heads = temp.numel()
+        tg = grad_targets(ctx.params)
+        into = None if tg is None else (tg[1], tg[2], tg[0])
+        dxm, dws, dbs, dtemp = ops.slice_weights_bwd(xm, ws, bs, temp, dsw.contiguous(), need_dx=ctx.needs_input_grad[0],
+                                                     into=into)
+        return (dxm,) + _ret(tg, (dtemp.view(1, heads, 1, 1), dws, dbs))
+
+
+class DesliceWeightsFn(Function):
+    """y [B,N,heads*D] = einsum("bhgc,bhng->bhnc", code, w) rearranged to [B,N,(h d)] (pa2d_deslice_weights_*)."""
+
+    @staticmethod
+    def forward(ctx, code, w):
+        code, w = code.detach().contiguous(), w.detach().contiguous()
+        ctx.saved = (code, w)
+        return ops.deslice_weights_fwd(code, w)
+
+    @staticmethod
+    def backward(ctx, dy):
+        code, w = ctx.saved
+        return ops.deslice_weights_bwd(code, w, dy.contiguous(), need_dcode=ctx.needs_input_grad[0],
+                                       need_dw=ctx.needs_input_grad[1])
+
+
+class ToOutTwiceFn(Function):
+    """2 * to_out(y): the auto-encoder's last block adds reconstruct_fx(code) and decode(code), which are the same
+    to_out(deslice(code, P(sw))).  One GEMM with the weight and bias doubled (exact: every product and partial sum
+    scales by 2), so the result is bit for bit what the reference's sum is."""
+
+    @staticmethod
+    def forward(ctx, y, engine, w, b):
+        shp = y.shape
+        y2d = y.detach().reshape(-1, shp[-1]).contiguous()
+        w2, b2 = 2.0 * w.detach(), 2.0 * b.detach()
+        out, _ = ops.linear_fwd(y2d, w2, b2, engine=engine)
+        ctx.saved, ctx.shp, ctx.engine = (y2d, w2), shp, engine
+        return out.view(*shp[:-1], w.shape[0])
+
+    @staticmethod
+    def backward(ctx, dout):
+        y2d, w2 = ctx.saved
+        d2 = dout.reshape(-1, w2.shape[0]).contiguous()
+        dy = ops.linear_bwd_data(d2, w2, engine=ctx.engine).view(ctx.shp) if ctx.needs_input_grad[0] else None
+        dw = db = None
+        if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
+            dw, db = ops.linear_bwd_weight(d2, y2d, engine=ctx.engine)
+            dw.mul_(2.0)
+            db.mul_(2.0)
+        return dy, None, dw, db
+
+
+def attention_encode(xn, H, W, heads, params, engine=None):
+    """(code, x_mid) of the auto-encoder attention; `params` in ENC_KEYS order."""
+    return EncodeFn.apply(xn, H, W, heads, engine, *params)
+
+
+def slice_weights(xm, temperature, ws, bs):
+    return SliceWeightsFn.apply(xm, temperature, ws, bs)
+
+
+def deslice_weights(code, w):
+    """Public de-slice with an explicit weight tensor: code [B,heads,M,D], w [B,heads,N,M] -> [B,N,heads*D]
+    (the reference's einsum("bhgc,bhng->bhnc") + rearrange; for callers such as the SequenSolver drivers)."""
+    return DesliceWeightsFn.apply(code, w)
+
+
+def to_out_twice(y, w, b, engine=None):
+    return ToOutTwiceFn.apply(y, engine, w, b)

@@ -13,6 +13,7 @@ so they cannot be imported; these functions reproduce their loops:
   / LookAheadCurriculum         wrapper, BPTT through n chained calls) and :216-223 (curriculum)
   central_diff / darcy_loss     exp_darcy.py:59-68, 209-234 (decode, rel-L2 + 0.1 x derivative loss,
   / darcy_train_step            clip, step) — the large-N single-call iteration
+  autoencoder_train_step        auto_encoder.py:166-181 (the auto-encoder reconstructs its own input fx)
 """
 from __future__ import annotations
 
@@ -326,3 +327,24 @@ def darcy_train_step(model, optimizer, scheduler, x, fx, y, y_normalizer, dx, s,
     if scheduler is not None:
         scheduler.step()
     return loss.detach(), l2.detach(), deriv.detach()
+
+
+def autoencoder_train_step(model, optimizer, scheduler, x, fx, max_grad_norm=None, grad_sync=None):
+    """One auto_encoder.py:166-181 iteration of the structured 2-D auto-encoder (model/Transolver_Structured_Mesh2D_Encoder):
+    TestLoss(size_average=False) of model(x, fx) against fx itself, zero_grad, backward, [grad_sync], [clip], step,
+    [scheduler].  With `optim.FusedAdamW` pass `grad_sync=optimizer.sync` and put the clip threshold in the optimizer.
+    Returns the detached loss."""
+    bsz = x.shape[0]
+    with ops.weights_frozen():
+        im = model(x, fx=fx)
+        loss = TestLoss(size_average=False)(im.reshape(bsz, -1), fx.reshape(bsz, -1))
+        optimizer.zero_grad()
+        loss.backward()
+    if grad_sync is not None:
+        grad_sync()
+    if max_grad_norm is not None:
+        torch.nn.utils.clip_grad_norm_(model.parameters(), max_grad_norm)
+    optimizer.step()
+    if scheduler is not None:
+        scheduler.step()
+    return loss.detach()

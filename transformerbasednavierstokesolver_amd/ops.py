@@ -568,6 +568,82 @@ def slice_bwd_points(xf, dy, ws_w, bs, temperature, o, ds, dn, B, N, heads, D, M
     return dxf, dws, dbs, dtemp
 
 
+# ---------------------------------------------------------------------------------------------- auto-encoder attention
+# Materialised slice weights and the de-slice with explicit weights (pa2d_slice_weights_* / pa2d_deslice_weights_*): exact
+# fp32 on every engine, so these take no `engine`.
+def _row_view(x, heads, D):
+    """(pitch, B, N) of an fp32 [B, N, >= heads*D] activation whose rows may be strided (a column view of the conv
+    output): unit stride along the features, rows at a constant pitch."""
+    if not x.is_cuda:
+        raise RuntimeError("libpa2d ops need tensors on the GPU (no CPU fallback exists in this package)")
+    if x.dtype != torch.float32:
+        raise TypeError(f"libpa2d ops are fp32; got {x.dtype}")
+    B, N, Cx = x.shape
+    if Cx < heads * D or x.stride(2) != 1 or (B > 1 and x.stride(0) != N * x.stride(1)):
+        raise ValueError("need rows of unit feature stride at one constant pitch")
+    return x.stride(1), B, N
+
+
+def slice_weights_fwd(xm, ws_w, bs, temperature, heads, clamp=True):
+    """xm [B, N, >= C] (x_mid; rows may be strided); returns the softmax slice weights sw [B, heads, N, M]."""
+    _chk(ws_w, bs, temperature)
+    M, D = ws_w.shape
+    ldx, B, N = _row_view(xm, heads, D)
+    sw = torch.empty(B, heads, N, M, dtype=torch.float32, device=xm.device)
+    e0, e1 = _events("slice_weights")
+    _lib.check(_L().pa2d_slice_weights_fwd(_p(xm), ldx, _p(ws_w), _p(bs), _p(temperature), _p(sw), B, N, heads, D, M,
+                                           int(clamp), _stream(), e0, e1), "slice_weights_fwd")
+    return sw
+
+
+def slice_weights_bwd(xm, ws_w, bs, temperature, dsw, clamp=True, need_dx=True, into=None):
+    """Returns dxm [B, N, C] (None without need_dx), dws [M, D], dbs [M], dtemperature [heads]."""
+    _chk(ws_w, bs, temperature, dsw)
+    M, D = ws_w.shape
+    heads = temperature.numel()
+    ldx, B, N = _row_view(xm, heads, D)
+    if tuple(dsw.shape) != (B, heads, N, M):
+        raise ValueError(f"dsw must be [B, heads, N, M] = {(B, heads, N, M)}; got {tuple(dsw.shape)}")
+    dxm = torch.empty(B, N, heads * D, dtype=torch.float32, device=xm.device) if need_dx else None
+    (dws, dbs, dtemp), acc = _grad_outputs(into, (ws_w.shape, bs.shape, (heads,)), dsw)
+    nb = _L().pa2d_slice_weights_bwd_workspace(B, N, heads, D, M)
+    ws = _ws(nb, dsw)
+    e0, e1 = _events("slice_weights_bwd")
+    _lib.check(_L().pa2d_slice_weights_bwd(_p(xm), ldx, _p(ws_w), _p(bs), _p(temperature), _p(dsw), _p(dxm), heads * D,
+                                           _p(dws), _p(dbs), _p(dtemp), ws.data_ptr(), nb, B, N, heads, D, M, int(clamp),
+                                           acc, _stream(), e0, e1), "slice_weights_bwd")
+    return dxm, dws, dbs, dtemp
+
+
+def deslice_weights_fwd(code, w):
+    """code [B, heads, M, D], w [B, heads, N, M] -> y [B, N, heads*D] (einsum "bhgc,bhng->bhnc" + rearrange)."""
+    _chk(code, w)
+    B, heads, M, D = code.shape
+    N = w.shape[2]
+    if tuple(w.shape) != (B, heads, N, M):
+        raise ValueError(f"slice weights must be [B, heads, N, M] = {(B, heads, N, M)}; got {tuple(w.shape)}")
+    y = torch.empty(B, N, heads * D, dtype=torch.float32, device=code.device)
+    e0, e1 = _events("deslice_weights")
+    _lib.check(_L().pa2d_deslice_weights_fwd(_p(code), _p(w), _p(y), heads * D, B, N, heads, D, M, _stream(), e0, e1),
+               "deslice_weights_fwd")
+    return y
+
+
+def deslice_weights_bwd(code, w, dy, need_dcode=True, need_dw=True):
+    """Returns (dcode [B, heads, M, D] or None, dw [B, heads, N, M] or None)."""
+    _chk(code, w, dy)
+    B, heads, M, D = code.shape
+    N = w.shape[2]
+    dcode = torch.empty_like(code) if need_dcode else None
+    dw = torch.empty_like(w) if need_dw else None
+    nb = _L().pa2d_deslice_weights_bwd_workspace(B, N, heads, D, M) if need_dcode else 0
+    ws = _ws(nb, code) if need_dcode else None
+    e0, e1 = _events("deslice_weights_bwd")
+    _lib.check(_L().pa2d_deslice_weights_bwd(_p(code), _p(w), _p(dy), heads * D, _p(dcode), _p(dw), _p(ws), nb, B, N,
+                                             heads, D, M, _stream(), e0, e1), "deslice_weights_bwd")
+    return dcode, dw
+
+
 def head_fwd(xn2d, w, b):
     """y is always fp32 (the model output), whatever the storage type of the activations."""
     _chk(w, b)
