@@ -9,18 +9,24 @@ resident in HBM.  N>1: batch sharded across ranks (one process per GPU), one RCC
 the flat gradient bucket per iteration.  `python bench.py --gpus N` starts its own N ranks (the parent
 never touches the GPU); under `python -m torch.distributed.run` it uses the ranks it was given.
 
+A plain run (`--gpus N --steps K --warmup W`) does only what its headline needs: it builds the model and the data, runs
+W warm-up and K timed iterations, writes `--dump-outputs` if asked and prints the line.  `--full` adds, after the timed
+steps, everything else the benchmark measures: the parity sample and the CPU baseline, the time-folded,
+exact-fp32-engine, bf16-storage and Darcy legs and the graph-captured rollouts (each of them can still be left out with
+its --no-* option).
+
   value        = trajectories/s = N * 32 * K / (max over ranks of the time of K iterations), on the default
                  GEMM engine (fp32-accurate 3xbf16 split for the conv GEMMs, exact fp32 MFMA elsewhere; the engine
-                 the `-m gpu` parity suite runs); the exact-fp32-MFMA engine is measured beside it
+                 the `-m gpu` parity suite runs); with --full the exact-fp32-MFMA engine is measured beside it
                  (`fp32_exact_engine`)
   roofline     = the dominant kernel (implicit-GEMM 3x3 conv, forward and data-gradient launches have identical
                  FLOPs): algorithmic FLOPs per launch 2*(B*N)*(9C)*(2C) / average launch duration measured with
-                 HIP events recorded on the launch stream inside the timed region
+                 HIP events recorded on the launch stream inside the timed region (every run: no run of its own)
   roofline_hbm = the slice / de-slice kernels north_star names, same method, against the 8 TB/s HBM peak
-  darcy421     = BASELINE configs[4] geometry (421x421, 8 layers, C=128, M=128): exp_darcy.py iteration, with
-                 its own two rooflines
-  cpu_baseline = the CPU oracle (port of the reference, pinned to it by oracle/make_golden.py) on this host by
-                 the BASELINE.md §3 protocol (rank 0, N=1 only)
+  darcy421     = (--full) BASELINE configs[4] geometry (421x421, 8 layers, C=128, M=128): exp_darcy.py iteration,
+                 with its own two rooflines
+  cpu_baseline = (--full) the CPU oracle (port of the reference, pinned to it by oracle/make_golden.py) on this host
+                 by the BASELINE.md §3 protocol (rank 0, N=1 only)
 """
 from __future__ import annotations
 
@@ -416,7 +422,7 @@ def darcy_leg(rk, pool, engine, batch, steps):
     return out
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3, help="timed steps of the flagship workload (ms_per_step is their mean)")
@@ -424,6 +430,10 @@ def main():
     ap.add_argument("--batch-per-gpu", type=int, default=32)
     ap.add_argument("--engine", default=None, choices=[None, "f32", "split", "bf16", "bf16s"],
                     help="GEMM engine of the measured model (default: PA2D_GEMM or the fp32-accurate split engine)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything beyond the headline: the parity sample and the CPU "
+                         "baseline, the time-folded, exact-engine, bf16-storage and Darcy legs, the rollouts (the --no-* "
+                         "options below leave single ones out; without --full none of them runs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-batch", type=int, default=8, help="trajectories of the CPU protocol iteration (config C1: 8)")
     ap.add_argument("--cpu-iters", type=int, default=3)
@@ -449,9 +459,30 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed (losses, parameters, gradients) as "
                          "DIR/<name>.npy (rank 0; seeded inputs, so runs with the same arguments compare output for output)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    return args
+
+
+def secondary_legs(args, engine, world):
+    """What a run measures besides the headline, after its timed steps: nothing without --full; with it, every leg
+    that its --no-* options, the engine and the timed loop (--fold-time and --graph replace the default loop the legs
+    are compared with) leave.  "cpu" runs on rank 0 only."""
+    if not args.full:
+        return set()
+    default_loop = not (args.fold_time or args.graph)
+    legs = {"folded": default_loop and not args.no_folded_leg,
+            "exact": engine != ops.ENGINE_F32 and default_loop and not args.no_exact_leg,
+            "rollout": not args.no_rollout,
+            "darcy": not args.no_darcy_leg,
+            "bf16": engine != ops.ENGINE_BF16S and default_loop and not args.no_bf16_leg,
+            "cpu": world == 1 and not args.no_cpu_baseline}
+    return {leg for leg, on in legs.items() if on}
+
+
+def main():
+    args = parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: this process has not touched the GPU (no torch.cuda call,
         # libpa2d not loaded) and never will — it starts N fresh ranks and relays their output.
@@ -483,12 +514,14 @@ def main():
     calls = yy.shape[-1]
     N, C = cfg["H"] * cfg["W"], cfg["n_hidden"]
 
-    # parity sample before the weights move: teacher-forced predictions with the initial weights (full batch, so
-    # every launch of the dominant kernel in this process has the same shape and the rocprofv3 per-kernel average
-    # is comparable with the live HIP-event average)
-    with torch.no_grad():
-        _, _, pred_gpu0 = harness.train_iteration(model, x, fx, yy)
-    pred_gpu0 = pred_gpu0[:args.cpu_batch].cpu()
+    legs = secondary_legs(args, engine, world)
+    if args.full:
+        # parity sample before the weights move: teacher-forced predictions with the initial weights (full batch, so
+        # every launch of the dominant kernel in this process has the same shape and the rocprofv3 per-kernel average
+        # is comparable with the live HIP-event average)
+        with torch.no_grad():
+            _, _, pred_gpu0 = harness.train_iteration(model, x, fx, yy)
+        pred_gpu0 = pred_gpu0[:args.cpu_batch].cpu()
 
     pool = HipEventPool()
     if args.graph:
@@ -539,7 +572,7 @@ def main():
         "metric": "ns64_train_samples_per_s", "value": round(world * B * args.steps / dt, 4), "unit": "samples/s",
         "n_gpus": world,
         "rccl_ranks": (dist.get_world_size() if world > 1 and rk.backend == "nccl" else (1 if world == 1 else 0)),
-        "dist_backend": rk.backend, "steps": args.steps, "warmup": args.warmup,
+        "dist_backend": rk.backend, "steps": args.steps, "warmup": args.warmup, "full": bool(args.full),
         "ms_per_step": round(1e3 * dt / args.steps, 2), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": {ops.ENGINE_F32: "f32", ops.ENGINE_SPLIT: "f32", ops.ENGINE_BF16: "bf16 MFMA compute, f32 accumulate+storage",
                   ops.ENGINE_BF16S: "bf16"}[engine], "data": "synthetic",
@@ -564,7 +597,7 @@ def main():
                                          if ar_ms else None)
         out["step_ms_per_rank"] = {"min": min(rank_ms), "max": max(rank_ms), "all": rank_ms} if rank_ms else None
 
-    if not (args.fold_time or args.graph or args.no_folded_leg):
+    if "folded" in legs:
         # Secondary leg, reported next to (never instead of) `value`: the same iteration with its teacher-forced
         # calls folded into one call on calls*B windows (harness.train_iteration(fold_time=True); identical
         # loss/gradients, tests/test_gpu_optim.py).  Needs the driver loop changed, so it is not the drop-in number.
@@ -578,7 +611,7 @@ def main():
                               "note": "10 teacher-forced calls run as one call on 10*B windows (caller-side change)"}
         log(f"time-folded leg: {out['time_folded']['value']} samples/s")
 
-    if engine != ops.ENGINE_F32 and not (args.fold_time or args.graph or args.no_exact_leg):
+    if "exact" in legs:
         # Secondary leg: the same sequential iteration on the exact-fp32-MFMA engine (every GEMM on
         # v_mfma_f32_32x32x2_f32) — a second model + optimizer on the same weights and data, own engine argument.
         m2 = harness.build_model(cfg, sd, dev, engine="f32").train()
@@ -599,7 +632,7 @@ def main():
         del m2, o2, s2
         torch.cuda.empty_cache()
 
-    if not args.no_rollout:
+    if "rollout" in legs:
         # unrolled-inference steps/s (ns_vorticity_unrolling.py:264-286), hipGraph-captured step.  Replicas
         # only: every rank rolls out its own trajectories, no communication; the aggregate is
         # N * batch * 20 frames / (max over ranks of the time of 20 steps).
@@ -620,13 +653,13 @@ def main():
         out["rollout_sample"] = f"{args.rollout_repeats} timed 20-step graph-captured rollouts per batch size: median (and best)"
         model.train()
 
-    if not args.no_darcy_leg:
+    if "darcy" in legs:
         ops.event_provider = pool.provider
         torch.cuda.empty_cache()
         out["darcy421"] = darcy_leg(rk, pool, engine, args.darcy_batch, min(max(args.steps, 3), 5))
         log(f"darcy421 leg: {out['darcy421']['ms_per_iter']} ms/iter, {out['darcy421']['value']} samples/s")
 
-    if engine != ops.ENGINE_BF16S and not (args.fold_time or args.graph or args.no_bf16_leg):
+    if "bf16" in legs:
         # Secondary leg: BASELINE configs[2] / [4] AS STATED — bf16.  The same exp_ns.py iteration (and the same Darcy
         # iteration) on the bf16-STORAGE path (activations, saved tensors and inter-kernel gradients bf16 in HBM; fp32
         # master weights, statistics and accumulators; optional bf16 gradient wire): a second model + optimizer on the
@@ -657,14 +690,14 @@ def main():
             leg["step_ms_per_rank"] = {"min": min(rk.last_rank_ms), "max": max(rk.last_rank_ms)} if rk.last_rank_ms else None
         del mb, ob
         torch.cuda.empty_cache()
-        if not args.no_darcy_leg:
+        if "darcy" in legs:
             leg["darcy421"] = darcy_leg(rk, pool, ops.ENGINE_BF16S, args.darcy_batch, min(max(args.steps, 3), 5))
         out["bf16_storage"] = leg
         log(f"bf16-storage leg: {leg['value']} samples/s"
             + (f", darcy421 {leg['darcy421']['ms_per_iter']} ms/iter" if "darcy421" in leg else ""))
 
     ops.event_provider = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and "cpu" in legs:
         log("cpu baseline: oracle by the BASELINE.md §3 protocol ...")
         cb = min(args.cpu_batch, B)
         rec, pred_cpu = cpu_baseline(cfg, sd, pos, a, u, cb, args.cpu_iters, 3, args.cpu_budget_s)

@@ -63,3 +63,57 @@ def test_bench_times_the_requested_steps_and_dumps_the_last_one(tmp_path):
     assert got["params"].size == 11240769 and got["grads"].size == 2 ** 20      # NS_CONFIG: every parameter
     # the loss the result line reports is the dumped loss of the last step
     assert abs(float(got["loss"]) / 2 / 10 - rec["final_loss_per_sample_call"]) < 1e-5
+
+
+# what only `--full` measures: the secondary legs and the CPU baseline, at --batch-per-gpu 2
+FULL_ONLY_KEYS = {"time_folded", "fp32_exact_engine", "rollout_steps_per_s_b2", "rollout_steps_per_s_b1", "rollout_sample",
+                  "darcy421", "bf16_storage", "cpu_baseline", "rel_l2_gpu_vs_cpu_oracle"}
+
+
+def test_plain_run_makes_no_secondary_measurement():
+    import bench
+    from transformerbasednavierstokesolver_amd import ops
+    plain = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert plain.full is False
+    for engine in (ops.ENGINE_F32, ops.ENGINE_SPLIT, ops.ENGINE_BF16, ops.ENGINE_BF16S):
+        assert bench.secondary_legs(plain, engine, 1) == set() and bench.secondary_legs(plain, engine, 2) == set()
+
+
+def test_full_run_keeps_every_leg_its_options_leave():
+    import bench
+    from transformerbasednavierstokesolver_amd import ops
+    every = {"folded", "exact", "rollout", "darcy", "bf16", "cpu"}
+    full = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full"])
+    assert full.full is True
+    assert bench.secondary_legs(full, ops.ENGINE_SPLIT, 1) == every
+    assert bench.secondary_legs(full, ops.ENGINE_SPLIT, 2) == every - {"cpu"}             # CPU baseline: N = 1 only
+    assert bench.secondary_legs(full, ops.ENGINE_F32, 1) == every - {"exact"}              # the headline is that engine
+    assert bench.secondary_legs(full, ops.ENGINE_BF16S, 1) == every - {"bf16"}
+    for opt, leg in (("--no-folded-leg", "folded"), ("--no-exact-leg", "exact"), ("--no-split-leg", "exact"),
+                     ("--no-rollout", "rollout"), ("--no-darcy-leg", "darcy"), ("--no-bf16-leg", "bf16"),
+                     ("--no-cpu-baseline", "cpu")):
+        assert bench.secondary_legs(bench.parse_args(["--full", opt]), ops.ENGINE_SPLIT, 1) == every - {leg}, opt
+    for loop in ("--graph", "--fold-time"):        # legs compared with the default loop need that loop
+        assert bench.secondary_legs(bench.parse_args(["--full", loop]), ops.ENGINE_SPLIT, 1) == {"rollout", "darcy", "cpu"}
+
+
+def _bench_line(args):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    return json.loads(lines[0])
+
+
+@pytest.mark.gpu
+def test_plain_run_reports_the_headline_alone_and_full_run_adds_the_legs():
+    base = ["--gpus", "1", "--steps", "1", "--warmup", "1", "--batch-per-gpu", "2"]
+    plain = _bench_line(base)
+    assert plain["full"] is False and not FULL_ONLY_KEYS & set(plain), sorted(FULL_ONLY_KEYS & set(plain))
+    assert plain["steps"] == 1 and plain["warmup"] == 1 and plain["ms_per_step"] > 0
+    # the rooflines come from HIP events inside the timed steps themselves: a plain run keeps them
+    assert plain["roofline"]["launches_timed"] > 0 and plain["roofline_hbm"]["kernels"]
+    full = _bench_line(base + ["--full", "--cpu-batch", "1", "--cpu-iters", "1", "--rollout-repeats", "1"])
+    assert full["full"] is True and FULL_ONLY_KEYS <= set(full), sorted(FULL_ONLY_KEYS - set(full))
+    assert full["steps"] == 1 and full["warmup"] == 1
+    assert full["rel_l2_gpu_vs_cpu_oracle"] < 1e-4

@@ -1,6 +1,6 @@
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/r03_darcy; rm -rf $O; mkdir -p $O
-BARGS="--steps 1 --warmup 1 --no-cpu-baseline --no-rollout --no-folded-leg --no-exact-leg --no-bf16-leg"
+BARGS="--full --steps 1 --warmup 1 --no-cpu-baseline --no-rollout --no-folded-leg --no-exact-leg --no-bf16-leg"
 timeout -k 10 400 rocprofv3 --kernel-trace --output-format csv -d $O/trace -- python bench.py $BARGS > $O/bench.json 2> $O/bench.err
 python - <<'PY'
 import csv, glob, json, collections
