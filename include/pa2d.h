@@ -227,6 +227,39 @@ int pa2d_deslice_weights_bwd(const float* code, const float* w, const float* dy,
                              void* ws_buf, size_t ws_bytes, int B, int N, int heads, int D, int M, pa2d_stream_t stream,
                              void* ev_start, void* ev_stop);
 
+/* ---- SequenSolver latent sequence model (reference SequenSolver.py, class SequenSolver).  Both stages run fp32 FMAs on the
+ * VALU (fp64 for the attention score sums and the small final reductions) whatever engine the rest of the model uses: no
+ * engine argument.  B = 0 is a no-op (parameter gradients zero-filled when
+ * accumulate = 0); an unsupported shape returns PA2D_ERR_UNSUPPORTED before any pointer is looked at.
+ * sequence attention among the T frame tokens of a sample, one head (SequenSolver.py:319-331): q, k, v [B, T, dim] (the three
+ * bias-free Linear(dim, dim) of the LayerNorm output: pa2d_gemm_bias_act_fwd), attn [B, T, T] = softmax_T(q k^T * scale),
+ * out [B, T, dim] = attn v (+ res: the block's residual `+ tokens`, :150; may be NULL).  1 <= T <= 32, dim % 4 == 0, 4 <= dim <= 1024 (the LayerNorm limit of the tokens); pointers
+ * 16-byte aligned.  attn is an output of the forward (saved for the backward; never NULL). */
+int pa2d_seq_attn_fwd(const float* q, const float* k, const float* v, const float* res, float* out, float* attn, int B,
+                      int T, int dim, float scale, pa2d_stream_t stream);
+/* dq, dk, dv [B, T, dim] from dout (autograd of SequenSolver.py:325-328); plain stores (activations: no accumulate flag) */
+size_t pa2d_seq_attn_bwd_workspace(int B, int T);
+int pa2d_seq_attn_bwd(const float* q, const float* k, const float* v, const float* attn, const float* dout, float* dq,
+                      float* dk, float* dv, void* ws, size_t ws_bytes, int B, int T, int dim, float scale,
+                      pa2d_stream_t stream);
+/* slice weights predicted from the code (SequenSolver.py:159-170, use_gt=False: the loop that fills a [B, N, M, C+2] tensor
+ * with cat(code[b, 0, m, :], pos[b, n, :2]), weight_projection = MLP(C+2, 64, 1) with n_layers=1 and res=True (:18-43, :102),
+ * softmax over M): sw[b, 0, n, :] = softmax_m(w3 . (h + gelu(w2 h + b2)) + b3), h = gelu(w1 [code_m ; pos_n] + b1), GELU exact.
+ * The concatenated tensor is never made.  code [B, M, C], pos [B, N, 2], w1 [hidden, C+2], b1 [hidden], w2 [hidden, hidden],
+ * b2 [hidden], w3 [1, hidden], b3 [1], sw [B, 1, N, M].  C in {8, 16, 32, 64}, 1 <= M <= 128, N >= 1, hidden = 64 and
+ * depth = 1 (the hidden layers of the MLP) only.  ev_start / ev_stop as for the slice stages. */
+int pa2d_code_slice_weights_fwd(const float* code, const float* pos, const float* w1, const float* b1, const float* w2,
+                                const float* b2, const float* w3, const float* b3, float* sw, int B, int N, int M, int C,
+                                int hidden, int depth, pa2d_stream_t stream, void* ev_start, void* ev_stop);
+/* backward from dsw [B, 1, N, M] (the forward is recomputed): dcode [B, M, C] (plain store; may be NULL) and the six
+ * parameter gradients, reduced over (b, n, m) in a fixed order, (+)= per `accumulate`.  The positions get no gradient. */
+size_t pa2d_code_slice_weights_bwd_workspace(int B, int N, int M, int C);
+int pa2d_code_slice_weights_bwd(const float* code, const float* pos, const float* w1, const float* b1, const float* w2,
+                                const float* b2, const float* w3, const float* b3, const float* dsw, float* dcode,
+                                float* dw1, float* db1, float* dw2, float* db2, float* dw3, float* db3, void* ws_buf,
+                                size_t ws_bytes, int B, int N, int M, int C, int hidden, int depth, int accumulate,
+                                pa2d_stream_t stream, void* ev_start, void* ev_stop);
+
 /* ---- output head mlp2 = nn.Linear(C, out_dim), out_dim <= 8 (…_2D.py:66,73) */
 int pa2d_head_fwd(const float* xn, const float* w, const float* b, float* y, int rows, int C, int out_dim,
                   pa2d_stream_t stream);

@@ -1,0 +1,249 @@
+"""SequenSolver without a GPU: the module's interface against the reference (tests/golden/G10_sequensolver.npz, written by
+tools/make_golden_sequensolver.py), the refusals, the new C ABI symbols with their host-side refusals, and the fixture's
+float64 results against the torch float64 restatement of tests/sequensolver_restatement.py (an oracle-vs-golden check,
+like test_oracle_golden.py)."""
+import ctypes
+import inspect
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import GOLDEN
+import sequensolver_restatement as R
+
+G10 = os.path.join(GOLDEN, "G10_sequensolver.npz")
+NEW_SYMBOLS = {      # name: number of arguments in include/pa2d.h
+    "pa2d_seq_attn_fwd": 11,
+    "pa2d_seq_attn_bwd_workspace": 2,
+    "pa2d_seq_attn_bwd": 15,
+    "pa2d_code_slice_weights_fwd": 18,
+    "pa2d_code_slice_weights_bwd_workspace": 4,
+    "pa2d_code_slice_weights_bwd": 28,
+}
+TINY_ENCODER = dict(space_dim=2, n_layers=2, n_hidden=16, n_head=1, slice_num=8, fun_dim=1, out_dim=1, mlp_ratio=1,
+                    unified_pos=0, H=6, W=5)
+LAST = "weight_projection.linear_post"
+
+
+@pytest.fixture(scope="module")
+def g10():
+    return np.load(G10)
+
+
+def _model(g10, case, **over):
+    from transformerbasednavierstokesolver_amd.SequenSolver import SequenSolver
+    cfg, geom = json.loads(str(g10[case + ".config"])), json.loads(str(g10["geometry"]))
+    kw = dict(T=cfg["T"], layers=cfg["layers"], B=cfg["B"], **geom)
+    kw.update(over)
+    return SequenSolver(None, **kw)
+
+
+def _tiny(**over):
+    from transformerbasednavierstokesolver_amd.SequenSolver import SequenSolver
+    kw = dict(T=2, W=5, H=6, M=8, C=16, B=1, layers=2, encoder_config=TINY_ENCODER)
+    kw.update(over)
+    return SequenSolver(None, **kw)
+
+
+def test_constructor_signature_and_defaults_match_reference(g10):
+    from transformerbasednavierstokesolver_amd.SequenSolver import SequenSolver
+    ref = [tuple(p) for p in json.loads(str(g10["signature"]))]
+    params = [(k, p) for k, p in inspect.signature(SequenSolver.__init__).parameters.items() if k != "self"]
+    ours = [(k, None if p.default is inspect.Parameter.empty else p.default) for k, p in params]
+    assert ours[:len(ref)] == ref and len(ref) == 11
+    assert [(k, p.kind, p.default) for k, p in params[len(ref):]] == [("encoder_config", inspect.Parameter.KEYWORD_ONLY, None)]
+
+
+@pytest.mark.parametrize("case", ["a", "b"])
+def test_state_dict_keys_shapes_strict_load_and_attributes(g10, case):
+    m = _model(g10, case)
+    ours = m.state_dict()
+    assert list(ours) == [str(k) for k in g10[case + ".keys"]]
+    assert [list(v.shape) for v in ours.values()] == json.loads(str(g10[case + ".shapes"]))
+    sd = {k: torch.from_numpy(v) for k, v in R.golden_state_dict(g10, case).items()}
+    res = m.load_state_dict(sd, strict=True)
+    assert not res.missing_keys and not res.unexpected_keys
+    cfg = json.loads(str(g10[case + ".config"]))
+    assert (m.T, m.W, m.H, m.M, m.C, m.N, m.B, m.dim, m.Head, m.layers) == (cfg["T"], 64, 64, 16, 32, 4096, cfg["B"], 512, 1,
+                                                                           cfg["layers"])
+    assert m.scale == 512 ** -0.5 and m.code is None and tuple(m.slice_weights.shape) == (cfg["B"], 1, 4096, 16)
+    assert not hasattr(m, "token_to_slice_list")
+    assert not m.encoder.training and not any(p.requires_grad for p in m.encoder.parameters())
+    m.train()
+    assert m.training and not m.encoder.training
+
+
+def test_transolver_path_as_file_mapping_or_none(g10, tmp_path):
+    from transformerbasednavierstokesolver_amd.SequenSolver import SequenSolver
+    enc = {k[len("encoder."):]: torch.from_numpy(v) for k, v in R.golden_state_dict(g10, "a").items()
+           if k.startswith("encoder.")}
+    path = tmp_path / "encoder.pt"
+    torch.save(enc, path)
+    kw = dict(T=3, W=64, H=64, M=16, C=32, B=2, layers=2)
+    for src in (str(path), path, enc, {k: v.numpy() for k, v in enc.items()}):
+        m = SequenSolver(src, **kw)
+        assert all(torch.equal(m.encoder.state_dict()[k], v) for k, v in enc.items())
+    partial = {k: v for k, v in enc.items() if not k.startswith("preprocess.")}      # strict=False, as the reference
+    SequenSolver(partial, **kw)
+
+
+def test_freeze_attention_freezes_the_reference_set(g10):
+    m = _model(g10, "a")
+    m.freeze_attention()
+    frozen = [k for k, p in m.named_parameters() if not p.requires_grad and not k.startswith("encoder.")]
+    assert frozen == json.loads(str(g10["a.frozen.names"])) and len(frozen) == 11
+    assert not any(mod.training for mod in (m.to_q, m.to_k, m.to_v, m.mlp, m.ln_1, m.ln_2))
+
+
+def test_refusals():
+    from transformerbasednavierstokesolver_amd import ops
+    from transformerbasednavierstokesolver_amd.SequenSolver import SequenSolver
+    m = _tiny()
+    with pytest.raises(NotImplementedError):
+        m.set_engine("bf16s")
+    m.set_engine("f32")
+    assert m.engine == ops.ENGINE_F32 and m.mlp.engine == ops.ENGINE_F32 and m.encoder.engine == ops.ENGINE_F32
+    x, fx, y = torch.zeros(1, 30, 2), torch.zeros(1, 30, 2), torch.zeros(1, 30, 1)
+    m.engine = ops.ENGINE_BF16S              # set behind set_engine's back: refused when the model runs
+    for call in (lambda: m(x, fx, y), lambda: m.get_code(x, fx, y), lambda: m.attention(torch.zeros(1, 1, 2, 128))):
+        with pytest.raises(NotImplementedError, match="bf16"):
+            call()
+    md = _tiny(dropout=0.1).train()
+    with pytest.raises(NotImplementedError, match="dropout"):
+        md(x, fx, y)
+    with pytest.raises(NotImplementedError, match="dropout"):
+        md.attention(torch.zeros(1, 1, 2, 128))
+    with pytest.raises(NotImplementedError, match="LearnSlice"):
+        m.solve_with_slice_learner("path", x, fx, y)
+    # geometry against the encoder: a ValueError here, a reshape error deep in forward() in the reference
+    for over in (dict(M=16), dict(C=32), dict(H=5, W=6), dict(H=12)):
+        with pytest.raises(ValueError):
+            _tiny(**over)
+    with pytest.raises(ValueError, match="heads"):
+        _tiny(encoder_config=dict(TINY_ENCODER, n_head=2, n_hidden=32))
+    with pytest.raises(ValueError):
+        SequenSolver(None, T=3, W=64, H=64, M=8, C=32, B=1)          # the reference's hard-coded encoder has 16 slices
+    with pytest.raises(NotImplementedError, match="T = 33"):
+        _tiny(T=33)
+    with pytest.raises(NotImplementedError, match="dim"):              # 64 slices x 32 channels = 2048 > the LayerNorm limit
+        _tiny(M=64, C=32, encoder_config=dict(TINY_ENCODER, slice_num=64, n_hidden=32))
+
+
+def test_c_abi_symbols_bound_with_header_arity():
+    from transformerbasednavierstokesolver_amd import _lib
+    _lib.load()
+    raw = ctypes.CDLL(_lib.LIB_PATH)
+    header = open(os.path.join(os.path.dirname(GOLDEN), "..", "include", "pa2d.h")).read()
+    flat = " ".join(header.split())
+    for name, arity in NEW_SYMBOLS.items():
+        assert hasattr(raw, name) and name in _lib.SIGNATURES, name
+        assert len(_lib.SIGNATURES[name][1]) == arity, name
+        decl = flat.split(name + "(", 1)[1].split(")", 1)[0]
+        assert len(decl.split(",")) == arity, name
+        assert "SequenSolver.py:" in header.split(name + "(", 1)[0].rsplit("/* ----", 1)[1], name     # cites its lines
+
+
+def test_host_side_refusals_with_null_pointers():
+    from transformerbasednavierstokesolver_amd import _lib
+    lib = _lib.load()
+    ARG, UNSUP, WS = 1001, 1002, 1003
+    # pa2d_seq_attn_fwd(q, k, v, res, out, attn, B, T, dim, scale, stream)
+    fwd = lib.pa2d_seq_attn_fwd
+    assert fwd(0, 0, 0, 0, 0, 0, 1, 0, 512, 1.0, 0) == UNSUP            # T = 0
+    assert fwd(0, 0, 0, 0, 0, 0, 1, 33, 512, 1.0, 0) == UNSUP           # T = 33
+    assert fwd(0, 0, 0, 0, 0, 0, 1, 10, 510, 1.0, 0) == UNSUP           # dim % 4 != 0
+    assert fwd(0, 0, 0, 0, 0, 0, 1, 10, 1028, 1.0, 0) == UNSUP          # beyond the LayerNorm limit
+    assert fwd(0, 0, 0, 0, 0, 0, -1, 10, 512, 1.0, 0) == ARG
+    assert fwd(0, 0, 0, 0, 0, 0, 1, 10, 512, 1.0, 0) == ARG             # supported shape, null pointers
+    assert fwd(0, 0, 0, 0, 0, 0, 0, 10, 512, 1.0, 0) == 0               # B = 0: no-op
+    # pa2d_seq_attn_bwd(q, k, v, attn, dout, dq, dk, dv, ws, ws_bytes, B, T, dim, scale, stream)
+    bwd = lib.pa2d_seq_attn_bwd
+    assert bwd(0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 0, 512, 1.0, 0) == UNSUP
+    assert bwd(0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 33, 512, 1.0, 0) == UNSUP
+    assert bwd(0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 10, 6, 1.0, 0) == UNSUP
+    assert bwd(16, 16, 16, 16, 16, 16, 16, 16, 0, 0, 1, 10, 512, 1.0, 0) == WS
+    assert bwd(0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 10, 512, 1.0, 0) == 0
+    assert lib.pa2d_seq_attn_bwd_workspace(3, 10) == 3 * 10 * 10 * 4 and lib.pa2d_seq_attn_bwd_workspace(0, 10) == 0
+    # pa2d_code_slice_weights_fwd(code, pos, w1, b1, w2, b2, w3, b3, sw, B, N, M, C, hidden, depth, stream, ev0, ev1)
+    f = lib.pa2d_code_slice_weights_fwd
+    assert f(0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 4096, 129, 32, 64, 1, 0, 0, 0) == UNSUP      # M = 129
+    assert f(0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 4096, 0, 32, 64, 1, 0, 0, 0) == UNSUP        # M = 0
+    assert f(0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 4096, 16, 12, 64, 1, 0, 0, 0) == UNSUP       # C = 12
+    assert f(0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 4096, 16, 32, 32, 1, 0, 0, 0) == UNSUP       # hidden width 32
+    assert f(0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 4096, 16, 32, 64, 0, 0, 0, 0) == UNSUP       # no hidden layer
+    assert f(0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 0, 16, 32, 64, 1, 0, 0, 0) == ARG            # N = 0
+    assert f(0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 4096, 16, 32, 64, 1, 0, 0, 0) == ARG         # supported shape, null pointers
+    assert f(0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 4096, 16, 32, 64, 1, 0, 0, 0) == 0           # B = 0: no-op
+    assert f(0, 0, 0, 0, 0, 0, 0, 0, 0, 1 << 16, 1 << 16, 128, 32, 64, 1, 0, 0, 0) == UNSUP      # > 4 GiB of weights
+    # pa2d_code_slice_weights_bwd(8 inputs, dsw, dcode, 6 gradients, ws, ws_bytes, B, N, M, C, hidden, depth, accumulate,
+    #                             stream, ev0, ev1)
+    b = lib.pa2d_code_slice_weights_bwd
+    assert b(*([0] * 18), 1, 4096, 129, 32, 64, 1, 0, 0, 0, 0) == UNSUP
+    assert b(*([0] * 18), 1, 4096, 16, 12, 64, 1, 0, 0, 0, 0) == UNSUP
+    assert b(*([0] * 18), 1, 4096, 16, 32, 64, 2, 0, 0, 0, 0) == UNSUP
+    assert b(*([16] * 16), 0, 0, 1, 4096, 16, 32, 64, 1, 0, 0, 0, 0) == WS
+    assert b(*([0] * 18), 0, 4096, 16, 32, 64, 1, 1, 0, 0, 0) == 0                      # B = 0, accumulate: untouched
+    ws = lib.pa2d_code_slice_weights_bwd_workspace
+    assert ws(1, 4096, 16, 32) > 0 and ws(0, 4096, 16, 32) == 0 and ws(1, 4096, 129, 32) == 0
+    assert ws(3, 4099, 128, 64) >= 3 * 128 * 64 * 4
+
+
+def test_ops_refuse_cpu_tensors():
+    from transformerbasednavierstokesolver_amd import ops
+    q = torch.zeros(1, 3, 64)
+    with pytest.raises(RuntimeError, match="GPU"):
+        ops.seq_attn_fwd(q, q, q, 1.0)
+    with pytest.raises(RuntimeError, match="GPU"):
+        ops.code_slice_weights_fwd(torch.zeros(1, 8, 16), torch.zeros(1, 5, 2),
+                                   (torch.zeros(64, 18), torch.zeros(64), torch.zeros(64, 64), torch.zeros(64),
+                                    torch.zeros(1, 64), torch.zeros(1)))
+
+
+# ---------------------------------------------------------------------------------------------- restatement vs golden
+def _restated(g10, case, use_gt):
+    cfg = json.loads(str(g10[case + ".config"]))
+    sd = {k: torch.from_numpy(v).double() for k, v in R.golden_state_dict(g10, case).items()}
+    for k, v in sd.items():
+        v.requires_grad_(not k.startswith("encoder."))
+    from transformerbasednavierstokesolver_amd.SequenSolver import REFERENCE_ENCODER
+    pos, fx, y, _ = (torch.from_numpy(a).double() for a in R.golden_inputs(g10, case))
+    out, code, sw = R.forward(sd, REFERENCE_ENCODER, cfg["layers"], pos, fx, y, use_gt=use_gt)
+    B = out.shape[0]
+    loss = (torch.linalg.vector_norm((out - y).reshape(B, -1), dim=1) / torch.linalg.vector_norm(y.reshape(B, -1), dim=1)).sum()
+    loss.backward()
+    return sd, out, code, sw, loss
+
+
+@pytest.mark.parametrize("case,branch", [("a", "gt"), ("a", "pred"), ("b", "gt"), ("b", "pred")])
+def test_float64_restatement_reproduces_the_fixture(g10, case, branch):
+    """The fixture holds the reference's float64 results rounded to float32 (6e-8); the restatement must meet them to 1e-6
+    (1e-5 for the gradients of to_q / to_k, which are differences of nearly equal terms near uniform attention)."""
+    sd, out, code, sw, loss = _restated(g10, case, use_gt=branch == "gt")
+    pre = f"{case}.{branch}."
+    assert R.golden_rel(g10, pre + "out", out) < 1e-6
+    assert R.golden_rel(g10, pre + "code", code) < 1e-6
+    assert R.golden_rel(g10, pre + "slice_weights", sw) < 1e-6
+    assert abs(float(sw.sum()) - float(g10[pre + "slice_weights.sum"])) < 1e-6 * sw.shape[0] * sw.shape[2]
+    assert abs(float(loss.detach()) - float(g10[pre + "loss"])) < 1e-9 * float(loss.detach())
+    none = [k for k, v in sd.items() if v.grad is None]
+    assert none == json.loads(str(g10[pre + "no_grad"]))
+    for k, v in sd.items():
+        if k in none or k == LAST + ".bias":         # the last bias: true gradient 0, judged with its layer's weight below
+            continue
+        tol = 1e-5 if k in ("to_q.weight", "to_k.weight") else 1e-6
+        assert R.golden_rel(g10, pre + "grad." + k, v.grad) < tol, k
+    if branch == "pred":
+        both = torch.cat((sd[LAST + ".weight"].grad.reshape(-1), sd[LAST + ".bias"].grad.reshape(-1)))
+        assert R.golden_rel(g10, pre + f"grad.{LAST}.[weight|bias]", both) < 1e-6
+
+
+def test_fixture_carries_the_float32_yardstick(g10):
+    keys = [k for k in g10.files if k.startswith("fp32_self_error.")]
+    assert len(keys) > 100
+    for k in ("a.gt.out", "b.pred.slice_weights", "a.train.losses", "a.rollout.pred", "b.get_code", "a.last_slice",
+              "b.frozen.grad.ln_3.weight"):
+        assert "fp32_self_error." + k in g10.files, k
+    assert len(g10["a.train.losses"]) == 3

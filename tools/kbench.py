@@ -5,6 +5,8 @@ The conv3d_* stages time the 3x3x3 conv of the structured 3-D mesh on a --B3 x -
 The ae_* stages run at auto_encoder.py's shape (--AB x 64 x 64, C=64, 4 heads, M=--AM, 3 layers): the four kernels of the
 auto-encoder attention (slice weights forward / backward, de-slice with explicit weights forward / backward; GB/s and the
 fraction of the 8 TB/s HBM peak) and one whole auto-encoder training iteration (autoencoder_train_step, FusedAdamW).
+The seq_attn_* / code_sw_* stages time the two SequenSolver kernels at the reference's shape (--SB samples, T=10 tokens of
+dim=512; 64 x 64 points, M=16, C=32), seq_iter one sequensolver_train_step (T=10, layers=8, Tout=1, FusedAdamW) at B=1 and B=8.
 Usage: python tools/kbench.py [--only conv_fwd,linear_fwd,...] [--iters 10] [--B 32]"""
 import argparse
 import os
@@ -43,6 +45,7 @@ def main():
     ap.add_argument("--S3", type=int, default=32, help="edge of the cubic mesh of the conv3d_* stages")
     ap.add_argument("--AB", type=int, default=8, help="batch of the ae_* stages (auto_encoder.py's shape)")
     ap.add_argument("--AM", type=int, default=32, help="slices of the ae_* stages")
+    ap.add_argument("--SB", type=int, default=8, help="batch of the seq_attn_* / code_sw_* stages (SequenSolver's shape)")
     args = ap.parse_args()
     E = ops.resolve_engine(args.engine)
     print(f"engine {E}  B={args.B} H={args.H} W={args.W} C={args.C} M={args.M}", flush=True)
@@ -132,8 +135,34 @@ def main():
         aopt = FusedAdamW(ae.parameters(), lr=1e-3, weight_decay=1e-5, max_grad_norm=1.0)
         apos, afx = torch.rand(AB, AN, 2, device=dev), rn(AB, AN, 1)
         tests["ae_iter"] = (lambda: harness.autoencoder_train_step(ae, aopt, None, apos, afx, grad_sync=aopt.sync), 0, "us")
+    # SequenSolver stages at the reference's shape: T=10 tokens of dim = 16 * 32; 4096 points, M=16, C=32
+    SB, ST, SM, SC = args.SB, 10, 16, 32
+    sdim = SM * SC
+    sq, sk, sv, sdo = (rn(SB, ST, sdim) for _ in range(4))
+    _, sattn = ops.seq_attn_fwd(sq, sk, sv, sdim ** -0.5)
+    tests["seq_attn_fwd"] = (lambda: ops.seq_attn_fwd(sq, sk, sv, sdim ** -0.5, sq), 0, "us")
+    tests["seq_attn_bwd"] = (lambda: ops.seq_attn_bwd(sq, sk, sv, sattn, sdo, sdim ** -0.5), 0, "us")
+    scode, spos = rn(SB, SM, SC), torch.rand(SB, 4096, 2, device=dev)
+    swp = (rn(64, SC + 2) * 0.2, rn(64) * 0.1, rn(64, 64) * 0.12, rn(64) * 0.1, rn(1, 64) * 0.25, rn(1))
+    sdsw = rn(SB, 1, 4096, SM)
+    csw_flops = 2.0 * SB * 4096 * SM * (64 * 64 + 64 * 3)            # the hidden layer, the rank-2 term and the last dot
+    tests["code_sw_fwd"] = (lambda: ops.code_slice_weights_fwd(scode, spos, swp), csw_flops, "VALU")
+    tests["code_sw_bwd"] = (lambda: ops.code_slice_weights_bwd(scode, spos, swp, sdsw), 3 * csw_flops, "VALU")
+    if only & {"seq_iter"}:
+        from transformerbasednavierstokesolver_amd import harness
+        from transformerbasednavierstokesolver_amd.SequenSolver import SequenSolver
+        from transformerbasednavierstokesolver_amd.optim import FusedAdamW
+        for sb in (1, 8):
+            torch.manual_seed(0)
+            sm = SequenSolver(None, T=ST, W=64, H=64, M=SM, C=SC, B=sb, layers=8).to(dev).set_engine(E)
+            sopt = FusedAdamW(sm.parameters(), lr=1e-3, weight_decay=1e-5)
+            sx, sfx, syy = torch.rand(sb, 4096, 2, device=dev), rn(sb, 4096, ST), rn(sb, 4096, 1)
+            for gt in (True, False):
+                tests[f"seq_iter B={sb} use_gt={gt}"] = (
+                    lambda sm=sm, sopt=sopt, sx=sx, sfx=sfx, syy=syy, gt=gt: harness.sequensolver_train_step(
+                        sm, sopt, None, sx, sfx, syy, use_gt=gt, grad_sync=sopt.sync), 0, "us")
     for name, (fn, work, unit) in tests.items():
-        if only and name not in only:
+        if only and name not in only and not (name.startswith("seq_iter") and "seq_iter" in only):
             continue
         ms = timeit(fn, args.iters)
         if unit == "TF":
@@ -141,6 +170,8 @@ def main():
         elif unit == "HBM":
             print(f"{name:20s} {ms * 1e3:9.1f} us  {work / ms / 1e6:8.0f} GB/s  ({work / ms / 1e9 / 8.0:.3f} of 8 TB/s HBM)",
                   flush=True)
+        elif unit == "VALU":
+            print(f"{name:20s} {ms * 1e3:9.1f} us  {work / ms / 1e9:8.1f} TFLOP/s useful fp32 (FMA = 2)", flush=True)
         elif unit == "GB":
             print(f"{name:20s} {ms:9.3f} ms  {work / ms / 1e6:8.0f} GB/s algorithmic", flush=True)
         else:

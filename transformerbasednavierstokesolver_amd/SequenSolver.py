@@ -1,0 +1,210 @@
+"""SequenSolver — the latent sequence model over the codes of the frozen structured 2-D auto-encoder; the drop-in for the
+reference's top-level SequenSolver.py (class SequenSolver, :45-388).
+
+  1. the last T frames go through the frozen encoder: each frame becomes one token of width dim = M*C;
+  2. `layers` weight-tied pre-LN blocks run over the T tokens: tokens += attention(ln_1 tokens) (single-head attention
+     among the T tokens, pa2d_seq_attn_*), tokens += mlp(ln_2 tokens) (dim -> mlp_ratio*dim -> dim);
+  3. the last token is the code [B, 1, M, C] of the next frame;
+  4. the code is de-sliced with slice weights [B, 1, N, M]: with use_gt=True the encoder's weights of the true next frame,
+     with use_gt=False predicted from the code and the point coordinates by `weight_projection` and a softmax over M
+     (pa2d_code_slice_weights_*: the reference's loop over the N points and its [B, N, M, C+2] tensor do not exist here);
+  5. output = mlp2(ln_3(.)).
+
+The constructor keeps the reference's names, order and defaults; `encoder_config` (keyword-only) is the one extension: the
+reference hard-codes its encoder (8 layers, n_hidden=32, 1 head, 16 slices, 64 x 64, unified_pos=1, fun_dim=1), which stays
+the default.  The state_dict has the reference's keys and shapes: `slice_projection` and `temporal_slice_projection` are
+created and never used (no gradient), `token_to_slice_list` (a plain list of N unused layers, not in the state_dict) is
+not built.  Every arithmetic step goes through functional.py; torch only slices, reshapes and owns memory.
+`solve_with_slice_learner` (plots, LearnSlice) is not provided."""
+import os
+
+import torch
+import torch.nn as nn
+
+from . import functional as Fn
+from . import ops
+from .model import Transolver_Structured_Mesh2D_Encoder
+from .model._core import ACTIVATION, MLP  # noqa: F401  (the reference module defines both names)
+
+REFERENCE_ENCODER = dict(space_dim=2, n_layers=8, n_hidden=32, dropout=0.0, n_head=1, slice_num=16, Time_Input=False,
+                         fun_dim=1, out_dim=1, unified_pos=1, H=64, W=64)
+WEIGHT_PROJECTION_HIDDEN = 64
+
+
+class SequenSolver(nn.Module):
+
+    def __init__(self, transolver_path, T, W, H, M, C, B, mlp_ratio=4, layers=5, act='gelu', dropout=0., *,
+                 encoder_config=None):
+        super().__init__()
+        self.T, self.W, self.H, self.M, self.C = T, W, H, M, C
+        self.N = H * W
+        self.B = B
+        self.dim = M * C
+        self.scale = self.dim ** -0.5
+        self.Head = 1
+        self.layers = layers
+        self.engine = None
+        self.batched_encoding = True      # the T (+1) frames of a call go through the encoder as ONE batch
+
+        cfg = dict(REFERENCE_ENCODER if encoder_config is None else encoder_config)
+        self.encoder = Transolver_Structured_Mesh2D_Encoder.Model(**cfg)
+        enc_h, enc_w, enc_m = self.encoder.H, self.encoder.W, self.encoder.blocks[-1].Attn.in_project_slice.out_features
+        enc_heads, enc_c = self.encoder.blocks[-1].Attn.heads, self.encoder.blocks[-1].Attn.dim_head
+        if (enc_h, enc_w) != (H, W):
+            raise ValueError(f"H x W = {H} x {W} does not match the encoder's mesh {enc_h} x {enc_w}")
+        if enc_heads != self.Head:
+            raise ValueError(f"the encoder has {enc_heads} heads; SequenSolver reads its code as one head of M x C")
+        if (enc_m, enc_c) != (M, C):
+            raise ValueError(f"M x C = {M} x {C} does not match the encoder's code {enc_m} slices x {enc_c} channels")
+        if not 1 <= T <= ops.SEQ_ATTN_MAX_T:
+            raise NotImplementedError(f"the sequence attention kernel serves 1 <= T <= {ops.SEQ_ATTN_MAX_T}; got T = {T}")
+        if self.dim > ops.SEQ_ATTN_MAX_DIM or self.dim % 4:
+            raise NotImplementedError(f"dim = M*C = {self.dim}: LayerNorm and the sequence attention kernel serve "
+                                      f"dim % 4 == 0 up to {ops.SEQ_ATTN_MAX_DIM}")
+        if transolver_path is not None:
+            sd = transolver_path
+            if isinstance(sd, (str, os.PathLike)):
+                sd = torch.load(sd, weights_only=True, map_location="cpu")
+            self.encoder.load_state_dict({k: torch.as_tensor(v) for k, v in sd.items()}, strict=False)
+        self.encoder.eval()
+        for param in self.encoder.parameters():
+            param.requires_grad = False
+
+        self.to_q = nn.Linear(self.dim, self.dim, bias=False)
+        self.to_k = nn.Linear(self.dim, self.dim, bias=False)
+        self.to_v = nn.Linear(self.dim, self.dim, bias=False)
+        self.softmax_attention = nn.Softmax(dim=-1)
+        self.dropout = nn.Dropout(dropout)
+
+        # follows .cuda() / .to() and stays out of the state_dict, like the reference's plain tensor attribute
+        self.register_buffer("slice_weights", torch.zeros(B, 1, self.N, self.M), persistent=False)
+        self.slice_weights_t = 0
+        self.slice_projection = nn.Linear(self.M, self.M)                           # never used (reference :93)
+        self.temporal_slice_projection = MLP(self.T, self.T * mlp_ratio, 1)         # never used (reference :95)
+        self.code = None
+        self.weight_projection = MLP(self.C + 2, WEIGHT_PROJECTION_HIDDEN, 1)
+        self.softmax_slice = nn.Softmax(dim=-1)
+
+        self.ln_1 = nn.LayerNorm(self.dim)
+        self.ln_2 = nn.LayerNorm(self.dim)
+        self.mlp = MLP(self.dim, self.dim * mlp_ratio, self.dim, n_layers=0, res=False, act=act)
+
+        self.ln_3 = nn.LayerNorm(self.C)
+        self.mlp2 = nn.Linear(self.C, 1)
+
+    # ---- engine
+    def set_engine(self, engine):
+        """GEMM engine of the encoder and of this model's dense layers ("f32" | "split" | "bf16" | None = default); bf16
+        storage ('bf16s') is refused, as for the encoder family.  The two SequenSolver stages are exact fp32 on every engine."""
+        self.encoder.set_engine(engine)          # refuses 'bf16s'
+        self.engine = None if engine is None else ops.resolve_engine(engine)
+        for m in (self.mlp, self.weight_projection, self.temporal_slice_projection):
+            m.engine = self.engine
+        return self
+
+    def train(self, mode=True):
+        super().train(mode)
+        self.encoder.eval()                      # the encoder is frozen and stays in eval()
+        return self
+
+    def _refuse(self):
+        if ops.resolve_engine(self.engine) == ops.ENGINE_BF16S:
+            raise NotImplementedError("bf16 storage (engine 'bf16s') is not implemented for SequenSolver")
+        if self.training and self.dropout.p > 0:
+            raise NotImplementedError("dropout > 0 is not implemented in the HIP path; refusing to ignore it")
+
+    # ---- encoding
+    def _encode_frames(self, spatial_pos, frames):
+        """frames: list of [B, N, 1] -> (tokens [B, Head, len(frames), dim], slice weights of the LAST frame [B, 1, N, M]).
+        The encoder's cached slice weights are left as the last frame's, as a frame-by-frame loop leaves them."""
+        B = frames[0].shape[0]
+        with torch.no_grad():
+            if self.batched_encoding and len(frames) > 1:
+                n = len(frames)
+                code = self.encoder.encode(spatial_pos.repeat(n, *([1] * (spatial_pos.dim() - 1))), torch.cat(frames, 0))
+                sw = self.encoder.get_attention_slice()[-B:].contiguous()
+                self.encoder.set_attention_slice(sw)
+                tokens = code.reshape(n, B, self.Head, self.dim).permute(1, 2, 0, 3).contiguous()
+            else:
+                codes = [self.encoder.encode(spatial_pos, f).reshape(B, self.Head, 1, self.dim) for f in frames]
+                sw = self.encoder.get_attention_slice()
+                tokens = torch.cat(codes, 2)
+        return tokens, sw
+
+    def _blocks(self, tokens):
+        mlp = self.mlp
+        pre, post = mlp.linear_pre[0], mlp.linear_post
+        for _ in range(self.layers):
+            tokens = self.attention(Fn.layer_norm(tokens, self.ln_1.weight, self.ln_1.bias), residual=tokens)
+            tokens = Fn.mlp_branch(tokens, self.ln_2.weight, self.ln_2.bias, mlp.act_name, pre.weight, pre.bias,
+                                   post.weight, post.bias, engine=self.engine)
+        return tokens
+
+    def _code(self, tokens):
+        B = tokens.shape[0]
+        return tokens[:, :, -1:, ].reshape(B, self.Head, self.M, self.C).contiguous()
+
+    def forward(self, spatial_pos, fx, y, use_gt=True):
+        """spatial_pos [B, N, 2] point coordinates, fx [B, N, T] the last T frames, y [B, N, 1] the next frame (read with
+        use_gt=True only) -> [B, N, 1]."""
+        self._refuse()
+        B = fx.shape[0]
+        frames = [fx[:, :, i:i + 1] for i in range(self.T)]
+        if use_gt:      # the target's slice weights: encoded with the T frames, last, so that they are the cached ones
+            tokens, sw = self._encode_frames(spatial_pos, frames + [y])
+            tokens = tokens[:, :, :self.T].contiguous()
+            self.slice_weights = sw
+        else:
+            tokens, _ = self._encode_frames(spatial_pos, frames)
+        tokens = self._blocks(tokens)
+        code = self._code(tokens)
+        self.code = code
+        if not use_gt:
+            if spatial_pos.dim() != 3 or spatial_pos.shape[-1] != 2:
+                raise ValueError("use_gt=False predicts the slice weights from the two point coordinates: spatial_pos "
+                                 f"must be [B, N, 2]; got {tuple(spatial_pos.shape)}")
+            wp = self.weight_projection
+            self.slice_weights = Fn.code_slice_weights(code.reshape(B, self.M, self.C), spatial_pos,
+                                                       wp.linear_pre[0].weight, wp.linear_pre[0].bias,
+                                                       wp.linears[0][0].weight, wp.linears[0][0].bias,
+                                                       wp.linear_post.weight, wp.linear_post.bias)
+        decoded = self.decode(code)
+        return Fn.head(Fn.layer_norm(decoded, self.ln_3.weight, self.ln_3.bias), self.mlp2.weight, self.mlp2.bias)
+
+    def solve_with_slice_learner(self, *args, **kwargs):
+        raise NotImplementedError("solve_with_slice_learner (reference SequenSolver.py:182-291) needs LearnSlice.py and "
+                                  "matplotlib plots, which this package does not restate; use forward(..., use_gt=False) "
+                                  "or decode() with slice weights of your own in `slice_weights`")
+
+    def get_code(self, spatial_pos, fx, y):
+        self._refuse()
+        tokens, _ = self._encode_frames(spatial_pos, [fx[:, :, i:i + 1] for i in range(self.T)])
+        return self._code(self._blocks(tokens))
+
+    def get_last_slice_weight(self, spatial_pos, fx):
+        with torch.no_grad():
+            self.encoder.encode(spatial_pos, fx[:, :, -1:])
+        return self.encoder.get_attention_slice()
+
+    def attention(self, tokens, residual=None):
+        """Attention among the T tokens: tokens [B, Head, T, dim] -> the same shape.  `residual` (extension): added in
+        the kernel's epilogue (the blocks use it)."""
+        self._refuse()
+        shp = tokens.shape
+        q = Fn.linear(tokens, self.to_q.weight, None, None, engine=self.engine)
+        k = Fn.linear(tokens, self.to_k.weight, None, None, engine=self.engine)
+        v = Fn.linear(tokens, self.to_v.weight, None, None, engine=self.engine)
+        flat = (-1, shp[-2], shp[-1])
+        res = None if residual is None else residual.reshape(flat)
+        return Fn.seq_attention(q.reshape(flat), k.reshape(flat), v.reshape(flat), self.scale, res=res).reshape(shp)
+
+    def decode(self, code):
+        return Fn.deslice_weights(code, self.slice_weights)
+
+    def freeze_attention(self):
+        frozen = (self.to_q, self.to_k, self.to_v, self.mlp, self.ln_1, self.ln_2)
+        for m in frozen + (self.softmax_attention,):
+            m.eval()
+        for m in frozen:
+            for param in m.parameters():
+                param.requires_grad = False

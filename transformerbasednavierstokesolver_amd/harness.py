@@ -14,6 +14,8 @@ so they cannot be imported; these functions reproduce their loops:
   central_diff / darcy_loss     exp_darcy.py:59-68, 209-234 (decode, rel-L2 + 0.1 x derivative loss,
   / darcy_train_step            clip, step) — the large-N single-call iteration
   autoencoder_train_step        auto_encoder.py:166-181 (the auto-encoder reconstructs its own input fx)
+  sequensolver_train_step       SequenSolver.py:572-606 (Tout teacher-forced calls of the latent sequence model, window slid
+  / sequensolver_rollout        with the true frame, summed rel-L2, one backward, step) and :613-630 (prediction feedback)
 """
 from __future__ import annotations
 
@@ -348,3 +350,53 @@ def autoencoder_train_step(model, optimizer, scheduler, x, fx, max_grad_norm=Non
     if scheduler is not None:
         scheduler.step()
     return loss.detach()
+
+
+def sequensolver_train_step(model, optimizer, scheduler, x, fx, yy, use_gt=True, max_grad_norm=None, grad_sync=None):
+    """One SequenSolver.py:581-606 iteration of the latent sequence model (SequenSolver.SequenSolver): Tout = yy.shape[-1]
+    teacher-forced calls model(x, fx, y, use_gt) on the window fx [B, N, T], which slides on with the TRUE frame y; the
+    TestLoss(size_average=False) terms are summed, then zero_grad, one backward, [grad_sync], [clip], step, [scheduler].
+    The reference hard-codes use_gt=True in this loop and switches to freeze_attention() from epoch 6 on; parameters
+    without requires_grad (the frozen encoder, whatever freeze_attention() froze) are in neither `optim.FusedAdamW` nor its
+    gradient bucket.  With FusedAdamW pass `grad_sync=optimizer.sync` and put the clip threshold in the optimizer.
+    Returns (summed step loss [detached], full loss of the Tout predictions against yy)."""
+    loss_fn = TestLoss(size_average=False)
+    bsz = x.shape[0]
+    with ops.weights_frozen():
+        loss, preds = 0, []
+        for t in range(yy.shape[-1]):
+            y = yy[..., t:t + 1]
+            im = model(x, fx, y, use_gt=use_gt)
+            loss = loss + loss_fn(im.reshape(bsz, -1), y.reshape(bsz, -1))
+            preds.append(im)
+            fx = torch.cat((fx[..., 1:], y), dim=-1)             # the ground truth enters the window
+        with torch.no_grad():
+            full = loss_fn(torch.cat(preds, -1).reshape(bsz, -1), yy.reshape(bsz, -1))
+        optimizer.zero_grad()
+        loss.backward()
+    if grad_sync is not None:
+        grad_sync()
+    if max_grad_norm is not None:
+        torch.nn.utils.clip_grad_norm_([p for p in model.parameters() if p.requires_grad], max_grad_norm)
+    optimizer.step()
+    if scheduler is not None:
+        scheduler.step()
+    return loss.detach(), full
+
+
+@torch.no_grad()
+def sequensolver_rollout(model, x, fx, yy, use_gt=True):
+    """SequenSolver.py:613-630: Tout = yy.shape[-1] calls with the PREDICTION fed back into the window (y still supplies
+    the slice weights when use_gt=True).  Returns (pred [B, N, Tout], summed step loss, full loss)."""
+    loss_fn = TestLoss(size_average=False)
+    bsz = x.shape[0]
+    loss, preds = 0, []
+    with ops.weights_frozen():
+        for t in range(yy.shape[-1]):
+            y = yy[..., t:t + 1]
+            im = model(x, fx, y, use_gt=use_gt)
+            loss = loss + loss_fn(im.reshape(bsz, -1), y.reshape(bsz, -1))
+            preds.append(im)
+            fx = torch.cat((fx[..., 1:], im), dim=-1)
+    pred = torch.cat(preds, -1)
+    return pred, loss, loss_fn(pred.reshape(bsz, -1), yy.reshape(bsz, -1))

@@ -644,6 +644,82 @@ def deslice_weights_bwd(code, w, dy, need_dcode=True, need_dw=True):
     return dcode, dw
 
 
+# ---------------------------------------------------------------------------------------------- SequenSolver stages
+# Sequence attention among the T frame tokens and the slice weights predicted from the code (pa2d_seq_attn_* /
+# pa2d_code_slice_weights_*): exact fp32 on every engine, so these take no `engine` either.
+SEQ_ATTN_MAX_T, SEQ_ATTN_MAX_DIM = 32, 1024
+CODE_SW_HIDDEN, CODE_SW_DEPTH = 64, 1
+
+
+def seq_attn_fwd(q, k, v, scale, res=None):
+    """q, k, v [B, T, dim] -> (out [B, T, dim], attn [B, T, T]) with attn = softmax(q k^T * scale), out = attn v (+ res)."""
+    _chk(q, k, v, res)
+    B, T, dim = q.shape
+    if k.shape != q.shape or v.shape != q.shape or (res is not None and res.shape != q.shape):
+        raise ValueError("q, k, v (and res) must share the shape [B, T, dim]")
+    out = torch.empty_like(q)
+    attn = torch.empty(B, T, T, dtype=torch.float32, device=q.device)
+    _lib.check(_L().pa2d_seq_attn_fwd(_p(q), _p(k), _p(v), _p(res), _p(out), _p(attn), B, T, dim, float(scale), _stream()),
+               "seq_attn_fwd")
+    return out, attn
+
+
+def seq_attn_bwd(q, k, v, attn, dout, scale):
+    """Returns (dq, dk, dv), each [B, T, dim]."""
+    _chk(q, k, v, attn, dout)
+    B, T, dim = q.shape
+    if dout.shape != q.shape or tuple(attn.shape) != (B, T, T):
+        raise ValueError("dout must be [B, T, dim] and attn [B, T, T]")
+    dq, dk, dv = torch.empty_like(q), torch.empty_like(q), torch.empty_like(q)
+    nb = _L().pa2d_seq_attn_bwd_workspace(B, T)
+    ws = _ws(nb, q)
+    _lib.check(_L().pa2d_seq_attn_bwd(_p(q), _p(k), _p(v), _p(attn), _p(dout), _p(dq), _p(dk), _p(dv), ws.data_ptr(), nb, B, T,
+                                      dim, float(scale), _stream()), "seq_attn_bwd")
+    return dq, dk, dv
+
+
+def _code_sw_shapes(code, pos, params):
+    w1, b1, w2, b2, w3, b3 = params
+    B, M, Cc = code.shape
+    N = pos.shape[1]
+    if tuple(pos.shape) != (B, N, 2):
+        raise ValueError(f"positions must be the two point coordinates [B, N, 2]; got {tuple(pos.shape)}")
+    hidden = w1.shape[0]
+    want = ((hidden, Cc + 2), (hidden,), (hidden, hidden), (hidden,), (1, hidden), (1,))
+    if tuple(tuple(p.shape) for p in params) != want:
+        raise ValueError("weight_projection must be MLP(C+2, hidden, 1) with one hidden layer: "
+                         f"shapes {want}, got {tuple(tuple(p.shape) for p in params)}")
+    return B, N, M, Cc, hidden
+
+
+def code_slice_weights_fwd(code, pos, params):
+    """code [B, M, C], pos [B, N, 2], params = (w1, b1, w2, b2, w3, b3) of weight_projection -> sw [B, 1, N, M]."""
+    _chk(code, pos, *params)
+    B, N, M, Cc, hidden = _code_sw_shapes(code, pos, params)
+    sw = torch.empty(B, 1, N, M, dtype=torch.float32, device=code.device)
+    e0, e1 = _events("code_slice_weights")
+    _lib.check(_L().pa2d_code_slice_weights_fwd(_p(code), _p(pos), *(_p(t) for t in params), _p(sw), B, N, M, Cc, hidden,
+                                                CODE_SW_DEPTH, _stream(), e0, e1), "code_slice_weights_fwd")
+    return sw
+
+
+def code_slice_weights_bwd(code, pos, params, dsw, need_dcode=True, into=None):
+    """Returns (dcode [B, M, C] or None, dw1, db1, dw2, db2, dw3, db3); `into` = the six gradient buffers to add into."""
+    _chk(code, pos, dsw, *params)
+    B, N, M, Cc, hidden = _code_sw_shapes(code, pos, params)
+    if tuple(dsw.shape) != (B, 1, N, M):
+        raise ValueError(f"dsw must be [B, 1, N, M] = {(B, 1, N, M)}; got {tuple(dsw.shape)}")
+    dcode = torch.empty_like(code) if need_dcode else None
+    grads, acc = _grad_outputs(into, tuple(p.shape for p in params), code)
+    nb = _L().pa2d_code_slice_weights_bwd_workspace(B, N, M, Cc)
+    ws = _ws(nb, code)
+    e0, e1 = _events("code_slice_weights_bwd")
+    _lib.check(_L().pa2d_code_slice_weights_bwd(_p(code), _p(pos), *(_p(t) for t in params), _p(dsw), _p(dcode),
+                                                *(_p(g) for g in grads), ws.data_ptr(), nb, B, N, M, Cc, hidden,
+                                                CODE_SW_DEPTH, acc, _stream(), e0, e1), "code_slice_weights_bwd")
+    return (dcode,) + tuple(grads)
+
+
 def head_fwd(xn2d, w, b):
     """y is always fp32 (the model output), whatever the storage type of the activations."""
     _chk(w, b)

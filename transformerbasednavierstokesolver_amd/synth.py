@@ -156,7 +156,7 @@ def spec_kind(key, shape):
         return "placeholder"
     if key.endswith(".bias"):
         return "bias"
-    if ".ln_" in key:
+    if ".ln_" in key or key.startswith("ln_"):      # top-level LayerNorms (SequenSolver) as well as a block's
         return "ln_w"
     if key.endswith(("to_q.weight", "to_k.weight")):
         return "qk_w"
