@@ -114,7 +114,8 @@ def test_conv_bf16(kernel_env, B, H, W, C, policy):
             assert torch.equal(ops.conv3x3x2_bwd(dout, xn, g(wx), g(wf), H, W)[0], dxn)
 
 
-@pytest.mark.parametrize("B,N,heads,D,M", [(2, 30, 4, 8, 12), (2, 4096, 8, 32, 64), (1, 1000, 8, 16, 128)])
+@pytest.mark.parametrize("B,N,heads,D,M", [(2, 30, 4, 8, 12), (2, 4096, 8, 32, 64), (1, 1000, 8, 16, 128),
+                                           (1, 1000, 4, 32, 128)])      # last: backward on the exact-fp32 kernel, bf16 storage
 def test_slice_path_bf16(B, N, heads, D, M):
     from transformerbasednavierstokesolver_amd import ops
     from oracle import transolver_oracle as orc

@@ -244,6 +244,8 @@ SLICE_CASES = [  # B, N, heads, D, M
     (2, 4096, 8, 32, 64),   # NS benchmark geometry (C=256)
     (1, 1000, 8, 16, 128),  # Darcy-like geometry (D=16, M=128), ragged N
     (1, 200, 2, 64, 20),
+    (1, 1000, 4, 8, 128),   # M = 128 with D != 16: every engine's backward runs the exact-fp32 kernel (D = 8: the only
+                            # such head width whose token backward fits the LDS)
 ]
 
 

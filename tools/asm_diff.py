@@ -5,7 +5,9 @@ Usage:
     hipcc -S --cuda-device-only --offload-arch=gfx950 -O3 -std=c++17 -fPIC [-fno-slp-vectorize] X.hip -o OUT/X.s
     python tools/asm_diff.py OLD_DIR NEW_DIR
 
-Every kernel of OLD_DIR/*.s is looked up in NEW_DIR/*.s of the same name.  Names are compared demangled, with a
+Every kernel of OLD_DIR/*.s is looked up in NEW_DIR/*.s of the same name.  Names are compared demangled, by kernel name and
+template arguments only (the parameter types are ignored: a parameter block that is renamed or moved between namespaces
+changes the mangled name and nothing else; no kernel of the library is overloaded on its parameters), with a
 trailing template argument `TAPS = 9` of the new build dropped (the 3x3 instantiations of kernels that gained a tap-count
 parameter, and kernels that became templates on it).  Bodies are compared after dropping comments, debug directives and
 the numbering of local labels and the text-section directive (a function template lives in a comdat section of its own);
@@ -26,15 +28,26 @@ def demangle(names):
     return dict(zip(names, out.splitlines()))
 
 
+_MANGLED = re.compile(r"^(_Z\d+[A-Za-z_]\w*?I(?:L[a-z]\d+E|DF16b|[a-z])+E)v")
+
+
 def canonical(dem):
     if dem.startswith("_Z"):                  # not demangled (e.g. __bf16 arguments): drop a trailing Li9E template arg
-        return re.sub(r"Li9EEv", "Ev", dem)
+        dem = re.sub(r"Li9EEv", "Ev", dem)
+        m = _MANGLED.match(dem)               # name + template arguments; the return type and parameter types go
+        return m.group(1) if m else dem
     if dem.startswith("void "):               # a function template's demangled name carries its return type
         dem = dem[len("void "):]
-    head, paren, tail = dem.partition("(")
-    head = re.sub(r", 9>$", ">", head)        # kernel<..., 9>  -> kernel<...>
-    head = re.sub(r"<9>$", "", head)          # kernel<9>       -> kernel
-    return head + paren + tail
+    if dem.endswith(")"):                     # drop the parameter list: the balanced group that ends the name
+        depth, i = 0, len(dem)
+        while i > 0:
+            i -= 1
+            depth += (dem[i] == ")") - (dem[i] == "(")
+            if depth == 0:
+                break
+        dem = dem[:i]
+    dem = re.sub(r", 9>$", ">", dem)          # kernel<..., 9>  -> kernel<...>
+    return re.sub(r"<9>$", "", dem)           # kernel<9>       -> kernel
 
 
 def bodies(path):

@@ -9,9 +9,7 @@
 // chunk index XOR-swizzled by ((row&3)<<2 | (row>>2)&3), which keeps the transposed reads conflict-free.
 // NT = 3: six MFMA terms of the exact hi+mid+lo split (fp32 accuracy); NT = 1: bf16 compute.
 #include "pa2d_gemm_common.h"
-
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
+#include "pa2d_bf16_split.h"      // s16x4 / s16x8 of the transposed LDS reads
 
 struct MCPlanesParams {
     const void* PA; int chA;      // dOut planes, chA = 2C/32 chunks per row

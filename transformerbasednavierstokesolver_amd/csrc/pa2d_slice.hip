@@ -15,10 +15,13 @@
 // feeds MFMA step t with element t): legal because A and B use the same permutation.
 // X / F / dY fragments are loaded straight from global memory (each element exactly once, 64-B
 // contiguous per point per instruction); no LDS in the forward kernels.
-#include "pa2d_internal.h"
+//
+// This file owns the exact-fp32 kernels (engine f32; the backward kernel also takes, for every engine and storage type,
+// the shapes the v3 backward is not built for) and the C ABI of every slice stage.  The v3 kernels on the bf16 matrix
+// cores are pa2d_slice3.hip (scatter, de-slice) and pa2d_slice3_bwd.hip; pa2d_slice_common.h holds what the three share.
+#include "pa2d_slice_common.h"
 #include <stdlib.h>
 
-#define NEG_BIG (-1e30f)
 #define PA2D_ENGINE_BF16_ID 2
 
 int pa2d_launch_reduce(const float* slab, int nslab, long long count, float* out, hipStream_t st);
@@ -34,41 +37,9 @@ struct SCfg {
 __device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
-// Reductions across the 16 lanes of a DPP row (lanes 16g..16g+15) with VALU-DPP operands instead
-// of ds_bpermute: quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror, row_mirror.  After the
-// four steps every lane of the row holds the row result.
-template <int CTRL>
-__device__ __forceinline__ float dpp_mov(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float row16_max(float v) {
-    v = fmaxf(v, dpp_mov<0xB1>(v));
-    v = fmaxf(v, dpp_mov<0x4E>(v));
-    v = fmaxf(v, dpp_mov<0x141>(v));
-    v = fmaxf(v, dpp_mov<0x140>(v));
-    return v;
-}
-__device__ __forceinline__ float row16_sum(float v) {
-    v += dpp_mov<0xB1>(v);
-    v += dpp_mov<0x4E>(v);
-    v += dpp_mov<0x141>(v);
-    v += dpp_mov<0x140>(v);
-    return v;
-}
 // exp(x) for x <= 0 (softmax after max subtraction) on the hardware exponential: 2^(x*log2 e).
 // Relative error ~1e-7 near 0 where the weights matter, growing only for terms that are ~0 anyway.
 __device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f); }
-__device__ __forceinline__ float kq_max(float v) {   // across the 4 lane groups l, l^16, l^32, l^48
-    v = fmaxf(v, __shfl_xor(v, 16, 64));
-    v = fmaxf(v, __shfl_xor(v, 32, 64));
-    return v;
-}
-__device__ __forceinline__ float kq_sum(float v) {
-    v += __shfl_xor(v, 16, 64);
-    v += __shfl_xor(v, 32, 64);
-    return v;
-}
-__device__ __forceinline__ float clamp_tau(float t) { return fminf(fmaxf(t, 0.1f), 5.0f); }
 
 // fragment of a [16 rows][D] panel for a contraction over d: lane (row = l&15, kq = l>>4) gets
 // elements k(v,t) = 4*VEC*v + VEC*kq + t of its row.
@@ -104,17 +75,6 @@ __device__ __forceinline__ void buf_kfrag(__amdgpu_buffer_rsrc_t r, unsigned off
         }
     }
 }
-
-struct SliceParams {
-    const void* xm; long long ldx;      // x_mid rows: xm[(b*N+n)*ldx + h*D + d]   (float or bf16 storage)
-    const void* v; long long ldv;       // values scattered (fx_mid forward, dY in backward phase A)
-    const float* ws; const float* bs; const float* temperature;   // [M,D], [M], [heads]
-    float* spart; float* npart;         // [B,heads,nchunk,M,D], [B,heads,nchunk,M] (npart may be null)
-    int B, N, heads, M, nchunk, ppc;    // ppc = points per chunk (multiple of 16)
-    unsigned x_bytes, v_bytes;          // extents for the buffer descriptors
-    int clamp;                          // 1: clamp(temperature, .1, 5) (structured mesh); 0: raw (irregular mesh)
-    int xcd_map;                        // workgroup numbering, see slice_decode
-};
 
 // S_partial[m][d] = sum_{n in chunk} W[n][m] * V[n][d];  n_partial[m] = sum_n W[n][m]
 template <int D, int MT, typename T>
@@ -218,7 +178,7 @@ __global__ __launch_bounds__(256) void slice_scatter_kernel(const SliceParams p)
 #undef SC_LOAD
     // deterministic cross-wave reduction: waves add in order 0,1,2,3
 #pragma unroll
-    for (int mt = 0; mt < MT; ++mt) nacc[mt] = kq_sum(nacc[mt]);
+    for (int mt = 0; mt < MT; ++mt) nacc[mt] = kq_sum_shfl(nacc[mt]);
     for (int wv = 0; wv < 4; ++wv) {
         if (wave == wv) {
 #pragma unroll
@@ -240,16 +200,6 @@ __global__ __launch_bounds__(256) void slice_scatter_kernel(const SliceParams p)
     if (p.npart)
         for (int i = tid; i < p.M; i += 256) p.npart[(size_t)bid * p.M + i] = nbuf[i];
 }
-
-struct DesliceParams {
-    const void* xm; long long ldx;
-    const float* o;                     // [B,heads,M,D]
-    const float* ws; const float* bs; const float* temperature;
-    void* y; long long ldy;             // y[(b*N+n)*ldy + h*D + d]
-    int B, N, heads, M, nchunk, ppc;
-    unsigned x_bytes, y_bytes;
-    int clamp, xcd_map;
-};
 
 // Y[n][h*D+d] = sum_m W[n][m] * O[m][d]
 template <int D, int MT, typename T>
@@ -306,7 +256,7 @@ __global__ __launch_bounds__(256) void deslice_kernel(const DesliceParams p) {
                 mx = fmaxf(mx, z);
             }
         }
-        mx = kq_max(mx);
+        mx = kq_max_shfl(mx);
         float sm = 0.f;
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt)
@@ -316,7 +266,7 @@ __global__ __launch_bounds__(256) void deslice_kernel(const DesliceParams p) {
                 w[mt][r] = e;
                 sm += e;
             }
-        sm = kq_sum(sm);
+        sm = kq_sum_shfl(sm);
         const float inv = 1.0f / sm;
         f32x4 yacc[DT];
 #pragma unroll
@@ -340,29 +290,31 @@ __global__ __launch_bounds__(256) void deslice_kernel(const DesliceParams p) {
     }
 }
 
-struct SliceBwdParams {
-    const void* xm; long long ldx;      // x_mid
-    const void* fm; long long ldf;      // fx_mid
-    const void* dy; long long lddy;     // gradient w.r.t. de-sliced y
+// The exact-fp32 backward keeps the argument layout it was compiled with before the parameter blocks were shared (no nrm,
+// a spare word behind planes_bytes): with its fields moved to the offsets of SliceBwdParams hipcc merges the argument
+// loads differently, and register allocation and schedule of all 64 instantiations change with them.
+struct SliceBwdF32Params {
+    const void* xm; long long ldx;
+    const void* fm; long long ldf;
+    const void* dy; long long lddy;
     const float* ws; const float* bs; const float* temperature;
-    const float* o; const float* ds; const float* dn;   // [B,heads,M,D] x2, [B,heads,M]
-    void* dxm; long long lddx;          // outputs
+    const float* o; const float* ds; const float* dn;
+    void* dxm; long long lddx;
     void* dfm; long long lddf;
-    void* planes; unsigned planes_bytes; int planes_nt;   // planes_nt > 0: [dX | dF] is written ONLY as the bf16 plane image
-                                        // [row][2C/32][nt][32] the conv GEMMs stage (no fp32 dxm / dfm), and the
-                                        // column sums of dX / dF (= the conv bias gradients) go to the block record
-    int stride;                         // floats per block record: M*D (dWs) + M (dbs) + 1 (dtau) + 2*D (dbx | dbf)
-    float* part;                        // per block: [M*D (dWs) | M (dbs) | 1 (dtau)]
+    void* planes; unsigned planes_bytes; int spare;
+    int stride;
+    float* part;
     int B, N, heads, M, nchunk, ppc;
     unsigned x_bytes, f_bytes, dy_bytes, dx_bytes, df_bytes;
     int clamp, xcd_map;
 };
+static_assert(sizeof(SliceBwdF32Params) == 216, "kernel-argument layout");
 
 // Backward phase C (per point): recompute W, then
 //   dW = dY.O^T + F.dS^T + dn ; dL = W*(dW - rowsum(dW*W)) ; dF = W.dS ; dX = dL.Ws/tau
 //   dWs += (dL/tau)^T.X ; dbs += sum dL/tau ; dtau -= sum(dL*L)/tau
 template <int D, int MT, typename T, int PL = 0>
-__global__ __launch_bounds__(256, (MT <= 4 && D <= 32 && sizeof(T) == 4) ? 2 : 1) void slice_bwd_kernel(const SliceBwdParams p) {
+__global__ __launch_bounds__(256, (MT <= 4 && D <= 32 && sizeof(T) == 4) ? 2 : 1) void slice_bwd_kernel(const SliceBwdF32Params p) {
     constexpr int KS = SCfg<D>::KS, DT = SCfg<D>::DT, VEC = SCfg<D>::VEC, NV = SCfg<D>::NV;
     constexpr unsigned ES = Act<T>::ES;
     constexpr int MP = 16 * MT, DP = 16 * DT, P = DP + 4;   // LDS row pitch (floats), 16-B aligned
@@ -498,7 +450,7 @@ __global__ __launch_bounds__(256, (MT <= 4 && D <= 32 && sizeof(T) == 4) ? 2 : 1
                 z[mt][r] = zz;
                 mx = fmaxf(mx, zz);
             }
-        mx = kq_max(mx);
+        mx = kq_max_shfl(mx);
         float sm = 0.f;
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt)
@@ -508,7 +460,7 @@ __global__ __launch_bounds__(256, (MT <= 4 && D <= 32 && sizeof(T) == 4) ? 2 : 1
                 w[mt][r] = e;
                 sm += e;
             }
-        sm = kq_sum(sm);
+        sm = kq_sum_shfl(sm);
         const float inv = pv ? 1.0f / sm : 0.f;
         float rd = 0.f;
 #pragma unroll
@@ -520,7 +472,7 @@ __global__ __launch_bounds__(256, (MT <= 4 && D <= 32 && sizeof(T) == 4) ? 2 : 1
                 dw[mt][r] += dnL[m];
                 rd += dw[mt][r] * w[mt][r];
             }
-        rd = kq_sum(rd);
+        rd = kq_sum_shfl(rd);
         // dL (stored in dw), dbs / dtau accumulation
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt)
@@ -713,16 +665,16 @@ __global__ __launch_bounds__(256) void conv_bias_finalize_kernel(const float* __
 }
 
 // ---------------------------------------------------------------------------------------------
-// dispatch over the compile-time (D, MT) grid
+// launchers of the exact-fp32 kernels over the compile-time (D, MT) grid (fp32 storage only: bf16 storage is always v3)
 template <int D, int MT>
-static void launch_scatter_t(const SliceParams& p, int grid, hipStream_t st, bool bf) {
-    if (bf) hipLaunchKernelGGL((slice_scatter_kernel<D, MT, bf16_t>), dim3(slice_grid(grid)), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((slice_scatter_kernel<D, MT, float>), dim3(slice_grid(grid)), dim3(256), 0, st, p);
+static int launch_scatter_t(const SliceParams& p, hipStream_t st) {
+    hipLaunchKernelGGL((slice_scatter_kernel<D, MT, float>), dim3(slice_grid(p.B * p.heads * p.nchunk)), dim3(256), 0, st, p);
+    return PA2D_OK;
 }
 template <int D, int MT>
-static void launch_deslice_t(const DesliceParams& p, int grid, hipStream_t st, bool bf) {
-    if (bf) hipLaunchKernelGGL((deslice_kernel<D, MT, bf16_t>), dim3(slice_grid(grid)), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((deslice_kernel<D, MT, float>), dim3(slice_grid(grid)), dim3(256), 0, st, p);
+static int launch_deslice_t(const DesliceParams& p, hipStream_t st) {
+    hipLaunchKernelGGL((deslice_kernel<D, MT, float>), dim3(slice_grid(p.B * p.heads * p.nchunk)), dim3(256), 0, st, p);
+    return PA2D_OK;
 }
 template <int D, int MT>
 static size_t bwd_smem_bytes() {
@@ -731,93 +683,57 @@ static size_t bwd_smem_bytes() {
     return sizeof(float) * (size_t)(3 * MP * P + 2 * MP + 4 * 16 * TP);
 }
 template <int D, int MT, typename T, int PL>
-static int launch_bwd_one(const SliceBwdParams& p, int grid, hipStream_t st, size_t smem) {
+static int launch_bwd_one(const SliceBwdF32Params& p, hipStream_t st) {
+    const size_t smem = bwd_smem_bytes<D, MT>();
     if (smem > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&slice_bwd_kernel<D, MT, T, PL>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
         if (e != hipSuccess) return (int)e;
     }
-    hipLaunchKernelGGL((slice_bwd_kernel<D, MT, T, PL>), dim3(slice_grid(grid)), dim3(256), smem, st, p);
+    hipLaunchKernelGGL((slice_bwd_kernel<D, MT, T, PL>), dim3(slice_grid(p.B * p.heads * p.nchunk)), dim3(256), smem, st, p);
     return PA2D_OK;
 }
 template <int D, int MT>
-static int launch_bwd_t(const SliceBwdParams& p, int grid, hipStream_t st, bool bf) {
-    const size_t smem = bwd_smem_bytes<D, MT>();
-    if (p.planes_nt == 3) return bf ? PA2D_ERR_ARG : launch_bwd_one<D, MT, float, 3>(p, grid, st, smem);
-    if (p.planes_nt == 1) return bf ? PA2D_ERR_ARG : launch_bwd_one<D, MT, float, 1>(p, grid, st, smem);
-    return bf ? launch_bwd_one<D, MT, bf16_t, 0>(p, grid, st, smem) : launch_bwd_one<D, MT, float, 0>(p, grid, st, smem);
+static int launch_bwd_t(const SliceBwdF32Params& p, int planes_nt, bool bf, hipStream_t st) {
+    if (planes_nt == 3) return bf ? PA2D_ERR_ARG : launch_bwd_one<D, MT, float, 3>(p, st);
+    if (planes_nt == 1) return bf ? PA2D_ERR_ARG : launch_bwd_one<D, MT, float, 1>(p, st);
+    return bf ? launch_bwd_one<D, MT, bf16_t, 0>(p, st) : launch_bwd_one<D, MT, float, 0>(p, st);
 }
 
-#define DISPATCH_MT(D_, CALL)                                    \
-    switch (mt) {                                                \
-        case 1: CALL(D_, 1); break;                              \
-        case 2: CALL(D_, 2); break;                              \
-        case 4: CALL(D_, 4); break;                              \
-        case 8: CALL(D_, 8); break;                              \
-        default: return PA2D_ERR_UNSUPPORTED;                    \
-    }
-#define DISPATCH_D(CALL)                                         \
-    switch (D) {                                                 \
-        case 8: DISPATCH_MT(8, CALL) break;                      \
-        case 16: DISPATCH_MT(16, CALL) break;                    \
-        case 32: DISPATCH_MT(32, CALL) break;                    \
-        case 64: DISPATCH_MT(64, CALL) break;                    \
-        default: return PA2D_ERR_UNSUPPORTED;                    \
-    }
-
-static int mt_for(int M) {
-    if (M <= 16) return 1;
-    if (M <= 32) return 2;
-    if (M <= 64) return 4;
-    if (M <= 128) return 8;
-    return 0;
+static int launch_scatter_f32(const SliceParams& p, int D, int mt, hipStream_t st) {
+#define CALL_SC(D_, MT_) launch_scatter_t<D_, MT_>(p, st)
+    SLICE_DISPATCH_D(CALL_SC)
+    return PA2D_ERR_UNSUPPORTED;
+}
+static int launch_deslice_f32(const DesliceParams& p, int D, int mt, hipStream_t st) {
+#define CALL_DS(D_, MT_) launch_deslice_t<D_, MT_>(p, st)
+    SLICE_DISPATCH_D(CALL_DS)
+    return PA2D_ERR_UNSUPPORTED;
+}
+static int launch_slice_bwd_f32(const SliceBwdParams& s, int D, int mt, int planes_nt, bool bf, hipStream_t st) {
+    const SliceBwdF32Params p = {s.xm, s.ldx, s.fm, s.ldf, s.dy, s.lddy, s.ws, s.bs, s.temperature, s.o, s.ds, s.dn,
+                                 s.dxm, s.lddx, s.dfm, s.lddf, s.planes, s.planes_bytes, 0, s.stride, s.part,
+                                 s.B, s.N, s.heads, s.M, s.nchunk, s.ppc,
+                                 s.x_bytes, s.f_bytes, s.dy_bytes, s.dx_bytes, s.df_bytes, s.clamp, s.xcd_map};
+#define CALL_BW(D_, MT_) launch_bwd_t<D_, MT_>(p, planes_nt, bf, st)
+    SLICE_DISPATCH_D(CALL_BW)
+    return PA2D_ERR_UNSUPPORTED;
 }
 
 extern "C" {
 
-// number of point chunks per (batch, head) and points per chunk used by every slice-stage kernel
-int pa2d_slice_nchunk(int B, int N, int heads) {
-    // one WAVE of the v3 kernels owns a (batch, head, chunk) unit: enough units for two waves on each of the 1024 SIMDs,
-    // at least 128 points (4 groups of 32) per unit; the token kernels sum any number of chunk records
-    const int bh = B * heads > 0 ? B * heads : 1;
-    if (N < 1) return 1;
-    int nchunk = ceil_div(2048, bh);
-    const int maxc = ceil_div(N, 128);
-    if (nchunk > maxc) nchunk = maxc;
-    if (nchunk < 1) nchunk = 1;
-    const int ppc = ceil_div(ceil_div(N, nchunk), 32) * 32;
-    return ceil_div(N, ppc);
-}
-static int ppc_for(int N, int nchunk) { return ceil_div(ceil_div(N, nchunk), 32) * 32; }
 // The slice stages exist twice.  PA2D_ENGINE_F32: the kernels of this file, every contraction on the exact-fp32 matrix
 // instruction (v_mfma_f32_16x16x4_f32).  PA2D_ENGINE_SPLIT / _BF16 and the bf16-storage entry points: the v3 kernels
 // (pa2d_slice3.hip, pa2d_slice3_bwd.hip), bf16 MFMA on exact 3-plane operand splits with fp32 accumulation.  The choice
 // is the caller's `engine` argument — nothing here reads the environment for it.
-__attribute__((visibility("hidden"))) int pa2d_launch_scatter3(const void* xm, long long ldx, const void* v, long long ldv, const float* ws, const float* bs,
-                           const float* temperature, float* spart, float* npart, int B, int N, int heads, int D, int M,
-                           int mt, int nchunk, int ppc, unsigned x_bytes, unsigned v_bytes, int clamp, int xcd_map, bool bf,
-                           hipStream_t st);
-__attribute__((visibility("hidden"))) int pa2d_launch_deslice3(const void* xm, long long ldx, const float* o, const float* ws, const float* bs,
-                           const float* temperature, void* y, long long ldy, int B, int N, int heads, int D, int M, int mt,
-                           int nchunk, int ppc, unsigned x_bytes, unsigned y_bytes, int clamp, bool bf, hipStream_t st);
-__attribute__((visibility("hidden"))) int pa2d_launch_slice_bwd3(
-    const void* xm, long long ldx, const void* fm, long long ldf, const void* dy, long long lddy, const float* ws,
-    const float* bs, const float* temperature, const float* o, const float* ds, const float* dn, const float* nrm, void* dxm,
-    long long lddx, void* dfm, long long lddf, void* planes, unsigned planes_bytes, int planes_nt, int stride, float* part,
-    int B, int N, int heads, int D, int M, int mt, int nchunk, int ppc, unsigned x_bytes, unsigned f_bytes,
-    unsigned dy_bytes, unsigned dx_bytes, unsigned df_bytes, int clamp, int xcd_map, bool bf, hipStream_t st);
+
+// number of point chunks per (batch, head) used by the scatter / de-slice kernels: one WAVE of the v3 kernels owns a
+// (batch, head, chunk) unit, enough units for two waves on each of the 1024 SIMDs; the token kernels sum any number of
+// chunk records
+int pa2d_slice_nchunk(int B, int N, int heads) { return slice_nchunk_for(B, N, heads, 2048); }
 // chunking of the slice BACKWARD kernel (its partial-sum records are its own): one 4-wave workgroup per (batch, head,
-// chunk), about two workgroups per CU in one round, at least 128 points per workgroup
-static int bwd_nchunk(int B, int N, int heads) {
-    const int bh = B * heads > 0 ? B * heads : 1;
-    if (N < 1) return 1;
-    int nchunk = ceil_div(512, bh);
-    const int maxc = ceil_div(N, 128);
-    if (nchunk > maxc) nchunk = maxc;
-    if (nchunk < 1) nchunk = 1;
-    const int ppc = ceil_div(ceil_div(N, nchunk), 32) * 32;
-    return ceil_div(N, ppc);
-}
+// chunk), about two workgroups per CU in one round
+static int bwd_nchunk(int B, int N, int heads) { return slice_nchunk_for(B, N, heads, 512); }
 static int slice_xcd_map() { return pa2d_env().slice_map; }      // PA2D_SLICE_MAP=legacy: chunk-fastest numbering (A/B timing)
 static bool slice_v3(int engine, bool bf) { return bf || engine != 0; }
 size_t pa2d_slice_bwd_workspace(int B, int N, int heads, int D, int M);
@@ -830,29 +746,16 @@ static int slice_scatter_impl(const void* xm, long long ldx, const void* v, long
     const int mt = mt_for(M);
     if ((ldx & 3) || (D & 7) || engine < 0 || engine > 2) return PA2D_ERR_ARG;
     if (B <= 0 || N <= 0) return PA2D_OK;
-    const unsigned long long es = bf ? 2ull : 4ull;
+    const unsigned long long es = bf ? 2ull : 4ull, rows = (unsigned long long)B * N, w = (unsigned long long)heads * D;
     SliceParams p;
     p.xm = xm; p.ldx = ldx; p.v = v; p.ldv = ldv; p.ws = ws; p.bs = bs; p.temperature = temperature;
     p.spart = spart; p.npart = npart; p.B = B; p.N = N; p.heads = heads; p.M = M; p.clamp = clamp_temperature; p.xcd_map = slice_xcd_map();
     p.nchunk = pa2d_slice_nchunk(B, N, heads);
     p.ppc = ppc_for(N, p.nchunk);
-    {
-        const unsigned long long rows = (unsigned long long)B * N;
-        const unsigned long long xb = ((rows - 1) * ldx + (unsigned long long)heads * D) * es;
-        const unsigned long long vb = ((rows - 1) * ldv + (unsigned long long)heads * D) * es;
-        if (xb >= 0xFFFFFFF0ull || vb >= 0xFFFFFFF0ull) return PA2D_ERR_UNSUPPORTED;
-        p.x_bytes = (unsigned)xb; p.v_bytes = (unsigned)vb;
-    }
-    const int grid = B * heads * p.nchunk;
+    if (slice_extent(rows, ldx, w, es, p.x_bytes) || slice_extent(rows, ldv, w, es, p.v_bytes)) return PA2D_ERR_UNSUPPORTED;
     if (ev_start && hipEventRecord(ev_start, st) != hipSuccess) return PA2D_ERR_ARG;
-    if (slice_v3(engine, bf)) {
-        const int rc = pa2d_launch_scatter3(xm, ldx, v, ldv, ws, bs, temperature, spart, npart, B, N, heads, D, M, mt,
-                                            p.nchunk, p.ppc, p.x_bytes, p.v_bytes, clamp_temperature, p.xcd_map, bf, st);
-        if (rc) return rc;
-    } else {
-#define CALL_SC(D_, MT_) launch_scatter_t<D_, MT_>(p, grid, st, bf)
-        DISPATCH_D(CALL_SC)
-    }
+    const int rc = slice_v3(engine, bf) ? launch_scatter3(p, D, mt, bf, st) : launch_scatter_f32(p, D, mt, st);
+    if (rc) return rc;
     PA2D_CHECK_LAUNCH();
     if (ev_stop && hipEventRecord(ev_stop, st) != hipSuccess) return PA2D_ERR_ARG;
     return PA2D_OK;
@@ -864,29 +767,16 @@ static int deslice_impl(const void* xm, long long ldx, const float* o, const flo
     const int mt = mt_for(M);
     if ((ldx & 3) || (ldy & 3) || (D & 7) || engine < 0 || engine > 2) return PA2D_ERR_ARG;
     if (B <= 0 || N <= 0) return PA2D_OK;
-    const unsigned long long es = bf ? 2ull : 4ull;
+    const unsigned long long es = bf ? 2ull : 4ull, rows = (unsigned long long)B * N, w = (unsigned long long)heads * D;
     DesliceParams p;
     p.xm = xm; p.ldx = ldx; p.o = o; p.ws = ws; p.bs = bs; p.temperature = temperature; p.y = y; p.ldy = ldy;
     p.B = B; p.N = N; p.heads = heads; p.M = M; p.clamp = clamp_temperature; p.xcd_map = slice_xcd_map();
     p.nchunk = pa2d_slice_nchunk(B, N, heads);
     p.ppc = ppc_for(N, p.nchunk);
-    {
-        const unsigned long long rows = (unsigned long long)B * N;
-        const unsigned long long xb = ((rows - 1) * ldx + (unsigned long long)heads * D) * es;
-        const unsigned long long yb = ((rows - 1) * ldy + (unsigned long long)heads * D) * es;
-        if (xb >= 0xFFFFFFF0ull || yb >= 0xFFFFFFF0ull) return PA2D_ERR_UNSUPPORTED;
-        p.x_bytes = (unsigned)xb; p.y_bytes = (unsigned)yb;
-    }
-    const int grid = B * heads * p.nchunk;
+    if (slice_extent(rows, ldx, w, es, p.x_bytes) || slice_extent(rows, ldy, w, es, p.y_bytes)) return PA2D_ERR_UNSUPPORTED;
     if (ev_start && hipEventRecord(ev_start, st) != hipSuccess) return PA2D_ERR_ARG;
-    if (slice_v3(engine, bf)) {
-        const int rc = pa2d_launch_deslice3(xm, ldx, o, ws, bs, temperature, y, ldy, B, N, heads, D, M, mt, p.nchunk, p.ppc,
-                                            p.x_bytes, p.y_bytes, clamp_temperature, bf, st);
-        if (rc) return rc;
-    } else {
-#define CALL_DS(D_, MT_) launch_deslice_t<D_, MT_>(p, grid, st, bf)
-        DISPATCH_D(CALL_DS)
-    }
+    const int rc = slice_v3(engine, bf) ? launch_deslice3(p, D, mt, bf, st) : launch_deslice_f32(p, D, mt, st);
+    if (rc) return rc;
     PA2D_CHECK_LAUNCH();
     if (ev_stop && hipEventRecord(ev_stop, st) != hipSuccess) return PA2D_ERR_ARG;
     return PA2D_OK;
@@ -910,50 +800,36 @@ static int slice_bwd_impl(const void* xm, long long ldx, const void* fm, long lo
         return rz ? rz : pa2d_zero(dtemperature, sizeof(float) * heads, st);
     }
     if (ws_bytes < pa2d_slice_bwd_workspace(B, N, heads, D, M)) return PA2D_ERR_WORKSPACE;
-    const unsigned long long es = bf ? 2ull : 4ull;
+    const unsigned long long es = bf ? 2ull : 4ull, rows = (unsigned long long)B * N, w = (unsigned long long)heads * D;
     SliceBwdParams p;
     p.xm = xm; p.ldx = ldx; p.fm = fm; p.ldf = ldf; p.dy = dy; p.lddy = lddy; p.ws = ws; p.bs = bs;
-    p.temperature = temperature; p.o = o; p.ds = ds; p.dn = dn; p.dxm = dxm; p.lddx = lddx; p.dfm = dfm;
+    p.temperature = temperature; p.o = o; p.ds = ds; p.dn = dn; p.nrm = nrm; p.dxm = dxm; p.lddx = lddx; p.dfm = dfm;
     p.lddf = lddf; p.part = (float*)ws_buf; p.B = B; p.N = N; p.heads = heads; p.M = M; p.clamp = clamp_temperature;
     p.xcd_map = slice_xcd_map();
     p.nchunk = bwd_nchunk(B, N, heads);
     p.ppc = ppc_for(N, p.nchunk);
     p.stride = M * D + M + 1 + 2 * D;
-    p.planes = planes; p.planes_nt = planes ? planes_nt : 0; p.planes_bytes = 0;
-    if (planes) {
+    p.planes = planes; p.planes_bytes = 0;
+    if (!planes) planes_nt = 0;
+    else {
         if ((planes_nt != 1 && planes_nt != 3) || ((heads * D) & 31) || (D & 3)) return PA2D_ERR_UNSUPPORTED;
         const unsigned long long pb = (unsigned long long)B * N * (2ull * heads * D) * planes_nt * 2ull;
         if (pb >= 0xFFFFFFF0ull) return PA2D_ERR_UNSUPPORTED;
         p.planes_bytes = (unsigned)pb;
-        if (!dxm) { p.dxm = const_cast<void*>(xm); lddx = ldx; p.lddx = ldx; }     // descriptors need a base; nothing is stored there
-        if (!dfm) { p.dfm = const_cast<void*>(fm); lddf = ldf; p.lddf = ldf; }
+        if (!dxm) { p.dxm = const_cast<void*>(xm); p.lddx = ldx; }     // descriptors need a base; nothing is stored there
+        if (!dfm) { p.dfm = const_cast<void*>(fm); p.lddf = ldf; }
     }
-    {
-        const unsigned long long rows = (unsigned long long)B * N, w = (unsigned long long)heads * D;
-        const unsigned long long e[5] = {((rows - 1) * ldx + w) * es, ((rows - 1) * ldf + w) * es,
-                                         ((rows - 1) * lddy + w) * es, ((rows - 1) * lddx + w) * es,
-                                         ((rows - 1) * lddf + w) * es};
-        for (int i = 0; i < 5; ++i)
-            if (e[i] >= 0xFFFFFFF0ull) return PA2D_ERR_UNSUPPORTED;
-        p.x_bytes = (unsigned)e[0]; p.f_bytes = (unsigned)e[1]; p.dy_bytes = (unsigned)e[2];
-        p.dx_bytes = (unsigned)e[3]; p.df_bytes = (unsigned)e[4];
-    }
+    if (slice_extent(rows, ldx, w, es, p.x_bytes) || slice_extent(rows, ldf, w, es, p.f_bytes) ||
+        slice_extent(rows, lddy, w, es, p.dy_bytes) || slice_extent(rows, p.lddx, w, es, p.dx_bytes) ||
+        slice_extent(rows, p.lddf, w, es, p.df_bytes))
+        return PA2D_ERR_UNSUPPORTED;
     const int grid = B * heads * p.nchunk;
-    int rc = PA2D_OK;
     if (ev_start && hipEventRecord(ev_start, st) != hipSuccess) return PA2D_ERR_ARG;
-    if (slice_v3(engine, bf)) {
-        if (planes && !nrm) return PA2D_ERR_ARG;
-        rc = pa2d_launch_slice_bwd3(p.xm, p.ldx, p.fm, p.ldf, p.dy, p.lddy, ws, bs, temperature, o, ds, dn, nrm, p.dxm, p.lddx, p.dfm,
-                                    p.lddf, p.planes, p.planes_bytes, p.planes_nt, p.stride, p.part, B, N, heads, D, M, mt,
-                                    p.nchunk, p.ppc, p.x_bytes, p.f_bytes, p.dy_bytes, p.dx_bytes, p.df_bytes,
-                                    clamp_temperature, p.xcd_map, bf, st);
-    } else {
-        rc = PA2D_ERR_UNSUPPORTED;
-    }
-    if (rc == PA2D_ERR_UNSUPPORTED) {
-#define CALL_BW(D_, MT_) rc = launch_bwd_t<D_, MT_>(p, grid, st, bf)
-        DISPATCH_D(CALL_BW)
-    }
+    // v3 if the engine or the storage type asks for it and it is built for this shape, else the exact-fp32 kernel
+    const bool v3 = slice_v3(engine, bf);
+    if (v3 && planes && !nrm) return PA2D_ERR_ARG;
+    int rc = (v3 && slice_bwd3_built(D, mt)) ? launch_slice_bwd3(p, D, mt, planes_nt, bf, st)
+                                             : launch_slice_bwd_f32(p, D, mt, planes_nt, bf, st);
     if (rc) return rc;
     PA2D_CHECK_LAUNCH();
     if (ev_stop && hipEventRecord(ev_stop, st) != hipSuccess) return PA2D_ERR_ARG;

@@ -1,8 +1,10 @@
-// Slice scatter / de-slice / slice backward on the bf16 matrix cores with a lean vector stream — gfx950 / CDNA4.
+// v3 slice scatter / de-slice on the bf16 matrix cores with a lean vector stream — gfx950 / CDNA4.  This file owns these two
+// kernels and their launchers; the operand split is pa2d_bf16_split.h, the parameter blocks, lane reductions and the
+// dispatch ladder are pa2d_slice_common.h, the entry points of the C ABI are in pa2d_slice.hip.
 //
-// Same math and the same exact operand splits as pa2d_slice_bf.hip (x = hi + mid + lo in bf16 planes, six product terms,
-// fp32 accumulation: a 24-bit significand), but the kernels there are bound by the VECTOR unit, not by HBM or the matrix
-// pipe (PMC, profiles/r02_e_pmc_slice_kernels.json: 1,230 VALU instructions per 32 points per wave).  What is removed:
+// Exact operand splits (x = hi + mid + lo in bf16 planes, six product terms, fp32 accumulation: a 24-bit significand).  The
+// first kernels of this scheme were bound by the VECTOR unit, not by HBM or the matrix pipe (PMC,
+// profiles/r02_e_pmc_slice_kernels.json: 1,230 VALU instructions per 32 points per wave).  What is removed here:
 //   * the logits come out of the MFMA chain already scaled and biased: Ws and bs are multiplied by log2(e) / tau once per
 //     workgroup, the bias (or -1e30 for padding slices) is the C operand of the first MFMA, so softmax is exp2(acc - max);
 //   * the softmax normalisation is applied to the D values of a point (scatter: F' = F / Z) or to the D outputs of a point
@@ -17,132 +19,12 @@
 // The k order inside a contraction over d is permuted (element j of lane group kq <-> d = 32 s + 4 kq + j for j < 4,
 // 32 s + 16 + 4 kq + (j - 4) otherwise): each of the two 16-byte loads of a point's k-fragment then covers 64 contiguous
 // bytes of the row; A and B use the same permutation.
-#include "pa2d_internal.h"
+#include "pa2d_slice_common.h"
+#include "pa2d_bf16_split.h"
 #include <stdlib.h>
 #include <type_traits>
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x8 __attribute__((ext_vector_type(8)));
-
-#define NEG_BIG (-1e30f)
-#define LOG2E 1.44269504088896340736f
-
 namespace {
-
-__device__ __forceinline__ f32x4 mfma_bf(bf16x8 a, bf16x8 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ float clamp_tau(float t) { return fminf(fmaxf(t, 0.1f), 5.0f); }
-__device__ __forceinline__ float ex2(float x) { return __builtin_amdgcn_exp2f(x); }
-
-// Reductions over the 16 lanes of a DPP row, four independent values at a time (the interleave covers the two wait
-// states a DPP read needs after a VALU write of the same register; the leading s_nop covers the producers of the inputs,
-// which the compiler's hazard recogniser does not see through the asm).  Every lane of the row ends with the row result.
-#ifndef S3_PRE
-#define S3_PRE "s_nop 1\n\t"
-#endif
-#ifndef S3_BC
-#define S3_BC ""
-#endif
-#define ROW16_OP4(OP)                                                                                        \
-    asm volatile(S3_PRE                                                                               \
-                 OP " %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf" S3_BC "\n\t"                         \
-                 OP " %1, %1, %1 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf" S3_BC "\n\t"                         \
-                 OP " %2, %2, %2 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf" S3_BC "\n\t"                         \
-                 OP " %3, %3, %3 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf" S3_BC "\n\t"                         \
-                 OP " %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf" S3_BC "\n\t"                         \
-                 OP " %1, %1, %1 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf" S3_BC "\n\t"                         \
-                 OP " %2, %2, %2 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf" S3_BC "\n\t"                         \
-                 OP " %3, %3, %3 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf" S3_BC "\n\t"                         \
-                 OP " %0, %0, %0 row_half_mirror row_mask:0xf bank_mask:0xf" S3_BC "\n\t"                             \
-                 OP " %1, %1, %1 row_half_mirror row_mask:0xf bank_mask:0xf" S3_BC "\n\t"                             \
-                 OP " %2, %2, %2 row_half_mirror row_mask:0xf bank_mask:0xf" S3_BC "\n\t"                             \
-                 OP " %3, %3, %3 row_half_mirror row_mask:0xf bank_mask:0xf" S3_BC "\n\t"                             \
-                 OP " %0, %0, %0 row_mirror row_mask:0xf bank_mask:0xf" S3_BC "\n\t"                                  \
-                 OP " %1, %1, %1 row_mirror row_mask:0xf bank_mask:0xf" S3_BC "\n\t"                                  \
-                 OP " %2, %2, %2 row_mirror row_mask:0xf bank_mask:0xf" S3_BC "\n\t"                                  \
-                 OP " %3, %3, %3 row_mirror row_mask:0xf bank_mask:0xf" S3_BC "\n\t"                                  \
-                 "s_nop 1"                                                                                   \
-                 : "+v"(a), "+v"(b), "+v"(c), "+v"(d))
-template <int CTRL>
-__device__ __forceinline__ float dpp_mov(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float row16_max_b(float v) {
-    v = fmaxf(v, dpp_mov<0xB1>(v)); v = fmaxf(v, dpp_mov<0x4E>(v)); v = fmaxf(v, dpp_mov<0x141>(v)); v = fmaxf(v, dpp_mov<0x140>(v));
-    return v;
-}
-__device__ __forceinline__ float row16_sum_b(float v) {
-    v += dpp_mov<0xB1>(v); v += dpp_mov<0x4E>(v); v += dpp_mov<0x141>(v); v += dpp_mov<0x140>(v);
-    return v;
-}
-__device__ __forceinline__ void row16_max4(float& a, float& b, float& c, float& d) { ROW16_OP4("v_max_f32_dpp"); }
-__device__ __forceinline__ void row16_sum4(float& a, float& b, float& c, float& d) { ROW16_OP4("v_add_f32_dpp"); }
-
-// Reductions over the four lane groups l, l ^ 16, l ^ 32, l ^ 48 (the kq index) with the gfx950 row swaps:
-// v_permlane16_swap exchanges the odd rows of its first operand with the even rows of the second, v_permlane32_swap the
-// upper half of the first with the lower half of the second.
-#define KQ_OP(OP)                                                                                            \
-    float t;                                                                                                 \
-    asm volatile("v_mov_b32 %1, %0\n\t"                                                                      \
-                 "s_nop 1\n\t"                                                                               \
-                 "v_permlane16_swap_b32 %0, %1\n\t"                                                          \
-                 OP " %0, %0, %1\n\t"                                                                        \
-                 "v_mov_b32 %1, %0\n\t"                                                                      \
-                 "s_nop 1\n\t"                                                                               \
-                 "v_permlane32_swap_b32 %0, %1\n\t"                                                          \
-                 OP " %0, %0, %1\n\t"                                                                        \
-                 "s_nop 0"                                                                                   \
-                 : "+v"(v), "=&v"(t));                                                                       \
-    return v
-__device__ __forceinline__ float kq_max(float v) { KQ_OP("v_max_f32"); }
-__device__ __forceinline__ float kq_sum(float v) { KQ_OP("v_add_f32"); }
-
-// exact split of 8 floats into NP bf16 planes (x = p0 + p1 + p2 up to 2^-25 |x|).  Written on the PACKED conversion result
-// (hipcc otherwise converts every element a second time on its own to form the residual: 7.5 instead of 4.5 instructions
-// per element): per pair 3 v_cvt_pk_bf16_f32 + 2 x (v_lshlrev, v_and, v_pk_add_f32).
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-template <int NP>
-__device__ __forceinline__ void split8(const f32x8 x, bf16x8 (&pl)[NP]) {
-    u32x4 p0, p1, p2;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const f32x2 a = {x[2 * q], x[2 * q + 1]};
-        const unsigned h = __builtin_bit_cast(unsigned, __builtin_convertvector(a, bf16x2));
-        p0[q] = h;
-        if constexpr (NP > 1) {
-            const f32x2 hf = {__uint_as_float(h << 16), __uint_as_float(h & 0xffff0000u)};
-            const f32x2 r = a - hf;                                  // explicit vector op -> v_pk_add_f32
-            const unsigned m = __builtin_bit_cast(unsigned, __builtin_convertvector(r, bf16x2));
-            p1[q] = m;
-            if constexpr (NP > 2) {
-                const f32x2 mf = {__uint_as_float(m << 16), __uint_as_float(m & 0xffff0000u)};
-                p2[q] = __builtin_bit_cast(unsigned, __builtin_convertvector(r - mf, bf16x2));
-            }
-        }
-    }
-    pl[0] = __builtin_bit_cast(bf16x8, p0);
-    if constexpr (NP > 1) pl[1] = __builtin_bit_cast(bf16x8, p1);
-    if constexpr (NP > 2) pl[2] = __builtin_bit_cast(bf16x8, p2);
-}
-
-template <typename T> struct Planes;
-template <> struct Planes<float> { static constexpr int ACT = 3, PAR = 3, WGT = 3; };
-template <> struct Planes<bf16_t> { static constexpr int ACT = 1, PAR = 3, WGT = 2; };
-
-// acc = c + sum over the kept terms a[i] * b[j] (i + j <= 2, smallest first)
-template <int NA, int NB>
-__device__ __forceinline__ f32x4 mfma_terms(const bf16x8 (&a)[NA], const bf16x8 (&b)[NB], f32x4 acc) {
-#pragma unroll
-    for (int s = 2; s >= 0; --s)
-#pragma unroll
-        for (int i = 0; i < NA; ++i) {
-            const int j = s - i;
-            if (j >= 0 && j < NB) acc = mfma_bf(a[i], b[j], acc);
-        }
-    return acc;
-}
 
 // d index of element j (0..7) of lane group kq in k-step s
 __device__ __forceinline__ constexpr int kd(int s, int kq, int j) { return 32 * s + (j < 4 ? 4 * kq + j : 16 + 4 * kq + (j - 4)); }
@@ -151,7 +33,6 @@ __device__ __forceinline__ constexpr int kd(int s, int kq, int j) { return 32 * 
 // d = 32 s + 4 kq and 32 s + 16 + 4 kq;  off = byte offset of element (row, head column 0), OOB_OFF -> zeros
 template <typename T> struct RawK;
 template <> struct RawK<float> { float4 a, b; };
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 template <> struct RawK<bf16_t> { u32x2 a, b; };       // stays packed: the values ARE the one plane
 // `off` = byte offset of the lane's first piece (row, head column + 4 kq) of k-step 0, OOB_OFF -> zeros
 template <int D, typename T>
@@ -284,16 +165,6 @@ __device__ __forceinline__ bool slice3_decode(int B, int heads, int nchunk, int&
     return hh < heads && b < B;
 }
 
-struct Scatter3Params {
-    const void* xm; long long ldx;
-    const void* v; long long ldv;
-    const float* ws; const float* bs; const float* temperature;
-    float* spart; float* npart;
-    int B, N, heads, M, nchunk, ppc;
-    unsigned x_bytes, v_bytes;
-    int clamp, xcd_map;
-};
-
 }  // namespace
 
 // S_partial[m][d] = sum_{n in chunk} W[n][m] * V[n][d];  n_partial[m] = sum_n W[n][m]
@@ -301,7 +172,7 @@ struct Scatter3Params {
 // kq) the 8 weights of points 4kq..4kq+3 and 16+4kq..16+4kq+3 = the A operand (rows = slices, k = points) of S += W^T V,
 // and the SAME lane holds the 8 normalisers 1/Z of exactly these points, which scale its 8 rows of V (B operand).
 template <int D, int MT, typename T>
-__global__ __launch_bounds__((MT <= 4 || D == 16) ? 512 : 256, (MT <= 4 || D == 16) ? 2 : 1) void scatter3_kernel(const Scatter3Params p) {
+__global__ __launch_bounds__((MT <= 4 || D == 16) ? 512 : 256, (MT <= 4 || D == 16) ? 2 : 1) void scatter3_kernel(const SliceParams p) {
     constexpr int KST = BCfg<D>::KST, DT = BCfg<D>::DT;
     constexpr int NA = Planes<T>::ACT, NW = Planes<T>::WGT;
     constexpr unsigned ES = Act<T>::ES;
@@ -487,30 +358,18 @@ __global__ __launch_bounds__((MT <= 4 || D == 16) ? 512 : 256, (MT <= 4 || D == 
     if (want_n) {
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
-            const float v = kq_sum(nacc[mt]);
+            const float v = kq_sum_swap(nacc[mt]);
             if (kq == 0 && 16 * mt + li < p.M) p.npart[(size_t)bid * p.M + 16 * mt + li] = v;
         }
     }
 }
-
-namespace {
-struct Deslice3Params {
-    const void* xm; long long ldx;
-    const float* o;
-    const float* ws; const float* bs; const float* temperature;
-    void* y; long long ldy;
-    int B, N, heads, M, nchunk, ppc;
-    unsigned x_bytes, y_bytes;
-    int clamp;
-};
-}  // namespace
 
 // Y[n][h*D+d] = sum_m W[n][m] * O[m][d]
 // T-layout: the logits tile of 16 points has rows = slices, columns = points: lane (point li, kq) holds the weights of its
 // point for the slices 16mt + 4kq + r, i.e. the B operand (k = slices, columns = points) of Y^T = O^T W^T; softmax is
 // in-lane plus the two row swaps, and the normalisation 1/Z multiplies the D outputs of the point.
 template <int D, int MT, typename T>
-__global__ __launch_bounds__((MT <= 4 || D == 16) ? 512 : 256, (MT <= 4 || D == 16) ? 2 : 1) void deslice3_kernel(const Deslice3Params p) {
+__global__ __launch_bounds__((MT <= 4 || D == 16) ? 512 : 256, (MT <= 4 || D == 16) ? 2 : 1) void deslice3_kernel(const DesliceParams p) {
     constexpr int KST = BCfg<D>::KST, DT = BCfg<D>::DT;
     constexpr int NA = Planes<T>::ACT, NW = Planes<T>::WGT;
     constexpr int MU = (MT + 1) / 2;                 // 32-slice k-steps of the contraction over m
@@ -613,7 +472,7 @@ __global__ __launch_bounds__((MT <= 4 || D == 16) ? 512 : 256, (MT <= 4 || D == 
             for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) mx = fmaxf(mx, w[t][mt][r]);
-            mx = kq_max(mx);
+            mx = kq_max_swap(mx);
             float sm = 0.f;
             const float nm = -mx * esc;
 #pragma unroll
@@ -624,7 +483,7 @@ __global__ __launch_bounds__((MT <= 4 || D == 16) ? 512 : 256, (MT <= 4 || D == 
                     w[t][mt][r] = e;
                     sm += e;
                 }
-            sm = kq_sum(sm);
+            sm = kq_sum_swap(sm);
             const float inv = __builtin_amdgcn_rcpf(sm);
             f32x4 yacc[DT];
 #pragma unroll
@@ -651,13 +510,9 @@ __global__ __launch_bounds__((MT <= 4 || D == 16) ? 512 : 256, (MT <= 4 || D == 
             }
         }
         yo[0] += ystep; yo[1] += ystep;
-#ifndef S3_SGB
-#define S3_SGB 4      // VALU instructions the scheduler places behind each MFMA of the group (measured 0.082 -> 0.075 ms)
-#endif
-#if S3_SGB > 0
+        // 4 VALU instructions placed behind each MFMA of the group (measured 0.082 -> 0.075 ms)
 #pragma unroll
-        for (int i = 0; i < 96; ++i) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x002, S3_SGB, 0); }
-#endif
+        for (int i = 0; i < 96; ++i) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x002, 4, 0); }
     };
     int n_left = p_end - p_begin;
     if (n_left >= 32) load_x(std::false_type{}, n_left);
@@ -675,52 +530,31 @@ static int slice3_hpw(int B, int heads, int nchunk, int mt, int D) {
     while (hpw > 1 && (long long)B * nchunk * ((heads + hpw - 1) / hpw) < 256) hpw >>= 1;
     return hpw;
 }
-#define S3_DISPATCH_MT(D_, CALL)                                 \
-    switch (mt) {                                                \
-        case 1: CALL(D_, 1); break;                              \
-        case 2: CALL(D_, 2); break;                              \
-        case 4: CALL(D_, 4); break;                              \
-        case 8: CALL(D_, 8); break;                              \
-        default: return PA2D_ERR_UNSUPPORTED;                    \
-    }
-#define S3_DISPATCH_D(CALL)                                      \
-    switch (D) {                                                 \
-        case 8: S3_DISPATCH_MT(8, CALL) break;                   \
-        case 16: S3_DISPATCH_MT(16, CALL) break;                 \
-        case 32: S3_DISPATCH_MT(32, CALL) break;                 \
-        case 64: S3_DISPATCH_MT(64, CALL) break;                 \
-        default: return PA2D_ERR_UNSUPPORTED;                    \
-    }
-
-extern "C" __attribute__((visibility("hidden"))) int pa2d_launch_scatter3(const void* xm, long long ldx, const void* v, long long ldv, const float* ws, const float* bs,
-                           const float* temperature, float* spart, float* npart, int B, int N, int heads, int D, int M,
-                           int mt, int nchunk, int ppc, unsigned x_bytes, unsigned v_bytes, int clamp, int xcd_map, bool bf,
-                           hipStream_t st) {
-    Scatter3Params p;
-    p.xm = xm; p.ldx = ldx; p.v = v; p.ldv = ldv; p.ws = ws; p.bs = bs; p.temperature = temperature;
-    p.spart = spart; p.npart = npart; p.B = B; p.N = N; p.heads = heads; p.M = M; p.nchunk = nchunk; p.ppc = ppc;
-    p.x_bytes = x_bytes; p.v_bytes = v_bytes; p.clamp = clamp; p.xcd_map = xcd_map;
-    const int hpw = slice3_hpw(B, heads, nchunk, mt, D);
-    const dim3 grid(B * nchunk * ((heads + hpw - 1) / hpw)), block(64 * hpw);
-#define CALL_S3(D_, MT_)                                                                                          \
-    if (bf) hipLaunchKernelGGL((scatter3_kernel<D_, MT_, bf16_t>), grid, block, 0, st, p);                        \
-    else hipLaunchKernelGGL((scatter3_kernel<D_, MT_, float>), grid, block, 0, st, p)
-    S3_DISPATCH_D(CALL_S3)
+template <int D, int MT>
+static int launch_scatter3_t(const SliceParams& p, dim3 grid, dim3 block, bool bf, hipStream_t st) {
+    if (bf) hipLaunchKernelGGL((scatter3_kernel<D, MT, bf16_t>), grid, block, 0, st, p);
+    else hipLaunchKernelGGL((scatter3_kernel<D, MT, float>), grid, block, 0, st, p);
+    return PA2D_OK;
+}
+template <int D, int MT>
+static int launch_deslice3_t(const DesliceParams& p, dim3 grid, dim3 block, bool bf, hipStream_t st) {
+    if (bf) hipLaunchKernelGGL((deslice3_kernel<D, MT, bf16_t>), grid, block, 0, st, p);
+    else hipLaunchKernelGGL((deslice3_kernel<D, MT, float>), grid, block, 0, st, p);
     return PA2D_OK;
 }
 
-extern "C" __attribute__((visibility("hidden"))) int pa2d_launch_deslice3(const void* xm, long long ldx, const float* o, const float* ws, const float* bs,
-                           const float* temperature, void* y, long long ldy, int B, int N, int heads, int D, int M, int mt,
-                           int nchunk, int ppc, unsigned x_bytes, unsigned y_bytes, int clamp, bool bf, hipStream_t st) {
-    Deslice3Params p;
-    p.xm = xm; p.ldx = ldx; p.o = o; p.ws = ws; p.bs = bs; p.temperature = temperature; p.y = y; p.ldy = ldy;
-    p.B = B; p.N = N; p.heads = heads; p.M = M; p.nchunk = nchunk; p.ppc = ppc; p.x_bytes = x_bytes; p.y_bytes = y_bytes;
-    p.clamp = clamp;
-    const int hpw = slice3_hpw(B, heads, nchunk, mt, D);
-    const dim3 grid(B * nchunk * ((heads + hpw - 1) / hpw)), block(64 * hpw);
-#define CALL_D3(D_, MT_)                                                                                          \
-    if (bf) hipLaunchKernelGGL((deslice3_kernel<D_, MT_, bf16_t>), grid, block, 0, st, p);                        \
-    else hipLaunchKernelGGL((deslice3_kernel<D_, MT_, float>), grid, block, 0, st, p)
-    S3_DISPATCH_D(CALL_D3)
-    return PA2D_OK;
+int launch_scatter3(const SliceParams& p, int D, int mt, bool bf, hipStream_t st) {
+    const int hpw = slice3_hpw(p.B, p.heads, p.nchunk, mt, D);
+    const dim3 grid(p.B * p.nchunk * ((p.heads + hpw - 1) / hpw)), block(64 * hpw);
+#define CALL_S3(D_, MT_) launch_scatter3_t<D_, MT_>(p, grid, block, bf, st)
+    SLICE_DISPATCH_D(CALL_S3)
+    return PA2D_ERR_UNSUPPORTED;
+}
+
+int launch_deslice3(const DesliceParams& p, int D, int mt, bool bf, hipStream_t st) {
+    const int hpw = slice3_hpw(p.B, p.heads, p.nchunk, mt, D);
+    const dim3 grid(p.B * p.nchunk * ((p.heads + hpw - 1) / hpw)), block(64 * hpw);
+#define CALL_D3(D_, MT_) launch_deslice3_t<D_, MT_>(p, grid, block, bf, st)
+    SLICE_DISPATCH_D(CALL_D3)
+    return PA2D_ERR_UNSUPPORTED;
 }

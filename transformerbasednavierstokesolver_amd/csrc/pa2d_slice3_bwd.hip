@@ -14,99 +14,15 @@
 // transposed reads (ds_read_b64_tr_b16).  dWs contracts over the point index, which sits on the lanes of both dL and X:
 // the wave writes the planes of X (once per group of 32 points) and of dL (32 slices at a time) to a private LDS scratch
 // in [point][column] order and reads both operands back transposed.
-#include "pa2d_internal.h"
+//
+// This file owns the v3 backward kernel, its launcher and the rule for which shapes it is built (slice_bwd3_built); the
+// operand split is pa2d_bf16_split.h, the parameter block, lane reductions and the dispatch ladder are pa2d_slice_common.h,
+// the entry points of the C ABI (and the exact-fp32 kernel that takes the other shapes) are in pa2d_slice.hip.
+#include "pa2d_slice_common.h"
+#include "pa2d_bf16_split.h"
 #include <type_traits>
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x8 __attribute__((ext_vector_type(8)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
-#ifdef S3B_NOBAR
-#define S3B_BARRIER
-#else
-#define S3B_BARRIER __builtin_amdgcn_sched_barrier(0);
-#endif
-#define NEG_BIG (-1e30f)
-#define LOG2E 1.44269504088896340736f
-
 namespace {
-
-__device__ __forceinline__ f32x4 mfma_bf(bf16x8 a, bf16x8 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ float clamp_tau(float t) { return fminf(fmaxf(t, 0.1f), 5.0f); }
-__device__ __forceinline__ float ex2(float x) { return __builtin_amdgcn_exp2f(x); }
-
-// reductions over the four lane groups l, l ^ 16, l ^ 32, l ^ 48 (see pa2d_slice3.hip)
-#define KQ_OP(OP)                                                                                            \
-    float t;                                                                                                 \
-    asm volatile("v_mov_b32 %1, %0\n\t"                                                                      \
-                 "s_nop 1\n\t"                                                                               \
-                 "v_permlane16_swap_b32 %0, %1\n\t"                                                          \
-                 OP " %0, %0, %1\n\t"                                                                        \
-                 "v_mov_b32 %1, %0\n\t"                                                                      \
-                 "s_nop 1\n\t"                                                                               \
-                 "v_permlane32_swap_b32 %0, %1\n\t"                                                          \
-                 OP " %0, %0, %1\n\t"                                                                        \
-                 "s_nop 0"                                                                                   \
-                 : "+v"(v), "=&v"(t));                                                                       \
-    return v
-__device__ __forceinline__ float kq_max(float v) { KQ_OP("v_max_f32"); }
-__device__ __forceinline__ float kq_sum(float v) { KQ_OP("v_add_f32"); }
-template <int CTRL>
-__device__ __forceinline__ float dpp_mov(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float row16_sum(float v) {      // epilogue only
-    v += dpp_mov<0xB1>(v); v += dpp_mov<0x4E>(v); v += dpp_mov<0x141>(v); v += dpp_mov<0x140>(v);
-    return v;
-}
-
-// exact split of 8 floats into NP bf16 planes (pa2d_slice3.hip)
-template <int NP>
-__device__ __forceinline__ void split8(const f32x8 x, bf16x8 (&pl)[NP]) {
-    u32x4 p0, p1, p2;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const f32x2 a = {x[2 * q], x[2 * q + 1]};
-        const unsigned h = __builtin_bit_cast(unsigned, __builtin_convertvector(a, bf16x2));
-        p0[q] = h;
-        if constexpr (NP > 1) {
-            const f32x2 hf = {__uint_as_float(h << 16), __uint_as_float(h & 0xffff0000u)};
-            const f32x2 r = a - hf;
-            const unsigned m = __builtin_bit_cast(unsigned, __builtin_convertvector(r, bf16x2));
-            p1[q] = m;
-            if constexpr (NP > 2) {
-                const f32x2 mf = {__uint_as_float(m << 16), __uint_as_float(m & 0xffff0000u)};
-                p2[q] = __builtin_bit_cast(unsigned, __builtin_convertvector(r - mf, bf16x2));
-            }
-        }
-    }
-    pl[0] = __builtin_bit_cast(bf16x8, p0);
-    if constexpr (NP > 1) pl[1] = __builtin_bit_cast(bf16x8, p1);
-    if constexpr (NP > 2) pl[2] = __builtin_bit_cast(bf16x8, p2);
-}
-
-template <typename T> struct Planes;
-template <> struct Planes<float> { static constexpr int ACT = 3, WGT = 3; };
-template <> struct Planes<bf16_t> { static constexpr int ACT = 1, WGT = 2; };
-
-// acc + sum over the kept terms a[i] * b[j] (i + j <= 2, smallest first)
-template <int NA, int NB>
-__device__ __forceinline__ f32x4 mfma_terms(const bf16x8 (&a)[NA], const bf16x8 (&b)[NB], f32x4 acc) {
-#pragma unroll
-    for (int s = 2; s >= 0; --s)
-#pragma unroll
-        for (int i = 0; i < NA; ++i) {
-            const int j = s - i;
-            if (j >= 0 && j < NB) acc = mfma_bf(a[i], b[j], acc);
-        }
-    return acc;
-}
 
 // k-fragment of one activation row: 8 consecutive elements d = 32 s + 8 kq .. + 7, raw
 template <typename T> struct Raw8;
@@ -129,15 +45,6 @@ __device__ __forceinline__ void raw_planes(const Raw8<T>& x, bf16x8 (&pl)[Planes
         const f32x8 v = {x.a.x, x.a.y, x.a.z, x.a.w, x.b.x, x.b.y, x.b.z, x.b.w};
         split8<3>(v, pl);
     }
-}
-
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-// two transposed reads = one 8-element MFMA fragment (elements 0..3 from `a0`, 4..7 from `a1`)
-__device__ __forceinline__ bf16x8 tr_frag(const unsigned char* a0, const unsigned char* a1) {
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)a0);
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)a1);
-    const s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-    return __builtin_bit_cast(bf16x8, v);
 }
 
 // chunk swizzle of the parameter images (64-byte rows): with c ^ 3 on rows 4..7 (mod 8) both the 16-byte row-fragment
@@ -166,21 +73,11 @@ template <int D, int MT> struct BwCfg {
     static constexpr int SMEM = IMGS + 2 * MP * 4 + WAVES * SCR;      // + bs, dn (fp32)
 };
 
-struct SliceBwd3Params {
-    const void* xm; long long ldx;
-    const void* fm; long long ldf;
-    const void* dy; long long lddy;
-    const float* ws; const float* bs; const float* temperature;
-    const float* o; const float* ds; const float* dn; const float* nrm;
-    void* dxm; long long lddx;
-    void* dfm; long long lddf;
-    void* planes; unsigned planes_bytes;
-    int stride;
-    float* part;
-    int B, N, heads, M, nchunk, ppc;
-    unsigned x_bytes, f_bytes, dy_bytes, dx_bytes, df_bytes;
-    int clamp, xcd_map;
-};
+// Shapes of the dispatch ladder the kernel is NOT built for: the exact-fp32 kernel of pa2d_slice.hip takes them, for every
+// engine and storage type.  (D = 64, M = 128) does not fit the LDS; M = 128 with D != 16 needs more than 256 registers here
+// (spills: measured 1.57 ms against 1.14 ms at Darcy 421^2).
+template <int D, int MT>
+constexpr bool bwd3_built() { return !(BwCfg<D, MT>::SMEM > 160 * 1024 || (MT == 8 && D != 16)); }
 
 }  // namespace
 
@@ -191,7 +88,7 @@ struct SliceBwd3Params {
 // d = 8 kq .., lanes kq >= 2 member "b" at d = 8 (kq - 2) ..; fp32 storage: ([w0|w0],[x0|x1]) ([w1|w0],[x0|x2])
 // ([w1|w2],[x1|x0]); bf16 storage: ([w0|w1],[x0|x0]) ([w2|-],[x0|0]).
 template <int D, int MT, typename T, int PL>
-__global__ __launch_bounds__(256, MT == 8 ? 1 : 2) void slice_bwd3_kernel(const SliceBwd3Params p) {
+__global__ __launch_bounds__(256, MT == 8 ? 1 : 2) void slice_bwd3_kernel(const SliceBwdParams p) {
     using C = BwCfg<D, MT>;
     constexpr bool K16 = C::K16;
     constexpr int NTH = 64 * C::WAVES;
@@ -350,7 +247,7 @@ __global__ __launch_bounds__(256, MT == 8 ? 1 : 2) void slice_bwd3_kernel(const 
                         }
 #pragma unroll
                         for (int c = NC - 1; c >= 0; --c) acc[mt] = mfma_bf(fr_[mt & 1][c], xc[c], acc[mt]);
-                        S3B_BARRIER
+                        __builtin_amdgcn_sched_barrier(0);
                     }
                 } else {
                 bf16x8 fr_[2][3];
@@ -367,7 +264,7 @@ __global__ __launch_bounds__(256, MT == 8 ? 1 : 2) void slice_bwd3_kernel(const 
                                                                                     (unsigned)(mt1 * 16 * RP * 2 + s1 * 64));
                     }
                     acc[mt] = mfma_terms<3, NA>(fr_[i & 1], bpl[s_], acc[mt]);
-                    S3B_BARRIER
+                    __builtin_amdgcn_sched_barrier(0);
                 }
                 }
             };
@@ -412,7 +309,7 @@ __global__ __launch_bounds__(256, MT == 8 ? 1 : 2) void slice_bwd3_kernel(const 
             for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) mx = fmaxf(mx, z[mt][r]);
-            mx = kq_max(mx);
+            mx = kq_max_swap(mx);
             const float nm = -mx * scale;
             f32x4 w[MT];
             float sm = 0.f;
@@ -424,7 +321,7 @@ __global__ __launch_bounds__(256, MT == 8 ? 1 : 2) void slice_bwd3_kernel(const 
                     w[mt][r] = e;
                     sm += e;
                 }
-            sm = kq_sum(sm);
+            sm = kq_sum_swap(sm);
             const float inv = pv ? __builtin_amdgcn_rcpf(sm) : 0.f;
             float rd = 0.f;
 #pragma unroll
@@ -434,7 +331,7 @@ __global__ __launch_bounds__(256, MT == 8 ? 1 : 2) void slice_bwd3_kernel(const 
                     w[mt][r] *= inv;
                     rd = fmaf(dw[mt][r], w[mt][r], rd);
                 }
-            rd = kq_sum(rd);
+            rd = kq_sum_swap(rd);
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
@@ -482,7 +379,7 @@ __global__ __launch_bounds__(256, MT == 8 ? 1 : 2) void slice_bwd3_kernel(const 
                 for (int i = 0; i < MU * DT; ++i) {
                     if (i + 1 < MU * DT) rd_(i + 1, fr_[(i + 1) & 1]);
                     acc[i % DT] = mfma_terms<3, NW>(fr_[i & 1], bpl[i / DT], acc[i % DT]);
-                    S3B_BARRIER
+                    __builtin_amdgcn_sched_barrier(0);
                 }
             };
             {
@@ -582,9 +479,6 @@ __global__ __launch_bounds__(256, MT == 8 ? 1 : 2) void slice_bwd3_kernel(const 
                         const auto s0 = __builtin_amdgcn_permlane16_swap(h[0][0], h[1][0], false, false);
                         const auto s1 = __builtin_amdgcn_permlane16_swap(h[0][1], h[1][1], false, false);
                         const u32x4 o = {s0[0], s1[0], s0[1], s1[1]};
-#ifdef S3B_NOSTORE
-                        if (o.x == 0x12345678u)
-#endif
                         __builtin_amdgcn_raw_buffer_store_b128(o, rpl, off == OOB_OFF ? OOB_OFF : off + q * 64u, 0, 0);
                     }
                 };
@@ -680,59 +574,34 @@ __global__ __launch_bounds__(256, MT == 8 ? 1 : 2) void slice_bwd3_kernel(const 
 
 // ---------------------------------------------------------------------------------------------- host side
 template <int D, int MT, typename T, int PL>
-static int launch_bwd3_one(const SliceBwd3Params& p, int grid, hipStream_t st) {
-    constexpr int smem = BwCfg<D, MT>::SMEM;
-    // not built for these shapes: the caller keeps the fp32-MFMA kernel.  (D = 64, M = 128) does not fit the LDS; M = 128 with
-    // fp32 storage needs more than 256 registers here (spills: measured 1.57 ms against 1.14 ms at Darcy 421^2)
-    if constexpr (smem > 160 * 1024 || (MT == 8 && D != 16)) return PA2D_ERR_UNSUPPORTED;
+static int launch_bwd3_one(const SliceBwdParams& p, hipStream_t st) {
+    if constexpr (!bwd3_built<D, MT>()) return PA2D_ERR_UNSUPPORTED;      // no instantiation; callers ask slice_bwd3_built
     else {
+    constexpr int smem = BwCfg<D, MT>::SMEM;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&slice_bwd3_kernel<D, MT, T, PL>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, smem);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL((slice_bwd3_kernel<D, MT, T, PL>), dim3(slice_grid(grid)), dim3(64 * BwCfg<D, MT>::WAVES), smem, st, p);
+    hipLaunchKernelGGL((slice_bwd3_kernel<D, MT, T, PL>), dim3(slice_grid(p.B * p.heads * p.nchunk)),
+                       dim3(64 * BwCfg<D, MT>::WAVES), smem, st, p);
     return PA2D_OK;
     }
 }
 template <int D, int MT>
-static int launch_bwd3_t(const SliceBwd3Params& p, int grid, hipStream_t st, bool bf, int planes_nt) {
-    if (planes_nt == 3) return bf ? PA2D_ERR_ARG : launch_bwd3_one<D, MT, float, 3>(p, grid, st);
-    if (planes_nt == 1) return bf ? PA2D_ERR_ARG : launch_bwd3_one<D, MT, float, 1>(p, grid, st);
-    return bf ? launch_bwd3_one<D, MT, bf16_t, 0>(p, grid, st) : launch_bwd3_one<D, MT, float, 0>(p, grid, st);
+static int launch_bwd3_t(const SliceBwdParams& p, int planes_nt, bool bf, hipStream_t st) {
+    if (planes_nt == 3) return bf ? PA2D_ERR_ARG : launch_bwd3_one<D, MT, float, 3>(p, st);
+    if (planes_nt == 1) return bf ? PA2D_ERR_ARG : launch_bwd3_one<D, MT, float, 1>(p, st);
+    return bf ? launch_bwd3_one<D, MT, bf16_t, 0>(p, st) : launch_bwd3_one<D, MT, float, 0>(p, st);
 }
 
-#define B3_DISPATCH_MT(D_, CALL)                                 \
-    switch (mt) {                                                \
-        case 1: CALL(D_, 1); break;                              \
-        case 2: CALL(D_, 2); break;                              \
-        case 4: CALL(D_, 4); break;                              \
-        case 8: CALL(D_, 8); break;                              \
-        default: return PA2D_ERR_UNSUPPORTED;                    \
-    }
-#define B3_DISPATCH_D(CALL)                                      \
-    switch (D) {                                                 \
-        case 8: B3_DISPATCH_MT(8, CALL) break;                   \
-        case 16: B3_DISPATCH_MT(16, CALL) break;                 \
-        case 32: B3_DISPATCH_MT(32, CALL) break;                 \
-        case 64: B3_DISPATCH_MT(64, CALL) break;                 \
-        default: return PA2D_ERR_UNSUPPORTED;                    \
-    }
+bool slice_bwd3_built(int D, int mt) {
+#define CALL_BUILT(D_, MT_) bwd3_built<D_, MT_>()
+    SLICE_DISPATCH_D(CALL_BUILT)
+    return false;
+}
 
-// called by pa2d_slice.hip with the fields of its SliceBwdParams; nchunk / ppc are the BACKWARD kernel's own chunking
-extern "C" __attribute__((visibility("hidden"))) int pa2d_launch_slice_bwd3(
-    const void* xm, long long ldx, const void* fm, long long ldf, const void* dy, long long lddy, const float* ws,
-    const float* bs, const float* temperature, const float* o, const float* ds, const float* dn, const float* nrm, void* dxm,
-    long long lddx, void* dfm, long long lddf, void* planes, unsigned planes_bytes, int planes_nt, int stride, float* part, int B, int N,
-    int heads, int D, int M, int mt, int nchunk, int ppc, unsigned x_bytes, unsigned f_bytes, unsigned dy_bytes,
-    unsigned dx_bytes, unsigned df_bytes, int clamp, int xcd_map, bool bf, hipStream_t st) {
-    SliceBwd3Params p;
-    p.xm = xm; p.ldx = ldx; p.fm = fm; p.ldf = ldf; p.dy = dy; p.lddy = lddy; p.ws = ws; p.bs = bs;
-    p.temperature = temperature; p.o = o; p.ds = ds; p.dn = dn; p.nrm = nrm; p.dxm = dxm; p.lddx = lddx; p.dfm = dfm; p.lddf = lddf;
-    p.planes = planes; p.planes_bytes = planes_bytes; p.stride = stride; p.part = part; p.B = B; p.N = N; p.heads = heads;
-    p.M = M; p.nchunk = nchunk; p.ppc = ppc; p.x_bytes = x_bytes; p.f_bytes = f_bytes; p.dy_bytes = dy_bytes;
-    p.dx_bytes = dx_bytes; p.df_bytes = df_bytes; p.clamp = clamp; p.xcd_map = xcd_map;
-    const int grid = B * heads * nchunk;
-    int rc = PA2D_OK;
-#define CALL_B3(D_, MT_) rc = launch_bwd3_t<D_, MT_>(p, grid, st, bf, planes_nt)
-    B3_DISPATCH_D(CALL_B3)
-    return rc;
+// p.nchunk / p.ppc are the BACKWARD kernel's own chunking
+int launch_slice_bwd3(const SliceBwdParams& p, int D, int mt, int planes_nt, bool bf, hipStream_t st) {
+#define CALL_B3(D_, MT_) launch_bwd3_t<D_, MT_>(p, planes_nt, bf, st)
+    SLICE_DISPATCH_D(CALL_B3)
+    return PA2D_ERR_UNSUPPORTED;
 }
