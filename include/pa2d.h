@@ -260,6 +260,32 @@ int pa2d_code_slice_weights_bwd(const float* code, const float* pos, const float
                                 size_t ws_bytes, int B, int N, int M, int C, int hidden, int depth, int accumulate,
                                 pa2d_stream_t stream, void* ev_start, void* ev_stop);
 
+/* ---- LearnSlice (reference LearnSlice.py:41-153, class LearnSlice; SequenSolver.py:182-291 loads it): slice weights from
+ * the code and P features per mesh point, weight_projection = MLP(C+P, 64, 1) on cat(code[b, m, :], feat[b, n, :]) and a
+ * softmax over M.  pa2d_code_slice_weights_* with the point part of the first layer P wide instead of 2: the point term
+ * W1p feat_n is made once per point.  code [B, M, C], feat [B, N, P], w1 [hidden, C+P], the other operands as above,
+ * sw [B, 1, N, M].  1 <= P <= 128, C in {8, 16, 32, 64}, 1 <= M <= 128, N >= 1, hidden = 64, depth = 1.  Exact fp32 FMAs on
+ * every engine; B = 0 and unsupported shapes as for the SequenSolver stages. */
+int pa2d_point_slice_weights_fwd(const float* code, const float* feat, const float* w1, const float* b1, const float* w2,
+                                 const float* b2, const float* w3, const float* b3, float* sw, int B, int N, int M, int C,
+                                 int P, int hidden, int depth, pa2d_stream_t stream, void* ev_start, void* ev_stop);
+/* backward from dsw [B, 1, N, M] (the forward is recomputed): dcode [B, M, C] (plain store; may be NULL) and the six
+ * parameter gradients, reduced over (b, n, m) in a fixed order, (+)= per `accumulate`.  The features get no gradient. */
+size_t pa2d_point_slice_weights_bwd_workspace(int B, int N, int M, int C, int P);
+int pa2d_point_slice_weights_bwd(const float* code, const float* feat, const float* w1, const float* b1, const float* w2,
+                                 const float* b2, const float* w3, const float* b3, const float* dsw, float* dcode,
+                                 float* dw1, float* db1, float* dw2, float* db2, float* dw3, float* db3, void* ws_buf,
+                                 size_t ws_bytes, int B, int N, int M, int C, int P, int hidden, int depth, int accumulate,
+                                 pa2d_stream_t stream, void* ev_start, void* ev_stop);
+/* the trainer's loss (LearnSlice.py:499-510, the sum over the points of F.mse_loss(w_n, target_n)): sw, target [rows, M]
+ * with rows = B*N, loss[0] = sum_rows (1/M) sum_m (sw - target)^2 (per-workgroup partial sums over fixed ranges, added in
+ * order in fp64); dsw = gout[0] * 2/M * (sw - target), gout a device scalar.  rows = 0: loss 0. */
+size_t pa2d_slice_mse_workspace(long long rows, int M);
+int pa2d_slice_mse_fwd(const float* sw, const float* target, float* loss, void* ws, size_t ws_bytes, long long rows, int M,
+                       pa2d_stream_t stream);
+int pa2d_slice_mse_bwd(const float* sw, const float* target, const float* gout, float* dsw, long long rows, int M,
+                       pa2d_stream_t stream);
+
 /* ---- output head mlp2 = nn.Linear(C, out_dim), out_dim <= 8 (…_2D.py:66,73) */
 int pa2d_head_fwd(const float* xn, const float* w, const float* b, float* y, int rows, int C, int out_dim,
                   pa2d_stream_t stream);

@@ -7,6 +7,8 @@ auto-encoder attention (slice weights forward / backward, de-slice with explicit
 fraction of the 8 TB/s HBM peak) and one whole auto-encoder training iteration (autoencoder_train_step, FusedAdamW).
 The seq_attn_* / code_sw_* stages time the two SequenSolver kernels at the reference's shape (--SB samples, T=10 tokens of
 dim=512; 64 x 64 points, M=16, C=32), seq_iter one sequensolver_train_step (T=10, layers=8, Tout=1, FusedAdamW) at B=1 and B=8.
+The point_sw_* stages time the LearnSlice kernel at the same shape with P = 2 / 64 / 74 point features and B = 1 / 8,
+learnslice_iter one frame of learnslice_train_step (frozen SequenSolver T=10, layers=8; FusedAdamW) for the three widths.
 Usage: python tools/kbench.py [--only conv_fwd,linear_fwd,...] [--iters 10] [--B 32]"""
 import argparse
 import os
@@ -161,8 +163,38 @@ def main():
                 tests[f"seq_iter B={sb} use_gt={gt}"] = (
                     lambda sm=sm, sopt=sopt, sx=sx, sfx=sfx, syy=syy, gt=gt: harness.sequensolver_train_step(
                         sm, sopt, None, sx, sfx, syy, use_gt=gt, grad_sync=sopt.sync), 0, "us")
+    # LearnSlice at the reference's shape (64 x 64, M=16, C=32): the point-feature stage at P = 2 / 64 / 74 and B = 1 / 8,
+    # and one frame of learnslice_train_step (target encode, get_code, forward, loss, backward, FusedAdamW step)
+    for pp in (2, 64, 74):
+        for sb in (1, 8):
+            pcode, pfeat, pdsw = rn(sb, SM, SC), torch.rand(sb, 4096, pp, device=dev), rn(sb, 1, 4096, SM)
+            pwp = (rn(64, SC + pp) * (2.0 / (SC + pp) ** 0.5), rn(64) * 0.1, rn(64, 64) * 0.12, rn(64) * 0.1,
+                   rn(1, 64) * 0.25, rn(1))
+            pfl = 2.0 * sb * 4096 * (SM * (64 * 64 + 64 * 2) + 64 * pp)      # rows: hidden layer, table add, last dot; points: W1p
+            tests[f"point_sw_fwd P={pp} B={sb}"] = (
+                lambda c=pcode, f=pfeat, w=pwp: ops.point_slice_weights_fwd(c, f, w), pfl, "VALU")
+            tests[f"point_sw_bwd P={pp} B={sb}"] = (
+                lambda c=pcode, f=pfeat, w=pwp, d=pdsw: ops.point_slice_weights_bwd(c, f, w, d), 3 * pfl, "VALU")
+    if only & {"learnslice_iter"}:
+        from transformerbasednavierstokesolver_amd import harness
+        from transformerbasednavierstokesolver_amd.LearnSlice import LearnSlice
+        from transformerbasednavierstokesolver_amd.SequenSolver import SequenSolver
+        from transformerbasednavierstokesolver_amd.optim import FusedAdamW
+        for sb in (1, 8):
+            torch.manual_seed(0)
+            lseq = SequenSolver(None, T=ST, W=64, H=64, M=SM, C=SC, B=sb, layers=8).to(dev).set_engine(E).eval()
+            for prm in lseq.parameters():
+                prm.requires_grad = False
+            lfx, lyy = rn(sb, 4096, ST), rn(sb, 4096, 1)
+            for up, uv, pp in ((0, 0, 2), (1, 0, 64), (1, 1, 74)):
+                lm = LearnSlice(up, uv).to(dev)
+                lopt = FusedAdamW(lm.parameters(), lr=1e-3, weight_decay=1e-5)
+                lx = torch.rand(sb, 4096, 64 if up else 2, device=dev)
+                tests[f"learnslice_iter P={pp} B={sb}"] = (
+                    lambda lm=lm, lopt=lopt, lseq=lseq, lx=lx, lfx=lfx, lyy=lyy, uv=uv: harness.learnslice_train_step(
+                        lm, lopt, None, lseq, lx, lfx, lyy, uv, grad_sync=lopt.sync), 0, "us")
     for name, (fn, work, unit) in tests.items():
-        if only and name not in only and not (name.startswith("seq_iter") and "seq_iter" in only):
+        if only and name not in only and name.split(" ")[0] not in only:
             continue
         ms = timeit(fn, args.iters)
         if unit == "TF":

@@ -15,7 +15,8 @@ reference hard-codes its encoder (8 layers, n_hidden=32, 1 head, 16 slices, 64 x
 the default.  The state_dict has the reference's keys and shapes: `slice_projection` and `temporal_slice_projection` are
 created and never used (no gradient), `token_to_slice_list` (a plain list of N unused layers, not in the state_dict) is
 not built.  Every arithmetic step goes through functional.py; torch only slices, reshapes and owns memory.
-`solve_with_slice_learner` (plots, LearnSlice) is not provided."""
+`solve_with_slice_learner` runs the default mode of the reference's (a trained LearnSlice.get_slice_weight on the code) without
+its prints and plots."""
 import os
 
 import torch
@@ -82,6 +83,7 @@ class SequenSolver(nn.Module):
         self.slice_projection = nn.Linear(self.M, self.M)                           # never used (reference :93)
         self.temporal_slice_projection = MLP(self.T, self.T * mlp_ratio, 1)         # never used (reference :95)
         self.code = None
+        self.learned_slice_weights = None      # what solve_with_slice_learner's LearnSlice predicted last
         self.weight_projection = MLP(self.C + 2, WEIGHT_PROJECTION_HIDDEN, 1)
         self.softmax_slice = nn.Softmax(dim=-1)
 
@@ -107,9 +109,9 @@ class SequenSolver(nn.Module):
         self.encoder.eval()                      # the encoder is frozen and stays in eval()
         return self
 
-    def _refuse(self):
+    def _refuse(self, what="SequenSolver"):
         if ops.resolve_engine(self.engine) == ops.ENGINE_BF16S:
-            raise NotImplementedError("bf16 storage (engine 'bf16s') is not implemented for SequenSolver")
+            raise NotImplementedError(f"bf16 storage (engine 'bf16s') is not implemented for {what}")
         if self.training and self.dropout.p > 0:
             raise NotImplementedError("dropout > 0 is not implemented in the HIP path; refusing to ignore it")
 
@@ -171,10 +173,40 @@ class SequenSolver(nn.Module):
         decoded = self.decode(code)
         return Fn.head(Fn.layer_norm(decoded, self.ln_3.weight, self.ln_3.bias), self.mlp2.weight, self.mlp2.bias)
 
-    def solve_with_slice_learner(self, *args, **kwargs):
-        raise NotImplementedError("solve_with_slice_learner (reference SequenSolver.py:182-291) needs LearnSlice.py and "
-                                  "matplotlib plots, which this package does not restate; use forward(..., use_gt=False) "
-                                  "or decode() with slice weights of your own in `slice_weights`")
+    def solve_with_slice_learner(self, slice_learner_path, spatial_pos, fx, y, unified_pos=0, use_vorticity=0,
+                                 use_previous_slice=False, learn_from_vort=False, use_code_for_vorticity=False, *,
+                                 decode_with_learned=False):
+        """Reference SequenSolver.py:182-291 without its prints and plots: the code of the next frame, the slice weights
+        that a trained LearnSlice predicts from it (kept in `learned_slice_weights` [B, 1, N, M]), and the output decoded
+        with the encoder's weights of the true frame y (left in `slice_weights`), as the reference's line 239 does.
+        `slice_learner_path`: a checkpoint file, a state_dict or a LearnSlice instance.  `decode_with_learned=True`
+        (extension) decodes with the learned weights instead.  spatial_pos is what the slice learner was trained on
+        ([B, N, 2], or [B, N, 64] with unified_pos); any B."""
+        from .LearnSlice import LearnSlice
+        self._refuse("solve_with_slice_learner (SequenSolver and LearnSlice keep fp32 activations)")
+        if use_previous_slice or learn_from_vort:
+            raise NotImplementedError("solve_with_slice_learner serves the default mode (LearnSlice.get_slice_weight); "
+                                      "use_previous_slice needs LearnSlice.forward_previous_slice and learn_from_vort "
+                                      "LearnSlice.forward_from_vorticity, which are not built")
+        learner = slice_learner_path
+        if not isinstance(learner, LearnSlice):      # a module built here is frozen, as the reference's; the caller's own is left as it is
+            sd = slice_learner_path
+            if isinstance(sd, (str, os.PathLike)):
+                sd = torch.load(sd, weights_only=True, map_location="cpu")
+            learner = LearnSlice(unified_pos=unified_pos, use_vorticity=use_vorticity,
+                                 use_code_for_vorticity=use_code_for_vorticity, C=self.C, M=self.M, T=self.T)
+            learner.load_state_dict({k: torch.as_tensor(v) for k, v in sd.items()}, strict=True)
+            learner = learner.to(fx.device).eval()
+            for param in learner.parameters():
+                param.requires_grad = False
+        frames = [fx[:, :, i:i + 1] for i in range(self.T)]
+        tokens, sw_gt = self._encode_frames(spatial_pos, frames + [y])       # y last: its slice weights are the cached ones
+        code = self._code(self._blocks(tokens[:, :, :self.T].contiguous()))
+        self.code = code
+        self.learned_slice_weights = learner.get_slice_weight(code, spatial_pos, fx, use_vorticity)
+        self.slice_weights = self.learned_slice_weights if decode_with_learned else sw_gt
+        decoded = self.decode(code)
+        return Fn.head(Fn.layer_norm(decoded, self.ln_3.weight, self.ln_3.bias), self.mlp2.weight, self.mlp2.bias)
 
     def get_code(self, spatial_pos, fx, y):
         self._refuse()

@@ -71,6 +71,13 @@ SIGNATURES = {
     "pa2d_code_slice_weights_bwd_workspace": (_sz, [_i, _i, _i, _i]),
     "pa2d_code_slice_weights_bwd": (_i, [_f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _sz, _i, _i, _i,
                                          _i, _i, _i, _i, _st, _st, _st]),
+    "pa2d_point_slice_weights_fwd": (_i, [_f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _st, _st, _st]),
+    "pa2d_point_slice_weights_bwd_workspace": (_sz, [_i, _i, _i, _i, _i]),
+    "pa2d_point_slice_weights_bwd": (_i, [_f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _sz, _i, _i, _i,
+                                          _i, _i, _i, _i, _i, _st, _st, _st]),
+    "pa2d_slice_mse_workspace": (_sz, [_ll, _i]),
+    "pa2d_slice_mse_fwd": (_i, [_f, _f, _f, _f, _sz, _ll, _i, _st]),
+    "pa2d_slice_mse_bwd": (_i, [_f, _f, _f, _f, _ll, _i, _st]),
     "pa2d_head_fwd": (_i, [_f, _f, _f, _f, _i, _i, _i, _st]),
     "pa2d_head_bwd_workspace": (_sz, [_i, _i, _i]),
     "pa2d_head_bwd": (_i, [_f, _f, _f, _f, _f, _f, _f, _sz, _i, _i, _i, _i, _st]),

@@ -18,67 +18,15 @@
 //   db2, dw3, db3, dW1p    wave butterfly sums, added to per-wave LDS accumulators by lane 0
 // One partial-sum record per workgroup, summed in a fixed order (fp64 in the three small passes); then dcode = dtb W1c, dW1c = sum_(b,m) dtb^T code,
 // db1 = sum_(b,m) dtb.  The positions get no gradient.  Exact fp32 FMA on the VALU on every engine: no engine argument.
-#include "pa2d_internal.h"
+#include "pa2d_code_sw_common.h"
 
 namespace {
 
-constexpr int HID = 64;          // hidden width of weight_projection (the only one the reference builds)
-constexpr int TS = HID + 1;      // pitch of the first-layer table: lanes read different rows at one column
 constexpr int FNT = 256;         // forward: threads = rows per tile
 constexpr int BNT = 128;         // backward: threads = rows per tile
 constexpr int RS = BNT + 4;      // pitch of the [64][rows] tiles (16-byte aligned rows)
-constexpr int REC_A = 4228;      // record A: dW2 [64*64] | db2 [64] | dw3 [64] | db3 [1] | pad
-constexpr int A_DB2 = 4096, A_DW3 = 4160, A_DB3 = 4224, A_END = 4225;
 constexpr int B_DTB = 2 * HID;   // record B: dW1p [64*2] | dtb [M*64]
 constexpr int NWACC = 4 * HID + 1;   // per-wave accumulators: dw3 [64] | db2 [64] | dW1p [128] | db3
-
-// GELU with a normal cdf that keeps its RELATIVE accuracy in the lower tail (0.5 erfc(-x / sqrt 2)): the gradient of a
-// slice whose first-layer pre-activations sit at -3 and below is made of such tail values, and the rational erfc of
-// pa2d_internal.h (absolute error 1.5e-7, the activation of the GEMM epilogues) is 1e-3 off in relative terms there.
-__device__ __forceinline__ float cdf_tail(float x) { return 0.5f * erfcf(-0.70710678118654752440f * x); }
-__device__ __forceinline__ float gelu_tail(float x) { return x * cdf_tail(x); }
-__device__ __forceinline__ float dgelu_tail(float x) {
-    return fmaf(x * 0.39894228040143267794f, expf(-0.5f * x * x), cdf_tail(x));
-}
-__device__ __forceinline__ void gelu_both(float x, float& g, float& dg) {
-    const float c = cdf_tail(x);
-    g = x * c;
-    dg = fmaf(x * 0.39894228040143267794f, expf(-0.5f * x * x), c);
-}
-
-// z = bias + w . h over the 64 hidden values, as four interleaved partial sums (the forward and the backward's recomputation
-// share it, so both see the same bits); w is read at one address by every lane
-__device__ __forceinline__ float hidden_dot(const float* __restrict__ w, float bias, const float (&h)[HID]) {
-    float z0 = bias, z1 = 0.f, z2 = 0.f, z3 = 0.f;
-#pragma unroll
-    for (int j = 0; j < HID; j += 4) {
-        z0 = fmaf(w[j], h[j], z0);
-        z1 = fmaf(w[j + 1], h[j + 1], z1);
-        z2 = fmaf(w[j + 2], h[j + 2], z2);
-        z3 = fmaf(w[j + 3], h[j + 3], z3);
-    }
-    return (z0 + z1) + (z2 + z3);
-}
-
-// tb[m][j] = b1[j] + sum_c W1[j][c] code[b][m][c]
-template <int NTH>
-__device__ __forceinline__ void make_table(float* tb, const float* __restrict__ code_b, const float* __restrict__ w1,
-                                           const float* __restrict__ b1, int M, int C) {
-    const int ldw = C + 2;
-    for (int e = threadIdx.x; e < M * HID; e += NTH) {
-        const int m = e / HID, j = e % HID;
-        const float* cr = code_b + m * C;
-        const float* wr = w1 + j * ldw;
-        float s0 = b1[j], s1 = 0.f, s2 = 0.f, s3 = 0.f;          // C % 8 == 0
-        for (int c = 0; c < C; c += 4) {
-            s0 = fmaf(wr[c], cr[c], s0);
-            s1 = fmaf(wr[c + 1], cr[c + 1], s1);
-            s2 = fmaf(wr[c + 2], cr[c + 2], s2);
-            s3 = fmaf(wr[c + 3], cr[c + 3], s3);
-        }
-        tb[m * TS + j] = (s0 + s1) + (s2 + s3);
-    }
-}
 
 // grid (chunks, B): the workgroup walks points [n0, n1) of sample b, NTH / M points per tile, one (point, slice) per thread
 __global__ __launch_bounds__(FNT) void code_sw_fwd_kernel(const float* __restrict__ code, const float* __restrict__ pos,
@@ -92,7 +40,7 @@ __global__ __launch_bounds__(FNT) void code_sw_fwd_kernel(const float* __restric
     const int tid = threadIdx.x, b = blockIdx.y;
     const int n0 = blockIdx.x * ppb, n1 = min(N, n0 + ppb);
     const int ldw = C + 2;
-    make_table<FNT>(tb, code + (long long)b * M * C, w1, b1, M, C);
+    make_table<FNT>(tb, code + (long long)b * M * C, w1, b1, M, C, ldw);
     const int PT = FNT / M;
     const bool active = tid < PT * M;
     const int pl = tid / M, m = active ? tid % M : 0;
@@ -149,7 +97,7 @@ __global__ __launch_bounds__(BNT) void code_sw_bwd_kernel(const float* __restric
     const int tid = threadIdx.x, b = blockIdx.y, lane = tid & 63, wave = tid >> 6;
     const int n0 = blockIdx.x * ppb, n1 = min(N, n0 + ppb);
     const int ldw = C + 2;
-    make_table<BNT>(tb, code + (long long)b * M * C, w1, b1, M, C);
+    make_table<BNT>(tb, code + (long long)b * M * C, w1, b1, M, C, ldw);
     for (int e = tid; e < M * HID; e += BNT) dtb[e] = 0.f;
     for (int e = tid; e < 2 * NWACC; e += BNT) wacc[e] = 0.f;
     const int PT = BNT / M;
@@ -304,20 +252,6 @@ __global__ __launch_bounds__(BNT) void code_sw_bwd_kernel(const float* __restric
     for (int e = tid; e < M * HID; e += BNT) rb[B_DTB + e] = dtb[e];
 }
 
-// sum of n values at stride `st` in a fixed order, in fp64 (the second-stage sums are a few thousand additions in all)
-__device__ __forceinline__ double strided_sum(const float* __restrict__ p, int n, long long st) {
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-    int c = 0;
-    for (; c + 4 <= n; c += 4) {
-        s0 += (double)p[c * st];
-        s1 += (double)p[(c + 1) * st];
-        s2 += (double)p[(c + 2) * st];
-        s3 += (double)p[(c + 3) * st];
-    }
-    for (; c < n; ++c) s0 += (double)p[c * st];
-    return (s0 + s1) + (s2 + s3);
-}
-
 // dtbf[b][e] = sum over the nx records of sample b, in a fixed order
 __global__ __launch_bounds__(256) void code_sw_dtb_reduce_kernel(const float* __restrict__ rec_b, float* __restrict__ dtbf,
                                                                  long long total, int MH, int nx) {
@@ -376,14 +310,6 @@ int check_shape(int B, int N, int M, int C, int hidden, int depth) {
     return PA2D_OK;
 }
 
-// points per workgroup: a multiple of the points per tile, about `target` workgroups in all
-int points_per_block(int B, int N, int pt, int target) {
-    int nx = ceil_div(target, B);
-    const int maxc = ceil_div(N, pt);
-    if (nx > maxc) nx = maxc;
-    if (nx < 1) nx = 1;
-    return ceil_div(ceil_div(N, nx), pt) * pt;
-}
 constexpr int FWD_TARGET = 2048, BWD_TARGET = 512;
 
 size_t fwd_lds(int M) { return sizeof(float) * ((size_t)M * TS + FNT); }

@@ -569,3 +569,51 @@ def seq_attention(q, k, v, scale, res=None):
 def code_slice_weights(code, pos, w1, b1, w2, b2, w3, b3):
     """code [B, M, C], pos [B, N, 2] and the six tensors of weight_projection = MLP(C+2, 64, 1) -> sw [B, 1, N, M]."""
     return CodeSliceWeightsFn.apply(code, pos, w1, b1, w2, b2, w3, b3)
+
+
+# ------------------------------------------------------------------------------ LearnSlice stages
+class PointSliceWeightsFn(Function):
+    """sw [B,1,N,M] = softmax_M(weight_projection(cat(code_m, feat_n))) with P features per point (LearnSlice.py:100-153;
+    pa2d_point_slice_weights_*).  The features get no gradient."""
+
+    @staticmethod
+    def forward(ctx, code, feat, *params):
+        ctx.params = params
+        code, feat = code.detach().contiguous(), feat.detach().contiguous()
+        P = tuple(p.detach().contiguous() for p in params)
+        ctx.saved = (code, feat, P)
+        return ops.point_slice_weights_fwd(code, feat, P)
+
+    @staticmethod
+    def backward(ctx, dsw):
+        code, feat, P = ctx.saved
+        tg = grad_targets(ctx.params)
+        dcode, *g = ops.point_slice_weights_bwd(code, feat, P, dsw.contiguous(), need_dcode=ctx.needs_input_grad[0], into=tg)
+        return (dcode, None) + _ret(tg, g)
+
+
+class SliceMSEFn(Function):
+    """loss (0-dim) = sum over the rows of mean_m (sw - target)^2: the reference trainer's sum over the points of
+    F.mse_loss(w_n, target_n) (LearnSlice.py:499-510; pa2d_slice_mse_*).  Gradient w.r.t. sw only."""
+
+    @staticmethod
+    def forward(ctx, sw, target):
+        sw, target = sw.detach().contiguous(), target.detach().contiguous()
+        ctx.saved = (sw, target)
+        return ops.slice_mse_fwd(sw, target).reshape(())
+
+    @staticmethod
+    def backward(ctx, gout):
+        sw, target = ctx.saved
+        return ops.slice_mse_bwd(sw, target, gout.reshape(1).contiguous()), None
+
+
+def point_slice_weights(code, feat, w1, b1, w2, b2, w3, b3):
+    """code [B, M, C], feat [B, N, P] (1 <= P <= 128) and the six tensors of weight_projection = MLP(C+P, 64, 1)
+    -> sw [B, 1, N, M]."""
+    return PointSliceWeightsFn.apply(code, feat, w1, b1, w2, b2, w3, b3)
+
+
+def slice_mse(sw, target):
+    """sw, target [..., M] -> the 0-dim loss sum_rows mean_m (sw - target)^2."""
+    return SliceMSEFn.apply(sw, target)

@@ -21,6 +21,7 @@ from __future__ import annotations
 
 import torch
 
+from . import functional as Fn
 from . import ops
 from .model.Transolver_Structured_Mesh_2D import Model
 from .utils.testloss import TestLoss
@@ -382,6 +383,39 @@ def sequensolver_train_step(model, optimizer, scheduler, x, fx, yy, use_gt=True,
     if scheduler is not None:
         scheduler.step()
     return loss.detach(), full
+
+
+def learnslice_train_step(model, optimizer, scheduler, sequen_solver, x, fx, yy, use_vorticity, max_grad_norm=None,
+                          grad_sync=None):
+    """The LearnSlice.py:477-526 loop over one batch: for each of the Tout = yy.shape[-1] output frames y, the target is
+    the frozen encoder's slice weights of y, the code comes from `sequen_solver.get_code` on the window fx [B, N, T]
+    (no gradient: the sequence model is frozen), the loss is functional.slice_mse of
+    model.get_slice_weight(code, x, fx, use_vorticity) against the target (the reference's sum over the points of
+    F.mse_loss), then zero_grad, backward, [grad_sync], [clip], step, [scheduler]: ONE optimizer step PER FRAME, and the
+    window slides on with the true frame.  The reference makes N calls of the MLP per step; here a step is one forward and
+    one backward launch.  Works with torch.optim.AdamW and with `optim.FusedAdamW` (pass `grad_sync=optimizer.sync`).
+    Returns the list of the Tout detached step losses."""
+    losses = []
+    with ops.weights_frozen():            # the sequence model's weights; LearnSlice's go through no packed GEMM
+        for t in range(yy.shape[-1]):
+            y = yy[..., t:t + 1]
+            with torch.no_grad():
+                sequen_solver.encoder.encode(x, y)
+                target = sequen_solver.encoder.get_attention_slice()
+                code = sequen_solver.get_code(x, fx, y)
+            loss = Fn.slice_mse(model.get_slice_weight(code, x, fx, use_vorticity=use_vorticity), target)
+            optimizer.zero_grad()
+            loss.backward()
+            if grad_sync is not None:
+                grad_sync()
+            if max_grad_norm is not None:
+                torch.nn.utils.clip_grad_norm_([p for p in model.parameters() if p.requires_grad], max_grad_norm)
+            optimizer.step()
+            if scheduler is not None:
+                scheduler.step()
+            losses.append(loss.detach())
+            fx = torch.cat((fx[..., 1:], y), dim=-1)             # the ground truth enters the window
+    return losses
 
 
 @torch.no_grad()

@@ -720,6 +720,86 @@ def code_slice_weights_bwd(code, pos, params, dsw, need_dcode=True, into=None):
     return (dcode,) + tuple(grads)
 
 
+# ---------------------------------------------------------------------------------------------- LearnSlice stages
+# The slice weights from the code and P features per point (pa2d_point_slice_weights_*: code_slice_weights_* with the point
+# part of the first layer 1 <= P <= 128 wide) and the trainer's loss (pa2d_slice_mse_*).  Exact fp32, no `engine`.
+POINT_SW_MAX_P = 128
+
+
+def _point_sw_shapes(code, feat, params):
+    w1, b1, w2, b2, w3, b3 = params
+    if code.dim() != 3 or feat.dim() != 3 or feat.shape[0] != code.shape[0]:
+        raise ValueError(f"code must be [B, M, C] and the point features [B, N, P]; got {tuple(code.shape)} and "
+                         f"{tuple(feat.shape)}")
+    B, M, Cc = code.shape
+    N, P = feat.shape[1], feat.shape[2]
+    hidden = w1.shape[0]
+    want = ((hidden, Cc + P), (hidden,), (hidden, hidden), (hidden,), (1, hidden), (1,))
+    if tuple(tuple(p.shape) for p in params) != want:
+        raise ValueError(f"weight_projection must be MLP(C+P, hidden, 1) with one hidden layer and C+P = {Cc} + {P}: "
+                         f"shapes {want}, got {tuple(tuple(p.shape) for p in params)}")
+    return B, N, M, Cc, P, hidden
+
+
+def point_slice_weights_fwd(code, feat, params):
+    """code [B, M, C], feat [B, N, P], params = (w1, b1, w2, b2, w3, b3) of weight_projection -> sw [B, 1, N, M]."""
+    B, N, M, Cc, P, hidden = _point_sw_shapes(code, feat, params)
+    _chk(code, feat, *params)
+    sw = torch.empty(B, 1, N, M, dtype=torch.float32, device=code.device)
+    e0, e1 = _events("point_slice_weights")
+    _lib.check(_L().pa2d_point_slice_weights_fwd(_p(code), _p(feat), *(_p(t) for t in params), _p(sw), B, N, M, Cc, P,
+                                                 hidden, CODE_SW_DEPTH, _stream(), e0, e1), "point_slice_weights_fwd")
+    return sw
+
+
+def point_slice_weights_bwd(code, feat, params, dsw, need_dcode=True, into=None):
+    """Returns (dcode [B, M, C] or None, dw1, db1, dw2, db2, dw3, db3); `into` = the six gradient buffers to add into."""
+    B, N, M, Cc, P, hidden = _point_sw_shapes(code, feat, params)
+    if tuple(dsw.shape) != (B, 1, N, M):
+        raise ValueError(f"dsw must be [B, 1, N, M] = {(B, 1, N, M)}; got {tuple(dsw.shape)}")
+    _chk(code, feat, dsw, *params)
+    dcode = torch.empty_like(code) if need_dcode else None
+    grads, acc = _grad_outputs(into, tuple(p.shape for p in params), code)
+    nb = _L().pa2d_point_slice_weights_bwd_workspace(B, N, M, Cc, P)
+    ws = _ws(nb, code)
+    e0, e1 = _events("point_slice_weights_bwd")
+    _lib.check(_L().pa2d_point_slice_weights_bwd(_p(code), _p(feat), *(_p(t) for t in params), _p(dsw), _p(dcode),
+                                                 *(_p(g) for g in grads), ws.data_ptr(), nb, B, N, M, Cc, P, hidden,
+                                                 CODE_SW_DEPTH, acc, _stream(), e0, e1), "point_slice_weights_bwd")
+    return (dcode,) + tuple(grads)
+
+
+def _slice_mse_shapes(sw, target):
+    if sw.dim() < 1 or sw.shape != target.shape:
+        raise ValueError(f"sw and target must share a shape [..., M]; got {tuple(sw.shape)} and {tuple(target.shape)}")
+    M = sw.shape[-1]
+    if M < 1:
+        raise ValueError("sw needs at least one slice")
+    return sw.numel() // M, M
+
+
+def slice_mse_fwd(sw, target):
+    """sw, target [..., M] -> loss [1] = sum over the rows of mean_m (sw - target)^2."""
+    rows, M = _slice_mse_shapes(sw, target)
+    _chk(sw, target)
+    loss = torch.empty(1, dtype=torch.float32, device=sw.device)
+    nb = _L().pa2d_slice_mse_workspace(rows, M)
+    ws = _ws(nb, sw)
+    _lib.check(_L().pa2d_slice_mse_fwd(_p(sw), _p(target), _p(loss), ws.data_ptr(), nb, rows, M, _stream()), "slice_mse_fwd")
+    return loss
+
+
+def slice_mse_bwd(sw, target, gout):
+    """dsw = gout * 2/M * (sw - target); gout: the upstream gradient of the loss, one value on the device."""
+    rows, M = _slice_mse_shapes(sw, target)
+    if gout.numel() != 1:
+        raise ValueError("gout must hold one value")
+    _chk(sw, target, gout)
+    dsw = torch.empty_like(sw)
+    _lib.check(_L().pa2d_slice_mse_bwd(_p(sw), _p(target), _p(gout), _p(dsw), rows, M, _stream()), "slice_mse_bwd")
+    return dsw
+
+
 def head_fwd(xn2d, w, b):
     """y is always fp32 (the model output), whatever the storage type of the activations."""
     _chk(w, b)
