@@ -132,6 +132,24 @@ int pa2d_conv3x3x2_bwd(const float* dout, const float* xn, const float* wx, cons
                        void* ws, size_t ws_bytes, int B, int H, int W, int C, int accumulate, int engine,
                        pa2d_stream_t stream, void* ev_start, void* ev_stop);
 
+/* ---- in_project_x of the conv slice predictors (reference SliceLearner.py:71,124-126; LearnSlice.py forward_from_vorticity):
+ * ONE Conv2d(C, C, 3, 1, 1) on the NHWC [B,N,C] tensor as the implicit GEMM [B*H*W, 9C] x [9C, C].  The kernels and the
+ * engine choice of the pair above (forward and data gradient with N = C, Cin = C, K = 9C; the weight gradient of one half);
+ * nothing of a second kernel is computed.  Same contract: C % 16 == 0, every engine, accumulate, dxn may be NULL, prepacked
+ * (direction 0 = forward pack, 1 = data-gradient pack), ev_start / ev_stop, B <= 0 a no-op (dw / db zero-filled when
+ * accumulate = 0); an operand past 4 GiB returns PA2D_ERR_UNSUPPORTED. */
+size_t pa2d_conv3x3_workspace(int B, int H, int W, int C, int engine);       /* backward */
+size_t pa2d_conv3x3_fwd_workspace(int B, int H, int W, int C, int engine);   /* forward  */
+size_t pa2d_conv3x3_pack_bytes(int C);
+int pa2d_conv3x3_pack(const float* w, void* pack, size_t pack_bytes, int B, int H, int W, int C, int direction, int engine,
+                      pa2d_stream_t stream);
+int pa2d_conv3x3_fwd(const float* xn, const float* w, const float* b, float* out, const void* prepacked /* NULL = pack here */,
+                     void* ws, size_t ws_bytes, int B, int H, int W, int C, int engine, pa2d_stream_t stream, void* ev_start,
+                     void* ev_stop);
+int pa2d_conv3x3_bwd(const float* dout, const float* xn, const float* w, float* dxn, float* dw, float* db,
+                     const void* prepacked /* NULL = pack here */, void* ws, size_t ws_bytes, int B, int H, int W, int C,
+                     int accumulate, int engine, pa2d_stream_t stream, void* ev_start, void* ev_stop);
+
 /* ---- in_project_x / in_project_fx of the structured 3-D mesh: two Conv3d(C, C, 3, 1, 1) on the same input,
  * reference model/Physics_Attention.py (Physics_Attention_Structured_Mesh_3D.forward), as ONE implicit GEMM
  * [B*H*W*D, 27C] x [27C, 2C] on the [B,N,C] tensor with N = H*W*D and point n = (h*W + w)*D + d (D fastest, the
@@ -285,6 +303,40 @@ int pa2d_slice_mse_fwd(const float* sw, const float* target, float* loss, void* 
                        pa2d_stream_t stream);
 int pa2d_slice_mse_bwd(const float* sw, const float* target, const float* gout, float* dsw, long long rows, int M,
                        pa2d_stream_t stream);
+
+/* ---- conv slice predictors (reference SliceLearner.py, class SliceLearner; LearnSlice.py:155-193 forward_from_vorticity).
+ * Exact fp32 on every engine (no engine argument); every sum over the rows is made of per-workgroup partial sums over fixed
+ * ranges, added in a fixed order (the final sums in fp64): no atomics, bitwise repeatable.  rows = 0 is a no-op (parameter
+ * gradients zero-filled when accumulate = 0); an unsupported shape returns PA2D_ERR_UNSUPPORTED before any pointer is looked
+ * at, an operand past 4 GiB likewise.
+ * z-score over a WHOLE tensor (LearnSlice.py: (t - t.mean()) / (t.std(unbiased=False) + 1e-8), batch included):
+ * y [rows, C] (contiguous) = (x - mu) / (sigma + 1e-8), x rows of pitch ldx (a column view of a wider tensor is fine);
+ * stats[0] = mu, stats[1] = sigma (population), both fp64 in device memory.  C % 4 == 0, rows >= 1; pointers 16-byte aligned.
+ * A constant input gives exact zeros and sigma = 0: a variance within rounding of zero (n*Q - S^2 <= 2^-46 n*Q for the fp64
+ * sums S, Q of x, x^2) is taken as zero. */
+size_t pa2d_zscore_workspace(long long rows, int C);
+int pa2d_zscore_fwd(const float* x, long long ldx, float* y, double* stats, void* ws, size_t ws_bytes, long long rows, int C,
+                    pa2d_stream_t stream);
+/* dx = (dy - mean(dy) - y * mean(dy*y) * (sigma + eps) / sigma) / (sigma + eps), rows of pitch lddy / lddx; y and stats from
+ * the forward.  sigma = 0 is outside the contract (the reference's autograd gives NaN there). */
+int pa2d_zscore_bwd(const float* dy, long long lddy, const float* y, const double* stats, float* dx, long long lddx, void* ws,
+                    size_t ws_bytes, long long rows, int C, pa2d_stream_t stream);
+/* wide slice weights (SliceLearner.py:127-128: softmax(in_project_slice(x_mid) / clamp(temperature, .1, 5)); the last layer
+ * of the code-conditioned predictor's MLP): sw[r, :] = softmax_m((x[r, :] . ws[m, :] + bs[m]) / t), x [rows, D] of pitch ldx,
+ * ws [M, D], bs [M], t = temperature[0] (clamped to [0.1, 5] with clamp_temperature = 1), sw [rows, M].
+ * D % 4 == 0, 16 <= D <= 512, 1 <= M <= 128 (any M, power of two or not).  One launch. */
+int pa2d_wide_slice_weights_fwd(const float* x, long long ldx, const float* ws, const float* bs, const float* temperature,
+                                float* sw, int rows, int D, int M, int clamp_temperature, pa2d_stream_t stream,
+                                void* ev_start, void* ev_stop);
+/* backward from dsw [rows, M] (the logits and weights are recomputed from x): dl = sw * (dsw - <sw, dsw>) / t;
+ * dx = dl . ws (plain store, rows of pitch lddx; may be NULL); dws [M, D], dbs [M], dtemperature [1] reduced over the rows,
+ * (+)= per `accumulate`; dtemperature = -(1/t) sum dl * logit, zero where the clamp is active.  ev_start / ev_stop around
+ * the point kernel. */
+size_t pa2d_wide_slice_weights_bwd_workspace(int rows, int D, int M);
+int pa2d_wide_slice_weights_bwd(const float* x, long long ldx, const float* ws, const float* bs, const float* temperature,
+                                const float* dsw, float* dx, long long lddx, float* dws, float* dbs, float* dtemperature,
+                                void* ws_buf, size_t ws_bytes, int rows, int D, int M, int clamp_temperature, int accumulate,
+                                pa2d_stream_t stream, void* ev_start, void* ev_stop);
 
 /* ---- output head mlp2 = nn.Linear(C, out_dim), out_dim <= 8 (…_2D.py:66,73) */
 int pa2d_head_fwd(const float* xn, const float* w, const float* b, float* y, int rows, int C, int out_dim,

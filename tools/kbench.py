@@ -9,6 +9,10 @@ The seq_attn_* / code_sw_* stages time the two SequenSolver kernels at the refer
 dim=512; 64 x 64 points, M=16, C=32), seq_iter one sequensolver_train_step (T=10, layers=8, Tout=1, FusedAdamW) at B=1 and B=8.
 The point_sw_* stages time the LearnSlice kernel at the same shape with P = 2 / 64 / 74 point features and B = 1 / 8,
 learnslice_iter one frame of learnslice_train_step (frozen SequenSolver T=10, layers=8; FusedAdamW) for the three widths.
+The conv3x3_* / zscore / wide_sw_* stages time the kernels of the conv slice predictors at 64 x 64, C = 256, B = 1 and 8: the
+single 3x3 conv beside the PAIR call at the same shape (conv_pair_*), the whole-tensor z-score, the wide slice weights at
+D = 256 (SliceLearner) and D = 384 (the code-conditioned MLP's last layer), M = 16; slice_predictor_iter one
+slice_predictor_train_step (frozen SequenSolver T=10, layers=8, Tout=1; FusedAdamW) of VorticitySliceLearner and SliceLearner.
 Usage: python tools/kbench.py [--only conv_fwd,linear_fwd,...] [--iters 10] [--B 32]"""
 import argparse
 import os
@@ -193,6 +197,49 @@ def main():
                 tests[f"learnslice_iter P={pp} B={sb}"] = (
                     lambda lm=lm, lopt=lopt, lseq=lseq, lx=lx, lfx=lfx, lyy=lyy, uv=uv: harness.learnslice_train_step(
                         lm, lopt, None, lseq, lx, lfx, lyy, uv, grad_sync=lopt.sync), 0, "us")
+    # conv slice predictors at 64 x 64, C = 256 (SliceLearner.py; LearnSlice.forward_from_vorticity), B = 1 and 8; the pair
+    # call at the same shape runs beside the single conv.  Operands are made only when one of these stages is asked for.
+    PRED = {"conv3x3_fwd", "conv3x3_bwd", "conv_pair_fwd", "conv_pair_bwd", "zscore", "wide_sw_fwd", "wide_sw_bwd"}
+    for sb in ((1, 8) if not only or any(n.split(" ")[0] in PRED for n in only) else ()):
+        pr = sb * 4096
+        pxn, pdo, pdo2 = rn(sb, 4096, 256), rn(sb, 4096, 256), rn(sb, 4096, 512)
+        pw, pw2, pb = rn(256, 256, 3, 3) * 0.02, rn(256, 256, 3, 3) * 0.02, rn(256)
+        cfl = 2.0 * pr * 9 * 256 * 256
+        tests[f"conv3x3_fwd B={sb}"] = (lambda a=pxn, w=pw, b=pb: ops.conv3x3_fwd(a, w, b, 64, 64, engine=E), cfl, "TF")
+        tests[f"conv3x3_bwd B={sb}"] = (lambda d=pdo, a=pxn, w=pw: ops.conv3x3_bwd(d, a, w, 64, 64, engine=E), 2 * cfl, "TF")
+        tests[f"conv_pair_fwd B={sb}"] = (lambda a=pxn, w=pw, v=pw2, b=pb: ops.conv3x3x2_fwd(a, w, b, v, b, 64, 64, engine=E),
+                                          2 * cfl, "TF")
+        tests[f"conv_pair_bwd B={sb}"] = (lambda d=pdo2, a=pxn, w=pw, v=pw2: ops.conv3x3x2_bwd(d, a, w, v, 64, 64, engine=E),
+                                          4 * cfl, "TF")
+        zy, zst = ops.zscore_fwd(pxn)
+        tests[f"zscore fwd B={sb}"] = (lambda a=pxn: ops.zscore_fwd(a), 3.0 * pr * 256 * 4, "HBM")       # x twice, y once
+        tests[f"zscore bwd B={sb}"] = (lambda d=pdo, y=zy, st=zst: ops.zscore_bwd(d, y, st), 5.0 * pr * 256 * 4, "HBM")
+        ptemp = torch.full((1,), 0.5, device=dev)
+        for dd in (256, 384):
+            wxx, wws, wbs, wds = rn(sb, 4096, dd), rn(16, dd) * (1.0 / dd ** 0.5), rn(16) * 0.1, rn(sb, 4096, 16)
+            wbytes = 4.0 * pr * (dd + 16)
+            tests[f"wide_sw_fwd D={dd} B={sb}"] = (lambda a=wxx, w=wws, b=wbs: ops.wide_slice_weights_fwd(a, w, b, ptemp),
+                                                   wbytes, "HBM")
+            tests[f"wide_sw_bwd D={dd} B={sb}"] = (lambda a=wxx, w=wws, b=wbs, d=wds: ops.wide_slice_weights_bwd(a, w, b, ptemp, d),
+                                                   4.0 * pr * (3 * dd + 2 * 16), "HBM")     # x (kernel + GEMM), dx, dsw, dl
+    if only & {"slice_predictor_iter"}:
+        from transformerbasednavierstokesolver_amd import harness
+        from transformerbasednavierstokesolver_amd.SequenSolver import SequenSolver
+        from transformerbasednavierstokesolver_amd.SliceLearner import SliceLearner, VorticitySliceLearner
+        from transformerbasednavierstokesolver_amd.optim import FusedAdamW
+        for sb in (1, 8):
+            torch.manual_seed(0)
+            pseq = SequenSolver(None, T=ST, W=64, H=64, M=SM, C=SC, B=sb, layers=8).to(dev).set_engine(E).eval()
+            for prm in pseq.parameters():
+                prm.requires_grad = False
+            px, pfx, pyy = torch.rand(sb, 4096, 2, device=dev), rn(sb, 4096, ST), rn(sb, 4096, 1)
+            for label, pm in (("vorticity", VorticitySliceLearner(0, True)),
+                              ("slicelearner", SliceLearner(space_dim=2, fun_dim=ST, H=64, W=64, slice_num=SM))):
+                pm = pm.to(dev).set_engine(E)
+                popt = FusedAdamW(pm.parameters(), lr=1e-3, weight_decay=1e-5)
+                tests[f"slice_predictor_iter {label} B={sb}"] = (
+                    lambda pm=pm, popt=popt, pseq=pseq, px=px, pfx=pfx, pyy=pyy: harness.slice_predictor_train_step(
+                        pm, popt, None, pseq, px, pfx, pyy, grad_sync=popt.sync), 0, "us")
     for name, (fn, work, unit) in tests.items():
         if only and name not in only and name.split(" ")[0] not in only:
             continue

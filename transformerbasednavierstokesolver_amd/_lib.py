@@ -40,6 +40,12 @@ SIGNATURES = {
     "pa2d_conv3x3x2_fwd": (_i, [_f, _f, _f, _f, _f, _f, _f, _f, _sz, _i, _i, _i, _i, _i, _st, _st, _st]),
     "pa2d_conv3x3x2_bwd": (_i, [_f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _sz, _i, _i, _i, _i, _i, _i, _st, _st,
                                 _st]),
+    "pa2d_conv3x3_workspace": (_sz, [_i, _i, _i, _i, _i]),
+    "pa2d_conv3x3_fwd_workspace": (_sz, [_i, _i, _i, _i, _i]),
+    "pa2d_conv3x3_pack_bytes": (_sz, [_i]),
+    "pa2d_conv3x3_pack": (_i, [_f, _f, _sz, _i, _i, _i, _i, _i, _i, _st]),
+    "pa2d_conv3x3_fwd": (_i, [_f, _f, _f, _f, _f, _f, _sz, _i, _i, _i, _i, _i, _st, _st, _st]),
+    "pa2d_conv3x3_bwd": (_i, [_f, _f, _f, _f, _f, _f, _f, _f, _sz, _i, _i, _i, _i, _i, _i, _st, _st, _st]),
     "pa2d_conv3x3x3x2_workspace": (_sz, [_i, _i, _i, _i, _i, _i]),
     "pa2d_conv3x3x3x2_fwd_workspace": (_sz, [_i, _i, _i, _i, _i, _i]),
     "pa2d_conv3x3x3x2_pack_bytes": (_sz, [_i]),
@@ -78,6 +84,13 @@ SIGNATURES = {
     "pa2d_slice_mse_workspace": (_sz, [_ll, _i]),
     "pa2d_slice_mse_fwd": (_i, [_f, _f, _f, _f, _sz, _ll, _i, _st]),
     "pa2d_slice_mse_bwd": (_i, [_f, _f, _f, _f, _ll, _i, _st]),
+    "pa2d_zscore_workspace": (_sz, [_ll, _i]),
+    "pa2d_zscore_fwd": (_i, [_f, _ll, _f, _f, _f, _sz, _ll, _i, _st]),
+    "pa2d_zscore_bwd": (_i, [_f, _ll, _f, _f, _f, _ll, _f, _sz, _ll, _i, _st]),
+    "pa2d_wide_slice_weights_fwd": (_i, [_f, _ll, _f, _f, _f, _f, _i, _i, _i, _i, _st, _st, _st]),
+    "pa2d_wide_slice_weights_bwd_workspace": (_sz, [_i, _i, _i]),
+    "pa2d_wide_slice_weights_bwd": (_i, [_f, _ll, _f, _f, _f, _f, _f, _ll, _f, _f, _f, _f, _sz, _i, _i, _i, _i, _i, _st,
+                                         _st, _st]),
     "pa2d_head_fwd": (_i, [_f, _f, _f, _f, _i, _i, _i, _st]),
     "pa2d_head_bwd_workspace": (_sz, [_i, _i, _i]),
     "pa2d_head_bwd": (_i, [_f, _f, _f, _f, _f, _f, _f, _sz, _i, _i, _i, _i, _st]),

@@ -135,16 +135,17 @@ static int launch_kc(const KCParams& p_in, bool im2col, hipStream_t st, hipEvent
 // mode 2: conv bwd pack    dst[ci][cic'][tap'][c16] = W_{..}[co = cic'*16+c16][ci][8 - tap']        ([Cin][9*2C])
 //         (K order of gemm_kc's implicit GEMM: 16-channel chunk outer, tap inner)
 // TAPS = 27: modes 1 / 2 for the [C,C,3,3,3] kernels of the 3x3x3 conv (taps flipped as 26 - tap)
+// NK = kernels in the pack: 2 = the pair [Wx | Wf]; 1 = no second kernel (pa2d_conv3x3_*: w1 is never read)
 template <int TAPS>
 __global__ void repack_kernel(const float* __restrict__ w0, const float* __restrict__ w1, float* __restrict__ dst,
-                              int mode, int N, int K, int C, int Cin) {
+                              int mode, int N, int K, int C, int Cin, int NK) {
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (mode == 0) {
         if (idx >= (long long)N * K) return;
         const int n = (int)(idx % N), k = (int)(idx / N);
         dst[idx] = w0[(size_t)n * K + k];
     } else if (mode == 1) {
-        if (idx >= (long long)2 * C * TAPS * Cin) return;
+        if (idx >= (long long)NK * C * TAPS * Cin) return;
         const int CH = K;      // channels per K-step (16 for the f32 engine, 32 for the split engine)
         const int c16 = (int)(idx % CH);
         const int tap = (int)((idx / CH) % TAPS);
@@ -154,12 +155,12 @@ __global__ void repack_kernel(const float* __restrict__ w0, const float* __restr
         const float* src = co < C ? w0 : w1;
         dst[idx] = src[((size_t)(co % C) * Cin + ci) * TAPS + tap];
     } else {
-        if (idx >= (long long)2 * C * TAPS * Cin) return;
+        if (idx >= (long long)NK * C * TAPS * Cin) return;
         const int CH = K;
         const int c16 = (int)(idx % CH);
         const int tap = (int)((idx / CH) % TAPS);
-        const int cic = (int)((idx / (TAPS * CH)) % (2 * C / CH));
-        const int ci = (int)(idx / ((long long)2 * C * TAPS));
+        const int cic = (int)((idx / (TAPS * CH)) % (NK * C / CH));
+        const int ci = (int)(idx / ((long long)NK * C * TAPS));
         const int co = cic * CH + c16;
         const float* src = co < C ? w0 : w1;
         dst[idx] = src[((size_t)(co % C) * Cin + ci) * TAPS + (TAPS - 1 - tap)];
@@ -168,12 +169,13 @@ __global__ void repack_kernel(const float* __restrict__ w0, const float* __restr
 
 static int launch_repack(const float* w0, const float* w1, float* dst, int mode, int N, int K, int C, int Cin,
                          hipStream_t st, int taps = 9) {
-    const long long count = mode == 0 ? (long long)N * K : (long long)2 * C * taps * Cin;
+    const int nk = w1 ? 2 : 1;
+    const long long count = mode == 0 ? (long long)N * K : (long long)nk * C * taps * Cin;
     const dim3 grid((unsigned)ceil_div_ll(count, 256));
     if (taps == 27)
-        hipLaunchKernelGGL(repack_kernel<27>, grid, dim3(256), 0, st, w0, w1, dst, mode, N, K, C, Cin);
+        hipLaunchKernelGGL(repack_kernel<27>, grid, dim3(256), 0, st, w0, w1, dst, mode, N, K, C, Cin, nk);
     else
-        hipLaunchKernelGGL(repack_kernel<9>, grid, dim3(256), 0, st, w0, w1, dst, mode, N, K, C, Cin);
+        hipLaunchKernelGGL(repack_kernel<9>, grid, dim3(256), 0, st, w0, w1, dst, mode, N, K, C, Cin, nk);
     PA2D_CHECK_LAUNCH();
     return PA2D_OK;
 }
@@ -455,6 +457,145 @@ int pa2d_conv3x3x2_bwd(const float* dout, const float* xn, const float* wx, cons
                        hipEvent_t ev_stop) {
     return conv_bwd(dout, xn, wx, wf, dxn, dwx, dbx, dwf, dbf, prepacked, ws, ws_bytes, B, H, W, 1, 9, C, accumulate, engine,
                     st, ev_start, ev_stop);
+}
+
+// ---- single 3x3 conv (SliceLearner.py: in_project_x alone): ONE Conv2d(C, C, 3, 1, 1) as the implicit GEMM
+// [B*N, 9C] x [9C, C].  The pair's kernels and engine choice on KCParams with N = C, Cin = C (forward and data gradient:
+// K = 9C both ways) and the weight gradient of one half (Mi = C); packs are the pair's layouts with one kernel in them.
+// Nothing of a second kernel is computed or staged.
+static size_t conv1_pack_floats(int C) { return ((size_t)3 * C * 9 * C + 1) / 2; }      // fp32 pack, or 3 bf16 planes (1.5x)
+// weight gradient of the bf16 engines from pre-split planes on the 256 x 256-tile kernel (Mi = C rows), else the gather kernel
+static bool conv1_dw_planes(int engine, int M, int C) {
+    return conv_planes_bytes(engine, M, C, C) != 0 && !pa2d_env().mc_big_off && C >= 256 && M >= 16 * 8 * 4;
+}
+static MCPlan conv1_dw_plan(int engine, int M, int C) {
+    return conv1_dw_planes(engine, M, C) ? plan_mc_planes_big(C, 9 * C, M) : plan_mc(C, 9 * C, M);
+}
+// backward workspace: [weight pack | slabs or column-sum partials | dOut planes | X planes]  (planes: bf16 engines)
+static size_t conv1_bwd_workspace(int M, int C, int engine) {
+    const MCPlan pl = conv1_dw_plan(engine, M, C);
+    const size_t sl = pl.slab_floats, cs = (size_t)colsum_blocks(M) * C;
+    const size_t apl = conv_planes_bytes(engine, M, C, C);
+    return (conv1_pack_floats(C) + (sl > cs ? sl : cs)) * sizeof(float) + apl + (conv1_dw_planes(engine, M, C) ? apl : 0);
+}
+static size_t conv1_fwd_workspace(int M, int C, int engine) {
+    return conv1_pack_floats(C) * sizeof(float) + conv_planes_bytes(engine, M, C, C);
+}
+static int conv1_pack(const float* w, float* pack, int M, int C, int direction, int engine, hipStream_t st) {
+    if (use_split(engine, C, true, C)) return launch_repack_split(w, nullptr, pack, direction, engine == 2 ? 1 : 3, C, C, st, 9);
+    return launch_repack(w, nullptr, pack, direction ? 2 : 1, 0, kc_tile(M, C, true, C).bk, C, C, st, 9);
+}
+static int conv1_check(int B, int H, int W, int C, int engine) {
+    if (!engine_ok(engine)) return PA2D_ERR_ARG;
+    if (C <= 0 || (C & 15)) return PA2D_ERR_UNSUPPORTED;
+    if (B <= 0) return PA2D_OK;
+    if (H <= 0 || W <= 0) return PA2D_ERR_ARG;
+    // an operand past 4 GiB (32-bit buffer descriptors; the rows must also fit an int)
+    if ((unsigned long long)B * H * W * C * 4ull >= 0xFFFFFFF0ull) return PA2D_ERR_UNSUPPORTED;
+    return PA2D_OK;
+}
+static int conv1_rows(int B, int H, int W, int C, int engine) { return (conv1_check(B, H, W, C, engine) || B <= 0) ? 0 : B * H * W; }
+
+size_t pa2d_conv3x3_workspace(int B, int H, int W, int C, int engine) {
+    return conv1_check(B, H, W, C, engine) ? 0 : conv1_bwd_workspace(conv1_rows(B, H, W, C, engine), C, engine);
+}
+size_t pa2d_conv3x3_fwd_workspace(int B, int H, int W, int C, int engine) {
+    return conv1_check(B, H, W, C, engine) ? 0 : conv1_fwd_workspace(conv1_rows(B, H, W, C, engine), C, engine);
+}
+size_t pa2d_conv3x3_pack_bytes(int C) { return conv1_pack_floats(C) * sizeof(float); }
+
+int pa2d_conv3x3_pack(const float* w, void* pack, size_t pack_bytes, int B, int H, int W, int C, int direction, int engine,
+                      hipStream_t st) {
+    const int rc = conv1_check(B, H, W, C, engine);
+    if (rc) return rc;
+    if (pack_bytes < pa2d_conv3x3_pack_bytes(C)) return PA2D_ERR_WORKSPACE;
+    return conv1_pack(w, (float*)pack, conv1_rows(B, H, W, C, engine), C, direction ? 1 : 0, engine, st);
+}
+
+// out[B*H*W, C] = conv3x3(xn, w) + b   (zero padding 1, NHWC); prepacked: NULL or pa2d_conv3x3_pack(direction 0)
+int pa2d_conv3x3_fwd(const float* xn, const float* w, const float* b, float* out, const void* prepacked, void* ws,
+                     size_t ws_bytes, int B, int H, int W, int C, int engine, hipStream_t st, hipEvent_t ev_start,
+                     hipEvent_t ev_stop) {
+    int rc = conv1_check(B, H, W, C, engine);
+    if (rc) return rc;
+    if (B <= 0) return PA2D_OK;
+    const int M = B * H * W;
+    if (!ws || ws_bytes < conv1_fwd_workspace(M, C, engine)) return PA2D_ERR_WORKSPACE;
+    const float* pack = (const float*)prepacked;
+    if (!pack) {
+        rc = conv1_pack(w, (float*)ws, M, C, 0, engine, st);
+        if (rc) return rc;
+        pack = (const float*)ws;
+    }
+    const size_t apl = conv_planes_bytes(engine, M, C, C);
+    void* const planes = (char*)ws + conv1_pack_floats(C) * sizeof(float);
+    if (apl) {
+        rc = launch_split_planes(xn, C, planes, (long long)M, C, engine == 2 ? 1 : 3, st);
+        if (rc) return rc;
+    }
+    KCParams p = {};
+    p.engine = engine;
+    p.A = apl ? (const float*)planes : xn; p.apre = apl ? 1 : 0;
+    p.lda = C; p.B = pack; p.ldb = 9 * C; p.C = out; p.ldc = C;
+    p.bias = b;
+    p.M = M; p.N = C; p.K = 9 * C; p.H = H; p.W = W; p.Cin = C;
+    p.taps = 9; p.depth = 1;
+    return launch_kc(p, true, st, ev_start, ev_stop);
+}
+
+// dxn[B*N, C] (plain store; may be NULL), dw [C,C,3,3], db [C] ((+)= per `accumulate`) from dout[B*N, C]
+int pa2d_conv3x3_bwd(const float* dout, const float* xn, const float* w, float* dxn, float* dw, float* db,
+                     const void* prepacked, void* ws, size_t ws_bytes, int B, int H, int W, int C, int accumulate, int engine,
+                     hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop) {
+    int rc = conv1_check(B, H, W, C, engine);
+    if (rc) return rc;
+    if (B <= 0) {
+        if (accumulate) return PA2D_OK;
+        rc = pa2d_zero(dw, sizeof(float) * (size_t)C * C * 9, st);
+        return rc ? rc : pa2d_zero(db, sizeof(float) * C, st);
+    }
+    const int M = B * H * W;
+    const size_t need = conv1_bwd_workspace(M, C, engine);
+    if (!ws || ws_bytes < need) return PA2D_ERR_WORKSPACE;
+    float* scratch = (float*)ws + conv1_pack_floats(C);
+    const int NT = engine == 2 ? 1 : 3;
+    const bool dwp = conv1_dw_planes(engine, M, C);
+    const size_t apl = conv_planes_bytes(engine, M, C, C), xpl = dwp ? apl : 0;
+    void* const planes = (char*)ws + need - apl - xpl;                                       // dOut planes
+    void* const xplanes = (char*)planes + apl;                                               // X planes
+    if (apl && (dxn || dwp)) {
+        rc = launch_split_planes(dout, C, planes, M, C, NT, st);
+        if (rc) return rc;
+    }
+    if (dxn) {
+        const float* pack = (const float*)prepacked;
+        if (!pack) {
+            rc = conv1_pack(w, (float*)ws, M, C, 1, engine, st);
+            if (rc) return rc;
+            pack = (const float*)ws;
+        }
+        KCParams p = {};
+        p.engine = engine;
+        p.A = apl ? (const float*)planes : dout; p.apre = apl ? 1 : 0;
+        p.lda = C; p.B = pack; p.ldb = 9 * C; p.C = dxn; p.ldc = C;
+        p.M = M; p.N = C; p.K = 9 * C; p.H = H; p.W = W; p.Cin = C;
+        p.taps = 9; p.depth = 1;
+        rc = launch_kc(p, true, st, ev_start, ev_stop);
+        if (rc) return rc;
+    }
+    const MCPlan pl = conv1_dw_plan(engine, M, C);
+    if (dwp) {
+        rc = launch_split_planes(xn, C, xplanes, M, C, NT, st);
+        if (rc) return rc;
+        rc = launch_mc_planes_big_raw(planes, C, xplanes, C, 9, M, H, W, scratch, pl, NT, st);
+    } else {
+        rc = launch_mc(dout, C, C, xn, C, 9 * C, M, true, H, W, C, scratch, pl, engine, st, nullptr, 9, 1);
+    }
+    if (rc) return rc;
+    // slab rows [C][9][Cin] -> dw [C][Cin][3][3]: the pair's un-pack with every row in the first half
+    rc = launch_reduce(scratch, pl.splits, (long long)C * 9 * C, dw, nullptr, 1, C, C, st, accumulate, 9);
+    if (rc) return rc;
+    return launch_colsum(dout, C, M, C, db, scratch, st, nullptr, 0, accumulate);
 }
 
 // ---- 3x3x3 conv (Physics_Attention_Structured_Mesh_3D: two Conv3d(C, C, 3, 1, 1) on [B, H, W, D, C]).

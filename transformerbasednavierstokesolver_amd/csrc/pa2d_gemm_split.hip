@@ -423,11 +423,12 @@ int launch_split_planes(const float* src, long long ld, void* dst, long long row
 // i.e. the LDS row image of gemm_kc_split_kernel (NT planes: hi | mid | lo).  bwd != 0: data-gradient
 // layout (rows = input channels, contraction over the 2C output channels, taps mirrored).
 // TAPS = 27: the same for the [C, Cin, 3, 3, 3] kernels of the 3x3x3 conv (data gradient: taps mirrored as 26 - tap).
+// NK = kernels in the pack: 2 = the pair; 1 = no second kernel (w1 == NULL, never read: rows / contraction over C, not 2C).
 template <int TAPS>
 __global__ void repack_split_kernel(const float* __restrict__ w0, const float* __restrict__ w1,
-                                    __bf16* __restrict__ dst, int bwd, int NT, int C, int Cin) {
+                                    __bf16* __restrict__ dst, int bwd, int NT, int C, int Cin, int NK) {
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (long long)2 * C * TAPS * Cin) return;
+    if (idx >= (long long)NK * C * TAPS * Cin) return;
     float v;
     int n, kc, c32;
     if (!bwd) {          // rows n = output channel co' in [0,2C), K = TAPS*Cin
@@ -441,14 +442,14 @@ __global__ void repack_split_kernel(const float* __restrict__ w0, const float* _
     } else {             // rows n = input channel ci in [0,Cin), K = TAPS*2C
         c32 = (int)(idx % 32);
         const int tap = (int)((idx / 32) % TAPS);
-        const int cic = (int)((idx / (32 * TAPS)) % (2 * C / 32));
-        n = (int)(idx / ((long long)2 * C * TAPS));
+        const int cic = (int)((idx / (32 * TAPS)) % (NK * C / 32));
+        n = (int)(idx / ((long long)NK * C * TAPS));
         kc = cic * TAPS + tap;
         const int co = cic * 32 + c32;
         const float* src = co < C ? w0 : w1;
         v = src[((size_t)(co % C) * Cin + n) * TAPS + (TAPS - 1 - tap)];
     }
-    const int nk = bwd ? (2 * C / 32) * TAPS : (Cin / 32) * TAPS;
+    const int nk = bwd ? (NK * C / 32) * TAPS : (Cin / 32) * TAPS;
     __bf16* d = dst + ((size_t)n * nk + kc) * NT * 32 + c32;
     const __bf16 h = (__bf16)v;
     d[0] = h;
@@ -462,11 +463,12 @@ __global__ void repack_split_kernel(const float* __restrict__ w0, const float* _
 
 int launch_repack_split(const float* w0, const float* w1, void* dst, int bwd, int NT, int C, int Cin, hipStream_t st,
                         int taps) {
-    const dim3 grid((unsigned)ceil_div_ll((long long)2 * C * taps * Cin, 256));
+    const int nk = w1 ? 2 : 1;
+    const dim3 grid((unsigned)ceil_div_ll((long long)nk * C * taps * Cin, 256));
     if (taps == 27)
-        hipLaunchKernelGGL(repack_split_kernel<27>, grid, dim3(256), 0, st, w0, w1, (__bf16*)dst, bwd, NT, C, Cin);
+        hipLaunchKernelGGL(repack_split_kernel<27>, grid, dim3(256), 0, st, w0, w1, (__bf16*)dst, bwd, NT, C, Cin, nk);
     else
-        hipLaunchKernelGGL(repack_split_kernel<9>, grid, dim3(256), 0, st, w0, w1, (__bf16*)dst, bwd, NT, C, Cin);
+        hipLaunchKernelGGL(repack_split_kernel<9>, grid, dim3(256), 0, st, w0, w1, (__bf16*)dst, bwd, NT, C, Cin, nk);
     PA2D_CHECK_LAUNCH();
     return PA2D_OK;
 }

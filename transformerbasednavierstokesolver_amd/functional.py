@@ -617,3 +617,89 @@ def point_slice_weights(code, feat, w1, b1, w2, b2, w3, b3):
 def slice_mse(sw, target):
     """sw, target [..., M] -> the 0-dim loss sum_rows mean_m (sw - target)^2."""
     return SliceMSEFn.apply(sw, target)
+
+
+# ------------------------------------------------------------------------------ conv slice predictors
+class Conv3x3Fn(Function):
+    """One Conv2d(C, C, 3, 1, 1) on the [B, N, C] tensor (pa2d_conv3x3_*): in_project_x of the conv slice predictors."""
+
+    @staticmethod
+    def forward(ctx, xn, H, W, engine, w, b):
+        ctx.params = (w, b)
+        xn = xn.detach().contiguous()
+        w, b = w.detach().contiguous(), b.detach().contiguous()
+        ctx.saved, ctx.geom = (xn, w), (H, W, engine)
+        return ops.conv3x3_fwd(xn, w, b, H, W, engine=engine)
+
+    @staticmethod
+    def backward(ctx, dout):
+        xn, w = ctx.saved
+        H, W, engine = ctx.geom
+        tg = grad_targets(ctx.params)
+        dxn, dw, db = ops.conv3x3_bwd(dout.contiguous(), xn, w, H, W, need_dx=ctx.needs_input_grad[0], engine=engine,
+                                      into=tg)
+        return (dxn, None, None, None) + _ret(tg, (dw, db))
+
+
+def _constant_pitch(x):
+    """x as the row-pitch stages take it: itself where its rows sit at one pitch (a column view), else a contiguous copy
+    (an expanded gradient, a permuted tensor)."""
+    if x.is_contiguous():
+        return x
+    try:
+        ops._rows_view(x)
+    except ValueError:
+        return x.contiguous()
+    return x
+
+
+class ZScoreFn(Function):
+    """(x - x.mean()) / (x.std(unbiased=False) + 1e-8) over the whole tensor, batch included (pa2d_zscore_*)."""
+
+    @staticmethod
+    def forward(ctx, x):
+        y, stats = ops.zscore_fwd(_constant_pitch(x.detach()))
+        ctx.saved = (y, stats)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        y, stats = ctx.saved
+        return ops.zscore_bwd(_constant_pitch(dy), y, stats)
+
+
+class WideSliceWeightsFn(Function):
+    """sw [..., M] = softmax((x . Ws^T + bs) / clamp(temperature, 0.1, 5)) for rows of 16..512 features
+    (pa2d_wide_slice_weights_*); the weights are recomputed in the backward, never saved."""
+
+    @staticmethod
+    def forward(ctx, x, temperature, ws, bs):
+        ctx.params = (temperature, ws, bs)
+        temp = temperature.detach().reshape(1).contiguous()
+        ws, bs = ws.detach().contiguous(), bs.detach().contiguous()
+        x = _constant_pitch(x.detach())
+        ctx.saved, ctx.tshape = (x, temp, ws, bs), temperature.shape
+        return ops.wide_slice_weights_fwd(x, ws, bs, temp)
+
+    @staticmethod
+    def backward(ctx, dsw):
+        x, temp, ws, bs = ctx.saved
+        tg = grad_targets(ctx.params)
+        into = None if tg is None else (tg[1], tg[2], tg[0])
+        dx, dws, dbs, dtemp = ops.wide_slice_weights_bwd(x, ws, bs, temp, dsw.contiguous(), need_dx=ctx.needs_input_grad[0],
+                                                         into=into)
+        return (dx,) + _ret(tg, (dtemp.view(ctx.tshape), dws, dbs))
+
+
+def conv3x3(xn, H, W, w, b, engine=None):
+    """[B, N, C] -> Conv2d(C, C, 3, 1, 1) of the [B, H, W, C] image, as [B, N, C]."""
+    return Conv3x3Fn.apply(xn, H, W, engine, w, b)
+
+
+def zscore(x):
+    return ZScoreFn.apply(x)
+
+
+def wide_slice_weights(x, temperature, ws, bs):
+    """x [..., D] -> [..., M]; temperature holds one scalar (any shape), clamped to [0.1, 5]."""
+    return WideSliceWeightsFn.apply(x, temperature, ws, bs)

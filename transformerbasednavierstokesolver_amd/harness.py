@@ -418,6 +418,66 @@ def learnslice_train_step(model, optimizer, scheduler, sequen_solver, x, fx, yy,
     return losses
 
 
+def _predict_slices(model, sequen_solver, x, fx):
+    """(slice weights [B, 1, N, M] of a conv slice predictor, code [B, 1, M, C] of the frozen sequence model).  The
+    code-conditioned predictor (SliceLearner.VorticitySliceLearner built with use_code_for_vorticity) reads the code;
+    SliceLearner gets none."""
+    with torch.no_grad():
+        code = sequen_solver.get_code(x, fx, None)
+    if hasattr(model, "use_code_for_vorticity"):
+        return model(x, fx, code if model.use_code_for_vorticity else None), code
+    return model(x, fx), code
+
+
+def slice_predictor_train_step(model, optimizer, scheduler, sequen_solver, x, fx, yy, max_grad_norm=None, grad_sync=None):
+    """One LearnSlice.py:929-962 iteration (train_from_vorticity) of a conv slice predictor (SliceLearner.SliceLearner or
+    SliceLearner.VorticitySliceLearner): for each of the Tout = yy.shape[-1] output frames y, the target is the frozen
+    encoder's slice weights of y, the code comes from `sequen_solver.get_code` on the window fx [B, N, T] (no gradient), the
+    term is F.mse_loss(model's slice weights, target) (the mean over ALL elements: functional.slice_mse scaled by 1 / (B N)),
+    and the window slides on with the true frame; the Tout terms are summed, then zero_grad, ONE backward, [grad_sync],
+    [clip], step, [scheduler].  Works with torch.optim.AdamW and with `optim.FusedAdamW` (pass `grad_sync=optimizer.sync`).
+    Returns the detached summed loss."""
+    loss = 0
+    with ops.weights_frozen():
+        for t in range(yy.shape[-1]):
+            y = yy[..., t:t + 1]
+            with torch.no_grad():
+                sequen_solver.encoder.encode(x, y)
+                target = sequen_solver.encoder.get_attention_slice()
+            pred, _ = _predict_slices(model, sequen_solver, x, fx)
+            loss = loss + Fn.slice_mse(pred, target) / (pred.shape[0] * pred.shape[2])
+            fx = torch.cat((fx[..., 1:], y), dim=-1)             # the ground truth enters the window
+        optimizer.zero_grad()
+        loss.backward()
+    if grad_sync is not None:
+        grad_sync()
+    if max_grad_norm is not None:
+        torch.nn.utils.clip_grad_norm_([p for p in model.parameters() if p.requires_grad], max_grad_norm)
+    optimizer.step()
+    if scheduler is not None:
+        scheduler.step()
+    return loss.detach()
+
+
+@torch.no_grad()
+def slice_predictor_rollout(model, sequen_solver, x, fx, nsteps):
+    """The evaluation loop of train_from_vorticity (LearnSlice.py:861-913) without its prints and plots: every step takes
+    the code of the frozen sequence model on the window fx [B, N, T], the slice weights that the predictor makes of the
+    window (and the code), decodes the code with THOSE weights, applies mlp2(ln_3(.)) and feeds the prediction back into
+    the window.  No ground truth is used.  Returns the predictions [B, N, nsteps]."""
+    preds = []
+    with ops.weights_frozen():
+        for _ in range(nsteps):
+            sw, code = _predict_slices(model, sequen_solver, x, fx)
+            sequen_solver.slice_weights = sw.contiguous()
+            decoded = sequen_solver.decode(code)
+            pred = Fn.head(Fn.layer_norm(decoded, sequen_solver.ln_3.weight, sequen_solver.ln_3.bias),
+                           sequen_solver.mlp2.weight, sequen_solver.mlp2.bias)
+            preds.append(pred)
+            fx = torch.cat((fx[..., 1:], pred), dim=-1)
+    return torch.cat(preds, -1)
+
+
 @torch.no_grad()
 def sequensolver_rollout(model, x, fx, yy, use_gt=True):
     """SequenSolver.py:613-630: Tout = yy.shape[-1] calls with the PREDICTION fed back into the window (y still supplies

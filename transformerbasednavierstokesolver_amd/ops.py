@@ -242,6 +242,7 @@ class _FrozenScope:
 
     def __init__(self):
         self.packs = {}
+        self.packs1 = {}      # packs of the single 3x3 conv (pa2d_conv3x3_pack): (w ptr, B, H, W, C, direction, engine)
         self.images = {}      # weight plane images of the row-stationary linear kernel: (w ptr, transposed, N, K, engine)
 
     def refresh(self):
@@ -249,6 +250,8 @@ class _FrozenScope:
         inside this scope, so the graph's conv launches always see the current weights."""
         for (_, _, B, H, W, depth, Cc, direction, eng), (wx, wf, pack) in self.packs.items():
             _make_pack(wx, wf, pack, B, H, W, Cc, direction, eng, depth)
+        for (_, B, H, W, Cc, direction, eng), (w, pack) in self.packs1.items():
+            _make_pack1(w, pack, B, H, W, Cc, direction, eng)
         for (_, transposed, N, K, eng), (w, img) in self.images.items():
             _make_image(w, transposed, img, N, K, eng)
 
@@ -365,6 +368,67 @@ def conv3x3x2_bwd(dout, xn, wx, wf, H, W, need_dx=True, engine=None, into=None):
                                        pre, ws.data_ptr(), nb, B, H, W, Cc, acc, eng, _stream(), e0, e1),
                "conv3x3x2_bwd")
     return dxn, dwx, dbx, dwf, dbf
+
+
+# ---------------------------------------------------------------------------------------------- single 3x3 conv
+# in_project_x of the conv slice predictors (pa2d_conv3x3_*): one Conv2d(C, C, 3, 1, 1), fp32 storage only.
+def _make_pack1(w, pack, B, H, W, Cc, direction, eng):
+    _lib.check(_L().pa2d_conv3x3_pack(_p(w), pack.data_ptr(), pack.numel(), B, H, W, Cc, direction, eng, _stream()),
+               "conv3x3_pack")
+
+
+def _conv1_pack(w, B, H, W, Cc, direction, eng):
+    """Pack pointer for the active weights_frozen scope (0 = let the conv call pack into its workspace)."""
+    if not _frozen:
+        return 0
+    scope = _frozen[-1]
+    key = (w.data_ptr(), B, H, W, Cc, direction, eng)
+    hit = scope.packs1.get(key)
+    if hit is None:
+        pack = torch.empty(_L().pa2d_conv3x3_pack_bytes(Cc), dtype=torch.uint8, device=w.device)
+        _make_pack1(w, pack, B, H, W, Cc, direction, eng)
+        hit = scope.packs1[key] = (w, pack)
+    return hit[1].data_ptr()
+
+
+def _conv1_engine(engine, *acts):
+    _chk(*acts)
+    if resolve_engine(engine) == ENGINE_BF16S:
+        raise ValueError("the single 3x3 conv has no bf16-storage variant; use the f32, split or bf16 engine")
+    return _abi_engine(engine)
+
+
+def conv3x3_fwd(xn, w, b, H, W, engine=None):
+    """xn [B,N,C] -> conv3x3(xn) + b, [B,N,C] (NHWC, zero padding 1)."""
+    eng = _conv1_engine(engine, xn, w, b)
+    B, N, Cc = xn.shape
+    if N != H * W or tuple(w.shape) != (Cc, Cc, 3, 3):
+        raise ValueError(f"need xn [B, H*W, C] and w [C, C, 3, 3]; got {tuple(xn.shape)}, {tuple(w.shape)}, H*W = {H * W}")
+    out = torch.empty(B, N, Cc, dtype=torch.float32, device=xn.device)
+    pre = _conv1_pack(w, B, H, W, Cc, 0, eng)
+    nb = _L().pa2d_conv3x3_fwd_workspace(B, H, W, Cc, eng)
+    ws = _ws(nb, xn)
+    e0, e1 = _events("conv")
+    _lib.check(_L().pa2d_conv3x3_fwd(_p(xn), _p(w), _p(b), _p(out), pre, ws.data_ptr(), nb, B, H, W, Cc, eng, _stream(),
+                                     e0, e1), "conv3x3_fwd")
+    return out
+
+
+def conv3x3_bwd(dout, xn, w, H, W, need_dx=True, engine=None, into=None):
+    """Returns (dxn, dw, db); `into` = (dw, db) buffers to accumulate into."""
+    eng = _conv1_engine(engine, dout, xn, w)
+    B, N, Cc = xn.shape
+    if N != H * W or dout.shape != xn.shape:
+        raise ValueError(f"need xn, dout [B, H*W, C]; got {tuple(xn.shape)}, {tuple(dout.shape)}")
+    dxn = torch.empty_like(xn) if need_dx else None
+    (dw, db), acc = _grad_outputs(into, (w.shape, (Cc,)), xn)
+    pre = _conv1_pack(w, B, H, W, Cc, 1, eng) if need_dx else 0
+    nb = _L().pa2d_conv3x3_workspace(B, H, W, Cc, eng)
+    ws = _ws(nb, xn)
+    e0, e1 = _events("conv") if need_dx else (0, 0)
+    _lib.check(_L().pa2d_conv3x3_bwd(_p(dout), _p(xn), _p(w), _p(dxn), _p(dw), _p(db), pre, ws.data_ptr(), nb, B, H, W, Cc,
+                                     acc, eng, _stream(), e0, e1), "conv3x3_bwd")
+    return dxn, dw, db
 
 
 def _conv3d_engine(engine, *acts):
@@ -767,6 +831,86 @@ def point_slice_weights_bwd(code, feat, params, dsw, need_dcode=True, into=None)
                                                  *(_p(g) for g in grads), ws.data_ptr(), nb, B, N, M, Cc, P, hidden,
                                                  CODE_SW_DEPTH, acc, _stream(), e0, e1), "point_slice_weights_bwd")
     return (dcode,) + tuple(grads)
+
+
+# ---------------------------------------------------------------------------------------------- conv slice predictors
+# z-score over a whole tensor and the wide slice weights (pa2d_zscore_* / pa2d_wide_slice_weights_*): exact fp32 on every
+# engine, so these take no `engine`.
+def _rows_view(x):
+    """(rows, C, pitch) of an fp32 [..., C] activation whose rows sit at one constant pitch (a column view of a wider
+    tensor is fine); unit stride along the features."""
+    if not x.is_cuda:
+        raise RuntimeError("libpa2d ops need tensors on the GPU (no CPU fallback exists in this package)")
+    if x.dtype != torch.float32:
+        raise TypeError(f"libpa2d ops are fp32; got {x.dtype}")
+    Cx = x.shape[-1]
+    rows = x.numel() // max(Cx, 1)
+    if x.is_contiguous():
+        return rows, Cx, Cx
+    if x.dim() < 2 or x.stride(-1) != 1:
+        raise ValueError("need rows of unit feature stride at one constant pitch")
+    pitch = x.stride(-2)
+    for d in range(x.dim() - 2, 0, -1):
+        if x.shape[d - 1] > 1 and x.stride(d - 1) != x.shape[d] * x.stride(d):
+            raise ValueError("need rows of unit feature stride at one constant pitch")
+    return rows, Cx, pitch
+
+
+def zscore_fwd(x):
+    """y = (x - x.mean()) / (x.std(unbiased=False) + 1e-8) over ALL elements; returns (y contiguous, stats fp64 [mu, sigma])."""
+    rows, Cc, ldx = _rows_view(x)
+    y = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    stats = torch.empty(2, dtype=torch.float64, device=x.device)
+    nb = _L().pa2d_zscore_workspace(rows, Cc)
+    ws = _ws(nb, x)
+    _lib.check(_L().pa2d_zscore_fwd(_p(x), ldx, _p(y), _p(stats), ws.data_ptr(), nb, rows, Cc, _stream()), "zscore_fwd")
+    return y, stats
+
+
+def zscore_bwd(dy, y, stats):
+    """dx (contiguous) from dy (rows may be strided), the forward's y and statistics."""
+    _chk(y)
+    rows, Cc, lddy = _rows_view(dy)
+    if dy.shape != y.shape or stats.dtype != torch.float64 or stats.numel() != 2:
+        raise ValueError("need dy of y's shape and the forward's fp64 statistics")
+    dx = torch.empty(y.shape, dtype=torch.float32, device=y.device)
+    nb = _L().pa2d_zscore_workspace(rows, Cc)
+    ws = _ws(nb, y)
+    _lib.check(_L().pa2d_zscore_bwd(_p(dy), lddy, _p(y), _p(stats), _p(dx), Cc, ws.data_ptr(), nb, rows, Cc, _stream()),
+               "zscore_bwd")
+    return dx
+
+
+def wide_slice_weights_fwd(x, ws_w, bs, temperature, clamp=True):
+    """x [..., D] (rows may be strided) -> sw [..., M] = softmax_m((x . ws^T + bs) / t), t = temperature (one scalar)."""
+    _chk(ws_w, bs, temperature)
+    M, D = ws_w.shape
+    rows, Dx, ldx = _rows_view(x)
+    if Dx != D or bs.numel() != M or temperature.numel() != 1:
+        raise ValueError(f"need x [..., {D}], bs [{M}] and one temperature; got {tuple(x.shape)}, {tuple(bs.shape)}")
+    sw = torch.empty(*x.shape[:-1], M, dtype=torch.float32, device=x.device)
+    e0, e1 = _events("wide_slice_weights")
+    _lib.check(_L().pa2d_wide_slice_weights_fwd(_p(x), ldx, _p(ws_w), _p(bs), _p(temperature), _p(sw), rows, D, M,
+                                                int(clamp), _stream(), e0, e1), "wide_slice_weights_fwd")
+    return sw
+
+
+def wide_slice_weights_bwd(x, ws_w, bs, temperature, dsw, clamp=True, need_dx=True, into=None):
+    """Returns dx [..., D] (None without need_dx), dws [M, D], dbs [M], dtemperature (temperature's shape)."""
+    _chk(ws_w, bs, temperature, dsw)
+    M, D = ws_w.shape
+    rows, Dx, ldx = _rows_view(x)
+    if Dx != D or dsw.numel() != rows * M or temperature.numel() != 1:
+        raise ValueError(f"need x [..., {D}] and dsw [..., {M}] over the same rows")
+    dx = torch.empty(x.shape, dtype=torch.float32, device=x.device) if need_dx else None
+    (dws, dbs, dtemp), acc = _grad_outputs(into, (ws_w.shape, bs.shape, temperature.shape), dsw)
+    nb = _L().pa2d_wide_slice_weights_bwd_workspace(rows, D, M)
+    ws = _ws(nb, dsw)
+    e0, e1 = _events("wide_slice_weights_bwd")
+    _lib.check(_L().pa2d_wide_slice_weights_bwd(_p(x), ldx, _p(ws_w), _p(bs), _p(temperature), _p(dsw), _p(dx), D, _p(dws),
+                                                _p(dbs), _p(dtemp), ws.data_ptr(), nb, rows, D, M, int(clamp), acc,
+                                                _stream(), e0, e1), "wide_slice_weights_bwd")
+    return dx, dws, dbs, dtemp
 
 
 def _slice_mse_shapes(sw, target):
