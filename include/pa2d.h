@@ -265,7 +265,15 @@ int pa2d_seq_attn_bwd(const float* q, const float* k, const float* v, const floa
  * softmax over M): sw[b, 0, n, :] = softmax_m(w3 . (h + gelu(w2 h + b2)) + b3), h = gelu(w1 [code_m ; pos_n] + b1), GELU exact.
  * The concatenated tensor is never made.  code [B, M, C], pos [B, N, 2], w1 [hidden, C+2], b1 [hidden], w2 [hidden, hidden],
  * b2 [hidden], w3 [1, hidden], b3 [1], sw [B, 1, N, M].  C in {8, 16, 32, 64}, 1 <= M <= 128, N >= 1, hidden = 64 and
- * depth = 1 (the hidden layers of the MLP) only.  ev_start / ev_stop as for the slice stages. */
+ * depth = 1 (the hidden layers of the MLP) only.  ev_start / ev_stop as for the slice stages.
+ * These three entry points are the P = 2 case of pa2d_point_slice_weights_* below (pos is feat, w1 is [hidden, C+P]) and
+ * forward to them: same kernels, same checks in the same order, same return codes.  Two consequences a caller can see:
+ * the backward workspace is the point path's, 256 B per point and its dW1p records included (8 MiB more at B = 8,
+ * N = 4096, M = 16 than these entry points once asked for; size the buffer from pa2d_code_slice_weights_bwd_workspace),
+ * and the extent limit is the point path's, B*N*max(M, 64)*4 < 4 GiB (for M < 64 about 16.7 M points per call, not
+ * 2^30 / M).  In the results, the two point columns dw1[:, C:C+2] are summed as the point path sums dW1p (fixed ranges of
+ * points, their records in fp64), which rounds differently from the per-tile wave sums these entry points once had; every
+ * other output keeps its bits. */
 int pa2d_code_slice_weights_fwd(const float* code, const float* pos, const float* w1, const float* b1, const float* w2,
                                 const float* b2, const float* w3, const float* b3, float* sw, int B, int N, int M, int C,
                                 int hidden, int depth, pa2d_stream_t stream, void* ev_start, void* ev_stop);
@@ -280,8 +288,8 @@ int pa2d_code_slice_weights_bwd(const float* code, const float* pos, const float
 
 /* ---- LearnSlice (reference LearnSlice.py:41-153, class LearnSlice; SequenSolver.py:182-291 loads it): slice weights from
  * the code and P features per mesh point, weight_projection = MLP(C+P, 64, 1) on cat(code[b, m, :], feat[b, n, :]) and a
- * softmax over M.  pa2d_code_slice_weights_* with the point part of the first layer P wide instead of 2: the point term
- * W1p feat_n is made once per point.  code [B, M, C], feat [B, N, P], w1 [hidden, C+P], the other operands as above,
+ * softmax over M.  The point part of the first layer is P wide and the point term W1p feat_n is made once per point;
+ * pa2d_code_slice_weights_* above is the case P = 2.  code [B, M, C], feat [B, N, P], w1 [hidden, C+P], the other operands as above,
  * sw [B, 1, N, M].  1 <= P <= 128, C in {8, 16, 32, 64}, 1 <= M <= 128, N >= 1, hidden = 64, depth = 1.  Exact fp32 FMAs on
  * every engine; B = 0 and unsupported shapes as for the SequenSolver stages. */
 int pa2d_point_slice_weights_fwd(const float* code, const float* feat, const float* w1, const float* b1, const float* w2,

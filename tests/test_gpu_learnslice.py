@@ -39,7 +39,7 @@ from conftest import GOLDEN, rel_l2
 from elementwise_check import poisoned
 import learnslice_restatement as L
 import sequensolver_restatement as R
-from test_gpu_sequensolver import EPS32, PNAMES, _bounded
+from test_gpu_sequensolver import EPS32, PNAMES, _bounded, _point_sw_operands, _sw_restated
 from test_sequensolver_host import TINY_ENCODER
 
 pytestmark = pytest.mark.gpu
@@ -68,26 +68,8 @@ POINT_SW_CASES = [      # B, N, M, C, P
 ]
 
 
-def _point_sw_operands(B, N, M, C, P, seed):
-    """As test_gpu_sequensolver._code_sw_operands, with P features per point."""
-    g = torch.Generator().manual_seed(seed)
-    code = torch.randn(B, M, C, generator=g)
-    feat = torch.rand(B, N, P, generator=g)
-    params = (torch.randn(64, C + P, generator=g) * (2.0 / (C + P) ** 0.5), torch.randn(64, generator=g) * 0.1,
-              torch.randn(64, 64, generator=g) * 0.2, torch.randn(64, generator=g) * 0.1,
-              torch.randn(1, 64, generator=g) * 0.5, torch.randn(1, generator=g))
-    dsw = torch.randn(B, 1, N, M, generator=g)
-    return code, feat, params, dsw
-
-
 def _point_sw_restated(code, feat, params, dsw, dtype):
-    code = code.to(dtype).clone().requires_grad_(True)
-    P = [p.to(dtype).clone().requires_grad_(True) for p in params]
-    sw = L.point_slice_weights(code, feat.to(dtype), *P)
-    sw.backward(dsw.to(dtype))
-    s, g = sw.detach(), dsw.to(dtype)
-    scale = (s * (g.abs() + (s * g).sum(-1, keepdim=True).abs())).sum()
-    return sw.detach(), code.grad, [p.grad for p in P], float(scale)
+    return _sw_restated(L.point_slice_weights, code, feat, params, dsw, dtype)
 
 
 @pytest.mark.parametrize("B,N,M,C,P", POINT_SW_CASES)

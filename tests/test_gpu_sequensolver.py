@@ -22,6 +22,10 @@ largest; TAU-table style):
   code_sw   db3 (absolute)    3.35e-08 / 1.34e-06  B=2 N=1 M=16     code_sw  db2    2.33e-06 / 4.55e-06   B=3 N=30 M=5 C=16
                                                                     code_sw  dw3    4.56e-06 / 8.82e-06   B=2 N=30 M=8 C=16
 
+The code_sw cases run the point-feature kernels of test_gpu_learnslice.py with P = 2 (the two-coordinate entry points forward
+to them) and are their coverage at N = 4096 / 4099; against the two-coordinate kernels the stage once had, only the two point
+columns of dw1 changed bits, and no figure above moved.
+
 The code gradient of the (2, 4096, 32, 64) case sits at 0.94 of its bound: that row is badly conditioned (rounding the
 first-layer pre-activations or the hidden pre-activations z to float32 ONCE already moves it by 6e-6 and 1e-5), and the
 kernel's fp32 sums of z are a few ulp worse than a blocked CPU GEMM's.  The model against G10 and the tiny model use at most
@@ -134,26 +138,36 @@ CODE_SW_CASES = [      # B, N, M, C
 PNAMES = ("dw1", "db1", "dw2", "db2", "dw3", "db3")
 
 
-def _code_sw_operands(B, N, M, C, seed):
+def _point_sw_operands(B, N, M, C, P, seed):
+    """Operands of the slice-weight stage with P features per point (test_gpu_learnslice.py draws its own from here)."""
     g = torch.Generator().manual_seed(seed)
     code = torch.randn(B, M, C, generator=g)
-    pos = torch.rand(B, N, 2, generator=g)
-    params = (torch.randn(64, C + 2, generator=g) * (2.0 / (C + 2) ** 0.5), torch.randn(64, generator=g) * 0.1,
+    feat = torch.rand(B, N, P, generator=g)
+    params = (torch.randn(64, C + P, generator=g) * (2.0 / (C + P) ** 0.5), torch.randn(64, generator=g) * 0.1,
               torch.randn(64, 64, generator=g) * 0.2, torch.randn(64, generator=g) * 0.1,
               torch.randn(1, 64, generator=g) * 0.5, torch.randn(1, generator=g))
     dsw = torch.randn(B, 1, N, M, generator=g)
-    return code, pos, params, dsw
+    return code, feat, params, dsw
 
 
-def _code_sw_restated(code, pos, params, dsw, dtype):
+def _code_sw_operands(B, N, M, C, seed):
+    return _point_sw_operands(B, N, M, C, 2, seed)
+
+
+def _sw_restated(restatement, code, feat, params, dsw, dtype):
+    """`restatement` (R.code_slice_weights or learnslice_restatement.point_slice_weights) and its autograd in `dtype`."""
     code = code.to(dtype).clone().requires_grad_(True)
     P = [p.to(dtype).clone().requires_grad_(True) for p in params]
-    sw = R.code_slice_weights(code, pos.to(dtype), *P)
+    sw = restatement(code, feat.to(dtype), *P)
     sw.backward(dsw.to(dtype))
     # sum p (|g| + |<p, g>|): the scale of the rounding in the (exactly zero) gradient of the last bias
     s, g = sw.detach(), dsw.to(dtype)
     scale = (s * (g.abs() + (s * g).sum(-1, keepdim=True).abs())).sum()
     return sw.detach(), code.grad, [p.grad for p in P], float(scale)
+
+
+def _code_sw_restated(code, pos, params, dsw, dtype):
+    return _sw_restated(R.code_slice_weights, code, pos, params, dsw, dtype)
 
 
 @pytest.mark.parametrize("B,N,M,C", CODE_SW_CASES)
@@ -183,6 +197,22 @@ def test_code_slice_weights_forward_backward_rows(B, N, M, C):
     twice = tuple(g.clone() for g in grads)
     ops.code_slice_weights_bwd(dev[0], dev[1], P, dev[2], into=twice)
     assert all(torch.equal(t, 2 * g) for t, g in zip(twice, grads))
+    # a second run gives the same bits
+    assert torch.equal(ops.code_slice_weights_fwd(dev[0], dev[1], P), sw)
+    dcode2, *grads2 = ops.code_slice_weights_bwd(dev[0], dev[1], P, dev[2])
+    assert torch.equal(dcode2, dcode) and all(torch.equal(a, g) for a, g in zip(grads2, grads))
+
+
+def test_single_slice_forward_above_64_kib_of_lds():
+    """M = 1 is the one slice count at which the forward asks for more than 64 KiB of dynamic LDS (a whole tile of 256
+    points in the point table) and must raise the kernel's limit first; two tiles, the second ragged.  A softmax over one
+    slice is expf(0) / 1: exactly one, through the two-coordinate entry and the point-feature entry alike."""
+    from transformerbasednavierstokesolver_amd import ops
+    code, pos, params, _ = _code_sw_operands(1, 300, 1, 16, seed=6)
+    P = tuple(p.cuda() for p in params)
+    for fwd in (ops.code_slice_weights_fwd, ops.point_slice_weights_fwd):
+        sw = poisoned(fwd, code.cuda(), pos.cuda(), P)
+        assert sw.shape == (1, 1, 300, 1) and torch.equal(sw, torch.ones(1, 1, 300, 1, device="cuda"))
 
 
 def test_code_slice_weights_refusals_and_empty_batch():

@@ -5,8 +5,9 @@ The conv3d_* stages time the 3x3x3 conv of the structured 3-D mesh on a --B3 x -
 The ae_* stages run at auto_encoder.py's shape (--AB x 64 x 64, C=64, 4 heads, M=--AM, 3 layers): the four kernels of the
 auto-encoder attention (slice weights forward / backward, de-slice with explicit weights forward / backward; GB/s and the
 fraction of the 8 TB/s HBM peak) and one whole auto-encoder training iteration (autoencoder_train_step, FusedAdamW).
-The seq_attn_* / code_sw_* stages time the two SequenSolver kernels at the reference's shape (--SB samples, T=10 tokens of
-dim=512; 64 x 64 points, M=16, C=32), seq_iter one sequensolver_train_step (T=10, layers=8, Tout=1, FusedAdamW) at B=1 and B=8.
+The seq_attn_* / code_sw_* stages time the two SequenSolver stages at the reference's shape (--SB samples, T=10 tokens of
+dim=512; 64 x 64 points, M=16, C=32; code_sw_* is the two-coordinate entry, served by the point_sw kernels with P = 2),
+seq_iter one sequensolver_train_step (T=10, layers=8, Tout=1, FusedAdamW) at B=1 and B=8.
 The point_sw_* stages time the LearnSlice kernel at the same shape with P = 2 / 64 / 74 point features and B = 1 / 8,
 learnslice_iter one frame of learnslice_train_step (frozen SequenSolver T=10, layers=8; FusedAdamW) for the three widths.
 The conv3x3_* / zscore / wide_sw_* stages time the kernels of the conv slice predictors at 64 x 64, C = 256, B = 1 and 8: the
@@ -151,7 +152,7 @@ def main():
     scode, spos = rn(SB, SM, SC), torch.rand(SB, 4096, 2, device=dev)
     swp = (rn(64, SC + 2) * 0.2, rn(64) * 0.1, rn(64, 64) * 0.12, rn(64) * 0.1, rn(1, 64) * 0.25, rn(1))
     sdsw = rn(SB, 1, 4096, SM)
-    csw_flops = 2.0 * SB * 4096 * SM * (64 * 64 + 64 * 3)            # the hidden layer, the rank-2 term and the last dot
+    csw_flops = 2.0 * SB * 4096 * SM * (64 * 64 + 64 * 3)            # the hidden layer, the two-coordinate point term and the last dot
     tests["code_sw_fwd"] = (lambda: ops.code_slice_weights_fwd(scode, spos, swp), csw_flops, "VALU")
     tests["code_sw_bwd"] = (lambda: ops.code_slice_weights_bwd(scode, spos, swp, sdsw), 3 * csw_flops, "VALU")
     if only & {"seq_iter"}:

@@ -7,7 +7,8 @@ reference's top-level SequenSolver.py (class SequenSolver, :45-388).
   3. the last token is the code [B, 1, M, C] of the next frame;
   4. the code is de-sliced with slice weights [B, 1, N, M]: with use_gt=True the encoder's weights of the true next frame,
      with use_gt=False predicted from the code and the point coordinates by `weight_projection` and a softmax over M
-     (pa2d_code_slice_weights_*: the reference's loop over the N points and its [B, N, M, C+2] tensor do not exist here);
+     (pa2d_code_slice_weights_*, the P = 2 case of LearnSlice's stage: the reference's loop over the N points and its
+     [B, N, M, C+2] tensor do not exist here);
   5. output = mlp2(ln_3(.)).
 
 The constructor keeps the reference's names, order and defaults; `encoder_config` (keyword-only) is the one extension: the

@@ -1,30 +1,106 @@
-// Slice weights from the code and P point features (reference LearnSlice.py:41-153, class LearnSlice: `forward` runs
-// weight_projection = MLP(C+P, 64, 1) on cat(code [M, C], point features expanded to [M, P]) with a softmax over the M
-// slices, `get_slice_weight` calls it in a Python loop over the N points; train() (:477-526) sums F.mse_loss over the points):
+// Slice weights from the code and P point features: the one implementation behind pa2d_point_slice_weights_* (reference
+// LearnSlice.py:41-153, class LearnSlice: `forward` runs weight_projection = MLP(C+P, 64, 1) on cat(code [M, C], point
+// features expanded to [M, P]) with a softmax over the M slices, `get_slice_weight` calls it in a Python loop over the N
+// points; train() (:477-526) sums F.mse_loss over the points) and pa2d_code_slice_weights_* (reference SequenSolver.py:159-170,
+// the use_gt=False branch, which fills a [B, N, M, C+2] tensor in such a loop: the two point coordinates are P = 2 features):
 //
 //   a[n,m,:]  = W1 [code_m ; feat_n] + b1 = (W1c code_m + b1) + W1p feat_n      W1 = [W1c | W1p]  [64, C+P]
 //   h = gelu(a),   u = h + gelu(W2 h + b2),   logit[n,m] = w3 . u + b3,   sw[b,0,n,:] = softmax_m(logit[n,:])
 //
 // P is 2 (coordinates), 64 (unified_pos distances), 74 (distances and T = 10 frames) or 12 in the reference; 1 <= P <= 128
-// is served.  This is pa2d_code_slice_weights.hip with the point term generalised, and the row arithmetic (one thread per
-// (point, slice) row, the 64x64 layer as 64 scalar-operand dot products, the softmax through LDS) is the same.  What differs:
-// the point term W1p feat_n is 64 P FMAs, at P = 74 more than the 64x64 layer of a row, so it is made ONCE PER POINT into a
-// table pf[points of the tile][64] in LDS (every thread makes a few entries; 64 P FMAs per point, P / (64 M) of the tile's
-// row work); rows then read a = tb[m] + pf[point].  The forward keeps W1p transposed in LDS ([P][64]: lane j reads column j
-// without a bank conflict).
+// is served.  The concatenated tensor never exists: the first layer separates into a table tb[m, 64] = W1c code_m + b1 per
+// sample (made by every workgroup in LDS: M*64*C FMAs, the work of C/67 points) and the point term.  A thread owns one
+// (point, slice) row: its 64 hidden values live in registers, the 64x64 layer (the FLOPs: 2*64*64 per row) is 64 dot products
+// against rows of W2 that every lane reads at the same address (scalar loads), the softmax over the M rows of a point goes
+// through LDS, so any 1 <= M <= 128 is served without padding to a power of two.  The point term W1p feat_n is 64 P FMAs, at
+// P = 74 more than the 64x64 layer of a row, so it is made ONCE PER POINT into a table pf[points of the tile][64] in LDS
+// (every thread makes a few entries; 64 P FMAs per point, P / (64 M) of the tile's row work); rows then read
+// a = tb[m] + pf[point].  The forward keeps W1p transposed in LDS ([P][64]: lane j reads column j without a bank conflict).
 //
 // Backward: a first small kernel makes the same table for all points into the workspace (pfw[b,n,:], 256 B per point; the
 // main kernel's LDS and registers are taken by the h / z tiles and the dW2 block: with the table's dot products inlined it
-// no longer compiles without a scratch reservation).  The main kernel is the backward of pa2d_code_slice_weights.hip without
-// its per-row dW1p wave sums: it copies its tile's rows of pfw to LDS and, at the end of the tile, overwrites the same rows
-// with dpf[b,n,:] = sum_m da[n,m,:] (plain store; a workgroup owns its points).  A third kernel forms
-// dW1p[64, P] = sum_(b,n) dpf[b,n,:]^T feat[b,n,:] over fixed ranges of points, one record per workgroup; the records are
-// summed in a fixed order in fp64 by the finish kernel.  The features get no gradient.  No float atomics anywhere.
+// no longer compiles without a scratch reservation).  The main kernel recomputes the forward per tile of 128 rows; h and the
+// pre-activations z = W2 h + b2 are kept in LDS as [64][rows] tiles, turned into dz = dl w3 gelu'(z) in place, and
+//   dW2 += dz^T h          (every thread owns a 4 x 8 block of the 64 x 64 matrix and walks the rows of the tile)
+//   dh = dl w3 + dz W2,  da = dh gelu'(a),   dtb[m, :] += da   (LDS table, each element owned by one thread)
+//   db2, dw3, db3          wave butterfly sums, added to per-wave LDS accumulators by lane 0
+// It copies its tile's rows of pfw to LDS and, at the end of the tile, overwrites the same rows with
+// dpf[b,n,:] = sum_m da[n,m,:] (plain store; a workgroup owns its points).  A third kernel forms
+// dW1p[64, P] = sum_(b,n) dpf[b,n,:]^T feat[b,n,:] over fixed ranges of points, one record per workgroup.  One partial-sum
+// record per workgroup of the main kernel; all records are summed in a fixed order (fp64 in the small passes), then
+// dcode = dtb W1c, dW1c = sum_(b,m) dtb^T code, db1 = sum_(b,m) dtb.  The features get no gradient.  No float atomics
+// anywhere.  Exact fp32 FMA on the VALU on every engine: no engine argument.
 //
 // The loss stage (LearnSlice.py:499-510): loss = sum_(b,n) (1/M) sum_m (sw - target)^2, dsw = g 2/M (sw - target).
-#include "pa2d_code_sw_common.h"
+#include "pa2d_internal.h"
 
 namespace {
+
+constexpr int HID = 64;          // hidden width of weight_projection (the only one the reference builds)
+constexpr int TS = HID + 1;      // pitch of the first-layer table: lanes read different rows at one column
+constexpr int REC_A = 4228;      // record A: dW2 [64*64] | db2 [64] | dw3 [64] | db3 [1] | pad
+constexpr int A_DB2 = 4096, A_DW3 = 4160, A_DB3 = 4224, A_END = 4225;
+
+// GELU with a normal cdf that keeps its RELATIVE accuracy in the lower tail (0.5 erfc(-x / sqrt 2)): the gradient of a
+// slice whose first-layer pre-activations sit at -3 and below is made of such tail values, and the rational erfc of
+// pa2d_internal.h (absolute error 1.5e-7, the activation of the GEMM epilogues) is 1e-3 off in relative terms there.
+__device__ __forceinline__ float cdf_tail(float x) { return 0.5f * erfcf(-0.70710678118654752440f * x); }
+__device__ __forceinline__ float gelu_tail(float x) { return x * cdf_tail(x); }
+__device__ __forceinline__ float dgelu_tail(float x) {
+    return fmaf(x * 0.39894228040143267794f, expf(-0.5f * x * x), cdf_tail(x));
+}
+__device__ __forceinline__ void gelu_both(float x, float& g, float& dg) {
+    const float c = cdf_tail(x);
+    g = x * c;
+    dg = fmaf(x * 0.39894228040143267794f, expf(-0.5f * x * x), c);
+}
+
+// z = bias + w . h over the 64 hidden values, as four interleaved partial sums (the forward and the backward's recomputation
+// share it, so both see the same bits); w is read at one address by every lane
+__device__ __forceinline__ float hidden_dot(const float* __restrict__ w, float bias, const float (&h)[HID]) {
+    float z0 = bias, z1 = 0.f, z2 = 0.f, z3 = 0.f;
+#pragma unroll
+    for (int j = 0; j < HID; j += 4) {
+        z0 = fmaf(w[j], h[j], z0);
+        z1 = fmaf(w[j + 1], h[j + 1], z1);
+        z2 = fmaf(w[j + 2], h[j + 2], z2);
+        z3 = fmaf(w[j + 3], h[j + 3], z3);
+    }
+    return (z0 + z1) + (z2 + z3);
+}
+
+// tb[m][j] = b1[j] + sum_c W1[j][c] code[b][m][c]; ldw = row pitch of W1 (C plus the width of the point part)
+template <int NTH>
+__device__ __forceinline__ void make_table(float* tb, const float* __restrict__ code_b, const float* __restrict__ w1,
+                                           const float* __restrict__ b1, int M, int C, int ldw) {
+    for (int e = threadIdx.x; e < M * HID; e += NTH) {
+        const int m = e / HID, j = e % HID;
+        const float* cr = code_b + m * C;
+        const float* wr = w1 + j * ldw;
+        float s0 = b1[j], s1 = 0.f, s2 = 0.f, s3 = 0.f;          // C % 8 == 0
+        for (int c = 0; c < C; c += 4) {
+            s0 = fmaf(wr[c], cr[c], s0);
+            s1 = fmaf(wr[c + 1], cr[c + 1], s1);
+            s2 = fmaf(wr[c + 2], cr[c + 2], s2);
+            s3 = fmaf(wr[c + 3], cr[c + 3], s3);
+        }
+        tb[m * TS + j] = (s0 + s1) + (s2 + s3);
+    }
+}
+
+// sum of n values at stride `st` in a fixed order, in fp64 (the second-stage sums are a few thousand additions in all)
+__device__ __forceinline__ double strided_sum(const float* __restrict__ p, int n, long long st) {
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    int c = 0;
+    for (; c + 4 <= n; c += 4) {
+        s0 += (double)p[c * st];
+        s1 += (double)p[(c + 1) * st];
+        s2 += (double)p[(c + 2) * st];
+        s3 += (double)p[(c + 3) * st];
+    }
+    for (; c < n; ++c) s0 += (double)p[c * st];
+    return (s0 + s1) + (s2 + s3);
+}
 
 constexpr int FNT = 256;         // forward: threads = rows per tile
 constexpr int BNT = 128;         // backward: threads = rows per tile
@@ -450,6 +526,15 @@ int check_shape(int B, int N, int M, int C, int P, int hidden, int depth) {
 
 constexpr int FWD_TARGET = 2048, BWD_TARGET = 512;
 
+// points per workgroup: a multiple of the points per tile, about `target` workgroups in all
+int points_per_block(int B, int N, int pt, int target) {
+    int nx = ceil_div(target, B);
+    const int maxc = ceil_div(N, pt);
+    if (nx > maxc) nx = maxc;
+    if (nx < 1) nx = 1;
+    return ceil_div(ceil_div(N, nx), pt) * pt;
+}
+
 size_t fwd_lds(int M, int P) { return sizeof(float) * ((size_t)M * TS + FNT + (size_t)(FNT / M) * TS + (size_t)P * HID); }
 size_t bwd_lds(int M) {
     return sizeof(float) * (2 * (size_t)HID * RS + (size_t)M * TS + (size_t)M * HID + 2 * BNT + 2 * NWACC + (size_t)(BNT / M) * TS);
@@ -560,6 +645,27 @@ int pa2d_point_slice_weights_bwd(const float* code, const float* feat, const flo
     segs.begin[0] = 0; segs.begin[1] = A_DB2; segs.begin[2] = A_DW3; segs.begin[3] = A_DB3; segs.begin[4] = A_END;
     segs.dst[0] = dw2; segs.dst[1] = db2; segs.dst[2] = dw3; segs.dst[3] = db3;
     return pa2d_launch_reduce_segs(rec_a, nrec, REC_A, segs, accumulate, st);
+}
+
+// The two point coordinates of SequenSolver.py:159-170 are P = 2 point features: pos [B, N, 2], w1 [hidden, C+2].
+int pa2d_code_slice_weights_fwd(const float* code, const float* pos, const float* w1, const float* b1, const float* w2,
+                                const float* b2, const float* w3, const float* b3, float* sw, int B, int N, int M, int C,
+                                int hidden, int depth, void* stream, void* ev_start, void* ev_stop) {
+    return pa2d_point_slice_weights_fwd(code, pos, w1, b1, w2, b2, w3, b3, sw, B, N, M, C, 2, hidden, depth, stream, ev_start,
+                                        ev_stop);
+}
+
+size_t pa2d_code_slice_weights_bwd_workspace(int B, int N, int M, int C) {
+    return pa2d_point_slice_weights_bwd_workspace(B, N, M, C, 2);
+}
+
+int pa2d_code_slice_weights_bwd(const float* code, const float* pos, const float* w1, const float* b1, const float* w2,
+                                const float* b2, const float* w3, const float* b3, const float* dsw, float* dcode,
+                                float* dw1, float* db1, float* dw2, float* db2, float* dw3, float* db3, void* ws_buf,
+                                size_t ws_bytes, int B, int N, int M, int C, int hidden, int depth, int accumulate,
+                                void* stream, void* ev_start, void* ev_stop) {
+    return pa2d_point_slice_weights_bwd(code, pos, w1, b1, w2, b2, w3, b3, dsw, dcode, dw1, db1, dw2, db2, dw3, db3, ws_buf,
+                                        ws_bytes, B, N, M, C, 2, hidden, depth, accumulate, stream, ev_start, ev_stop);
 }
 
 size_t pa2d_slice_mse_workspace(long long rows, int M) {

@@ -540,26 +540,6 @@ class SeqAttnFn(Function):
         return ops.seq_attn_bwd(q, k, v, attn, dout, ctx.scale) + (dout if ctx.has_res else None, None)
 
 
-class CodeSliceWeightsFn(Function):
-    """sw [B,1,N,M] = softmax_M(weight_projection(cat(code_m, pos_n))) without the concatenated tensor
-    (SequenSolver.py:159-170; pa2d_code_slice_weights_*).  The positions get no gradient."""
-
-    @staticmethod
-    def forward(ctx, code, pos, *params):
-        ctx.params = params
-        code, pos = code.detach().contiguous(), pos.detach().contiguous()
-        P = tuple(p.detach().contiguous() for p in params)
-        ctx.saved = (code, pos, P)
-        return ops.code_slice_weights_fwd(code, pos, P)
-
-    @staticmethod
-    def backward(ctx, dsw):
-        code, pos, P = ctx.saved
-        tg = grad_targets(ctx.params)
-        dcode, *g = ops.code_slice_weights_bwd(code, pos, P, dsw.contiguous(), need_dcode=ctx.needs_input_grad[0], into=tg)
-        return (dcode, None) + _ret(tg, g)
-
-
 def seq_attention(q, k, v, scale, res=None):
     """Single-head attention among T <= 32 tokens of width dim <= 1024 (dim % 4 == 0): q, k, v [B, T, dim]; `res`
     [B, T, dim] is added to the result in the kernel's epilogue."""
@@ -568,7 +548,8 @@ def seq_attention(q, k, v, scale, res=None):
 
 def code_slice_weights(code, pos, w1, b1, w2, b2, w3, b3):
     """code [B, M, C], pos [B, N, 2] and the six tensors of weight_projection = MLP(C+2, 64, 1) -> sw [B, 1, N, M]."""
-    return CodeSliceWeightsFn.apply(code, pos, w1, b1, w2, b2, w3, b3)
+    ops._two_coordinates(code, pos)
+    return PointSliceWeightsFn.apply(code, pos, w1, b1, w2, b2, w3, b3)
 
 
 # ------------------------------------------------------------------------------ LearnSlice stages

@@ -709,8 +709,8 @@ def deslice_weights_bwd(code, w, dy, need_dcode=True, need_dw=True):
 
 
 # ---------------------------------------------------------------------------------------------- SequenSolver stages
-# Sequence attention among the T frame tokens and the slice weights predicted from the code (pa2d_seq_attn_* /
-# pa2d_code_slice_weights_*): exact fp32 on every engine, so these take no `engine` either.
+# Sequence attention among the T frame tokens (pa2d_seq_attn_*) and the slice weights predicted from the code and the two
+# point coordinates (the P = 2 case of the LearnSlice stage below): exact fp32 on every engine, so these take no `engine`.
 SEQ_ATTN_MAX_T, SEQ_ATTN_MAX_DIM = 32, 1024
 CODE_SW_HIDDEN, CODE_SW_DEPTH = 64, 1
 
@@ -742,51 +742,27 @@ def seq_attn_bwd(q, k, v, attn, dout, scale):
     return dq, dk, dv
 
 
-def _code_sw_shapes(code, pos, params):
-    w1, b1, w2, b2, w3, b3 = params
-    B, M, Cc = code.shape
-    N = pos.shape[1]
-    if tuple(pos.shape) != (B, N, 2):
+def _two_coordinates(code, pos):
+    if pos.dim() != 3 or tuple(pos.shape) != (code.shape[0], pos.shape[1], 2):
         raise ValueError(f"positions must be the two point coordinates [B, N, 2]; got {tuple(pos.shape)}")
-    hidden = w1.shape[0]
-    want = ((hidden, Cc + 2), (hidden,), (hidden, hidden), (hidden,), (1, hidden), (1,))
-    if tuple(tuple(p.shape) for p in params) != want:
-        raise ValueError("weight_projection must be MLP(C+2, hidden, 1) with one hidden layer: "
-                         f"shapes {want}, got {tuple(tuple(p.shape) for p in params)}")
-    return B, N, M, Cc, hidden
 
 
 def code_slice_weights_fwd(code, pos, params):
-    """code [B, M, C], pos [B, N, 2], params = (w1, b1, w2, b2, w3, b3) of weight_projection -> sw [B, 1, N, M]."""
-    _chk(code, pos, *params)
-    B, N, M, Cc, hidden = _code_sw_shapes(code, pos, params)
-    sw = torch.empty(B, 1, N, M, dtype=torch.float32, device=code.device)
-    e0, e1 = _events("code_slice_weights")
-    _lib.check(_L().pa2d_code_slice_weights_fwd(_p(code), _p(pos), *(_p(t) for t in params), _p(sw), B, N, M, Cc, hidden,
-                                                CODE_SW_DEPTH, _stream(), e0, e1), "code_slice_weights_fwd")
-    return sw
+    """code [B, M, C], pos [B, N, 2], params = (w1, b1, w2, b2, w3, b3) of weight_projection -> sw [B, 1, N, M]: the
+    coordinates are P = 2 point features of point_slice_weights_fwd."""
+    _two_coordinates(code, pos)
+    return point_slice_weights_fwd(code, pos, params)
 
 
 def code_slice_weights_bwd(code, pos, params, dsw, need_dcode=True, into=None):
     """Returns (dcode [B, M, C] or None, dw1, db1, dw2, db2, dw3, db3); `into` = the six gradient buffers to add into."""
-    _chk(code, pos, dsw, *params)
-    B, N, M, Cc, hidden = _code_sw_shapes(code, pos, params)
-    if tuple(dsw.shape) != (B, 1, N, M):
-        raise ValueError(f"dsw must be [B, 1, N, M] = {(B, 1, N, M)}; got {tuple(dsw.shape)}")
-    dcode = torch.empty_like(code) if need_dcode else None
-    grads, acc = _grad_outputs(into, tuple(p.shape for p in params), code)
-    nb = _L().pa2d_code_slice_weights_bwd_workspace(B, N, M, Cc)
-    ws = _ws(nb, code)
-    e0, e1 = _events("code_slice_weights_bwd")
-    _lib.check(_L().pa2d_code_slice_weights_bwd(_p(code), _p(pos), *(_p(t) for t in params), _p(dsw), _p(dcode),
-                                                *(_p(g) for g in grads), ws.data_ptr(), nb, B, N, M, Cc, hidden,
-                                                CODE_SW_DEPTH, acc, _stream(), e0, e1), "code_slice_weights_bwd")
-    return (dcode,) + tuple(grads)
+    _two_coordinates(code, pos)
+    return point_slice_weights_bwd(code, pos, params, dsw, need_dcode=need_dcode, into=into)
 
 
 # ---------------------------------------------------------------------------------------------- LearnSlice stages
-# The slice weights from the code and P features per point (pa2d_point_slice_weights_*: code_slice_weights_* with the point
-# part of the first layer 1 <= P <= 128 wide) and the trainer's loss (pa2d_slice_mse_*).  Exact fp32, no `engine`.
+# The slice weights from the code and P features per point (pa2d_point_slice_weights_*: the point part of the first layer is
+# 1 <= P <= 128 wide) and the trainer's loss (pa2d_slice_mse_*).  Exact fp32, no `engine`.
 POINT_SW_MAX_P = 128
 
 
