@@ -204,3 +204,89 @@ def test_weight_image_entry_point_rejects_before_launching():
     assert lib.pa2d_gemm_weight_image(0, 256, 0, 16, 1024, 256, 256, 1, 0) == 1003      # buffer too small
     assert lib.pa2d_gemm_weight_image(0, 256, 1, 0, 256 * 256 * 6, 256, 256, 1, 0) == 1003   # no buffer
 
+
+def test_conv_entry_points_reject_before_launching():
+    """Every conv family (pair, single, 3x3x3, operand planes, bf16 storage) refuses on the host, with its own checks in its
+    own order: NULL pointers and stream 0 throughout, only inputs that return before anything is launched or recorded."""
+    from transformerbasednavierstokesolver_amd import _lib
+    lib = _lib.load()
+    ARG, UNSUPPORTED, WORKSPACE, big = 1001, 1002, 1003, 1 << 40
+    n = (0,)      # NULL pointers: n * k
+    ev = (0, 0, 0)      # stream, ev_start, ev_stop
+    got = []
+
+    def expect(code, name, *args):
+        got.append((name, args, getattr(lib, name)(*args), code))
+
+    for e in (7, -1):      # engine out of range
+        expect(ARG, "pa2d_conv3x3x2_fwd", *n * 8, big, 2, 16, 16, 64, e, *ev)
+        expect(ARG, "pa2d_conv3x3x2_bwd", *n * 11, big, 2, 16, 16, 64, 0, e, *ev)
+        expect(ARG, "pa2d_conv3x3x2_pack", *n * 3, big, 2, 16, 16, 64, 0, e, 0)
+        expect(ARG, "pa2d_conv3x3_fwd", *n * 6, big, 2, 16, 16, 64, e, *ev)
+        expect(ARG, "pa2d_conv3x3_bwd", *n * 8, big, 2, 16, 16, 64, 0, e, *ev)
+        expect(ARG, "pa2d_conv3x3_pack", *n * 2, big, 2, 16, 16, 64, 0, e, 0)
+        expect(ARG, "pa2d_conv3x3_pack", *n * 2, big, 2, 16, 16, 24, 0, e, 0)      # the engine is checked before C
+        expect(ARG, "pa2d_conv3x3x3x2_fwd", *n * 8, big, 2, 4, 4, 4, 64, e, *ev)
+        expect(ARG, "pa2d_conv3x3x3x2_bwd", *n * 11, big, 2, 4, 4, 4, 64, 0, e, *ev)
+        expect(ARG, "pa2d_conv3x3x3x2_pack", *n * 3, big, 2, 4, 4, 4, 24, 0, e, 0)
+        # the planes interface has no engine check of its own: no operand is a plane image under such an engine
+        expect(UNSUPPORTED, "pa2d_conv3x3x2_fwd_planes", *n * 8, big, 2, 16, 16, 64, e, *ev)
+        expect(UNSUPPORTED, "pa2d_conv3x3x2_bwd_planes", *n * 9, big, 2, 16, 16, 64, 0, e, *ev)
+    for e in (0, 1, 2):
+        for shp in ((2, 16, 16, 64), (1, 24, 24, 256), (2, 24, 24, 192)):      # a workspace of 0 bytes, B > 0
+            expect(WORKSPACE, "pa2d_conv3x3x2_fwd", *n * 8, 0, *shp, e, *ev)
+            expect(WORKSPACE, "pa2d_conv3x3x2_bwd", *n * 11, 0, *shp, 0, e, *ev)
+            expect(WORKSPACE, "pa2d_conv3x3_fwd", *n * 5, 1, 0, *shp, e, *ev)
+            expect(WORKSPACE, "pa2d_conv3x3_bwd", *n * 7, 1, 0, *shp, 0, e, *ev)
+            expect(WORKSPACE, "pa2d_conv3x3_fwd", *n * 6, big, *shp, e, *ev)      # the single conv also refuses a NULL workspace
+            expect(WORKSPACE, "pa2d_conv3x3_bwd", *n * 8, big, *shp, 0, e, *ev)
+        expect(WORKSPACE, "pa2d_conv3x3x3x2_fwd", *n * 8, 0, 2, 4, 4, 4, 64, e, *ev)
+        expect(WORKSPACE, "pa2d_conv3x3x3x2_bwd", *n * 11, 0, 2, 4, 4, 4, 64, 0, e, *ev)
+        # C not a multiple of 16, non-positive extents, operand past 4 GiB, rows past int
+        expect(UNSUPPORTED, "pa2d_conv3x3_fwd", *n * 6, big, 2, 16, 16, 24, e, *ev)
+        expect(UNSUPPORTED, "pa2d_conv3x3_bwd", *n * 8, big, 2, 16, 16, 24, 0, e, *ev)
+        expect(UNSUPPORTED, "pa2d_conv3x3_pack", *n * 2, big, 2, 16, 16, 24, 0, e, 0)
+        expect(ARG, "pa2d_conv3x3_fwd", *n * 6, big, 2, 0, 16, 64, e, *ev)
+        expect(ARG, "pa2d_conv3x3_bwd", *n * 8, big, 2, 16, -1, 64, 0, e, *ev)
+        expect(UNSUPPORTED, "pa2d_conv3x3_fwd", *n * 6, big, 32, 2048, 2048, 64, e, *ev)
+        expect(UNSUPPORTED, "pa2d_conv3x3_bwd", *n * 8, big, 32, 2048, 2048, 64, 0, e, *ev)
+        expect(UNSUPPORTED, "pa2d_conv3x3_pack", *n * 2, big, 32, 2048, 2048, 64, 1, e, 0)
+        expect(UNSUPPORTED, "pa2d_conv3x3x3x2_fwd", *n * 8, big, 2, 4, 4, 4, 24, e, *ev)
+        expect(UNSUPPORTED, "pa2d_conv3x3x3x2_bwd", *n * 11, big, 2, 4, 4, 4, 24, 0, e, *ev)
+        expect(UNSUPPORTED, "pa2d_conv3x3x3x2_pack", *n * 3, big, 2, 4, 4, 4, 24, 0, e, 0)
+        expect(ARG, "pa2d_conv3x3x3x2_fwd", *n * 8, big, 2, 4, 0, 4, 64, e, *ev)
+        expect(ARG, "pa2d_conv3x3x3x2_bwd", *n * 11, big, 2, 4, 4, 0, 64, 0, e, *ev)
+        expect(UNSUPPORTED, "pa2d_conv3x3x3x2_fwd", *n * 8, big, 32, 1024, 1024, 64, 64, e, *ev)
+        expect(UNSUPPORTED, "pa2d_conv3x3x3x2_bwd", *n * 11, big, 32, 1024, 1024, 64, 64, 0, e, *ev)
+        expect(UNSUPPORTED, "pa2d_conv3x3x3x2_pack", *n * 3, big, 32, 1024, 1024, 64, 64, 0, e, 0)
+        # a pack buffer that is too small
+        expect(WORKSPACE, "pa2d_conv3x3x2_pack", *n * 3, 16, 2, 16, 16, 64, 0, e, 0)
+        expect(WORKSPACE, "pa2d_conv3x3_pack", *n * 2, 16, 2, 16, 16, 64, 1, e, 0)
+        expect(WORKSPACE, "pa2d_conv3x3x3x2_pack", *n * 3, 16, 2, 4, 4, 4, 64, 0, e, 0)
+        # operand planes: the shape decides before the workspace does (mask & 1 forward, mask == 7 backward)
+        for shp, masks in (((2, 6, 5, 32), (0, 0, 0)), ((2, 16, 16, 64), (0, 1, 1)), ((2, 24, 24, 192), (0, 7, 7))):
+            mask = masks[e]
+            assert lib.pa2d_conv3x3x2_planes_mask(*shp, e) == mask
+            expect(WORKSPACE if mask & 1 else UNSUPPORTED, "pa2d_conv3x3x2_fwd_planes", *n * 8, 0, *shp, e, *ev)
+            expect(WORKSPACE if mask == 7 else UNSUPPORTED, "pa2d_conv3x3x2_bwd_planes", *n * 9, 0, *shp, 0, e, *ev)
+    # bf16 storage: C % 32 first, then the sizes
+    expect(UNSUPPORTED, "pa2d_conv3x3x2_pack_bf16", *n * 3, big, 48, 0, 0)
+    expect(UNSUPPORTED, "pa2d_conv3x3x2_fwd_bf16", *n * 8, big, 2, 16, 16, 48, *ev)
+    expect(UNSUPPORTED, "pa2d_conv3x3x2_bwd_bf16", *n * 11, big, 2, 16, 16, 48, 0, *ev)
+    expect(WORKSPACE, "pa2d_conv3x3x2_pack_bf16", *n * 3, 16, 64, 1, 0)
+    expect(WORKSPACE, "pa2d_conv3x3x2_fwd_bf16", *n * 8, 0, 2, 16, 16, 64, *ev)
+    expect(WORKSPACE, "pa2d_conv3x3x2_bwd_bf16", *n * 11, 0, 2, 16, 16, 64, 0, *ev)
+    # an empty batch is no error and no work (backward: accumulate = 1, so nothing is zeroed either)
+    expect(0, "pa2d_conv3x3x2_fwd", *n * 8, 0, 0, 16, 16, 64, 1, *ev)
+    expect(0, "pa2d_conv3x3x2_bwd", *n * 11, 0, 0, 16, 16, 64, 1, 1, *ev)
+    expect(0, "pa2d_conv3x3_fwd", *n * 6, 0, 0, 16, 16, 64, 1, *ev)
+    expect(0, "pa2d_conv3x3_bwd", *n * 8, 0, 0, 16, 16, 64, 1, 1, *ev)
+    expect(0, "pa2d_conv3x3x3x2_fwd", *n * 8, 0, 0, 4, 4, 4, 64, 1, *ev)
+    expect(0, "pa2d_conv3x3x3x2_bwd", *n * 11, 0, 0, 4, 4, 4, 64, 1, 1, *ev)
+    expect(0, "pa2d_conv3x3x2_fwd_planes", *n * 8, 0, 0, 16, 16, 64, 7, *ev)
+    expect(0, "pa2d_conv3x3x2_bwd_planes", *n * 9, 0, 0, 16, 16, 64, 1, 7, *ev)
+    expect(0, "pa2d_conv3x3x2_fwd_bf16", *n * 8, 0, 0, 16, 16, 64, *ev)
+    expect(0, "pa2d_conv3x3x2_bwd_bf16", *n * 11, 0, 0, 16, 16, 64, 1, *ev)
+    wrong = [(name, args, rc, code) for name, args, rc, code in got if rc != code]
+    assert not wrong, wrong
+

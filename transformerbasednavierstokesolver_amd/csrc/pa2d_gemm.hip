@@ -1,4 +1,5 @@
-// Engine selection, weight re-layouts and the C ABI of the dense (GEMM / conv) stages.  Kernels live in
+// Engine selection, launch_kc (the one dispatch of every forward / data-gradient GEMM), the fp32 weight re-layouts and
+// the C ABI of the dense (linear) stages; the C ABI of the conv stages is pa2d_conv.hip.  Kernels live in
 // pa2d_gemm_kc.hip (exact fp32), pa2d_gemm_split.hip (bf16 engines) and pa2d_gemm_mc.hip (weight gradients).
 #include "pa2d_gemm_common.h"
 #include <string.h>
@@ -7,7 +8,6 @@
 // models in one process can use different engines): 0 = exact fp32 MFMA (v_mfma_f32_32x32x2_f32), 1 = 6-term bf16
 // split at fp32 accuracy (conv GEMMs and large-M plain GEMMs; small GEMMs stay exact), 2 = bf16 compute for every GEMM (fp32 accumulate
 // and storage).  pa2d_default_engine() only reads the environment (PA2D_GEMM=f32|split|bf16), default = split.
-static bool engine_ok(int e) { return e >= 0 && e <= 2; }
 
 // ---- the one place the library reads the environment (pa2d_internal.h: Pa2dEnv)
 static Pa2dEnv read_env() {
@@ -62,8 +62,7 @@ bool use_split(int engine, int N, bool im2col, int Cin) {
     return false;
 }
 
-static int launch_kc(const KCParams& p_in, bool im2col, hipStream_t st, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
-static int launch_kc(const KCParams& p_in, bool im2col, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
+int launch_kc(const KCParams& p_in, bool im2col, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
     KCParams p = p_in;
     if (!engine_ok(p.engine)) return PA2D_ERR_ARG;
     if (p.M <= 0 || p.N <= 0 || p.K <= 0) return PA2D_OK;
@@ -167,8 +166,8 @@ __global__ void repack_kernel(const float* __restrict__ w0, const float* __restr
     }
 }
 
-static int launch_repack(const float* w0, const float* w1, float* dst, int mode, int N, int K, int C, int Cin,
-                         hipStream_t st, int taps = 9) {
+int launch_repack(const float* w0, const float* w1, float* dst, int mode, int N, int K, int C, int Cin, hipStream_t st,
+                  int taps) {
     const int nk = w1 ? 2 : 1;
     const long long count = mode == 0 ? (long long)N * K : (long long)nk * C * taps * Cin;
     const dim3 grid((unsigned)ceil_div_ll(count, 256));
@@ -178,6 +177,33 @@ static int launch_repack(const float* w0, const float* w1, float* dst, int mode,
         hipLaunchKernelGGL(repack_kernel<9>, grid, dim3(256), 0, st, w0, w1, dst, mode, N, K, C, Cin, nk);
     PA2D_CHECK_LAUNCH();
     return PA2D_OK;
+}
+
+// KCParams of y = act(x . w^T + bias) (+ res), pre = the pre-activation (or its derivative, PA2D_ACT_SAVE_DERIVATIVE_BIT);
+// io_bf16: x, res, y, pre are bf16 (always the bf16 engine)
+static KCParams dense_fwd_params(const void* x, long long ldx, const float* w, long long ldw, const float* bias,
+                                 const void* res, long long ldres, void* y, long long ldy, void* pre, long long ldpre, int M,
+                                 int N, int K, int act, int engine, bool io_bf16) {
+    KCParams p = {};
+    p.engine = engine; p.io_bf16 = io_bf16 ? 1 : 0; p.apre = io_bf16 ? 1 : 0;
+    p.aux_deriv = (act & PA2D_ACT_SAVE_DERIVATIVE_BIT) ? 1 : 0;
+    act &= ~PA2D_ACT_SAVE_DERIVATIVE_BIT;
+    p.A = (const float*)x; p.lda = ldx; p.B = w; p.ldb = ldw; p.C = (float*)y; p.ldc = ldy; p.bias = bias;
+    p.res = (const float*)res; p.ldres = ldres; p.aux = (float*)pre; p.ldaux = ldpre; p.M = M; p.N = N; p.K = K; p.act = act;
+    p.epi = (act != ACT_NONE ? EPI_ACT : 0) | (pre ? EPI_STORE_PRE : 0);
+    return p;
+}
+// KCParams of dx[M,K] = (dy[M,N] . w[N,K]) * act'(pre[M,K]) on the transposed weight wt[K][N]
+static KCParams dense_bwd_data_params(const void* dy, long long lddy, const float* wt, const void* pre, long long ldpre,
+                                      int act, void* dx, long long lddx, int M, int N, int K, int engine, bool io_bf16) {
+    KCParams p = {};
+    p.engine = engine; p.io_bf16 = io_bf16 ? 1 : 0; p.apre = io_bf16 ? 1 : 0;
+    p.aux_deriv = (act & PA2D_ACT_SAVE_DERIVATIVE_BIT) ? 1 : 0;
+    act &= ~PA2D_ACT_SAVE_DERIVATIVE_BIT;
+    p.A = (const float*)dy; p.lda = lddy; p.B = wt; p.ldb = N; p.C = (float*)dx; p.ldc = lddx; p.M = M; p.N = K; p.K = N;
+    p.aux = (float*)const_cast<void*>(pre); p.ldaux = ldpre; p.act = act;
+    p.epi = (pre && act != ACT_NONE) ? EPI_MUL_DACT : 0;
+    return p;
 }
 
 // =============================================================================================
@@ -214,13 +240,7 @@ int pa2d_gemm_bias_act_fwd(const float* x, long long ldx, const float* w, long l
                            const float* res, long long ldres, float* y, long long ldy, float* pre, long long ldpre,
                            const void* wimg, void* ws, size_t ws_bytes, int M, int N, int K, int act, int engine,
                            hipStream_t st) {
-    KCParams p = {};
-    p.engine = engine;
-    p.aux_deriv = (act & PA2D_ACT_SAVE_DERIVATIVE_BIT) ? 1 : 0;
-    act &= ~PA2D_ACT_SAVE_DERIVATIVE_BIT;
-    p.A = x; p.lda = ldx; p.B = w; p.ldb = ldw; p.C = y; p.ldc = ldy; p.bias = bias; p.res = res; p.ldres = ldres;
-    p.aux = pre; p.ldaux = ldpre; p.M = M; p.N = N; p.K = K; p.act = act;
-    p.epi = (act != ACT_NONE ? EPI_ACT : 0) | (pre ? EPI_STORE_PRE : 0);
+    KCParams p = dense_fwd_params(x, ldx, w, ldw, bias, res, ldres, y, ldy, pre, ldpre, M, N, K, act, engine, false);
     const size_t img = rowpanel_image_bytes(N, K, engine);
     if (img && wimg) p.wimg = const_cast<void*>(wimg);      // ready-made (p.wsrc stays NULL: nothing to pack)
     else if (ws && img && ws_bytes >= img) { p.wimg = ws; p.wsrc = w; p.wsn = ldw; p.wsk = 1; }
@@ -238,13 +258,7 @@ int pa2d_gemm_bwd_data(const float* dy, long long lddy, const float* w, long lon
     if (M <= 0) return PA2D_OK;
     if (ws_bytes < (size_t)N * K * sizeof(float)) return PA2D_ERR_WORKSPACE;
     float* const wt_ws = (float*)ws;
-    KCParams p = {};
-    p.engine = engine;
-    p.aux_deriv = (act & PA2D_ACT_SAVE_DERIVATIVE_BIT) ? 1 : 0;
-    act &= ~PA2D_ACT_SAVE_DERIVATIVE_BIT;
-    p.A = dy; p.lda = lddy; p.B = wt_ws; p.ldb = N; p.C = dx; p.ldc = lddx; p.M = M; p.N = K; p.K = N;
-    p.aux = const_cast<float*>(pre); p.ldaux = ldpre; p.act = act;
-    p.epi = (pre && act != ACT_NONE) ? EPI_MUL_DACT : 0;
+    KCParams p = dense_bwd_data_params(dy, lddy, wt_ws, pre, ldpre, act, dx, lddx, M, N, K, engine, false);
     const size_t img = rowpanel_image_bytes(K, N, engine);
     if (img && wimg) p.wimg = const_cast<void*>(wimg);      // ready-made image of w^T (pa2d_gemm_weight_image, transposed = 1)
     else if (img && ws_bytes >= (size_t)N * K * sizeof(float) + img) {
@@ -288,477 +302,17 @@ int pa2d_gemm_bwd_weight(const float* dy, long long lddy, const float* x, long l
     return rc;
 }
 
-// bf16 engines: bytes of the pre-split activation planes of a [rows, Cin] operand (0 when the engine selected for
-// this GEMM reads fp32 operands)
-static size_t conv_planes_bytes(int engine, int M, int N, int Cin) {
-    if (!use_split(engine, N, true, Cin)) return 0;
-    return (planes_bytes(M, Cin, engine == 2 ? 1 : 3) + 255) & ~(size_t)255;
-}
-
-// bf16 engines: the weight gradient also runs from pre-split planes (of dOut and of X) when the tile shapes allow
-// 0 = fp32 operands (gather kernel), 1 = planes, 128 x 128 tiles, 2 = planes, 256 x 256 tiles (one round of workgroups).
-// The planes kernels are 3x3 only: the 3x3x3 conv (taps = 27) always takes the gather kernel.
-static int conv_dw_kind(int engine, int M, int C, int taps = 9) {
-    if (taps != 9 || conv_planes_bytes(engine, M, C, 2 * C) == 0) return 0;
-    if (mc_planes_big_applies(C, C, M)) return 2;
-    return (mc_planes_supported(C, C) && plan_mc(2 * C, 9 * C, M).big) ? 1 : 0;
-}
-static MCPlan conv_dw_plan(int engine, int M, int C, int taps = 9) {
-    return conv_dw_kind(engine, M, C, taps) == 2 ? plan_mc_planes_big(2 * C, 9 * C, M) : plan_mc(2 * C, taps * C, M);
-}
-static size_t conv_xplanes_bytes(int engine, int M, int C, int taps = 9) {
-    return conv_dw_kind(engine, M, C, taps) ? ((planes_bytes(M, C, engine == 2 ? 1 : 3) + 255) & ~(size_t)255) : 0;
-}
-// weight pack: fp32 pack (2C * taps*C floats) or 3 bf16 planes (1.5x)
-static size_t conv_pack_floats(int C, int taps) { return (size_t)3 * C * taps * C; }
-
-// backward workspace: [weight pack | slabs or column-sum partials | dOut planes | X planes]  (planes: bf16 engines)
-static size_t conv_bwd_workspace(int M, int C, int engine, int taps) {
-    const MCPlan pl = conv_dw_plan(engine, M, C, taps);
-    size_t sl = pl.slab_floats, cs = (size_t)colsum_blocks(M) * 2 * C;
-    return (conv_pack_floats(C, taps) + (sl > cs ? sl : cs)) * sizeof(float) + conv_planes_bytes(engine, M, C, 2 * C) +
-           conv_xplanes_bytes(engine, M, C, taps);
-}
-// forward workspace: [weight pack (unused if prepacked) | activation planes (bf16 engines)]
-static size_t conv_fwd_workspace(int M, int C, int engine, int taps) {
-    return conv_pack_floats(C, taps) * sizeof(float) + conv_planes_bytes(engine, M, 2 * C, C);
-}
-
-size_t pa2d_conv3x3x2_workspace(int B, int H, int W, int C, int engine) { return conv_bwd_workspace(B * H * W, C, engine, 9); }
-size_t pa2d_conv3x3x2_fwd_workspace(int B, int H, int W, int C, int engine) {
-    return conv_fwd_workspace(B * H * W, C, engine, 9);
-}
-
-// Packed conv weights in the layout the engine selected for these dims wants (channel chunk = K-step of the
-// tile, fp32 or bf16 planes by GEMM mode).  direction 0: forward pack ([2C][taps*C]); 1: data-gradient pack
-// ([C][taps*2C], taps flipped).  pack: conv_pack_floats(C, taps) floats.  A pack stays valid while the weights,
-// the dims and the GEMM mode do not change.
-static int conv_pack(const float* wx, const float* wf, float* pack, int M, int C, int direction, int engine,
-                     hipStream_t st, int taps = 9) {
-    const int N = direction ? C : 2 * C, Cin = direction ? 2 * C : C;
-    if (use_split(engine, N, true, Cin)) {
-        return launch_repack_split(wx, wf, pack, direction, engine == 2 ? 1 : 3, C, C, st, taps);
-    }
-    return launch_repack(wx, wf, pack, direction ? 2 : 1, 0, kc_tile(M, N, true, Cin).bk, C, C, st, taps);
-}
-
-size_t pa2d_conv3x3x2_pack_bytes(int C) { return conv_pack_floats(C, 9) * sizeof(float); }
-
-int pa2d_conv3x3x2_pack(const float* wx, const float* wf, void* pack, size_t pack_bytes, int B, int H, int W, int C,
-                        int direction, int engine, hipStream_t st) {
-    if (!engine_ok(engine)) return PA2D_ERR_ARG;
-    if (pack_bytes < pa2d_conv3x3x2_pack_bytes(C)) return PA2D_ERR_WORKSPACE;
-    return conv_pack(wx, wf, (float*)pack, B * H * W, C, direction ? 1 : 0, engine, st);
-}
-
-// Forward of the fused pair on M = B*H*W*depth rows: taps = 9 (depth 1) is the 3x3 conv of pa2d_conv3x3x2_fwd, taps = 27
-// the 3x3x3 conv of pa2d_conv3x3x3x2_fwd.  One implicit GEMM [M, taps*C] x [taps*C, 2C].
-static int conv_fwd(const float* xn, const float* wx, const float* bx, const float* wf, const float* bf, float* out,
-                    const void* prepacked, void* ws, size_t ws_bytes, int B, int H, int W, int depth, int taps, int C,
-                    int engine, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop) {
-    if (!engine_ok(engine)) return PA2D_ERR_ARG;
-    if (B <= 0) return PA2D_OK;
-    const int M = B * H * W * depth;
-    if (ws_bytes < conv_fwd_workspace(M, C, engine, taps)) return PA2D_ERR_WORKSPACE;
-    const float* pack = (const float*)prepacked;
-    if (!pack) {
-        const int rc = conv_pack(wx, wf, (float*)ws, M, C, 0, engine, st, taps);
-        if (rc) return rc;
-        pack = (const float*)ws;
-    }
-    const size_t apl = conv_planes_bytes(engine, M, 2 * C, C);
-    void* const planes = (char*)ws + conv_pack_floats(C, taps) * sizeof(float);
-    if (apl) {
-        const int rc = launch_split_planes(xn, C, planes, (long long)M, C, engine == 2 ? 1 : 3, st);
-        if (rc) return rc;
-    }
-    KCParams p = {};
-    p.engine = engine;
-    p.A = apl ? (const float*)planes : xn; p.apre = apl ? 1 : 0;
-    p.lda = C; p.B = pack; p.ldb = taps * C; p.C = out; p.ldc = 2 * C;
-    p.bias = bx; p.bias2 = bf; p.bias_split = C;
-    p.M = M; p.N = 2 * C; p.K = taps * C; p.H = H; p.W = W; p.Cin = C;
-    p.taps = taps; p.depth = depth;
-    return launch_kc(p, true, st, ev_start, ev_stop);
-}
-
-// Backward of the fused pair (taps / depth as in conv_fwd): dxn (plain store, may be NULL), dwx / dwf, dbx / dbf
-static int conv_bwd(const float* dout, const float* xn, const float* wx, const float* wf, float* dxn, float* dwx,
-                    float* dbx, float* dwf, float* dbf, const void* prepacked, void* ws, size_t ws_bytes, int B, int H,
-                    int W, int depth, int taps, int C, int accumulate, int engine, hipStream_t st, hipEvent_t ev_start,
-                    hipEvent_t ev_stop) {
-    if (!engine_ok(engine)) return PA2D_ERR_ARG;
-    if (B <= 0) {
-        if (accumulate) return PA2D_OK;
-        const size_t wb = sizeof(float) * (size_t)C * C * taps, bb = sizeof(float) * C;
-        int rz = pa2d_zero(dwx, wb, st);
-        if (!rz) rz = pa2d_zero(dwf, wb, st);
-        if (!rz) rz = pa2d_zero(dbx, bb, st);
-        return rz ? rz : pa2d_zero(dbf, bb, st);
-    }
-    const int M = B * H * W * depth;
-    const size_t need = conv_bwd_workspace(M, C, engine, taps);
-    if (ws_bytes < need) return PA2D_ERR_WORKSPACE;
-    float* scratch = (float*)ws + conv_pack_floats(C, taps);
-    int rc;
-    const int NT = engine == 2 ? 1 : 3;
-    const size_t apl = conv_planes_bytes(engine, M, C, 2 * C), xpl = conv_xplanes_bytes(engine, M, C, taps);
-    void* const planes = (char*)ws + need - apl - xpl;                                       // dOut planes
-    void* const xplanes = (char*)planes + apl;                                               // X planes
-    if (apl && (dxn || xpl)) {
-        rc = launch_split_planes(dout, 2 * C, planes, M, 2 * C, NT, st);
-        if (rc) return rc;
-    }
-    if (dxn) {
-        const float* pack = (const float*)prepacked;
-        if (!pack) {
-            rc = conv_pack(wx, wf, (float*)ws, M, C, 1, engine, st, taps);
-            if (rc) return rc;
-            pack = (const float*)ws;
-        }
-        KCParams p = {};
-        p.engine = engine;
-        p.A = apl ? (const float*)planes : dout; p.apre = apl ? 1 : 0;
-        p.lda = 2 * C; p.B = pack; p.ldb = taps * 2 * C; p.C = dxn; p.ldc = C;
-        p.M = M; p.N = C; p.K = taps * 2 * C; p.H = H; p.W = W; p.Cin = 2 * C;
-        p.taps = taps; p.depth = depth;
-        rc = launch_kc(p, true, st, ev_start, ev_stop);
-        if (rc) return rc;
-    }
-    const MCPlan pl = conv_dw_plan(engine, M, C, taps);
-    if (xpl) {      // bf16 engines: both operands as pre-split planes, transposed LDS reads, no conversion in the GEMM
-        rc = launch_split_planes(xn, C, xplanes, M, C, NT, st);
-        if (rc) return rc;
-        rc = pl.big == 2 ? launch_mc_planes_big(planes, xplanes, C, C, M, H, W, scratch, pl, NT, st)
-                         : launch_mc_planes(planes, xplanes, C, C, M, H, W, scratch, pl, NT, st);
-    } else {
-        rc = launch_mc(dout, 2 * C, 2 * C, xn, C, taps * C, M, true, H, W, C, scratch, pl, engine, st, nullptr, taps, depth);
-    }
-    if (rc) return rc;
-    rc = launch_reduce(scratch, pl.splits, (long long)2 * C * taps * C, dwx, dwf, 1, C, C, st, accumulate, taps);
-    if (rc) return rc;
-    return launch_colsum(dout, 2 * C, M, 2 * C, dbx, scratch, st, dbf, C, accumulate);
-}
-
-// out[B*H*W, 2C] = [conv3x3(xn, wx) + bx | conv3x3(xn, wf) + bf]   (zero padding 1, NHWC)
-// Physics_Attention.py:94,96 — both projections read the same input, so they run as ONE implicit
-// GEMM [B*N, 9C] x [9C, 2C].  prepacked: NULL (weights are packed into ws by this call) or a pack made by
-// pa2d_conv3x3x2_pack(direction 0) for the same B, H, W, C.
-int pa2d_conv3x3x2_fwd(const float* xn, const float* wx, const float* bx, const float* wf, const float* bf,
-                       float* out, const void* prepacked, void* ws, size_t ws_bytes, int B, int H, int W, int C,
-                       int engine, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop) {
-    return conv_fwd(xn, wx, bx, wf, bf, out, prepacked, ws, ws_bytes, B, H, W, 1, 9, C, engine, st, ev_start, ev_stop);
-}
-
-// dxn[B*N, C] (plain store), dwx/dwf [C,C,3,3], dbx/dbf [C] (accumulate != 0: added to) from dout[B*N, 2C]
-int pa2d_conv3x3x2_bwd(const float* dout, const float* xn, const float* wx, const float* wf, float* dxn, float* dwx,
-                       float* dbx, float* dwf, float* dbf, const void* prepacked, void* ws, size_t ws_bytes, int B,
-                       int H, int W, int C, int accumulate, int engine, hipStream_t st, hipEvent_t ev_start,
-                       hipEvent_t ev_stop) {
-    return conv_bwd(dout, xn, wx, wf, dxn, dwx, dbx, dwf, dbf, prepacked, ws, ws_bytes, B, H, W, 1, 9, C, accumulate, engine,
-                    st, ev_start, ev_stop);
-}
-
-// ---- single 3x3 conv (SliceLearner.py: in_project_x alone): ONE Conv2d(C, C, 3, 1, 1) as the implicit GEMM
-// [B*N, 9C] x [9C, C].  The pair's kernels and engine choice on KCParams with N = C, Cin = C (forward and data gradient:
-// K = 9C both ways) and the weight gradient of one half (Mi = C); packs are the pair's layouts with one kernel in them.
-// Nothing of a second kernel is computed or staged.
-static size_t conv1_pack_floats(int C) { return ((size_t)3 * C * 9 * C + 1) / 2; }      // fp32 pack, or 3 bf16 planes (1.5x)
-// weight gradient of the bf16 engines from pre-split planes on the 256 x 256-tile kernel (Mi = C rows), else the gather kernel
-static bool conv1_dw_planes(int engine, int M, int C) {
-    return conv_planes_bytes(engine, M, C, C) != 0 && !pa2d_env().mc_big_off && C >= 256 && M >= 16 * 8 * 4;
-}
-static MCPlan conv1_dw_plan(int engine, int M, int C) {
-    return conv1_dw_planes(engine, M, C) ? plan_mc_planes_big(C, 9 * C, M) : plan_mc(C, 9 * C, M);
-}
-// backward workspace: [weight pack | slabs or column-sum partials | dOut planes | X planes]  (planes: bf16 engines)
-static size_t conv1_bwd_workspace(int M, int C, int engine) {
-    const MCPlan pl = conv1_dw_plan(engine, M, C);
-    const size_t sl = pl.slab_floats, cs = (size_t)colsum_blocks(M) * C;
-    const size_t apl = conv_planes_bytes(engine, M, C, C);
-    return (conv1_pack_floats(C) + (sl > cs ? sl : cs)) * sizeof(float) + apl + (conv1_dw_planes(engine, M, C) ? apl : 0);
-}
-static size_t conv1_fwd_workspace(int M, int C, int engine) {
-    return conv1_pack_floats(C) * sizeof(float) + conv_planes_bytes(engine, M, C, C);
-}
-static int conv1_pack(const float* w, float* pack, int M, int C, int direction, int engine, hipStream_t st) {
-    if (use_split(engine, C, true, C)) return launch_repack_split(w, nullptr, pack, direction, engine == 2 ? 1 : 3, C, C, st, 9);
-    return launch_repack(w, nullptr, pack, direction ? 2 : 1, 0, kc_tile(M, C, true, C).bk, C, C, st, 9);
-}
-static int conv1_check(int B, int H, int W, int C, int engine) {
-    if (!engine_ok(engine)) return PA2D_ERR_ARG;
-    if (C <= 0 || (C & 15)) return PA2D_ERR_UNSUPPORTED;
-    if (B <= 0) return PA2D_OK;
-    if (H <= 0 || W <= 0) return PA2D_ERR_ARG;
-    // an operand past 4 GiB (32-bit buffer descriptors; the rows must also fit an int)
-    if ((unsigned long long)B * H * W * C * 4ull >= 0xFFFFFFF0ull) return PA2D_ERR_UNSUPPORTED;
-    return PA2D_OK;
-}
-static int conv1_rows(int B, int H, int W, int C, int engine) { return (conv1_check(B, H, W, C, engine) || B <= 0) ? 0 : B * H * W; }
-
-size_t pa2d_conv3x3_workspace(int B, int H, int W, int C, int engine) {
-    return conv1_check(B, H, W, C, engine) ? 0 : conv1_bwd_workspace(conv1_rows(B, H, W, C, engine), C, engine);
-}
-size_t pa2d_conv3x3_fwd_workspace(int B, int H, int W, int C, int engine) {
-    return conv1_check(B, H, W, C, engine) ? 0 : conv1_fwd_workspace(conv1_rows(B, H, W, C, engine), C, engine);
-}
-size_t pa2d_conv3x3_pack_bytes(int C) { return conv1_pack_floats(C) * sizeof(float); }
-
-int pa2d_conv3x3_pack(const float* w, void* pack, size_t pack_bytes, int B, int H, int W, int C, int direction, int engine,
-                      hipStream_t st) {
-    const int rc = conv1_check(B, H, W, C, engine);
-    if (rc) return rc;
-    if (pack_bytes < pa2d_conv3x3_pack_bytes(C)) return PA2D_ERR_WORKSPACE;
-    return conv1_pack(w, (float*)pack, conv1_rows(B, H, W, C, engine), C, direction ? 1 : 0, engine, st);
-}
-
-// out[B*H*W, C] = conv3x3(xn, w) + b   (zero padding 1, NHWC); prepacked: NULL or pa2d_conv3x3_pack(direction 0)
-int pa2d_conv3x3_fwd(const float* xn, const float* w, const float* b, float* out, const void* prepacked, void* ws,
-                     size_t ws_bytes, int B, int H, int W, int C, int engine, hipStream_t st, hipEvent_t ev_start,
-                     hipEvent_t ev_stop) {
-    int rc = conv1_check(B, H, W, C, engine);
-    if (rc) return rc;
-    if (B <= 0) return PA2D_OK;
-    const int M = B * H * W;
-    if (!ws || ws_bytes < conv1_fwd_workspace(M, C, engine)) return PA2D_ERR_WORKSPACE;
-    const float* pack = (const float*)prepacked;
-    if (!pack) {
-        rc = conv1_pack(w, (float*)ws, M, C, 0, engine, st);
-        if (rc) return rc;
-        pack = (const float*)ws;
-    }
-    const size_t apl = conv_planes_bytes(engine, M, C, C);
-    void* const planes = (char*)ws + conv1_pack_floats(C) * sizeof(float);
-    if (apl) {
-        rc = launch_split_planes(xn, C, planes, (long long)M, C, engine == 2 ? 1 : 3, st);
-        if (rc) return rc;
-    }
-    KCParams p = {};
-    p.engine = engine;
-    p.A = apl ? (const float*)planes : xn; p.apre = apl ? 1 : 0;
-    p.lda = C; p.B = pack; p.ldb = 9 * C; p.C = out; p.ldc = C;
-    p.bias = b;
-    p.M = M; p.N = C; p.K = 9 * C; p.H = H; p.W = W; p.Cin = C;
-    p.taps = 9; p.depth = 1;
-    return launch_kc(p, true, st, ev_start, ev_stop);
-}
-
-// dxn[B*N, C] (plain store; may be NULL), dw [C,C,3,3], db [C] ((+)= per `accumulate`) from dout[B*N, C]
-int pa2d_conv3x3_bwd(const float* dout, const float* xn, const float* w, float* dxn, float* dw, float* db,
-                     const void* prepacked, void* ws, size_t ws_bytes, int B, int H, int W, int C, int accumulate, int engine,
-                     hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop) {
-    int rc = conv1_check(B, H, W, C, engine);
-    if (rc) return rc;
-    if (B <= 0) {
-        if (accumulate) return PA2D_OK;
-        rc = pa2d_zero(dw, sizeof(float) * (size_t)C * C * 9, st);
-        return rc ? rc : pa2d_zero(db, sizeof(float) * C, st);
-    }
-    const int M = B * H * W;
-    const size_t need = conv1_bwd_workspace(M, C, engine);
-    if (!ws || ws_bytes < need) return PA2D_ERR_WORKSPACE;
-    float* scratch = (float*)ws + conv1_pack_floats(C);
-    const int NT = engine == 2 ? 1 : 3;
-    const bool dwp = conv1_dw_planes(engine, M, C);
-    const size_t apl = conv_planes_bytes(engine, M, C, C), xpl = dwp ? apl : 0;
-    void* const planes = (char*)ws + need - apl - xpl;                                       // dOut planes
-    void* const xplanes = (char*)planes + apl;                                               // X planes
-    if (apl && (dxn || dwp)) {
-        rc = launch_split_planes(dout, C, planes, M, C, NT, st);
-        if (rc) return rc;
-    }
-    if (dxn) {
-        const float* pack = (const float*)prepacked;
-        if (!pack) {
-            rc = conv1_pack(w, (float*)ws, M, C, 1, engine, st);
-            if (rc) return rc;
-            pack = (const float*)ws;
-        }
-        KCParams p = {};
-        p.engine = engine;
-        p.A = apl ? (const float*)planes : dout; p.apre = apl ? 1 : 0;
-        p.lda = C; p.B = pack; p.ldb = 9 * C; p.C = dxn; p.ldc = C;
-        p.M = M; p.N = C; p.K = 9 * C; p.H = H; p.W = W; p.Cin = C;
-        p.taps = 9; p.depth = 1;
-        rc = launch_kc(p, true, st, ev_start, ev_stop);
-        if (rc) return rc;
-    }
-    const MCPlan pl = conv1_dw_plan(engine, M, C);
-    if (dwp) {
-        rc = launch_split_planes(xn, C, xplanes, M, C, NT, st);
-        if (rc) return rc;
-        rc = launch_mc_planes_big_raw(planes, C, xplanes, C, 9, M, H, W, scratch, pl, NT, st);
-    } else {
-        rc = launch_mc(dout, C, C, xn, C, 9 * C, M, true, H, W, C, scratch, pl, engine, st, nullptr, 9, 1);
-    }
-    if (rc) return rc;
-    // slab rows [C][9][Cin] -> dw [C][Cin][3][3]: the pair's un-pack with every row in the first half
-    rc = launch_reduce(scratch, pl.splits, (long long)C * 9 * C, dw, nullptr, 1, C, C, st, accumulate, 9);
-    if (rc) return rc;
-    return launch_colsum(dout, C, M, C, db, scratch, st, nullptr, 0, accumulate);
-}
-
-// ---- 3x3x3 conv (Physics_Attention_Structured_Mesh_3D: two Conv3d(C, C, 3, 1, 1) on [B, H, W, D, C]).
-// Point n = (h*W + w)*D + d; weights [C_out, C_in, 3, 3, 3], tap t = kh*9 + kw*3 + kd.  The same kernels as the 3x3
-// conv with 27 taps selected explicitly (KCParams::taps); never the halo-in-LDS conv or the planes weight gradient.
-// Rows of the GEMMs (B*H*W*D) must fit an int: larger problems return PA2D_ERR_UNSUPPORTED.
-static long long conv3d_rows(int B, int H, int W, int D) {
-    if (B <= 0 || H <= 0 || W <= 0 || D <= 0) return 0;
-    return (long long)B * H * W * D;
-}
-static int conv3d_check(int B, int H, int W, int D, int C) {
-    if (C <= 0 || (C & 15)) return PA2D_ERR_UNSUPPORTED;
-    if (B <= 0) return PA2D_OK;
-    if (H <= 0 || W <= 0 || D <= 0) return PA2D_ERR_ARG;
-    return conv3d_rows(B, H, W, D) > 0x7fffffffLL ? PA2D_ERR_UNSUPPORTED : PA2D_OK;
-}
-static int conv3d_ws_rows(int B, int H, int W, int D) {
-    const long long r = conv3d_rows(B, H, W, D);
-    return r > 0x7fffffffLL ? 0 : (int)r;      // oversized: the call itself refuses
-}
-
-size_t pa2d_conv3x3x3x2_workspace(int B, int H, int W, int D, int C, int engine) {
-    return conv_bwd_workspace(conv3d_ws_rows(B, H, W, D), C, engine, 27);
-}
-size_t pa2d_conv3x3x3x2_fwd_workspace(int B, int H, int W, int D, int C, int engine) {
-    return conv_fwd_workspace(conv3d_ws_rows(B, H, W, D), C, engine, 27);
-}
-size_t pa2d_conv3x3x3x2_pack_bytes(int C) { return conv_pack_floats(C, 27) * sizeof(float); }
-
-int pa2d_conv3x3x3x2_pack(const float* wx, const float* wf, void* pack, size_t pack_bytes, int B, int H, int W, int D,
-                          int C, int direction, int engine, hipStream_t st) {
-    if (!engine_ok(engine)) return PA2D_ERR_ARG;
-    const int rc = conv3d_check(B, H, W, D, C);
-    if (rc) return rc;
-    if (pack_bytes < pa2d_conv3x3x3x2_pack_bytes(C)) return PA2D_ERR_WORKSPACE;
-    return conv_pack(wx, wf, (float*)pack, conv3d_ws_rows(B, H, W, D), C, direction ? 1 : 0, engine, st, 27);
-}
-
-int pa2d_conv3x3x3x2_fwd(const float* xn, const float* wx, const float* bx, const float* wf, const float* bf, float* out,
-                         const void* prepacked, void* ws, size_t ws_bytes, int B, int H, int W, int D, int C, int engine,
-                         hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop) {
-    if (!engine_ok(engine)) return PA2D_ERR_ARG;
-    const int rc = conv3d_check(B, H, W, D, C);
-    if (rc) return rc;
-    return conv_fwd(xn, wx, bx, wf, bf, out, prepacked, ws, ws_bytes, B, H, W, D, 27, C, engine, st, ev_start, ev_stop);
-}
-
-int pa2d_conv3x3x3x2_bwd(const float* dout, const float* xn, const float* wx, const float* wf, float* dxn, float* dwx,
-                         float* dbx, float* dwf, float* dbf, const void* prepacked, void* ws, size_t ws_bytes, int B, int H,
-                         int W, int D, int C, int accumulate, int engine, hipStream_t st, hipEvent_t ev_start,
-                         hipEvent_t ev_stop) {
-    if (!engine_ok(engine)) return PA2D_ERR_ARG;
-    const int rc = conv3d_check(B, H, W, D, C);
-    if (rc) return rc;
-    return conv_bwd(dout, xn, wx, wf, dxn, dwx, dbx, dwf, dbf, prepacked, ws, ws_bytes, B, H, W, D, 27, C, accumulate, engine,
-                    st, ev_start, ev_stop);
-}
-
-// =============================================================================================
-// Operand-planes interface of the bf16 engines (fp32 storage): the producers of the conv operands (LayerNorm forward,
-// slice backward) can emit the bf16 plane image directly (pa2d_layernorm_fwd_planes, pa2d_slice_bwd_points_planes); these
-// entry points consume it, so no fp32 copy of the operand and no split pre-pass exists.
-
-// bytes of the plane image of a [rows, C] tensor under `engine` (0 for PA2D_ENGINE_F32)
-size_t pa2d_planes_bytes(long long rows, int C, int engine) {
-    if (engine != 1 && engine != 2) return 0;
-    return planes_bytes(rows, C, engine == 2 ? 1 : 3);
-}
-
-// which conv operands `engine` consumes as planes at this shape: bit 0 = X in the forward GEMM, bit 1 = X in the weight
-// gradient, bit 2 = dOut in the data AND weight gradient.  The *_planes entry points need all three (mask == 7).
-int pa2d_conv3x3x2_planes_mask(int B, int H, int W, int C, int engine) {
-    if (!engine_ok(engine) || B <= 0) return 0;
-    const int M = B * H * W;
-    int m = 0;
-    if (conv_planes_bytes(engine, M, 2 * C, C)) m |= 1;
-    if (conv_dw_kind(engine, M, C)) m |= 2;
-    if (conv_planes_bytes(engine, M, C, 2 * C) && conv_dw_kind(engine, M, C)) m |= 4;
-    return m;
-}
-
-int pa2d_conv3x3x2_fwd_planes(const void* xn_planes, const float* wx, const float* bx, const float* wf, const float* bf,
-                              float* out, const void* prepacked, void* ws, size_t ws_bytes, int B, int H, int W, int C,
-                              int engine, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop) {
-    if (B <= 0) return PA2D_OK;
-    if ((pa2d_conv3x3x2_planes_mask(B, H, W, C, engine) & 1) == 0) return PA2D_ERR_UNSUPPORTED;
-    if (ws_bytes < pa2d_conv3x3x2_pack_bytes(C)) return PA2D_ERR_WORKSPACE;
-    const float* pack = (const float*)prepacked;
-    if (!pack) {
-        const int rc = conv_pack(wx, wf, (float*)ws, B * H * W, C, 0, engine, st);
-        if (rc) return rc;
-        pack = (const float*)ws;
-    }
-    KCParams p = {};
-    p.engine = engine;
-    p.A = (const float*)xn_planes; p.apre = 1;
-    p.lda = C; p.B = pack; p.ldb = 9 * C; p.C = out; p.ldc = 2 * C;
-    p.bias = bx; p.bias2 = bf; p.bias_split = C;
-    p.M = B * H * W; p.N = 2 * C; p.K = 9 * C; p.H = H; p.W = W; p.Cin = C;
-    return launch_kc(p, true, st, ev_start, ev_stop);
-}
-
-size_t pa2d_conv3x3x2_workspace_planes(int B, int H, int W, int C, int engine) {
-    const MCPlan pl = conv_dw_plan(engine, B * H * W, C);
-    return pa2d_conv3x3x2_pack_bytes(C) + pl.slab_floats * sizeof(float);
-}
-
-// dxn (may be NULL), dwx / dwf ((+)= per accumulate) from the plane images of dOut [B*H*W, 2C] and X [B*H*W, C];
-// the bias gradients come from pa2d_slice_bwd_points_planes
-int pa2d_conv3x3x2_bwd_planes(const void* dout_planes, const void* xn_planes, const float* wx, const float* wf, float* dxn,
-                              float* dwx, float* dwf, const void* prepacked, void* ws, size_t ws_bytes, int B, int H, int W,
-                              int C, int accumulate, int engine, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop) {
-    if (B <= 0) {
-        if (accumulate) return PA2D_OK;
-        const size_t wb = sizeof(float) * (size_t)C * C * 9;
-        const int rz = pa2d_zero(dwx, wb, st);
-        return rz ? rz : pa2d_zero(dwf, wb, st);
-    }
-    if (pa2d_conv3x3x2_planes_mask(B, H, W, C, engine) != 7) return PA2D_ERR_UNSUPPORTED;
-    if (ws_bytes < pa2d_conv3x3x2_workspace_planes(B, H, W, C, engine)) return PA2D_ERR_WORKSPACE;
-    float* scratch = (float*)((char*)ws + pa2d_conv3x3x2_pack_bytes(C));
-    const int M = B * H * W, NT = engine == 2 ? 1 : 3;
-    int rc;
-    if (dxn) {
-        const float* pack = (const float*)prepacked;
-        if (!pack) {
-            rc = conv_pack(wx, wf, (float*)ws, M, C, 1, engine, st);
-            if (rc) return rc;
-            pack = (const float*)ws;
-        }
-        KCParams p = {};
-        p.engine = engine;
-        p.A = (const float*)dout_planes; p.apre = 1;
-        p.lda = 2 * C; p.B = pack; p.ldb = 9 * 2 * C; p.C = dxn; p.ldc = C;
-        p.M = M; p.N = C; p.K = 9 * 2 * C; p.H = H; p.W = W; p.Cin = 2 * C;
-        rc = launch_kc(p, true, st, ev_start, ev_stop);
-        if (rc) return rc;
-    }
-    const MCPlan pl = conv_dw_plan(engine, M, C);
-    rc = pl.big == 2 ? launch_mc_planes_big(dout_planes, xn_planes, C, C, M, H, W, scratch, pl, NT, st)
-                     : launch_mc_planes(dout_planes, xn_planes, C, C, M, H, W, scratch, pl, NT, st);
-    if (rc) return rc;
-    return launch_reduce(scratch, pl.splits, (long long)2 * C * 9 * C, dwx, dwf, 1, C, C, st, accumulate);
-}
-
 // =============================================================================================
 // bf16-STORAGE variants (BASELINE configs[2] / [4] as stated): activations, saved tensors and inter-kernel gradients are
 // bf16 in HBM; weights, biases and every parameter gradient stay fp32; all products are ONE bf16 MFMA term with fp32
 // accumulation (the arithmetic of PA2D_ENGINE_BF16, minus its fp32 round trips: a bf16 tensor IS the 1-plane operand
 // image the bf16 kernels stage, so the activation pre-passes disappear).  ld* are in ELEMENTS.  Requires K % 32 == 0
-// for the dense layers and C % 32 == 0 for the conv (PA2D_ERR_UNSUPPORTED otherwise, never a silent fallback).
+// (PA2D_ERR_UNSUPPORTED otherwise, never a silent fallback).  The conv of this family is in pa2d_conv.hip.
 
 int pa2d_gemm_bias_act_fwd_bf16(const void* x, long long ldx, const float* w, long long ldw, const float* bias,
                                 const void* res, long long ldres, void* y, long long ldy, void* pre, long long ldpre,
                                 int M, int N, int K, int act, hipStream_t st) {
-    KCParams p = {};
-    p.engine = 2; p.io_bf16 = 1; p.apre = 1;
-    p.aux_deriv = (act & PA2D_ACT_SAVE_DERIVATIVE_BIT) ? 1 : 0;
-    act &= ~PA2D_ACT_SAVE_DERIVATIVE_BIT;
-    p.A = (const float*)x; p.lda = ldx; p.B = w; p.ldb = ldw; p.C = (float*)y; p.ldc = ldy; p.bias = bias;
-    p.res = (const float*)res; p.ldres = ldres; p.aux = (float*)pre; p.ldaux = ldpre; p.M = M; p.N = N; p.K = K; p.act = act;
-    p.epi = (act != ACT_NONE ? EPI_ACT : 0) | (pre ? EPI_STORE_PRE : 0);
-    return launch_kc(p, false, st);
+    return launch_kc(dense_fwd_params(x, ldx, w, ldw, bias, res, ldres, y, ldy, pre, ldpre, M, N, K, act, 2, true), false, st);
 }
 
 // dx[M,K] = (dy[M,N] . w[N,K]) * act'(pre[M,K]); dy, pre, dx bf16; w fp32; wt_ws: K*N floats (transposed weight)
@@ -770,14 +324,7 @@ int pa2d_gemm_bwd_data_bf16(const void* dy, long long lddy, const float* w, long
     if (M <= 0) return PA2D_OK;
     int rc = launch_repack(w, nullptr, wt_ws, 0, N, K, 0, 0, st);
     if (rc) return rc;
-    KCParams p = {};
-    p.engine = 2; p.io_bf16 = 1; p.apre = 1;
-    p.aux_deriv = (act & PA2D_ACT_SAVE_DERIVATIVE_BIT) ? 1 : 0;
-    act &= ~PA2D_ACT_SAVE_DERIVATIVE_BIT;
-    p.A = (const float*)dy; p.lda = lddy; p.B = wt_ws; p.ldb = N; p.C = (float*)dx; p.ldc = lddx; p.M = M; p.N = K; p.K = N;
-    p.aux = (float*)const_cast<void*>(pre); p.ldaux = ldpre; p.act = act;
-    p.epi = (pre && act != ACT_NONE) ? EPI_MUL_DACT : 0;
-    return launch_kc(p, false, st);
+    return launch_kc(dense_bwd_data_params(dy, lddy, wt_ws, pre, ldpre, act, dx, lddx, M, N, K, 2, true), false, st);
 }
 
 size_t pa2d_gemm_bwd_weight_workspace_bf16(int M, int N, int K) {
@@ -804,85 +351,6 @@ int pa2d_gemm_bwd_weight_bf16(const void* dy, long long lddy, const void* x, lon
     if (rc) return rc;
     if (db) rc = launch_colsum_bf16(dy, lddy, M, N, db, (float*)ws, st, nullptr, 0, accumulate);
     return rc;
-}
-
-// weight pack of the bf16-storage conv: ALWAYS the 1-plane bf16 K-step image (these entry points use the bf16 kernels
-// for every shape, also the narrow ones the fp32-I/O engines hand to the exact kernel)
-int pa2d_conv3x3x2_pack_bf16(const float* wx, const float* wf, void* pack, size_t pack_bytes, int C, int direction,
-                             hipStream_t st) {
-    if (C & 31) return PA2D_ERR_UNSUPPORTED;
-    if (pack_bytes < pa2d_conv3x3x2_pack_bytes(C)) return PA2D_ERR_WORKSPACE;
-    return launch_repack_split(wx, wf, pack, direction ? 1 : 0, 1, C, C, st);
-}
-
-size_t pa2d_conv3x3x2_fwd_workspace_bf16(int B, int H, int W, int C) {
-    (void)B; (void)H; (void)W;
-    return pa2d_conv3x3x2_pack_bytes(C);
-}
-size_t pa2d_conv3x3x2_workspace_bf16(int B, int H, int W, int C) {
-    const MCPlan pl = plan_mc_planes_big(2 * C, 9 * C, B * H * W);
-    size_t sl = pl.slab_floats, cs = (size_t)colsum_blocks(B * H * W) * 2 * C;
-    return pa2d_conv3x3x2_pack_bytes(C) + (sl > cs ? sl : cs) * sizeof(float);
-}
-
-// xn [B*H*W, C] bf16 -> out [B*H*W, 2C] bf16; weights / biases fp32 (prepacked: pa2d_conv3x3x2_pack with PA2D_ENGINE_BF16)
-int pa2d_conv3x3x2_fwd_bf16(const void* xn, const float* wx, const float* bx, const float* wf, const float* bf, void* out,
-                            const void* prepacked, void* ws, size_t ws_bytes, int B, int H, int W, int C, hipStream_t st,
-                            hipEvent_t ev_start, hipEvent_t ev_stop) {
-    if (C & 31) return PA2D_ERR_UNSUPPORTED;
-    if (B <= 0) return PA2D_OK;
-    if (ws_bytes < pa2d_conv3x3x2_fwd_workspace_bf16(B, H, W, C)) return PA2D_ERR_WORKSPACE;
-    const float* pack = (const float*)prepacked;
-    if (!pack) {
-        const int rc = launch_repack_split(wx, wf, ws, 0, 1, C, C, st);
-        if (rc) return rc;
-        pack = (const float*)ws;
-    }
-    KCParams p = {};
-    p.engine = 2; p.io_bf16 = 1; p.apre = 1;
-    p.A = (const float*)xn; p.lda = C; p.B = pack; p.ldb = 9 * C; p.C = (float*)out; p.ldc = 2 * C;
-    p.bias = bx; p.bias2 = bf; p.bias_split = C;
-    p.M = B * H * W; p.N = 2 * C; p.K = 9 * C; p.H = H; p.W = W; p.Cin = C;
-    return launch_kc(p, true, st, ev_start, ev_stop);
-}
-
-// dout [B*H*W, 2C] bf16, xn bf16 -> dxn bf16 (may be NULL); dwx/dwf/dbx/dbf fp32 ((+)= per accumulate)
-int pa2d_conv3x3x2_bwd_bf16(const void* dout, const void* xn, const float* wx, const float* wf, void* dxn, float* dwx,
-                            float* dbx, float* dwf, float* dbf, const void* prepacked, void* ws, size_t ws_bytes, int B,
-                            int H, int W, int C, int accumulate, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop) {
-    if (C & 31) return PA2D_ERR_UNSUPPORTED;
-    if (B <= 0) {
-        if (accumulate) return PA2D_OK;
-        const size_t wb = sizeof(float) * (size_t)C * C * 9, bb = sizeof(float) * C;
-        int rz = pa2d_zero(dwx, wb, st);
-        if (!rz) rz = pa2d_zero(dwf, wb, st);
-        if (!rz) rz = pa2d_zero(dbx, bb, st);
-        return rz ? rz : pa2d_zero(dbf, bb, st);
-    }
-    if (ws_bytes < pa2d_conv3x3x2_workspace_bf16(B, H, W, C)) return PA2D_ERR_WORKSPACE;
-    float* scratch = (float*)((char*)ws + pa2d_conv3x3x2_pack_bytes(C));
-    const int M = B * H * W;
-    int rc;
-    if (dxn) {
-        const float* pack = (const float*)prepacked;
-        if (!pack) {
-            rc = launch_repack_split(wx, wf, ws, 1, 1, C, C, st);
-            if (rc) return rc;
-            pack = (const float*)ws;
-        }
-        KCParams p = {};
-        p.engine = 2; p.io_bf16 = 1; p.apre = 1;
-        p.A = (const float*)dout; p.lda = 2 * C; p.B = pack; p.ldb = 9 * 2 * C; p.C = (float*)dxn; p.ldc = C;
-        p.M = M; p.N = C; p.K = 9 * 2 * C; p.H = H; p.W = W; p.Cin = 2 * C;
-        rc = launch_kc(p, true, st, ev_start, ev_stop);
-        if (rc) return rc;
-    }
-    const MCPlan pl = plan_mc_planes_big(2 * C, 9 * C, M);
-    rc = launch_mc_planes_big_raw(dout, 2 * C, xn, C, 9, M, H, W, scratch, pl, 1, st);
-    if (rc) return rc;
-    rc = launch_reduce(scratch, pl.splits, (long long)2 * C * 9 * C, dwx, dwf, 1, C, C, st, accumulate);
-    if (rc) return rc;
-    return launch_colsum_bf16(dout, 2 * C, M, 2 * C, dbx, scratch, st, dbf, C, accumulate);
 }
 
 }  // extern "C"

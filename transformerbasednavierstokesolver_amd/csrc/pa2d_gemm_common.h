@@ -1,7 +1,8 @@
-// Internal declarations shared by the GEMM translation units of libpa2d (pa2d_gemm.hip = engine selection + C ABI,
-// pa2d_gemm_kc.hip = exact fp32 engine, pa2d_gemm_split.hip = bf16 split / bf16 compute engines,
-// pa2d_gemm_mc.hip = weight-gradient engine and the deterministic reductions).  Split only so that the
-// translation units compile in parallel; nothing here is part of the C ABI.
+// Internal declarations shared by the GEMM translation units of libpa2d (pa2d_gemm.hip = engine selection, launch_kc +
+// C ABI of the linears, pa2d_conv.hip = C ABI of the conv stages (host code only), pa2d_gemm_kc.hip = exact fp32 engine,
+// pa2d_gemm_split.hip = bf16 split / bf16 compute engines, pa2d_gemm_mc.hip = weight-gradient engine and the
+// deterministic reductions).  Split only so that the translation units compile in parallel; nothing here is part of
+// the C ABI.
 #pragma once
 #include "pa2d_internal.h"
 #include "pa2d_bf16_split.h"      // bf16x8 / bf16x4, split3
@@ -33,8 +34,8 @@ struct KCParams {
     const float* wsrc; long long wsn, wsk;   // the image's source: B[n][k] = wsrc[n * wsn + k * wsk]
     int io_bf16; // bf16-storage entry points: A (row-major [M][K] or the NHWC image), C, res and aux hold bf16; lda / ldc /
                  // ldres / ldaux stay in ELEMENTS; a bf16 A is read as pre-made 1-plane "planes" (apre = 1)
-    int taps;    // im2col view: 27 = 3x3x3 conv on an image [B,H,W,depth,Cin] (K = 27*Cin; set only by the
-                 // pa2d_conv3x3x3x2_* entry points, which select the 27-tap kernels with it); anything else = 3x3, K = 9*Cin
+    int taps;    // im2col view: 27 = 3x3x3 conv on an image [B,H,W,depth,Cin] (K = 27*Cin; the pa2d_conv3x3x3x2_* entry
+                 // points select the 27-tap kernels with it); anything else (the conv ABI passes 9) = 3x3, K = 9*Cin
 };
 
 // 27-tap geometry of the 3x3x3 implicit GEMMs: tap t = kh*9 + kw*3 + kd has offset (kh-1, kw-1, kd-1) on (H, W, depth);
@@ -135,8 +136,14 @@ struct MCPlan { int big; int splits; int chunks_per_split; size_t slab_floats; }
 struct KCTile { int bm, bn, bk; };
 
 // engine selection / tile choice (pa2d_gemm.hip)
+static inline bool engine_ok(int e) { return e >= 0 && e <= 2; }
 bool use_split(int engine, int N, bool im2col, int Cin);
 KCTile kc_tile(int M, int N, bool im2col, int Cin);
+// the one dispatch of every forward / data-gradient GEMM: checks, buffer extents, kernel choice; ev0 / ev1 go round it
+int launch_kc(const KCParams& p_in, bool im2col, hipStream_t st, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+// fp32 weight re-layouts: mode 0 = transpose, 1 / 2 = conv forward / data-gradient pack (w1 = NULL: one kernel in it)
+int launch_repack(const float* w0, const float* w1, float* dst, int mode, int N, int K, int C, int Cin, hipStream_t st,
+                  int taps = 9);
 // exact fp32 engine (pa2d_gemm_kc.hip): launches the tile variant `t` on a filled-in KCParams
 int launch_kc_f32(const KCParams& p, bool im2col, const KCTile& t, hipStream_t st);
 // bf16 engines (pa2d_gemm_split.hip)
