@@ -260,6 +260,29 @@ size_t pa2d_seq_attn_bwd_workspace(int B, int T);
 int pa2d_seq_attn_bwd(const float* q, const float* k, const float* v, const float* attn, const float* dout, float* dq,
                       float* dk, float* dv, void* ws, size_t ws_bytes, int B, int T, int dim, float scale,
                       pa2d_stream_t stream);
+/* causal mode (the merged model's mask, SequenSolverMerged.py SequenSolver.attention): same operands, limits and workspace
+ * as pa2d_seq_attn_fwd / _bwd; the row softmax runs over j <= i only and attn[i, j > i] is stored as exactly 0; in the
+ * backward the ds sum runs over k <= i and ds[i, j > i] is exactly 0 */
+int pa2d_seq_attn_causal_fwd(const float* q, const float* k, const float* v, const float* res, float* out, float* attn,
+                             int B, int T, int dim, float scale, pa2d_stream_t stream);
+int pa2d_seq_attn_causal_bwd(const float* q, const float* k, const float* v, const float* attn, const float* dout, float* dq,
+                             float* dk, float* dv, void* ws, size_t ws_bytes, int B, int T, int dim, float scale,
+                             pa2d_stream_t stream);
+/* fused head attention of the merged SequenSolver (SequenSolverMerged.py, SequenSolver.attention): x [G, T, sd] is the
+ * LayerNorm output [B, T, dim] read as G = B*heads groups of T pseudo-rows of sd = dim / heads floats; wq, wk, wv [sd, sd]
+ * (bias-free Linear(sd, sd), shared by all groups); per group q, k, v = x wq^T, x wk^T, x wv^T,
+ * attn [G, T, T] = softmax_T(q k^T * scale) (causal != 0: over j <= i, attn[i, j > i] = 0 exactly),
+ * out [G, T, sd] = attn v (+ res, may be NULL).  One launch.  1 <= T <= 32, sd % 4 == 0, 4 <= sd <= 64; pointers 16-byte
+ * aligned; G = 0 is a no-op.  attn is an output of the forward (the only tensor saved for the backward; never NULL). */
+int pa2d_head_seq_attn_fwd(const float* x, const float* wq, const float* wk, const float* wv, const float* res, float* out,
+                           float* attn, int G, int T, int sd, float scale, int causal, pa2d_stream_t stream);
+/* dx [G, T, sd] = dq wq + dk wk + dv wv (plain store) and dwq, dwk, dwv [sd, sd] (+)= per `accumulate`; q, k, v are
+ * recomputed from x.  The workspace holds one partial record of the three weight gradients per workgroup (at most 32),
+ * summed in a fixed order in fp64 by a second launch. */
+size_t pa2d_head_seq_attn_bwd_workspace(int G, int T, int sd);
+int pa2d_head_seq_attn_bwd(const float* x, const float* wq, const float* wk, const float* wv, const float* attn,
+                           const float* dout, float* dx, float* dwq, float* dwk, float* dwv, void* ws, size_t ws_bytes,
+                           int G, int T, int sd, float scale, int causal, int accumulate, pa2d_stream_t stream);
 /* slice weights predicted from the code (SequenSolver.py:159-170, use_gt=False: the loop that fills a [B, N, M, C+2] tensor
  * with cat(code[b, 0, m, :], pos[b, n, :2]), weight_projection = MLP(C+2, 64, 1) with n_layers=1 and res=True (:18-43, :102),
  * softmax over M): sw[b, 0, n, :] = softmax_m(w3 . (h + gelu(w2 h + b2)) + b3), h = gelu(w1 [code_m ; pos_n] + b1), GELU exact.

@@ -8,6 +8,11 @@ fraction of the 8 TB/s HBM peak) and one whole auto-encoder training iteration (
 The seq_attn_* / code_sw_* stages time the two SequenSolver stages at the reference's shape (--SB samples, T=10 tokens of
 dim=512; 64 x 64 points, M=16, C=32; code_sw_* is the two-coordinate entry, served by the point_sw kernels with P = 2),
 seq_iter one sequensolver_train_step (T=10, layers=8, Tout=1, FusedAdamW) at B=1 and B=8.
+The head_seq_attn_* stages time the merged SequenSolver's attention at the reference's shape (--SB samples, T=10, 16 heads of
+seq_dim=32): the fused kernel (one launch forward, two backward) and, as *_unfused, the same through three linears and the
+causal seq_attn (functional.head_seq_attention, forward, and forward plus backward through autograd); merged_iter one
+sequensolver_train_step of SequenSolverMerged (T=10, layers=8, sequential_head=16, Tout=1, use_gt=False, FusedAdamW) at B=1
+with the fused kernel and without, ten runs each (median and range).
 The point_sw_* stages time the LearnSlice kernel at the same shape with P = 2 / 64 / 74 point features and B = 1 / 8,
 learnslice_iter one frame of learnslice_train_step (frozen SequenSolver T=10, layers=8; FusedAdamW) for the three widths.
 The conv3x3_* / zscore / wide_sw_* stages time the kernels of the conv slice predictors at 64 x 64, C = 256, B = 1 and 8: the
@@ -155,6 +160,50 @@ def main():
     csw_flops = 2.0 * SB * 4096 * SM * (64 * 64 + 64 * 3)            # the hidden layer, the two-coordinate point term and the last dot
     tests["code_sw_fwd"] = (lambda: ops.code_slice_weights_fwd(scode, spos, swp), csw_flops, "VALU")
     tests["code_sw_bwd"] = (lambda: ops.code_slice_weights_bwd(scode, spos, swp, sdsw), 3 * csw_flops, "VALU")
+    # the merged model's head attention: SB samples x 16 heads of T=10 pseudo-rows of 32 floats
+    HH, HS = 16, sdim // 16
+    hx, hdo = rn(SB * HH, ST, HS), rn(SB * HH, ST, HS)
+    hwq, hwk, hwv = rn(HS, HS) * 0.18, rn(HS, HS) * 0.18, rn(HS, HS) * 0.18
+    _, hattn = ops.head_seq_attn_fwd(hx, hwq, hwk, hwv, sdim ** -0.5)
+    tests["head_seq_attn_fwd"] = (lambda: ops.head_seq_attn_fwd(hx, hwq, hwk, hwv, sdim ** -0.5, hx), 0, "us")
+    tests["head_seq_attn_bwd"] = (lambda: ops.head_seq_attn_bwd(hx, hwq, hwk, hwv, hattn, hdo, sdim ** -0.5), 0, "us")
+
+    def unfused_fwd():
+        q, k, v = (ops.linear_fwd(hx.view(-1, HS), w_, engine=E)[0].view(hx.shape) for w_ in (hwq, hwk, hwv))
+        return q, k, v, ops.seq_attn_fwd(q, k, v, sdim ** -0.5, hx, causal=True)
+
+    uq, uk, uv, (_, uattn) = unfused_fwd()
+
+    def unfused_bwd():
+        dq, dk, dv = ops.seq_attn_bwd(uq, uk, uv, uattn, hdo, sdim ** -0.5, causal=True)
+        dx = None
+        for d_, w_ in ((dq, hwq), (dk, hwk), (dv, hwv)):
+            ops.linear_bwd_weight(d_.view(-1, HS), hx.view(-1, HS), want_bias=False, engine=E)
+            t_ = ops.linear_bwd_data(d_.view(-1, HS), w_, engine=E)
+            dx = t_ if dx is None else dx.add_(t_)
+        return dx
+
+    tests["head_seq_attn_fwd_unfused"] = (unfused_fwd, 0, "us")
+    tests["head_seq_attn_bwd_unfused"] = (unfused_bwd, 0, "us")
+    if only & {"merged_iter"}:
+        import statistics
+        from transformerbasednavierstokesolver_amd import harness
+        from transformerbasednavierstokesolver_amd.SequenSolverMerged import SequenSolver as MergedSolver
+        from transformerbasednavierstokesolver_amd.optim import FusedAdamW
+        torch.manual_seed(0)
+        mm = MergedSolver(None, T=ST, W=64, H=64, M=SM, C=SC, B=1, layers=8, sequential_head=HH).to(dev).set_engine(E)
+        mopt = FusedAdamW(mm.parameters(), lr=1e-3, weight_decay=1e-5)
+        mx, mfx, myy = torch.rand(1, 4096, 64, device=dev), rn(1, 4096, ST), rn(1, 4096, 1)
+        step = lambda: harness.sequensolver_train_step(mm, mopt, None, mx, mfx, myy, use_gt=False, grad_sync=mopt.sync)
+        runs = {True: [], False: []}
+        for _ in range(10):                      # the two routes alternate, so that drift hits both alike
+            for fused in (True, False):
+                mm.fused = None if fused else False
+                runs[fused].append(timeit(step, args.iters))
+        for fused, ms in runs.items():
+            print(f"merged_iter B=1 fused={fused}: median {statistics.median(ms):.3f} ms, range {min(ms):.3f} .. "
+                  f"{max(ms):.3f} ms over {len(ms)} runs of {args.iters} iterations, in order: "
+                  + " ".join(f"{t:.2f}" for t in ms), flush=True)
     if only & {"seq_iter"}:
         from transformerbasednavierstokesolver_amd import harness
         from transformerbasednavierstokesolver_amd.SequenSolver import SequenSolver

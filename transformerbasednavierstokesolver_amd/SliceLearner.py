@@ -102,6 +102,41 @@ class SliceLearner(_EngineMixin, nn.Module):
         return sw.reshape(B, 1, N, sw.shape[-1])
 
 
+def code_conditioned_slice_weights(x, fx, code, preprocess, in_project_x, in_project_slice, temperature, H, W, M, C, engine):
+    """The reference's `LearnSlice.forward_from_vorticity` / merged `SequenSolver.forward_slice` over the caller's own
+    sub-modules (the ONE implementation behind VorticitySliceLearner.forward and SequenSolverMerged.forward_slice):
+    x [B, N, 64 or 2], fx [B, N, T], code [B, 1, M, C] or None -> slice weights [B, 1, N, M].  `preprocess` and
+    `in_project_slice` are MLPs of model/_core.py, `in_project_x` a Conv2d(n_hidden, n_hidden, 3, 1, 1), `temperature` one
+    scalar (a Parameter or a plain tensor)."""
+    z = preprocess(torch.cat((x, fx), -1))
+    B, N, nh = z.shape
+    if N != H * W:
+        raise ValueError(f"this predictor is built for a {H} x {W} mesh; got {N} points")
+    x_mid = Fn.conv3x3(z, H, W, in_project_x.weight, in_project_x.bias, engine=engine)
+    mlp = in_project_slice
+    first, hidden, last = mlp.linear_pre[0], mlp.linears[0][0], mlp.linear_post
+    act, eng = mlp.act_name, engine
+    if code is None:
+        h = Fn.linear(x_mid, first.weight, first.bias, act, engine=eng)
+    else:
+        if code.numel() != B * M * C:
+            raise ValueError(f"need a code [B, 1, M, C] = {(B, 1, M, C)}; got {tuple(code.shape)}")
+        zc = Fn.zscore(code.reshape(B, M * C))
+        zx = Fn.zscore(x_mid)
+        # first layer on cat(z(x_mid), z(code)) without the concatenation: the code term is one row per sample
+        # (the two column blocks of the weight are cut out once per forward, not once per sample)
+        w1x, w1c = first.weight[:, :nh].contiguous(), first.weight[:, nh:].contiguous()
+        tb = Fn.linear(zc, w1c, first.bias, None, engine=eng)                             # [B, hidden]
+        if B == 1:      # every use in the reference: no per-sample pieces to put together
+            h = Fn.linear(zx, w1x, tb[0], act, engine=eng)
+        else:
+            h = torch.stack([Fn.linear(zx[b], w1x, tb[b], act, engine=eng) for b in range(B)])
+    y = Fn.linear(h, hidden.weight, hidden.bias, act, engine=eng)
+    h = y + h if mlp.res else y
+    sw = Fn.wide_slice_weights(h, temperature, last.weight, last.bias)
+    return sw.reshape(B, 1, N, M)
+
+
 class VorticitySliceLearner(_EngineMixin, nn.Module):
     """The code-conditioned conv predictor: forward(x, fx, code=None) is the reference's
     `LearnSlice.forward_from_vorticity` / merged `SequenSolver.forward_slice`.  x [B, N, 64 or 2] (the unified_pos distances
@@ -137,32 +172,7 @@ class VorticitySliceLearner(_EngineMixin, nn.Module):
             raise ValueError(f"built with use_code_for_vorticity={self.use_code_for_vorticity}: in_project_slice takes "
                              f"{self.concatenated} features, so the code must be " +
                              ("given" if self.use_code_for_vorticity else "None"))
-        z = self.preprocess(torch.cat((x, fx), -1))
-        B, N, nh = z.shape
-        if N != self.H * self.W:
-            raise ValueError(f"this predictor is built for a {self.H} x {self.W} mesh; got {N} points")
-        x_mid = Fn.conv3x3(z, self.H, self.W, self.in_project_x.weight, self.in_project_x.bias, engine=self.engine)
-        mlp = self.in_project_slice
-        first, hidden, last = mlp.linear_pre[0], mlp.linears[0][0], mlp.linear_post
-        act, eng = mlp.act_name, self.engine
-        if code is None:
-            h = Fn.linear(x_mid, first.weight, first.bias, act, engine=eng)
-        else:
-            if code.numel() != B * self.M * self.C:
-                raise ValueError(f"need a code [B, 1, M, C] = {(B, 1, self.M, self.C)}; got {tuple(code.shape)}")
-            zc = Fn.zscore(code.reshape(B, self.M * self.C))
-            zx = Fn.zscore(x_mid)
-            # first layer on cat(z(x_mid), z(code)) without the concatenation: the code term is one row per sample
-            # (the two column blocks of the weight are cut out once per forward, not once per sample)
-            w1x, w1c = first.weight[:, :nh].contiguous(), first.weight[:, nh:].contiguous()
-            tb = Fn.linear(zc, w1c, first.bias, None, engine=eng)                             # [B, hidden]
-            if B == 1:      # every use in the reference: no per-sample pieces to put together
-                h = Fn.linear(zx, w1x, tb[0], act, engine=eng)
-            else:
-                h = torch.stack([Fn.linear(zx[b], w1x, tb[b], act, engine=eng) for b in range(B)])
-        y = Fn.linear(h, hidden.weight, hidden.bias, act, engine=eng)
-        h = y + h if mlp.res else y
-        sw = Fn.wide_slice_weights(h, self.temperature, last.weight, last.bias)
-        return sw.reshape(B, 1, N, self.M)
+        return code_conditioned_slice_weights(x, fx, code, self.preprocess, self.in_project_x, self.in_project_slice,
+                                              self.temperature, self.H, self.W, self.M, self.C, self.engine)
 
     forward_from_vorticity = forward

@@ -73,6 +73,11 @@ SIGNATURES = {
     "pa2d_seq_attn_fwd": (_i, [_f, _f, _f, _f, _f, _f, _i, _i, _i, C.c_float, _st]),
     "pa2d_seq_attn_bwd_workspace": (_sz, [_i, _i]),
     "pa2d_seq_attn_bwd": (_i, [_f, _f, _f, _f, _f, _f, _f, _f, _f, _sz, _i, _i, _i, C.c_float, _st]),
+    "pa2d_seq_attn_causal_fwd": (_i, [_f, _f, _f, _f, _f, _f, _i, _i, _i, C.c_float, _st]),
+    "pa2d_seq_attn_causal_bwd": (_i, [_f, _f, _f, _f, _f, _f, _f, _f, _f, _sz, _i, _i, _i, C.c_float, _st]),
+    "pa2d_head_seq_attn_fwd": (_i, [_f, _f, _f, _f, _f, _f, _f, _i, _i, _i, C.c_float, _i, _st]),
+    "pa2d_head_seq_attn_bwd_workspace": (_sz, [_i, _i, _i]),
+    "pa2d_head_seq_attn_bwd": (_i, [_f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _sz, _i, _i, _i, C.c_float, _i, _i, _st]),
     "pa2d_code_slice_weights_fwd": (_i, [_f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _st, _st, _st]),
     "pa2d_code_slice_weights_bwd_workspace": (_sz, [_i, _i, _i, _i]),
     "pa2d_code_slice_weights_bwd": (_i, [_f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _sz, _i, _i, _i,

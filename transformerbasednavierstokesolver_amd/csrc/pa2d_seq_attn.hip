@@ -27,7 +27,9 @@ constexpr int CW = 256;          // channels per workgroup of the apply kernel
 constexpr int SP = TMAX + 1;     // pitch of the score matrix in LDS
 
 // MODE 0: out = softmax(x y^T * scale) rows;  MODE 1: out = a * (x y^T - <a, x y^T>_row) * scale with a = attn
-template <int MODE>
+// CAUSAL (the merged SequenSolver's mask, SequenSolverMerged.py): row i sees the entries j <= i only: their dot products are
+// the only ones formed, the softmax and the ds sum run over them, and out[i, j > i] is stored as exactly 0
+template <int MODE, bool CAUSAL>
 __global__ __launch_bounds__(NT) void seq_scores_kernel(const float* __restrict__ x, const float* __restrict__ y,
                                                         const float* __restrict__ attn, float* __restrict__ out, int T,
                                                         int dim, float scale) {
@@ -59,7 +61,7 @@ __global__ __launch_bounds__(NT) void seq_scores_kernel(const float* __restrict_
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
             const int e = tid + s * NT;
-            if (e < TT) {
+            if (e < TT && (!CAUSAL || e % T <= e / T)) {
                 const float4* xr = reinterpret_cast<const float4*>(xs + (e / T) * QS);
                 const float4* yr = reinterpret_cast<const float4*>(ys + (e % T) * QS);
                 double a0 = 0.0, a1 = 0.0;
@@ -84,18 +86,20 @@ __global__ __launch_bounds__(NT) void seq_scores_kernel(const float* __restrict_
     if (tid >= T) return;
     const float* row = sc + tid * SP;
     float* o = out + (long long)b * TT + tid * T;
+    const int n = CAUSAL ? tid + 1 : T;
+    for (int j = n; j < T; ++j) o[j] = 0.f;
     if (MODE == 0) {
         float mx = -INFINITY;
-        for (int j = 0; j < T; ++j) mx = fmaxf(mx, row[j] * scale);
+        for (int j = 0; j < n; ++j) mx = fmaxf(mx, row[j] * scale);
         float sum = 0.f;
-        for (int j = 0; j < T; ++j) sum += expf(row[j] * scale - mx);
-        for (int j = 0; j < T; ++j) o[j] = expf(row[j] * scale - mx) / sum;
+        for (int j = 0; j < n; ++j) sum += expf(row[j] * scale - mx);
+        for (int j = 0; j < n; ++j) o[j] = expf(row[j] * scale - mx) / sum;
     } else {
         const float* a = attn + (long long)b * TT + tid * T;
         // dA_j - <a, dA> written as sum_k a_k (dA_j - dA_k) (sum a = 1): nothing is lost to cancellation near one-hot rows
-        for (int j = 0; j < T; ++j) {
+        for (int j = 0; j < n; ++j) {
             float sd = 0.f;
-            for (int k = 0; k < T; ++k) sd = fmaf(a[k], row[j] - row[k], sd);
+            for (int k = 0; k < n; ++k) sd = fmaf(a[k], row[j] - row[k], sd);
             o[j] = a[j] * sd * scale;
         }
     }
@@ -167,19 +171,17 @@ int check_shape(int B, int T, int dim) {
 }
 bool misaligned(const void* p) { return ((uintptr_t)p & 15) != 0; }
 
-}  // namespace
-
-extern "C" {
-
-int pa2d_seq_attn_fwd(const float* q, const float* k, const float* v, const float* res, float* out, float* attn, int B,
-                      int T, int dim, float scale, void* stream) {
+template <bool CAUSAL>
+int seq_attn_fwd(const float* q, const float* k, const float* v, const float* res, float* out, float* attn, int B, int T,
+                 int dim, float scale, void* stream) {
     const int rc = check_shape(B, T, dim);
     if (rc) return rc;
     if (B == 0) return PA2D_OK;
     if (!q || !k || !v || !out || !attn) return PA2D_ERR_ARG;
     if (misaligned(q) || misaligned(k) || misaligned(v) || misaligned(out) || misaligned(res)) return PA2D_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(seq_scores_kernel<0>, dim3(B), dim3(NT), 0, st, q, k, (const float*)nullptr, attn, T, dim, scale);
+    hipLaunchKernelGGL((seq_scores_kernel<0, CAUSAL>), dim3(B), dim3(NT), 0, st, q, k, (const float*)nullptr, attn, T, dim,
+                       scale);
     PA2D_CHECK_LAUNCH();
     ApplyArgs a = {};
     a.w[0] = attn; a.v[0] = v; a.r[0] = res; a.o[0] = out; a.trans[0] = 0;
@@ -188,23 +190,24 @@ int pa2d_seq_attn_fwd(const float* q, const float* k, const float* v, const floa
     return PA2D_OK;
 }
 
-size_t pa2d_seq_attn_bwd_workspace(int B, int T) {
+size_t bwd_workspace(int B, int T) {
     if (B <= 0 || T < 1 || T > TMAX) return 0;
     return sizeof(float) * (size_t)B * T * T;
 }
 
-int pa2d_seq_attn_bwd(const float* q, const float* k, const float* v, const float* attn, const float* dout, float* dq,
-                      float* dk, float* dv, void* ws, size_t ws_bytes, int B, int T, int dim, float scale, void* stream) {
+template <bool CAUSAL>
+int seq_attn_bwd(const float* q, const float* k, const float* v, const float* attn, const float* dout, float* dq, float* dk,
+                 float* dv, void* ws, size_t ws_bytes, int B, int T, int dim, float scale, void* stream) {
     const int rc = check_shape(B, T, dim);
     if (rc) return rc;
     if (B == 0) return PA2D_OK;
     if (!q || !k || !v || !attn || !dout || !dq || !dk || !dv) return PA2D_ERR_ARG;
     if (misaligned(q) || misaligned(k) || misaligned(v) || misaligned(dout) || misaligned(dq) || misaligned(dk) || misaligned(dv))
         return PA2D_ERR_ARG;
-    if (!ws || ws_bytes < pa2d_seq_attn_bwd_workspace(B, T)) return PA2D_ERR_WORKSPACE;
+    if (!ws || ws_bytes < bwd_workspace(B, T)) return PA2D_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     float* ds = (float*)ws;
-    hipLaunchKernelGGL(seq_scores_kernel<1>, dim3(B), dim3(NT), 0, st, dout, v, attn, ds, T, dim, scale);
+    hipLaunchKernelGGL((seq_scores_kernel<1, CAUSAL>), dim3(B), dim3(NT), 0, st, dout, v, attn, ds, T, dim, scale);
     PA2D_CHECK_LAUNCH();
     ApplyArgs a = {};
     a.w[0] = ds;   a.v[0] = k;    a.o[0] = dq; a.trans[0] = 0;      // dq = ds k
@@ -213,6 +216,33 @@ int pa2d_seq_attn_bwd(const float* q, const float* k, const float* v, const floa
     hipLaunchKernelGGL(seq_apply_kernel, dim3(ceil_div(dim, CW), B, 3), dim3(NT), 0, st, a, T, dim);
     PA2D_CHECK_LAUNCH();
     return PA2D_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pa2d_seq_attn_fwd(const float* q, const float* k, const float* v, const float* res, float* out, float* attn, int B,
+                      int T, int dim, float scale, void* stream) {
+    return seq_attn_fwd<false>(q, k, v, res, out, attn, B, T, dim, scale, stream);
+}
+
+size_t pa2d_seq_attn_bwd_workspace(int B, int T) { return bwd_workspace(B, T); }
+
+int pa2d_seq_attn_bwd(const float* q, const float* k, const float* v, const float* attn, const float* dout, float* dq,
+                      float* dk, float* dv, void* ws, size_t ws_bytes, int B, int T, int dim, float scale, void* stream) {
+    return seq_attn_bwd<false>(q, k, v, attn, dout, dq, dk, dv, ws, ws_bytes, B, T, dim, scale, stream);
+}
+
+int pa2d_seq_attn_causal_fwd(const float* q, const float* k, const float* v, const float* res, float* out, float* attn,
+                             int B, int T, int dim, float scale, void* stream) {
+    return seq_attn_fwd<true>(q, k, v, res, out, attn, B, T, dim, scale, stream);
+}
+
+int pa2d_seq_attn_causal_bwd(const float* q, const float* k, const float* v, const float* attn, const float* dout, float* dq,
+                             float* dk, float* dv, void* ws, size_t ws_bytes, int B, int T, int dim, float scale,
+                             void* stream) {
+    return seq_attn_bwd<true>(q, k, v, attn, dout, dq, dk, dv, ws, ws_bytes, B, T, dim, scale, stream);
 }
 
 }  // extern "C"

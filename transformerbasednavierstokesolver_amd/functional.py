@@ -527,23 +527,71 @@ class SeqAttnFn(Function):
     the backward."""
 
     @staticmethod
-    def forward(ctx, q, k, v, res, scale):
+    def forward(ctx, q, k, v, res, scale, causal=False):
         q, k, v = (t.detach().contiguous() for t in (q, k, v))
-        out, attn = ops.seq_attn_fwd(q, k, v, scale, res=None if res is None else res.detach().contiguous())
-        ctx.saved, ctx.scale, ctx.has_res = (q, k, v, attn), scale, res is not None
+        out, attn = ops.seq_attn_fwd(q, k, v, scale, res=None if res is None else res.detach().contiguous(), causal=causal)
+        ctx.saved, ctx.scale, ctx.has_res, ctx.causal = (q, k, v, attn), scale, res is not None, causal
         return out
 
     @staticmethod
     def backward(ctx, dout):
         q, k, v, attn = ctx.saved
         dout = dout.contiguous()
-        return ops.seq_attn_bwd(q, k, v, attn, dout, ctx.scale) + (dout if ctx.has_res else None, None)
+        return ops.seq_attn_bwd(q, k, v, attn, dout, ctx.scale, causal=ctx.causal) + (dout if ctx.has_res else None, None,
+                                                                                     None)
 
 
-def seq_attention(q, k, v, scale, res=None):
+def seq_attention(q, k, v, scale, res=None, causal=False):
     """Single-head attention among T <= 32 tokens of width dim <= 1024 (dim % 4 == 0): q, k, v [B, T, dim]; `res`
-    [B, T, dim] is added to the result in the kernel's epilogue."""
-    return SeqAttnFn.apply(q, k, v, res, scale)
+    [B, T, dim] is added to the result in the kernel's epilogue.  `causal`: token i attends to the tokens j <= i."""
+    return SeqAttnFn.apply(q, k, v, res, scale, bool(causal))
+
+
+class HeadSeqAttnFn(Function):
+    """The merged SequenSolver's attention on x [G, T, sd] (G = B*heads groups of the LayerNorm output) as ONE node and one
+    forward launch: the three shared Linear(sd, sd), the (causal) softmax attention and the residual
+    (pa2d_head_seq_attn_*).  Only x and the [G, T, T] attention matrix are kept; the backward recomputes q, k, v."""
+
+    @staticmethod
+    def forward(ctx, x, res, scale, causal, wq, wk, wv):
+        ctx.params = (wq, wk, wv)
+        x = x.detach().contiguous()
+        W = tuple(w.detach().contiguous() for w in (wq, wk, wv))
+        out, attn = ops.head_seq_attn_fwd(x, *W, scale, res=None if res is None else res.detach().contiguous(),
+                                          causal=causal)
+        ctx.saved, ctx.scale, ctx.causal, ctx.has_res = (x, W, attn), scale, causal, res is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, W, attn = ctx.saved
+        dout = dout.contiguous()
+        tg = grad_targets(ctx.params)
+        dx, *g = ops.head_seq_attn_bwd(x, *W, attn, dout, ctx.scale, causal=ctx.causal, into=tg)
+        return (dx, dout if ctx.has_res else None, None, None) + _ret(tg, g)
+
+
+def head_seq_attention(xn, wq, wk, wv, heads, scale, res=None, causal=True, engine=None, fused=None):
+    """Attention of the merged SequenSolver: xn [B, T, dim] (already layer-normed) is read, as contiguous memory, as
+    [B*heads, T, sd] with sd = dim // heads; wq, wk, wv [sd, sd] are shared by all groups; `res` [B, T, dim] is added in
+    the kernel's epilogue.  Returns [B, T, dim].  fused=None: the fused kernel where sd <= ops.HEAD_SEQ_ATTN_MAX_SD, else
+    three `linear` and a causal `seq_attention` on the [B*heads, T, sd] view (fused=False forces that route; fused=True
+    raises where the fused kernel does not serve the shape).  `engine` is the GEMM engine of the unfused route's linears;
+    the fused kernel is exact fp32 on every engine."""
+    B, T, dim = xn.shape
+    if heads < 1 or dim % heads:
+        raise ValueError(f"heads = {heads} must divide dim = {dim}")
+    sd = dim // heads
+    x = xn.reshape(B * heads, T, sd)
+    r = None if res is None else res.reshape(B * heads, T, sd)
+    if fused is None:
+        fused = sd <= ops.HEAD_SEQ_ATTN_MAX_SD
+    if fused:
+        out = HeadSeqAttnFn.apply(x, r, scale, bool(causal), wq, wk, wv)
+    else:
+        q, k, v = (linear(x, w, None, None, engine=engine) for w in (wq, wk, wv))
+        out = seq_attention(q, k, v, scale, res=r, causal=causal)
+    return out.reshape(B, T, dim)
 
 
 def code_slice_weights(code, pos, w1, b1, w2, b2, w3, b3):

@@ -360,6 +360,8 @@ def sequensolver_train_step(model, optimizer, scheduler, x, fx, yy, use_gt=True,
     The reference hard-codes use_gt=True in this loop and switches to freeze_attention() from epoch 6 on; parameters
     without requires_grad (the frozen encoder, whatever freeze_attention() froze) are in neither `optim.FusedAdamW` nor its
     gradient bucket.  With FusedAdamW pass `grad_sync=optimizer.sync` and put the clip threshold in the optimizer.
+    The merged model (SequenSolverMerged.SequenSolver) has the same call signature and the same loop in its reference
+    file, which runs it with use_gt=False (x is then the 64-wide unified encoding [B, N, 64]).
     Returns (summed step loss [detached], full loss of the Tout predictions against yy)."""
     loss_fn = TestLoss(size_average=False)
     bsz = x.shape[0]
@@ -481,7 +483,9 @@ def slice_predictor_rollout(model, sequen_solver, x, fx, nsteps):
 @torch.no_grad()
 def sequensolver_rollout(model, x, fx, yy, use_gt=True):
     """SequenSolver.py:613-630: Tout = yy.shape[-1] calls with the PREDICTION fed back into the window (y still supplies
-    the slice weights when use_gt=True).  Returns (pred [B, N, Tout], summed step loss, full loss)."""
+    the slice weights when use_gt=True).  Also the two evaluation loops of SequenSolverMerged.py on its model: the one
+    inside train() passes use_gt=True, train(eval=True) use_gt=False; either way that model decodes with predicted slice
+    weights.  Returns (pred [B, N, Tout], summed step loss, full loss)."""
     loss_fn = TestLoss(size_average=False)
     bsz = x.shape[0]
     loss, preds = 0, []

@@ -712,23 +712,25 @@ def deslice_weights_bwd(code, w, dy, need_dcode=True, need_dw=True):
 # Sequence attention among the T frame tokens (pa2d_seq_attn_*) and the slice weights predicted from the code and the two
 # point coordinates (the P = 2 case of the LearnSlice stage below): exact fp32 on every engine, so these take no `engine`.
 SEQ_ATTN_MAX_T, SEQ_ATTN_MAX_DIM = 32, 1024
+HEAD_SEQ_ATTN_MAX_T, HEAD_SEQ_ATTN_MAX_SD = 32, 64      # the fused head attention (pa2d_head_seq_attn_*); sd % 4 == 0
 CODE_SW_HIDDEN, CODE_SW_DEPTH = 64, 1
 
 
-def seq_attn_fwd(q, k, v, scale, res=None):
-    """q, k, v [B, T, dim] -> (out [B, T, dim], attn [B, T, T]) with attn = softmax(q k^T * scale), out = attn v (+ res)."""
+def seq_attn_fwd(q, k, v, scale, res=None, causal=False):
+    """q, k, v [B, T, dim] -> (out [B, T, dim], attn [B, T, T]) with attn = softmax(q k^T * scale), out = attn v (+ res);
+    `causal`: the softmax of row i runs over j <= i, attn[i, j > i] = 0 (pa2d_seq_attn_causal_*)."""
     _chk(q, k, v, res)
     B, T, dim = q.shape
     if k.shape != q.shape or v.shape != q.shape or (res is not None and res.shape != q.shape):
         raise ValueError("q, k, v (and res) must share the shape [B, T, dim]")
     out = torch.empty_like(q)
     attn = torch.empty(B, T, T, dtype=torch.float32, device=q.device)
-    _lib.check(_L().pa2d_seq_attn_fwd(_p(q), _p(k), _p(v), _p(res), _p(out), _p(attn), B, T, dim, float(scale), _stream()),
-               "seq_attn_fwd")
+    fn = _L().pa2d_seq_attn_causal_fwd if causal else _L().pa2d_seq_attn_fwd
+    _lib.check(fn(_p(q), _p(k), _p(v), _p(res), _p(out), _p(attn), B, T, dim, float(scale), _stream()), "seq_attn_fwd")
     return out, attn
 
 
-def seq_attn_bwd(q, k, v, attn, dout, scale):
+def seq_attn_bwd(q, k, v, attn, dout, scale, causal=False):
     """Returns (dq, dk, dv), each [B, T, dim]."""
     _chk(q, k, v, attn, dout)
     B, T, dim = q.shape
@@ -737,9 +739,58 @@ def seq_attn_bwd(q, k, v, attn, dout, scale):
     dq, dk, dv = torch.empty_like(q), torch.empty_like(q), torch.empty_like(q)
     nb = _L().pa2d_seq_attn_bwd_workspace(B, T)
     ws = _ws(nb, q)
-    _lib.check(_L().pa2d_seq_attn_bwd(_p(q), _p(k), _p(v), _p(attn), _p(dout), _p(dq), _p(dk), _p(dv), ws.data_ptr(), nb, B, T,
-                                      dim, float(scale), _stream()), "seq_attn_bwd")
+    fn = _L().pa2d_seq_attn_causal_bwd if causal else _L().pa2d_seq_attn_bwd
+    _lib.check(fn(_p(q), _p(k), _p(v), _p(attn), _p(dout), _p(dq), _p(dk), _p(dv), ws.data_ptr(), nb, B, T, dim, float(scale),
+                  _stream()), "seq_attn_bwd")
     return dq, dk, dv
+
+
+def seq_attn_causal_fwd(q, k, v, scale, res=None):
+    return seq_attn_fwd(q, k, v, scale, res=res, causal=True)
+
+
+def seq_attn_causal_bwd(q, k, v, attn, dout, scale):
+    return seq_attn_bwd(q, k, v, attn, dout, scale, causal=True)
+
+
+def _head_attn_shapes(x, wq, wk, wv):
+    if x.dim() != 3:
+        raise ValueError(f"x must be [G, T, sd] (G = B*heads groups); got {tuple(x.shape)}")
+    G, T, sd = x.shape
+    if any(tuple(w.shape) != (sd, sd) for w in (wq, wk, wv)):
+        raise ValueError(f"wq, wk, wv must be [sd, sd] = {(sd, sd)}; got {[tuple(w.shape) for w in (wq, wk, wv)]}")
+    return G, T, sd
+
+
+def head_seq_attn_fwd(x, wq, wk, wv, scale, res=None, causal=True):
+    """x [G, T, sd] (the LayerNorm output as G = B*heads groups), wq, wk, wv [sd, sd] -> (out [G, T, sd], attn [G, T, T]):
+    projections, (causal) softmax attention and the residual in one launch (pa2d_head_seq_attn_fwd; T <= HEAD_SEQ_ATTN_MAX_T,
+    sd % 4 == 0, sd <= HEAD_SEQ_ATTN_MAX_SD)."""
+    _chk(x, wq, wk, wv, res)
+    G, T, sd = _head_attn_shapes(x, wq, wk, wv)
+    if res is not None and res.shape != x.shape:
+        raise ValueError("res must have the shape of x")
+    out = torch.empty_like(x)
+    attn = torch.empty(G, T, T, dtype=torch.float32, device=x.device)
+    _lib.check(_L().pa2d_head_seq_attn_fwd(_p(x), _p(wq), _p(wk), _p(wv), _p(res), _p(out), _p(attn), G, T, sd, float(scale),
+                                           int(bool(causal)), _stream()), "head_seq_attn_fwd")
+    return out, attn
+
+
+def head_seq_attn_bwd(x, wq, wk, wv, attn, dout, scale, causal=True, into=None):
+    """Returns (dx [G, T, sd], dwq, dwk, dwv [sd, sd]); `into` = the three gradient buffers to add into."""
+    _chk(x, wq, wk, wv, attn, dout)
+    G, T, sd = _head_attn_shapes(x, wq, wk, wv)
+    if dout.shape != x.shape or tuple(attn.shape) != (G, T, T):
+        raise ValueError("dout must be [G, T, sd] and attn [G, T, T]")
+    dx = torch.empty_like(x)
+    grads, acc = _grad_outputs(into, (wq.shape, wk.shape, wv.shape), x)
+    nb = _L().pa2d_head_seq_attn_bwd_workspace(G, T, sd)
+    ws = _ws(nb, x)
+    _lib.check(_L().pa2d_head_seq_attn_bwd(_p(x), _p(wq), _p(wk), _p(wv), _p(attn), _p(dout), _p(dx), *(_p(g) for g in grads),
+                                           ws.data_ptr(), nb, G, T, sd, float(scale), int(bool(causal)), acc, _stream()),
+               "head_seq_attn_bwd")
+    return (dx,) + tuple(grads)
 
 
 def _two_coordinates(code, pos):
