@@ -399,6 +399,23 @@ int pa2d_rel_l2_fwd(const float* pred, const float* y, float* dnorm, float* ynor
 int pa2d_rel_l2_bwd(const float* pred, const float* y, const float* dnorm, const float* ynorm,
                     const float* gout, float* dpred, int B, long long L, pa2d_stream_t stream);
 
+/* ---- the exp_darcy loss (exp_darcy.py:213-226) on the normalised head output, fused: out_n, y_n [B, s*s];
+ * `mean` / `std` are the y-normaliser's scalars ON THE DEVICE (utils/normalizer.py; no host read); o = out_n std + mean,
+ * y = y_n std + mean; l2_b = ||o - y|| / ||y||; o~ = o with its one-pixel border zeroed; gx / gy = zero-padded central
+ * differences / (2 dx) (central_diff, exp_darcy.py:59-68); dxr_b = ||gx(o~) - gx(y)|| / ||gx(y)||, dyr_b likewise.
+ * fwd: sums[3] = (sum_b l2_b + 0.1 sum_b (dxr_b + dyr_b), sum_b l2_b, sum_b (dxr_b + dyr_b)); norms [6][B] = the six
+ * per-sample norms in the order above (difference, target) x (l2, d/dx, d/dy), saved for bwd.  Partial sums per row
+ * tile are added in a fixed order: two calls give the same bits.  ws: pa2d_darcy_loss_workspace(B, s) bytes.
+ * bwd: dout = d (coef[0] sum_b l2_b + coef[1] sum_b (dxr_b + dyr_b)) / d out_n, coef = 2 floats on the device; the
+ * derivative terms vanish on the border ring; a zero difference norm gives that term the zero sub-gradient.
+ * There is no gradient to y_n.  B = 0: sums are zero-filled, nothing else is touched.  An image whose rows do not fit
+ * the LDS tile (s > 2048) returns PA2D_ERR_UNSUPPORTED. */
+size_t pa2d_darcy_loss_workspace(int B, int s);
+int pa2d_darcy_loss_fwd(const float* out_n, const float* y_n, const float* mean, const float* std, float* norms,
+                        float* sums, void* ws, size_t ws_bytes, int B, int s, float dx, pa2d_stream_t stream);
+int pa2d_darcy_loss_bwd(const float* out_n, const float* y_n, const float* mean, const float* std, const float* norms,
+                        const float* coef, float* dout, int B, int s, float dx, pa2d_stream_t stream);
+
 /* ==== operand-planes interface of the bf16 engines (fp32 storage; PA2D_ENGINE_SPLIT: 3 planes, PA2D_ENGINE_BF16: 1).
  * The conv GEMMs of these engines stage their activation operand as a bf16 plane image [row][C/32][NT][32].  By default
  * pa2d_conv3x3x2_fwd/bwd make it from the fp32 tensor in a pre-pass; with the entry points below the PRODUCER of the

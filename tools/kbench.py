@@ -19,6 +19,8 @@ The conv3x3_* / zscore / wide_sw_* stages time the kernels of the conv slice pre
 single 3x3 conv beside the PAIR call at the same shape (conv_pair_*), the whole-tensor z-score, the wide slice weights at
 D = 256 (SliceLearner) and D = 384 (the code-conditioned MLP's last layer), M = 16; slice_predictor_iter one
 slice_predictor_train_step (frozen SequenSolver T=10, layers=8, Tout=1; FusedAdamW) of VorticitySliceLearner and SliceLearner.
+The darcy_loss stages time harness.darcy_loss (exp_darcy.py's loss) at s = 85, B = 4 (scripts/Transolver_Darcy.sh) and
+s = 421, B = 2, forward alone and forward plus backward, through the fused kernels and through the torch path.
 Usage: python tools/kbench.py [--only conv_fwd,linear_fwd,...] [--iters 10] [--B 32]"""
 import argparse
 import os
@@ -290,6 +292,28 @@ def main():
                 tests[f"slice_predictor_iter {label} B={sb}"] = (
                     lambda pm=pm, popt=popt, pseq=pseq, px=px, pfx=pfx, pyy=pyy: harness.slice_predictor_train_step(
                         pm, popt, None, pseq, px, pfx, pyy, grad_sync=popt.sync), 0, "us")
+    if not only or only & {"darcy_loss"}:
+        from transformerbasednavierstokesolver_amd import harness, synth
+        from transformerbasednavierstokesolver_amd.utils.normalizer import UnitTransformer
+        for ds, db in ((85, 4), (421, 2)):
+            _, _, dsol = synth.darcy_batch(db, ds, seed=3)
+            dsol = torch.from_numpy(dsol).to(dev)
+            dyn = UnitTransformer(dsol)
+            dy_n = dyn.encode(dsol)
+            dout_n = (dy_n + 0.1 * rn(db, ds * ds)).requires_grad_(True)
+            dbytes = 2.0 * db * ds * ds * 4                       # forward: out_n and y_n once; backward: + d out_n
+
+            def dl_fwd(fused, o=dout_n, y=dy_n, n=dyn, s=ds):
+                with torch.no_grad():
+                    return harness.darcy_loss(o, y, n, 1.0 / s, s, fused=fused)
+
+            def dl_fwd_bwd(fused, o=dout_n, y=dy_n, n=dyn, s=ds):
+                o.grad = None
+                harness.darcy_loss(o, y, n, 1.0 / s, s, fused=fused)[0].backward()
+
+            for label, fused in (("fused", True), ("torch", False)):
+                tests[f"darcy_loss {label} fwd s={ds} B={db}"] = (lambda f=dl_fwd, u=fused: f(u), dbytes, "HBM")
+                tests[f"darcy_loss {label} fwd+bwd s={ds} B={db}"] = (lambda f=dl_fwd_bwd, u=fused: f(u), 2.5 * dbytes, "HBM")
     for name, (fn, work, unit) in tests.items():
         if only and name not in only and name.split(" ")[0] not in only:
             continue

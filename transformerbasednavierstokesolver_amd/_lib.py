@@ -106,6 +106,9 @@ SIGNATURES = {
                              C.c_float, _st]),
     "pa2d_rel_l2_fwd": (_i, [_f, _f, _f, _f, _f, _i, _ll, _st]),
     "pa2d_rel_l2_bwd": (_i, [_f, _f, _f, _f, _f, _f, _i, _ll, _st]),
+    "pa2d_darcy_loss_workspace": (_sz, [_i, _i]),
+    "pa2d_darcy_loss_fwd": (_i, [_f, _f, _f, _f, _f, _f, _f, _sz, _i, _i, C.c_float, _st]),
+    "pa2d_darcy_loss_bwd": (_i, [_f, _f, _f, _f, _f, _f, _f, _i, _i, C.c_float, _st]),
 }
 # bf16-storage variants: identical argument lists (activation pointers simply hold bf16); the GEMM / conv ones have no
 # `engine` argument (they ARE the bf16 engine)

@@ -1,7 +1,7 @@
 """Data ingress either side of the hot path.
 
 * `load_ns_mat` / `split_ns_trajectories`   the `.mat` -> (a, u) slicing of exp_ns.py:64-80
-* `load_darcy_mat` / `split_darcy`           exp_darcy.py:76-99 (coeff/sol fields + UnitTransformer encoding)
+* `load_darcy_mat` / `darcy_from_mats` / `split_darcy`   exp_darcy.py:76-99 (coeff/sol fields + UnitTransformer encoding)
 * `grid_positions`                          the driver-side position input (exp_ns.py:88-94)
 * `ResidentDataset`                         the whole split kept in HBM and batched by device-side index
                                             selection: replaces TensorDataset + DataLoader(num_workers=0) +
@@ -54,15 +54,20 @@ def split_darcy(coeff, sol, n, r=1):
     return x, y, s
 
 
-def load_darcy_mat(train_path, test_path, ntrain, ntest, r=1):
-    """Returns encoded train/test tensors, the two normalisers (fitted on the TRAIN split), s and dx = 1/s."""
-    import scipy.io as scio
-    tr, te = scio.loadmat(train_path), scio.loadmat(test_path)
+def darcy_from_mats(tr, te, ntrain, ntest, r=1):
+    """exp_darcy.py:77-98 on the two loaded `.mat` dicts ('coeff', 'sol'): encoded train/test inputs, the encoded train
+    target, the RAW test target, the two normalisers (fitted on the TRAIN split), s and dx = 1/s."""
     x_train, y_train, s = split_darcy(tr["coeff"], tr["sol"], ntrain, r)
     x_test, y_test, _ = split_darcy(te["coeff"], te["sol"], ntest, r)
     xn, yn = UnitTransformer(x_train), UnitTransformer(y_train)
     return dict(s=s, dx=1.0 / s, x_normalizer=xn, y_normalizer=yn, x_train=xn.encode(x_train),
                 y_train=yn.encode(y_train), x_test=xn.encode(x_test), y_test=y_test)
+
+
+def load_darcy_mat(train_path, test_path, ntrain, ntest, r=1):
+    """Returns encoded train/test tensors, the two normalisers (fitted on the TRAIN split), s and dx = 1/s."""
+    import scipy.io as scio
+    return darcy_from_mats(scio.loadmat(train_path), scio.loadmat(test_path), ntrain, ntest, r)
 
 
 def grid_positions(h, w=None):
@@ -89,9 +94,15 @@ class ResidentDataset:
         n = len(self) // world_size
         return ResidentDataset(*[t[rank * n:(rank + 1) * n] for t in self.tensors])
 
-    def batches(self, batch_size, shuffle=False, generator=None, drop_last=False):
+    def batches(self, batch_size, shuffle=False, generator=None, drop_last=False, order=None):
+        """`order`: an index tensor (or sequence) that overrides `shuffle`: the samples are taken in exactly this order,
+        the short last batch included (a recorded permutation replayed, harness.fit_*'s `epoch_orders`)."""
         n, dev = len(self), self.tensors[0].device
-        order = torch.randperm(n, device=dev, generator=generator) if shuffle else torch.arange(n, device=dev)
+        if order is not None:
+            order = torch.as_tensor(order, dtype=torch.long).to(dev)
+            n = order.numel()
+        else:
+            order = torch.randperm(n, device=dev, generator=generator) if shuffle else torch.arange(n, device=dev)
         for i in range(0, n, batch_size):
             idx = order[i:i + batch_size]
             if drop_last and idx.numel() < batch_size:

@@ -378,6 +378,32 @@ def rel_l2(pred, y):
     return RelL2Fn.apply(pred, y)
 
 
+class DarcyLossFn(Function):
+    """The exp_darcy.py:213-226 loss of the normalised prediction `out_n` [B, s*s] against the normalised target `y_n`:
+    decode with the y-normaliser's (mean, std) device scalars, rel-L2 plus 0.1 x the rel-L2 of the zero-padded central
+    differences of the border-zeroed prediction, in one stencil kernel each way (ops.darcy_loss_fwd / _bwd).
+    Returns (loss, sum l2, sum (dxr + dyr)); gradient w.r.t. out_n only."""
+
+    @staticmethod
+    def forward(ctx, out_n, y_n, mean, std, dx, s):
+        o2, y2 = out_n.detach().contiguous(), y_n.detach().contiguous()
+        mean, std = mean.detach().contiguous(), std.detach().contiguous()
+        sums, norms = ops.darcy_loss_fwd(o2, y2, mean, std, dx, s)
+        ctx.saved, ctx.geom = (o2, y2, mean, std, norms), (dx, s)
+        return sums[0], sums[1], sums[2]
+
+    @staticmethod
+    def backward(ctx, gloss, gl2, gderiv):
+        o2, y2, mean, std, norms = ctx.saved
+        coef = torch.stack((gloss + gl2, 0.1 * gloss + gderiv)).to(torch.float32).contiguous()
+        dout = ops.darcy_loss_bwd(o2, y2, mean, std, norms, coef, *ctx.geom)
+        return dout, None, None, None, None, None
+
+
+def darcy_loss(out_n, y_n, mean, std, dx, s):
+    return DarcyLossFn.apply(out_n, y_n, mean, std, dx, s)
+
+
 # ------------------------------------------------------------------------------ auto-encoder attention
 # Physics_Attention_Structured_Mesh_2D_Auto_Encoder (reference model/Physics_Attention.py): `encode` returns the slice
 # tokens after token attention (the code) and caches the softmax slice weights; `reconstruct_fx` / `decode` project the

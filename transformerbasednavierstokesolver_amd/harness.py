@@ -1,7 +1,8 @@
 """Callers of the hot path, restated for the MI355X build.
 
-The reference's driver scripts execute argparse and a hard-coded Windows data path at import time,
-so they cannot be imported; these functions reproduce their loops:
+The reference's driver scripts run argparse at import and keep their work in main(); these functions reproduce
+their loops, iteration by iteration and (fit_*) epoch by epoch, pinned by fixtures that the drivers' own main()
+made (tests/golden/G14-G16, tools/make_golden_drivers.py):
 
   train_iteration / train_step  exp_ns.py:191-218   (T/step teacher-forced model calls, summed rel-L2,
                                                     one backward, AdamW(wd=1e-5) + OneCycleLR step)
@@ -13,11 +14,15 @@ so they cannot be imported; these functions reproduce their loops:
   / LookAheadCurriculum         wrapper, BPTT through n chained calls) and :216-223 (curriculum)
   central_diff / darcy_loss     exp_darcy.py:59-68, 209-234 (decode, rel-L2 + 0.1 x derivative loss,
   / darcy_train_step            clip, step) — the large-N single-call iteration
+  fit_ns / fit_unrolled         exp_ns.py:184-257, ns_vorticity_unrolling.py:204-329, exp_darcy.py:205-268: the epoch loops
+  / fit_darcy, evaluate_*       (shuffled batches, per-epoch test pass, the drivers' metric normalisation, checkpoints)
   autoencoder_train_step        auto_encoder.py:166-181 (the auto-encoder reconstructs its own input fx)
   sequensolver_train_step       SequenSolver.py:572-606 (Tout teacher-forced calls of the latent sequence model, window slid
   / sequensolver_rollout        with the true frame, summed rel-L2, one backward, step) and :613-630 (prediction feedback)
 """
 from __future__ import annotations
+
+import os
 
 import torch
 
@@ -298,9 +303,17 @@ def central_diff(x, h, resolution):
     return gx, gy
 
 
-def darcy_loss(out, y, y_normalizer, dx, s, loss_fn=None):
+def darcy_loss(out, y, y_normalizer, dx, s, loss_fn=None, fused=False):
     """out, y: [B, N] normalised prediction / target.  Returns (loss, l2loss, deriv_loss) with
-    loss = l2 + 0.1 * (rel-L2 of d/dx + rel-L2 of d/dy), prediction border zeroed first."""
+    loss = l2 + 0.1 * (rel-L2 of d/dx + rel-L2 of d/dy), prediction border zeroed first.
+
+    `fused=True`: fp32 CUDA tensors with a scalar fp32 normaliser go through the libpa2d Darcy-loss kernels
+    (functional.DarcyLossFn: one stencil kernel each way instead of ~25 + ~40 elementwise launches; the normaliser's
+    mean / std are read on the device; `loss_fn` is not consulted).  Anything else takes the torch path below with
+    `loss_fn`: the float64 target a real `.mat` gives (it promotes the loss to float64, as in the reference), an image
+    wider than 2048 pixels, or a target / normaliser that requires a gradient (the kernels give one to `out` only)."""
+    if fused and _darcy_fusable(out, y, y_normalizer, s):
+        return Fn.darcy_loss(out, y, y_normalizer.mean, y_normalizer.std, dx, s)
     loss_fn = loss_fn or TestLoss(size_average=False)
     out = y_normalizer.decode(out)
     y = y_normalizer.decode(y)
@@ -315,12 +328,26 @@ def darcy_loss(out, y, y_normalizer, dx, s, loss_fn=None):
     return 0.1 * deriv + l2, l2, deriv
 
 
+DARCY_FUSED_MAX_S, DARCY_FUSED_MAX_B = 2048, 65535      # what pa2d_darcy_loss_* serve (one image row per LDS tile; grid.y)
+
+
+def _darcy_fusable(out, y, y_normalizer, s):
+    """fp32 CUDA [B, s*s] tensors with a one-element fp32 normaliser, within the kernels' sizes, and a target that asks
+    for no gradient (the kernels give none to y)."""
+    mean, std = y_normalizer.mean, y_normalizer.std
+    ts = (out, y, mean, std)
+    return (all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 for t in ts)
+            and out.dim() == 2 and out.shape == y.shape and mean.numel() == 1 and std.numel() == 1
+            and s <= DARCY_FUSED_MAX_S and out.shape[0] <= DARCY_FUSED_MAX_B
+            and not (y.requires_grad or mean.requires_grad or std.requires_grad))
+
+
 def darcy_train_step(model, optimizer, scheduler, x, fx, y, y_normalizer, dx, s, max_grad_norm=None,
-                     grad_sync=None):
-    """exp_darcy.py:209-234: ONE model call per iteration (fun_dim = 1)."""
+                     grad_sync=None, fused=False, loss_fn=None):
+    """exp_darcy.py:209-234: ONE model call per iteration (fun_dim = 1).  `fused`, `loss_fn`: see darcy_loss."""
     optimizer.zero_grad(set_to_none=False)
     out = model(x, fx=fx.unsqueeze(-1)).squeeze(-1)
-    loss, l2, deriv = darcy_loss(out, y, y_normalizer, dx, s)
+    loss, l2, deriv = darcy_loss(out, y, y_normalizer, dx, s, loss_fn=loss_fn, fused=fused)
     loss.backward()
     if grad_sync is not None:
         grad_sync()
@@ -498,3 +525,239 @@ def sequensolver_rollout(model, x, fx, yy, use_gt=True):
             fx = torch.cat((fx[..., 1:], im), dim=-1)
     pred = torch.cat(preds, -1)
     return pred, loss, loss_fn(pred.reshape(bsz, -1), yy.reshape(bsz, -1))
+
+
+# ------------------------------------------------------------------------------ epoch loops of the reference drivers
+def _device_of(model):
+    return next(model.parameters()).device
+
+
+def _epoch_batches(dataset, batch_size, ep, epoch_orders, generator):
+    """Shuffled batches with the short last batch kept (DataLoader(shuffle=True), drop_last=False); `epoch_orders[ep]`
+    replays a recorded permutation instead."""
+    if epoch_orders is not None:
+        return dataset.batches(batch_size, order=epoch_orders[ep])
+    return dataset.batches(batch_size, shuffle=True, generator=generator)
+
+
+def _save_state(module, save_path):
+    """torch.save of the state_dict (CPU tensors, the reference's key names: loads strict=True into its Model)."""
+    folder = os.path.dirname(save_path)
+    if folder:
+        os.makedirs(folder, exist_ok=True)
+    torch.save({k: v.detach().cpu() for k, v in module.state_dict().items()}, save_path)
+
+
+@torch.no_grad()
+def _ns_test_pass(model, test, batch_size, T, step, loss_fn, acc, full=True):
+    """exp_ns.py:225-241: prediction-feedback rollout of every test batch; acc[2] += step loss, acc[3] += full loss."""
+    for x, fx, yy in test.batches(batch_size):
+        yy = yy[..., :T]
+        bsz = x.shape[0]
+        loss, preds = 0, []
+        with ops.weights_frozen():
+            for t in range(0, T, step):
+                y = yy[..., t:t + step]
+                im = model(x, fx=fx)
+                loss = loss + loss_fn(im.reshape(bsz, -1), y.reshape(bsz, -1))
+                preds.append(im)
+                fx = torch.cat((fx[..., step:], im), dim=-1)
+        acc[2] += loss
+        if full:
+            acc[3] += loss_fn(torch.cat(preds, -1).reshape(bsz, -1), yy.reshape(bsz, -1))
+
+
+def evaluate_ns(model, test, batch_size, T=10, step=1, loss_fn=None):
+    """The test pass alone (exp_ns.py:137-183 without the plots): {'test_step', 'test_full'} normalised like fit_ns."""
+    loss_fn = loss_fn or TestLoss(size_average=False)
+    acc = torch.zeros(4, dtype=torch.float64, device=_device_of(model))
+    model.eval()
+    _ns_test_pass(model, test, batch_size, T, step, loss_fn, acc)
+    a = acc.tolist()
+    return dict(test_step=a[2] / len(test) / (T / step), test_full=a[3] / len(test))
+
+
+@torch.no_grad()
+def _darcy_test_pass(model, test, batch_size, positions, y_normalizer, loss_fn, acc):
+    """exp_darcy.py:243-254: the prediction is decoded, the target is the raw solution; acc[2] += summed rel-L2."""
+    for fx, y in test.batches(batch_size):
+        out = model(positions(fx.shape[0]), fx=fx.unsqueeze(-1)).squeeze(-1)
+        acc[2] += loss_fn(y_normalizer.decode(out), y)
+
+
+def _darcy_setup(model, data, want_train=True):
+    """(device, y-normaliser ON the device, train set or None, test set, positions(bsz)).  The caller's normaliser is left
+    where it is: a shallow copy is moved."""
+    import copy
+    from .data import ResidentDataset, grid_positions
+    dev = _device_of(model)
+    yn = copy.copy(data["y_normalizer"]).to(dev)
+    train = ResidentDataset(data["x_train"], data["y_train"], device=dev) if want_train else None
+    test = ResidentDataset(data["x_test"], data["y_test"], device=dev)
+    pos1 = grid_positions(data["s"]).to(dev)
+    pos = {}
+
+    def positions(bsz):         # one [bsz, N, 2] copy per batch size (full and short batch), not one per sample
+        if bsz not in pos:
+            pos[bsz] = pos1.expand(bsz, -1, -1).contiguous()
+        return pos[bsz]
+
+    return dev, yn, train, test, positions
+
+
+def evaluate_darcy(model, data, batch_size, loss_fn=None):
+    """The test pass alone (exp_darcy.py:154-203 without the plots): {'rel_err'} = summed rel-L2 / ntest."""
+    loss_fn = loss_fn or TestLoss(size_average=False)
+    dev, yn, _, test, positions = _darcy_setup(model, data, want_train=False)
+    acc = torch.zeros(3, dtype=torch.float64, device=dev)
+    model.eval()
+    _darcy_test_pass(model, test, batch_size, positions, yn, loss_fn, acc)
+    return dict(rel_err=acc.tolist()[2] / len(test))
+
+
+def fit_ns(model, optimizer, scheduler, train, test, *, epochs, batch_size, T=10, step=1, max_grad_norm=None, loss_fn=None,
+           epoch_orders=None, generator=None, save_path=None, save_every=100, graphed=False, grad_sync=None, on_epoch=None):
+    """The epoch loop of exp_ns.main() (exp_ns.py:184-257).  `train` / `test`: data.ResidentDataset of (x [n, N, 2],
+    fx [n, N, T_in], yy [n, N, >= T]) on the model's device (any device: a CPU module goes through the same loop).
+
+    Each epoch: model.train(); shuffled batches, the short last batch kept; per batch the teacher-forced iteration
+    `train_step` (T/step model calls, summed rel-L2, zero_grad, backward, [grad_sync], [clip], optimizer.step(),
+    scheduler.step()); then model.eval() and the prediction-feedback test pass under no_grad.  The caller builds the
+    scheduler (the reference: OneCycleLR(max_lr=lr, epochs=epochs, steps_per_epoch=ceil(ntrain / batch_size))).
+
+    Returns one dict per epoch with the metrics the reference prints, unrounded (exp_ns.py:243-246):
+    train_step = sum / ntrain / (T / step), train_full = sum / ntrain, test_step = sum / ntest / (T / step),
+    test_full = sum / ntest.  The sums are accumulated on the device: ONE host synchronisation per epoch.
+
+    `epoch_orders[ep]`: the sample order of epoch ep (a recorded permutation); otherwise a fresh permutation from
+    `generator`.  `save_path`: the state_dict is written when ep % save_every == 0 and after the last epoch.
+    `graphed=True` (CUDA, optim.FusedAdamW): full batches replay one GraphedTrainStep (bit-identical to the eager
+    iteration); the short last batch runs eagerly.  `grad_sync` is passed through to the eager iteration; a replayed batch
+    calls the optimizer's own `sync` (the same bucket), and clips through the optimizer only: `max_grad_norm` together
+    with `graphed=True` raises.
+    `on_epoch(ep, metrics)`: called after every epoch's synchronisation (progress lines of a command line)."""
+    if graphed and max_grad_norm is not None:
+        raise ValueError("fit_ns(graphed=True) clips inside optim.FusedAdamW: build it with max_grad_norm=... and pass "
+                         "max_grad_norm=None here (a replayed batch would otherwise go unclipped)")
+    loss_fn = loss_fn or TestLoss(size_average=False)
+    dev = _device_of(model)
+    ntrain, ntest, calls = len(train), len(test), T / step
+    graph = None
+    history = []
+    for ep in range(epochs):
+        model.train()
+        acc = torch.zeros(4, dtype=torch.float64, device=dev)
+        for x, fx, yy in _epoch_batches(train, batch_size, ep, epoch_orders, generator):
+            yy = yy[..., :T]
+            if graphed and x.shape[0] == batch_size:
+                if graph is None:
+                    graph = GraphedTrainStep(model, optimizer, scheduler, x, fx, yy, step=step, loss_fn=loss_fn)
+                loss, full = graph(x, fx, yy)
+            else:
+                loss, full = train_step(model, optimizer, scheduler, x, fx, yy, step=step, max_grad_norm=max_grad_norm,
+                                        grad_sync=grad_sync, loss_fn=loss_fn)
+            acc[0] += loss
+            acc[1] += full
+        model.eval()
+        _ns_test_pass(model, test, batch_size, T, step, loss_fn, acc)
+        a = acc.tolist()                                         # the epoch's only host synchronisation
+        history.append(dict(train_step=a[0] / ntrain / calls, train_full=a[1] / ntrain,
+                            test_step=a[2] / ntest / calls, test_full=a[3] / ntest))
+        if on_epoch is not None:
+            on_epoch(ep, history[-1])
+        if save_path is not None and ep % save_every == 0:
+            _save_state(model, save_path)
+    if save_path is not None:
+        _save_state(model, save_path)
+    return history
+
+
+def fit_unrolled(sol_model, optimizer, scheduler, train, test, *, epochs, batch_size, T=10, step=1, look_ahead=1,
+                 max_look_ahead=10, loss_fn=None, epoch_orders=None, generator=None, save_path=None, save_every=100,
+                 grad_sync=None, on_epoch=None):
+    """The epoch loop of ns_vorticity_unrolling.main() (ns_vorticity_unrolling.py:204-329) on the SOL wrapper
+    (model/SOL_Transolver_Structured_Mesh_2D).  The look-ahead follows `LookAheadCurriculum` (it doubles, capped at
+    `max_look_ahead`, when ep % thresh == 0 and ep >= thresh; thresh = epochs / 2 is a float that then halves); per
+    batch `unrolled_train_iteration` (BPTT through the chained calls), zero_grad, backward, [grad_sync], step,
+    scheduler.step(): this loop never clips.  The test pass (:264-286) runs the inner `transolver_model` with
+    prediction feedback and keeps the step loss only.
+
+    Returns one dict per epoch: train_step = the RAW epoch sum (what :257 prints), test_step = sum / ntest / (T / step),
+    look_ahead = the epoch's look-ahead.  One host synchronisation per epoch.  Saves
+    `sol_model.transolver_model.state_dict()` (ep % save_every == 0 and after the last epoch).  No graph mode."""
+    loss_fn = loss_fn or TestLoss(size_average=False)
+    dev = _device_of(sol_model)
+    ntest, calls = len(test), T / step
+    curriculum = LookAheadCurriculum(epochs, look_ahead, max_look_ahead)
+    inner = sol_model.transolver_model
+    sol_model.n = look_ahead
+    history = []
+    for ep in range(epochs):
+        sol_model.train()
+        acc = torch.zeros(4, dtype=torch.float64, device=dev)
+        la = curriculum.update(ep)
+        for x, fx, yy in _epoch_batches(train, batch_size, ep, epoch_orders, generator):
+            with ops.weights_frozen():
+                loss = unrolled_train_iteration(sol_model, x, fx, yy[..., :T], la, step, loss_fn)
+                optimizer.zero_grad()
+                loss.backward()
+            if grad_sync is not None:
+                grad_sync()
+            optimizer.step()
+            if scheduler is not None:
+                scheduler.step()
+            acc[0] += loss.detach()
+        sol_model.eval()
+        _ns_test_pass(inner, test, batch_size, T, step, loss_fn, acc, full=False)
+        a = acc.tolist()
+        history.append(dict(train_step=a[0], test_step=a[2] / ntest / calls, look_ahead=la))
+        if on_epoch is not None:
+            on_epoch(ep, history[-1])
+        if save_path is not None and ep % save_every == 0:
+            _save_state(inner, save_path)
+    if save_path is not None:
+        _save_state(inner, save_path)
+    return history
+
+
+def fit_darcy(model, optimizer, scheduler, data, *, epochs, batch_size, max_grad_norm=None, loss_fn=None,
+              epoch_orders=None, generator=None, save_path=None, save_every=100, fused=True, grad_sync=None,
+              on_epoch=None):
+    """The epoch loop of exp_darcy.main() (exp_darcy.py:205-268).  `data`: the dict `data.load_darcy_mat` returns
+    (encoded x_train / y_train / x_test, the RAW y_test, both normalisers, s, dx); everything is moved to the model's
+    device, the positions are `data.grid_positions(s)`.
+
+    Per batch `darcy_train_step` (zero_grad, one model call, `darcy_loss`, backward, [grad_sync], [clip], step,
+    scheduler.step()), with the fused Darcy-loss kernels where they apply (`fused=True`: fp32 CUDA tensors; a float64
+    target or a CPU module keeps the torch path, which calls `loss_fn`).  Test pass (always `loss_fn`): the prediction is DECODED, the target is the raw solution (never
+    encoded), rel-L2 summed.  Returns one dict per epoch: reg = sum of the derivative losses / ntrain, train_loss = sum
+    of the l2 losses / ntrain, rel_err = sum / ntest.  One host synchronisation per epoch.
+
+    Quirk of the reference kept OUT of this function: exp_darcy builds its OneCycleLR with epochs=500 whatever
+    --epochs says (its module global `epochs`), so a shorter run never leaves the warm-up.  The caller builds the
+    scheduler; pass OneCycleLR(..., epochs=500, ...) to reproduce the reference, or the real count not to."""
+    test_loss = loss_fn or TestLoss(size_average=False)
+    dev, yn, train, test, positions = _darcy_setup(model, data)
+    s, dx = data["s"], data["dx"]
+    ntrain, ntest = len(train), len(test)
+    history = []
+    for ep in range(epochs):
+        model.train()
+        acc = torch.zeros(3, dtype=torch.float64, device=dev)
+        for fx, y in _epoch_batches(train, batch_size, ep, epoch_orders, generator):
+            _, l2, deriv = darcy_train_step(model, optimizer, scheduler, positions(fx.shape[0]), fx, y, yn, dx, s,
+                                            max_grad_norm=max_grad_norm, grad_sync=grad_sync, fused=fused,
+                                            loss_fn=loss_fn)
+            acc[0] += l2
+            acc[1] += deriv
+        model.eval()
+        _darcy_test_pass(model, test, batch_size, positions, yn, test_loss, acc)
+        a = acc.tolist()
+        history.append(dict(reg=a[1] / ntrain, train_loss=a[0] / ntrain, rel_err=a[2] / ntest))
+        if on_epoch is not None:
+            on_epoch(ep, history[-1])
+        if save_path is not None and ep % save_every == 0:
+            _save_state(model, save_path)
+    if save_path is not None:
+        _save_state(model, save_path)
+    return history

@@ -1038,3 +1038,37 @@ def rel_l2_bwd(pred2d, y2d, dn, yn, gout):
     _lib.check(_L().pa2d_rel_l2_bwd(_p(pred2d), _p(y2d), _p(dn), _p(yn), _p(gout), _p(dpred), B, L, _stream()),
                "rel_l2_bwd")
     return dpred
+
+
+def _darcy_loss_shapes(out_n, y_n, mean, std, s):
+    _chk(out_n, y_n, mean, std)
+    if out_n.dim() != 2 or out_n.shape != y_n.shape or out_n.shape[1] != s * s:
+        raise ValueError(f"darcy_loss needs out_n, y_n of one shape [B, s*s]; got {tuple(out_n.shape)}, {tuple(y_n.shape)}, s={s}")
+    if mean.numel() != 1 or std.numel() != 1:
+        raise ValueError("darcy_loss needs a scalar normaliser (mean and std of one element each)")
+    return out_n.shape[0]
+
+
+def darcy_loss_fwd(out_n, y_n, mean, std, dx, s):
+    """out_n, y_n [B, s*s]; mean / std: the y-normaliser's one-element tensors, read on the device.
+    Returns (sums [3] = (loss, sum l2, sum (dxr + dyr)), norms [6, B])."""
+    B = _darcy_loss_shapes(out_n, y_n, mean, std, s)
+    sums = torch.empty(3, dtype=torch.float32, device=out_n.device)
+    norms = torch.empty(6, B, dtype=torch.float32, device=out_n.device)
+    nb = _L().pa2d_darcy_loss_workspace(B, s)
+    ws = _ws(nb, out_n)
+    _lib.check(_L().pa2d_darcy_loss_fwd(_p(out_n), _p(y_n), _p(mean), _p(std), _p(norms), _p(sums), ws.data_ptr(), nb, B, s,
+                                        float(dx), _stream()), "darcy_loss_fwd")
+    return sums, norms
+
+
+def darcy_loss_bwd(out_n, y_n, mean, std, norms, coef, dx, s):
+    """coef [2] on the device: the upstream gradients of (sum l2, sum (dxr + dyr)).  Returns d out_n."""
+    B = _darcy_loss_shapes(out_n, y_n, mean, std, s)
+    _chk(norms, coef)
+    if norms.numel() != 6 * B or coef.numel() != 2:
+        raise ValueError("darcy_loss_bwd needs norms [6, B] and coef [2]")
+    dout = torch.empty_like(out_n)
+    _lib.check(_L().pa2d_darcy_loss_bwd(_p(out_n), _p(y_n), _p(mean), _p(std), _p(norms), _p(coef), _p(dout), B, s,
+                                        float(dx), _stream()), "darcy_loss_bwd")
+    return dout

@@ -1,0 +1,198 @@
+"""Command line in place of the reference's exp_ns.py, ns_vorticity_unrolling.py and exp_darcy.py:
+
+    python -m transformerbasednavierstokesolver_amd.train --driver ns --model Transolver_Structured_Mesh_2D \\
+        --n-hidden 256 --n-heads 8 --n-layers 8 --slice_num 32 --unified_pos 1 --ref 8 --batch-size 2 \\
+        --data_path /data/fno --save_name ns_Transolver
+
+The flags and their defaults are the reference drivers' own, per driver (`--driver {ns,unrolled,darcy}` selects the table).
+Added: `--driver`, `--engine` (GEMM engine: f32 | split | bf16 | bf16s, default PA2D_GEMM / split), `--ntrain` / `--ntest`
+(the drivers' hard-coded module globals; exp_darcy already has --ntrain).  `--gpu` is the device index.  `--data_path` is
+honoured (exp_ns.py and ns_vorticity_unrolling.py ignore it for a hard-coded path): a `.mat` file, or the directory that
+holds NavierStokes_V1e-5_N1200_T20.mat (directly or in a folder of that name) / piececonst_r421_N1024_smooth{1,2}.mat.
+
+The model comes from `model_dict.get_model(args)` (the unrolled driver builds the SOL wrapper, as the reference does
+whatever --model says), the optimizer is `optim.FusedAdamW` (clip threshold --max_grad_norm inside it), the schedule
+`OneCycleLR` over the whole run, the data a `data.ResidentDataset`, the loop `harness.fit_ns` / `fit_unrolled` /
+`fit_darcy` (fused Darcy loss).  The Darcy schedule spans max(500, --epochs) epochs: exp_darcy.py builds it from its module
+global `epochs = 500`, not from --epochs.  The state_dict goes to ./checkpoints/<save_name>.pt every 100 epochs and at the
+end; `--eval 1` loads it and prints the test metric (no plots)."""
+from __future__ import annotations
+
+import argparse
+import math
+import os
+import sys
+
+DRIVERS = ("ns", "unrolled", "darcy")
+# what differs between the three reference parsers / module globals
+_PER_DRIVER = {
+    "ns": dict(epochs=30, gpu="0", downsample=1, save_name="ns_2d_UniPDE", ntrain=50, ntest=50),
+    "unrolled": dict(epochs=5, gpu="0", downsample=1, save_name="ns_2d_UniPDE", ntrain=100, ntest=50),
+    "darcy": dict(epochs=500, gpu="1", downsample=5, save_name="darcy_Transolver", ntrain=1000, ntest=200),
+}
+DARCY_SCHEDULE_EPOCHS = 500
+T_IN = T = 10
+STEP = 1
+MAX_LOOK_AHEAD = 10
+NS_FILE = "NavierStokes_V1e-5_N1200_T20"
+DARCY_FILES = ("piececonst_r421_N1024_smooth1.mat", "piececonst_r421_N1024_smooth2.mat")
+
+
+def build_parser(driver):
+    d = _PER_DRIVER[driver]
+    p = argparse.ArgumentParser("Training Transolver" if driver == "darcy" else "Training Transformer")
+    p.add_argument("--lr", type=float, default=1e-3)
+    p.add_argument("--epochs", type=int, default=d["epochs"])
+    p.add_argument("--weight_decay", type=float, default=1e-5)
+    p.add_argument("--model", type=str, default="Transolver_2D")
+    p.add_argument("--n-hidden", type=int, default=64, help="hidden dim")
+    p.add_argument("--n-layers", type=int, default=3, help="layers")
+    p.add_argument("--n-heads", type=int, default=4)
+    p.add_argument("--batch-size", type=int, default=8)
+    p.add_argument("--gpu", type=str, default=d["gpu"], help="GPU index to use")
+    p.add_argument("--max_grad_norm", type=float, default=None)
+    p.add_argument("--downsample", type=int, default=d["downsample"])
+    p.add_argument("--mlp_ratio", type=int, default=1)
+    p.add_argument("--dropout", type=float, default=0.0)
+    p.add_argument("--ntrain", type=int, default=d["ntrain"])
+    p.add_argument("--unified_pos", type=int, default=0)
+    p.add_argument("--ref", type=int, default=8)
+    p.add_argument("--slice_num", type=int, default=32)
+    p.add_argument("--eval", type=int, default=0)
+    p.add_argument("--save_name", type=str, default=d["save_name"])
+    p.add_argument("--data_path", type=str, default="/data/fno")
+    # not in the reference
+    p.add_argument("--driver", choices=DRIVERS, default=driver)
+    p.add_argument("--engine", type=str, default=None, help="GEMM engine: f32 | split | bf16 | bf16s")
+    p.add_argument("--ntest", type=int, default=d["ntest"])
+    return p
+
+
+def parse_args(argv=None):
+    pre = argparse.ArgumentParser(add_help=False)
+    pre.add_argument("--driver", choices=DRIVERS, default="ns")
+    driver = pre.parse_known_args(argv)[0].driver
+    return build_parser(driver).parse_args(argv)
+
+
+def _find(data_path, names):
+    if os.path.isfile(data_path):
+        return data_path
+    for n in names:
+        if os.path.isfile(os.path.join(data_path, n)):
+            return os.path.join(data_path, n)
+    raise FileNotFoundError(f"none of {list(names)} under --data_path {data_path}")
+
+
+def _device(args):
+    import torch
+    idx = int(args.gpu)
+    if not torch.cuda.is_available() or idx >= torch.cuda.device_count():
+        raise SystemExit(f"--gpu {args.gpu}: no such GPU ({torch.cuda.device_count()} visible); this package has no CPU path")
+    torch.cuda.set_device(idx)
+    return torch.device("cuda", idx)
+
+
+def _model_kwargs(args, h, fun_dim):
+    return dict(space_dim=2, n_layers=args.n_layers, n_hidden=args.n_hidden, dropout=args.dropout, n_head=args.n_heads,
+                Time_Input=False, mlp_ratio=args.mlp_ratio, fun_dim=fun_dim, out_dim=1, slice_num=args.slice_num,
+                ref=args.ref, unified_pos=args.unified_pos, H=h, W=h)
+
+
+def _checkpoint(args):
+    return os.path.join("./checkpoints", args.save_name + ".pt")
+
+
+def _optim(args, model, steps_per_epoch, schedule_epochs, clip):
+    import torch
+    from .optim import FusedAdamW
+    opt = FusedAdamW(model.parameters(), lr=args.lr, weight_decay=args.weight_decay, max_grad_norm=clip)
+    sched = torch.optim.lr_scheduler.OneCycleLR(opt, max_lr=args.lr, epochs=schedule_epochs, steps_per_epoch=steps_per_epoch)
+    return opt, sched
+
+
+def run_ns(args, unrolled):
+    import torch
+    from . import data, harness, model_dict
+    from .model.SOL_Transolver_Structured_Mesh_2D import SOL_Transolver_Structured_Mesh_2D
+    from .utils.testloss import FusedTestLoss
+    dev = _device(args)
+    r = args.downsample
+    split = data.load_ns_mat(_find(args.data_path, (NS_FILE + ".mat", os.path.join(NS_FILE, NS_FILE + ".mat"))),
+                             args.ntrain, args.ntest, T_IN, T, r)
+    h = split["h"]
+    pos = data.grid_positions(h)
+    train = data.ResidentDataset(pos.repeat(args.ntrain, 1, 1), split["train_a"].float(), split["train_u"].float(), device=dev)
+    test = data.ResidentDataset(pos.repeat(args.ntest, 1, 1), split["test_a"].float(), split["test_u"].float(), device=dev)
+    kw = _model_kwargs(args, h, T_IN)
+    if unrolled:
+        model = SOL_Transolver_Structured_Mesh_2D(**kw, step=STEP, look_ahead=1).to(dev)
+        inner = model.transolver_model
+    else:
+        model = inner = model_dict.get_model(args).Model(**kw).to(dev)
+    if args.engine is not None:
+        inner.set_engine(args.engine)
+    print(args)
+    print(f"Total Trainable Params: {sum(p.numel() for p in model.parameters() if p.requires_grad)}")
+    loss_fn = FusedTestLoss(size_average=False)
+    if args.eval:
+        inner.load_state_dict(torch.load(_checkpoint(args), map_location=dev, weights_only=True), strict=True)
+        m = harness.evaluate_ns(inner, test, args.batch_size, T, STEP, loss_fn)
+        print(m["test_full"])
+        return m
+    steps = math.ceil(args.ntrain / args.batch_size)
+    if unrolled:
+        opt, sched = _optim(args, model, steps, args.epochs, None)          # this loop never clips
+        return harness.fit_unrolled(
+            model, opt, sched, train, test, epochs=args.epochs, batch_size=args.batch_size, T=T, step=STEP, look_ahead=1,
+            max_look_ahead=MAX_LOOK_AHEAD, loss_fn=loss_fn, save_path=_checkpoint(args), grad_sync=opt.sync,
+            on_epoch=lambda ep, m: print("Epoch {} , train_step_loss:{:.5f} , test_step_loss:{:.5f} , look_ahead:{}".format(
+                ep, m["train_step"], m["test_step"], m["look_ahead"]), flush=True))
+    opt, sched = _optim(args, model, steps, args.epochs, args.max_grad_norm)
+    return harness.fit_ns(
+        model, opt, sched, train, test, epochs=args.epochs, batch_size=args.batch_size, T=T, step=STEP, loss_fn=loss_fn,
+        save_path=_checkpoint(args), grad_sync=opt.sync,
+        on_epoch=lambda ep, m: print(
+            "Epoch {} , train_step_loss:{:.5f} , train_full_loss:{:.5f} , test_step_loss:{:.5f} , test_full_loss:{:.5f}".format(
+                ep, m["train_step"], m["train_full"], m["test_step"], m["test_full"]), flush=True))
+
+
+def run_darcy(args):
+    import torch
+    from . import data, harness, model_dict
+    from .utils.testloss import FusedTestLoss, TestLoss
+    dev = _device(args)
+    d = data.load_darcy_mat(_find(args.data_path, DARCY_FILES[:1]), _find(args.data_path, DARCY_FILES[1:]), args.ntrain,
+                            args.ntest, args.downsample)
+    model = model_dict.get_model(args).Model(**_model_kwargs(args, d["s"], 1)).to(dev)
+    if args.engine is not None:
+        model.set_engine(args.engine)
+    print(args)
+    print(f"Total Trainable Params: {sum(p.numel() for p in model.parameters() if p.requires_grad)}")
+    # a real .mat holds a float64 solution: the test metric is then evaluated in float64 by torch, as in the reference
+    loss_fn = (FusedTestLoss if d["y_test"].dtype == torch.float32 else TestLoss)(size_average=False)
+    if args.eval:
+        model.load_state_dict(torch.load(_checkpoint(args), map_location=dev, weights_only=True), strict=True)
+        m = harness.evaluate_darcy(model, d, args.batch_size, loss_fn)
+        print("rel_err:{}".format(m["rel_err"]))
+        return m
+    opt, sched = _optim(args, model, math.ceil(args.ntrain / args.batch_size), max(DARCY_SCHEDULE_EPOCHS, args.epochs),
+                        args.max_grad_norm)
+
+    def line(ep, m):
+        print("Epoch {} Reg : {:.5f} Train loss : {:.5f}".format(ep, m["reg"], m["train_loss"]))
+        print("rel_err:{}".format(m["rel_err"]), flush=True)
+
+    return harness.fit_darcy(model, opt, sched, d, epochs=args.epochs, batch_size=args.batch_size, loss_fn=loss_fn,
+                             save_path=_checkpoint(args), fused=True, grad_sync=opt.sync, on_epoch=line)
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    if args.driver == "darcy":
+        return run_darcy(args)
+    return run_ns(args, unrolled=args.driver == "unrolled")
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])
