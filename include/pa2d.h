@@ -416,6 +416,40 @@ int pa2d_darcy_loss_fwd(const float* out_n, const float* y_n, const float* mean,
 int pa2d_darcy_loss_bwd(const float* out_n, const float* y_n, const float* mean, const float* std, const float* norms,
                         const float* coef, float* dout, int B, int s, float dx, pa2d_stream_t stream);
 
+/* ---- the decoded, strided relative-L2 loss of the airfoil / pipe / elasticity / plasticity drivers (exp_pipe.py:210-213):
+ * per sample ||o - y|| / ||y|| with o = pred std + mean, y = y_n std + mean (both decoded, then subtracted, as
+ * pa2d_darcy_loss does).  mean / std: one-element device tensors, or NULL for BOTH = identity.  pred: [B, L] contiguous;
+ * the target element (b, i) is y[b * y_batch_stride + i * y_elem_stride] (strides in elements, y_elem_stride >= 1), so a
+ * slice such as yy[..., t:t+1] of [B, N, 4, T] is read in place.  Pointers need 4-byte alignment only; the kernels use
+ * 16-byte accesses where the operands of a row are aligned alike and scalar accesses elsewhere.
+ * fwd: a sample is split over up to PA2D_REL_L2_AFFINE_SPLIT workgroups whose partial sums are added in a fixed order
+ * (two calls give the same bits); dnorm / ynorm [B] are saved for bwd, ratio [B] are the per-sample losses.
+ * ws: at least 2 * B * PA2D_REL_L2_AFFINE_SPLIT floats.
+ * bwd: dpred[b] = gout[b] std (o_b - y_b) / (dnorm_b ynorm_b); gout [B] is the per-sample upstream gradient; a sample
+ * with dnorm_b == 0 gets the zero sub-gradient.  There is no gradient to y.  B = 0 or L = 0: nothing is touched. */
+#define PA2D_REL_L2_AFFINE_SPLIT 64
+int pa2d_rel_l2_affine_fwd(const float* pred, const float* y, long long y_elem_stride, long long y_batch_stride,
+                           const float* mean, const float* std, float* dnorm, float* ynorm, float* ratio, void* ws,
+                           size_t ws_bytes, int B, long long L, pa2d_stream_t stream);
+int pa2d_rel_l2_affine_bwd(const float* pred, const float* y, long long y_elem_stride, long long y_batch_stride,
+                           const float* mean, const float* std, const float* dnorm, const float* ynorm,
+                           const float* gout, float* dpred, int B, long long L, pa2d_stream_t stream);
+
+/* ---- the broadcast adds of the input embedding (model/_core.py TransolverBase._embed):
+ * fwd: z[b, n, :] = (h[b, n, :] + placeholder[:]) + tvec[b, :], the sums of the torch expressions in their order, so
+ * the same bits.  placeholder [C] and tvec [B, C] may each be NULL; z may be h.
+ * bwd: the gradient to h is dz itself; dtvec[b, c] = sum_n dz[b, n, c] and dplaceholder[c] = sum_b dtvec[b, c], by one
+ * partial-sum pass and a fixed-order finish (two calls give the same bits).  dtvec NULL: dplaceholder is reduced
+ * straight from the [B N, C] rows; dplaceholder NULL: only dtvec.  Outputs are overwritten (zero-filled when B N == 0).
+ * ws: at least PA2D_EMBED_BIAS_CHUNKS * (dtvec ? B : 1) * C floats.
+ * C % 4 != 0 returns PA2D_ERR_UNSUPPORTED.  h, placeholder, tvec, z, dz and ws are accessed 16 bytes at a time and must be
+ * 16-byte aligned (else PA2D_ERR_ARG); dplaceholder and dtvec are written element by element (4-byte alignment). */
+#define PA2D_EMBED_BIAS_CHUNKS 64
+int pa2d_embed_bias_fwd(const float* h, const float* placeholder, const float* tvec, float* z, int B, int N, int C,
+                        pa2d_stream_t stream);
+int pa2d_embed_bias_bwd(const float* dz, float* dplaceholder, float* dtvec, void* ws, size_t ws_bytes, int B, int N,
+                        int C, pa2d_stream_t stream);
+
 /* ==== operand-planes interface of the bf16 engines (fp32 storage; PA2D_ENGINE_SPLIT: 3 planes, PA2D_ENGINE_BF16: 1).
  * The conv GEMMs of these engines stage their activation operand as a bf16 plane image [row][C/32][NT][32].  By default
  * pa2d_conv3x3x2_fwd/bwd make it from the fp32 tensor in a pre-pass; with the entry points below the PRODUCER of the

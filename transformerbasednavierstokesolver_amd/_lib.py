@@ -109,7 +109,13 @@ SIGNATURES = {
     "pa2d_darcy_loss_workspace": (_sz, [_i, _i]),
     "pa2d_darcy_loss_fwd": (_i, [_f, _f, _f, _f, _f, _f, _f, _sz, _i, _i, C.c_float, _st]),
     "pa2d_darcy_loss_bwd": (_i, [_f, _f, _f, _f, _f, _f, _f, _i, _i, C.c_float, _st]),
+    "pa2d_rel_l2_affine_fwd": (_i, [_f, _f, _ll, _ll, _f, _f, _f, _f, _f, _f, _sz, _i, _ll, _st]),
+    "pa2d_rel_l2_affine_bwd": (_i, [_f, _f, _ll, _ll, _f, _f, _f, _f, _f, _f, _i, _ll, _st]),
+    "pa2d_embed_bias_fwd": (_i, [_f, _f, _f, _f, _i, _i, _i, _st]),
+    "pa2d_embed_bias_bwd": (_i, [_f, _f, _f, _f, _sz, _i, _i, _i, _st]),
 }
+REL_L2_AFFINE_SPLIT = 64     # PA2D_REL_L2_AFFINE_SPLIT
+EMBED_BIAS_CHUNKS = 64       # PA2D_EMBED_BIAS_CHUNKS
 # bf16-storage variants: identical argument lists (activation pointers simply hold bf16); the GEMM / conv ones have no
 # `engine` argument (they ARE the bf16 engine)
 for _name in ("pa2d_layernorm_fwd", "pa2d_layernorm_bwd", "pa2d_head_fwd", "pa2d_head_bwd"):

@@ -2,6 +2,9 @@
 
 * `load_ns_mat` / `split_ns_trajectories`   the `.mat` -> (a, u) slicing of exp_ns.py:64-80
 * `load_darcy_mat` / `darcy_from_mats` / `split_darcy`   exp_darcy.py:76-99 (coeff/sol fields + UnitTransformer encoding)
+* `load_airfoil_npy` / `load_pipe_npy` / `load_elas_npy` / `load_plas_mat` (and their `*_from_arrays` / `plas_from_mat`)
+                                            the `.npy` / `.mat` slicing and UnitTransformer encoding of exp_airfoil.py:50-79,
+                                            exp_pipe.py:52-91, exp_elas.py:54-72, exp_plas.py:105-137
 * `grid_positions`                          the driver-side position input (exp_ns.py:88-94)
 * `ResidentDataset`                         the whole split kept in HBM and batched by device-side index
                                             selection: replaces TensorDataset + DataLoader(num_workers=0) +
@@ -15,6 +18,7 @@
 from __future__ import annotations
 
 import math
+import os
 
 import numpy as np
 import torch
@@ -143,3 +147,112 @@ def simulate_ns_vorticity(w0, visc=1e-5, T=20.0, dt=1e-3, record=20, forcing=Tru
             out[..., rec] = torch.fft.ifft2(w_h).real.float()
             rec += 1
     return out
+
+
+# ------------------------------------------------------------------ the airfoil / pipe / elasticity / plasticity sets
+def _mesh_size(full, r):
+    return int(((full - 1) / r) + 1)
+
+
+def split_mesh_fields(X, Y, q, train, test, r1=1, r2=1):
+    """exp_airfoil.py:62-79 / exp_pipe.py:65-81 on loaded arrays: X, Y, q [S, H, W]; `train` / `test`: slices of the
+    sample axis.  Returns (x_train [n, s1*s2, 2], y_train [n, s1*s2], x_test, y_test, s1, s2), float32, strided by
+    (r1, r2) and cut to s1 x s2 = (H-1)/r1+1 x (W-1)/r2+1 points, flattened row-major."""
+    xy = torch.stack([torch.tensor(np.asarray(X), dtype=torch.float), torch.tensor(np.asarray(Y), dtype=torch.float)], dim=-1)
+    q = torch.tensor(np.asarray(q), dtype=torch.float)
+    s1, s2 = _mesh_size(xy.shape[1], r1), _mesh_size(xy.shape[2], r2)
+    cut = lambda t, sl: t[sl, ::r1, ::r2][:, :s1, :s2]
+    x_train, x_test = cut(xy, train), cut(xy, test)
+    y_train, y_test = cut(q, train), cut(q, test)
+    return (x_train.reshape(x_train.shape[0], -1, 2), y_train.reshape(y_train.shape[0], -1),
+            x_test.reshape(x_test.shape[0], -1, 2), y_test.reshape(y_test.shape[0], -1), s1, s2)
+
+
+def airfoil_from_arrays(X, Y, Q, ntrain=1000, ntest=200, r1=1, r2=1):
+    """exp_airfoil.py:62-79 on the loaded arrays (X, Y [S, 221, 51], Q [S, >= 5, 221, 51]): the target is channel 4 of Q; the
+    mesh is strided by (r1, r2); train = the first `ntrain` samples, test = samples ntrain .. ntrain + ntest.  No
+    normaliser: x and y are raw.  Returns x_train [n, N, 2], y_train [n, N], x_test, y_test, x_normalizer = y_normalizer =
+    None, s1, s2."""
+    x_train, y_train, x_test, y_test, s1, s2 = split_mesh_fields(X, Y, np.asarray(Q)[:, 4], slice(0, ntrain),
+                                                                 slice(ntrain, ntrain + ntest), r1, r2)
+    return dict(x_train=x_train, y_train=y_train, x_test=x_test, y_test=y_test, x_normalizer=None, y_normalizer=None,
+                s1=s1, s2=s2)
+
+
+def load_airfoil_npy(path, ntrain=1000, ntest=200, r1=1, r2=1):
+    """exp_airfoil.py:50-79: NACA_Cylinder_{X,Y,Q}.npy under `path`, see `airfoil_from_arrays`."""
+    X, Y, Q = (np.load(os.path.join(path, f"NACA_Cylinder_{k}.npy")) for k in "XYQ")
+    return airfoil_from_arrays(X, Y, Q, ntrain, ntest, r1, r2)
+
+
+PIPE_SAMPLES = 1200      # exp_pipe.py:58: the script's `N`; train / test are taken from the first N samples
+
+
+def pipe_from_arrays(X, Y, Q, ntrain=1000, ntest=200, r1=1, r2=1):
+    """exp_pipe.py:65-91 on the loaded arrays (X, Y [S, 129, 129], Q [S, >= 1, 129, 129]): the target is channel 0 of Q; the
+    mesh is strided by (r1, r2); train = the first `ntrain`, test = the LAST `ntest` of the first N = 1200 samples.
+    UnitTransformer on x (per coordinate) and on y (one mean / std), both fitted on the train split; x_train, x_test and
+    y_train are encoded, y_test stays RAW."""
+    n = PIPE_SAMPLES
+    x_train, y_train, x_test, y_test, s1, s2 = split_mesh_fields(np.asarray(X)[:n], np.asarray(Y)[:n], np.asarray(Q)[:n, 0],
+                                                                 slice(0, ntrain), slice(-ntest, None), r1, r2)
+    xn, yn = UnitTransformer(x_train), UnitTransformer(y_train)
+    return dict(x_train=xn.encode(x_train), y_train=yn.encode(y_train), x_test=xn.encode(x_test), y_test=y_test,
+                x_normalizer=xn, y_normalizer=yn, s1=s1, s2=s2)
+
+
+def load_pipe_npy(path, ntrain=1000, ntest=200, r1=1, r2=1):
+    """exp_pipe.py:52-91: Pipe_{X,Y,Q}.npy under `path`, see `pipe_from_arrays`."""
+    X, Y, Q = (np.load(os.path.join(path, f"Pipe_{k}.npy")) for k in "XYQ")
+    return pipe_from_arrays(X, Y, Q, ntrain, ntest, r1, r2)
+
+
+def elas_from_arrays(sigma, xy, ntrain=1000, ntest=200):
+    """exp_elas.py:57-72 on the loaded arrays: sigma [N, S] -> [S, N], xy [N, 2, S] -> [S, N, 2]; train = the first
+    `ntrain` samples, test = the LAST `ntest`; UnitTransformer on y only (fitted on the train split): y_train is encoded,
+    y_test RAW, the point coordinates raw."""
+    s = torch.tensor(np.asarray(sigma), dtype=torch.float).permute(1, 0)
+    p = torch.tensor(np.asarray(xy), dtype=torch.float).permute(2, 0, 1)
+    y_train = s[:ntrain]
+    yn = UnitTransformer(y_train)
+    return dict(x_train=p[:ntrain], y_train=yn.encode(y_train), x_test=p[-ntest:], y_test=s[-ntest:], x_normalizer=None,
+                y_normalizer=yn, s1=None, s2=None)
+
+
+ELAS_FILES = ("elasticity/Meshes/Random_UnitCell_sigma_10.npy", "elasticity/Meshes/Random_UnitCell_XY_10.npy")
+
+
+def load_elas_npy(path, ntrain=1000, ntest=200):
+    """exp_elas.py:54-72: <path>/elasticity/Meshes/Random_UnitCell_{sigma,XY}_10.npy, see `elas_from_arrays`."""
+    return elas_from_arrays(np.load(os.path.join(path, ELAS_FILES[0])), np.load(os.path.join(path, ELAS_FILES[1])),
+                            ntrain, ntest)
+
+
+PLAS_MESH, PLAS_T, PLAS_DEFORMATION = (101, 31), 20, 4
+
+
+def plas_from_mat(mat, ntrain=900, ntest=80):
+    """exp_plas.py:105-137 on the loaded `.mat` dict: 'input' [S, 101] (the die profile) is repeated along the 31 mesh
+    columns -> x [n, N, 1]; 'output' [S, 101, 31, T = 20, 4] is transposed to [..., 4, T] -> y [n, N, 4, T]; train = the
+    first `ntrain`, test = the LAST `ntest`.  UnitTransformer on x only (fitted on the train split); y is raw.
+    `pos` [1, N, 2] is the script's np.meshgrid(linspace(0, 1, 101), linspace(0, 1, 31)) raveled: ITS point order runs
+    along the 101-axis fastest, while x and y are flattened with the 31-axis fastest; kept as the script has it.
+    `t` [T] = linspace(0, 1, T)."""
+    s1, s2 = PLAS_MESH
+    inp = torch.tensor(np.asarray(mat["input"]), dtype=torch.float)
+    out = torch.tensor(np.asarray(mat["output"]), dtype=torch.float).transpose(-2, -1)
+    T = out.shape[-1]
+    grow = lambda a: a[:, :s1].reshape(a.shape[0], s1, 1).repeat(1, 1, s2).reshape(a.shape[0], -1, 1)
+    x_train, x_test = grow(inp[:ntrain]), grow(inp[-ntest:])
+    y_train = out[:ntrain, :s1, :s2].reshape(ntrain, -1, PLAS_DEFORMATION, T)
+    y_test = out[-ntest:, :s1, :s2].reshape(ntest, -1, PLAS_DEFORMATION, T)
+    xn = UnitTransformer(x_train)
+    return dict(x_train=xn.encode(x_train), y_train=y_train, x_test=xn.encode(x_test), y_test=y_test, x_normalizer=xn,
+                y_normalizer=None, pos=grid_positions(s2, s1), t=torch.tensor(np.linspace(0, 1, T), dtype=torch.float),
+                s1=s1, s2=s2, T=T)
+
+
+def load_plas_mat(path, ntrain=900, ntest=80):
+    """exp_plas.py:105: plas_N987_T20.mat ('input', 'output'), see `plas_from_mat`."""
+    import scipy.io as scio
+    return plas_from_mat(scio.loadmat(path), ntrain, ntest)

@@ -378,6 +378,70 @@ def rel_l2(pred, y):
     return RelL2Fn.apply(pred, y)
 
 
+class RelL2AffineFn(Function):
+    """Per-sample ||o - y|| / ||y|| of the DECODED prediction and target (o = pred std + mean, y = y_n std + mean; mean /
+    std the normaliser's one-element device tensors, None = identity) with the target read through its strides
+    (ops.rel_l2_affine_fwd / _bwd): the loss of the airfoil, pipe, elasticity and plasticity drivers.  Gradient w.r.t.
+    pred only."""
+
+    @staticmethod
+    def forward(ctx, pred, y, mean, std):
+        B = pred.shape[0]
+        L = pred.numel() // max(B, 1)                    # B = 0: an empty [0, 0] problem, the kernels touch nothing
+        p2, y = pred.detach().reshape(B, L).contiguous(), y.detach()
+        if ops.uniform_strides(y) is None:
+            y = y.reshape(B, L).contiguous()
+        if mean is not None:
+            mean, std = mean.detach().contiguous(), std.detach().contiguous()
+        dn, yn, ratio = ops.rel_l2_affine_fwd(p2, y, mean, std)
+        ctx.saved, ctx.shp = (p2, y, mean, std, dn, yn), pred.shape
+        return ratio
+
+    @staticmethod
+    def backward(ctx, gratio):
+        p2, y, mean, std, dn, yn = ctx.saved
+        dpred = ops.rel_l2_affine_bwd(p2, y, mean, std, dn, yn, gratio.contiguous())
+        return dpred.view(ctx.shp), None, None, None
+
+
+def rel_l2_affine(pred, y, mean=None, std=None):
+    return RelL2AffineFn.apply(pred, y, mean, std)
+
+
+class EmbedBiasFn(Function):
+    """z = (h + placeholder[None, None, :]) + tvec[:, None, :] in one launch (ops.embed_bias_fwd); the backward hands dz on
+    as dh and makes dplaceholder / dtvec by one fixed-order column reduction (ops.embed_bias_bwd)."""
+
+    @staticmethod
+    def forward(ctx, h, placeholder, tvec):
+        det = lambda t: None if t is None else t.detach().contiguous()
+        ctx.has = (placeholder is not None, tvec is not None)
+        return ops.embed_bias_fwd(det(h), det(placeholder), det(tvec))
+
+    @staticmethod
+    def backward(ctx, dz):
+        want_p = ctx.has[0] and ctx.needs_input_grad[1]
+        want_t = ctx.has[1] and ctx.needs_input_grad[2]
+        if not (want_p or want_t):
+            return dz, None, None
+        src = dz.contiguous()
+        if src.data_ptr() % 16:          # a view at an odd offset: the reduction reads 16 bytes at a time
+            src = src.clone()
+        dp, dt = ops.embed_bias_bwd(src, want_p, want_t)
+        return dz, dp, dt
+
+
+def embed_bias(h, placeholder=None, tvec=None):
+    """The input embedding's broadcast adds.  Where the kernels do not apply (C % 4 != 0, not fp32 on the GPU) the torch
+    expression stays: the same sums in the same order."""
+    if (placeholder is None and tvec is None):
+        return h
+    if not ops.embed_bias_supported(h, placeholder, tvec):
+        z = h if placeholder is None else h + placeholder[None, None, :]
+        return z if tvec is None else z + tvec[:, None, :]
+    return EmbedBiasFn.apply(h, placeholder, tvec)
+
+
 class DarcyLossFn(Function):
     """The exp_darcy.py:213-226 loss of the normalised prediction `out_n` [B, s*s] against the normalised target `y_n`:
     decode with the y-normaliser's (mean, std) device scalars, rel-L2 plus 0.1 x the rel-L2 of the zero-padded central

@@ -761,3 +761,223 @@ def fit_darcy(model, optimizer, scheduler, data, *, epochs, batch_size, max_grad
     if save_path is not None:
         _save_state(model, save_path)
     return history
+
+
+# ------------------------------------------------------------------ exp_airfoil / exp_pipe / exp_elas: one call per batch
+def _rel_decoded(loss_fn, out, y, y_normalizer):
+    """The training loss of the static drivers: rel-L2 of the decoded prediction against the decoded target.  A loss
+    object with `rel_decoded` (utils.testloss.TestLoss; FusedTestLoss runs it on the decoded rel-L2 kernels, with the
+    normaliser read on the device) is asked for it; any other callable gets the two decoded tensors."""
+    if hasattr(loss_fn, "rel_decoded"):
+        return loss_fn.rel_decoded(out, y, y_normalizer)
+    if y_normalizer is None:
+        return loss_fn(out, y)
+    return loss_fn(y_normalizer.decode(out), y_normalizer.decode(y))
+
+
+def static_train_step(model, optimizer, scheduler, x, y, y_normalizer=None, max_grad_norm=None, grad_sync=None,
+                      loss_fn=None):
+    """exp_airfoil.py:187-199 / exp_pipe.py:204-221 / exp_elas.py:163-176: zero_grad, ONE call model(x, None) (fun_dim = 0:
+    the placeholder path), the rel-L2 of the decoded prediction and target (raw without a normaliser), backward,
+    [grad_sync], [clip], step, [scheduler] (pass None where the schedule is stepped per epoch).  Returns the detached
+    loss."""
+    loss_fn = loss_fn or TestLoss(size_average=False)
+    optimizer.zero_grad(set_to_none=False)
+    out = model(x, None).squeeze(-1)
+    loss = _rel_decoded(loss_fn, out, y, y_normalizer)
+    loss.backward()
+    if grad_sync is not None:
+        grad_sync()
+    if max_grad_norm is not None:
+        torch.nn.utils.clip_grad_norm_(model.parameters(), max_grad_norm)
+    optimizer.step()
+    if scheduler is not None:
+        scheduler.step()
+    return loss.detach()
+
+
+@torch.no_grad()
+def _static_test_pass(model, test, batch_size, y_normalizer, loss_fn, acc):
+    """exp_pipe.py:229-235: the prediction is decoded (where there is a normaliser), the target is RAW; acc[1] += rel-L2."""
+    for x, y in test.batches(batch_size):
+        out = model(x, None).squeeze(-1)
+        acc[1] += loss_fn(out if y_normalizer is None else y_normalizer.decode(out), y)
+
+
+def _static_setup(model, data, want_train=True):
+    import copy
+    from .data import ResidentDataset
+    dev = _device_of(model)
+    yn = data.get("y_normalizer")
+    yn = None if yn is None else copy.copy(yn).to(dev)        # the caller's normaliser stays where it is
+    train = ResidentDataset(data["x_train"], data["y_train"], device=dev) if want_train else None
+    return dev, yn, train, ResidentDataset(data["x_test"], data["y_test"], device=dev)
+
+
+def evaluate_static(model, data, batch_size, loss_fn=None):
+    """The test pass alone (the `eval` branch of the three scripts without the plots): {'rel_err'} = summed rel-L2 / ntest."""
+    loss_fn = loss_fn or TestLoss(size_average=False)
+    dev, yn, _, test = _static_setup(model, data, want_train=False)
+    acc = torch.zeros(2, dtype=torch.float64, device=dev)
+    model.eval()
+    _static_test_pass(model, test, batch_size, yn, loss_fn, acc)
+    return dict(rel_err=acc.tolist()[1] / len(test))
+
+
+def fit_static(model, optimizer, scheduler, data, *, epochs, batch_size, max_grad_norm=None, loss_fn=None,
+               epoch_orders=None, generator=None, save_path=None, save_every=100, scheduler_per_epoch=False, grad_sync=None,
+               on_epoch=None):
+    """The epoch loop of exp_airfoil.main() (:182-226), exp_pipe.main() (:199-249) and exp_elas.main() (:158-204).  `data`:
+    the dict of `data.load_airfoil_npy` / `load_pipe_npy` / `load_elas_npy` (x_train [n, N, 2], y_train [n, N], x_test, the
+    RAW y_test, y_normalizer or None); everything is moved to the model's device.
+
+    Per batch `static_train_step`: one model(x, None) call and the rel-L2 loss.  What the three scripts do differently
+    follows from `data["y_normalizer"]` and one flag, and is kept:
+      * airfoil (no normaliser): raw loss, raw test metric;
+      * pipe: the training loss decodes prediction AND target; the test pass decodes the prediction, its target is raw;
+      * elas: as pipe, and the scheduler is stepped once per EPOCH (exp_elas.py:177): `scheduler_per_epoch=True`.
+    The caller builds the scheduler.  exp_airfoil / exp_pipe: OneCycleLR(max_lr=lr, epochs=epochs, steps_per_epoch=
+    ceil(ntrain / batch_size)).  exp_elas.py:102 builds CosineAnnealingLR(T_max=epochs) from an UNDEFINED global `epochs`
+    and raises as shipped; this project's command line passes CosineAnnealingLR(T_max=args.epochs), the evident intent.
+
+    `loss_fn`: a TestLoss(size_average=False)-like object; utils.testloss.FusedTestLoss runs the training loss on the
+    decoded rel-L2 kernels.  Returns one dict per epoch: train_loss = sum / ntrain, rel_err = sum / ntest.  Accumulators
+    stay on the device: ONE host synchronisation per epoch.  `epoch_orders`, `generator`, `save_path` / `save_every`,
+    `grad_sync`, `on_epoch`: as fit_ns."""
+    loss_fn = loss_fn or TestLoss(size_average=False)
+    dev, yn, train, test = _static_setup(model, data)
+    ntrain, ntest = len(train), len(test)
+    history = []
+    for ep in range(epochs):
+        model.train()
+        acc = torch.zeros(2, dtype=torch.float64, device=dev)
+        for x, y in _epoch_batches(train, batch_size, ep, epoch_orders, generator):
+            acc[0] += static_train_step(model, optimizer, None if scheduler_per_epoch else scheduler, x, y, yn,
+                                        max_grad_norm=max_grad_norm, grad_sync=grad_sync, loss_fn=loss_fn)
+        if scheduler_per_epoch and scheduler is not None:
+            scheduler.step()
+        model.eval()
+        _static_test_pass(model, test, batch_size, yn, loss_fn, acc)
+        a = acc.tolist()                                         # the epoch's only host synchronisation
+        history.append(dict(train_loss=a[0] / ntrain, rel_err=a[1] / ntest))
+        if on_epoch is not None:
+            on_epoch(ep, history[-1])
+        if save_path is not None and ep % save_every == 0:
+            _save_state(model, save_path)
+    if save_path is not None:
+        _save_state(model, save_path)
+    return history
+
+
+# ------------------------------------------------------------------ exp_plas: T time-conditioned calls and steps per batch
+def plas_train_step(model, optimizer, x, fx, tim, yy, max_grad_norm=None, grad_sync=None, loss_fn=None):
+    """exp_plas.py:242-253 on one batch: for every t < T = yy.shape[-1]: ONE call model(x, fx, T=tim[:, t:t+1]), the raw
+    rel-L2 of the [B, N * 4] prediction against yy[..., t:t+1] (read in place through its strides by the fused loss),
+    zero_grad, backward, [grad_sync], [clip], optimizer.step(): T optimizer steps.  The scheduler is the caller's (once
+    per batch).  Returns the detached sum of the T step losses."""
+    loss_fn = loss_fn or TestLoss(size_average=False)
+    bsz = x.shape[0]
+    total = 0
+    for t in range(yy.shape[-1]):
+        im = model(x, fx, T=tim[:, t:t + 1].reshape(bsz, 1))
+        loss = _rel_decoded(loss_fn, im.reshape(bsz, -1), yy[..., t:t + 1], None)
+        total = total + loss.detach()
+        optimizer.zero_grad(set_to_none=False)
+        loss.backward()
+        if grad_sync is not None:
+            grad_sync()
+        if max_grad_norm is not None:
+            torch.nn.utils.clip_grad_norm_(model.parameters(), max_grad_norm)
+        optimizer.step()
+    return total
+
+
+@torch.no_grad()
+def _plas_test_pass(model, test, batch_size, positions, t, loss_fn, acc):
+    """exp_plas.py:260-277: acc[1] += the T step losses, acc[2] += the loss of the whole [B, N * 4 * T] trajectory."""
+    for fx, yy in test.batches(batch_size):
+        bsz = fx.shape[0]
+        x, tim = positions(bsz), t.expand(bsz, -1)
+        loss, preds = 0, []
+        with ops.weights_frozen():
+            for k in range(yy.shape[-1]):
+                im = model(x, fx, T=tim[:, k:k + 1].reshape(bsz, 1))
+                loss = loss + _rel_decoded(loss_fn, im.reshape(bsz, -1), yy[..., k:k + 1], None)
+                preds.append(im.unsqueeze(-1))
+        acc[1] += loss
+        acc[2] += loss_fn(torch.cat(preds, -1).reshape(bsz, -1), yy.reshape(bsz, -1))
+
+
+def _plas_setup(model, data, want_train=True):
+    from .data import ResidentDataset
+    dev = _device_of(model)
+    train = ResidentDataset(data["x_train"], data["y_train"], device=dev) if want_train else None
+    test = ResidentDataset(data["x_test"], data["y_test"], device=dev)
+    pos1, pos = data["pos"].to(dev), {}
+
+    def positions(bsz):
+        if bsz not in pos:
+            pos[bsz] = pos1.expand(bsz, -1, -1).contiguous()
+        return pos[bsz]
+
+    return dev, train, test, positions, data["t"].to(dev)
+
+
+def evaluate_plas(model, data, batch_size, loss_fn=None):
+    """The test pass alone (exp_plas.py:168-231 without the plots): {'test_step', 'test_full'} normalised like fit_plas."""
+    loss_fn = loss_fn or TestLoss(size_average=False)
+    dev, _, test, positions, t = _plas_setup(model, data, want_train=False)
+    acc = torch.zeros(3, dtype=torch.float64, device=dev)
+    model.eval()
+    _plas_test_pass(model, test, batch_size, positions, t, loss_fn, acc)
+    a = acc.tolist()
+    return dict(test_step=a[1] / len(test) / t.numel(), test_full=a[2] / len(test))
+
+
+def fit_plas(model, optimizer, scheduler, data, *, epochs, batch_size, max_grad_norm=None, loss_fn=None, epoch_orders=None,
+             time_orders=None, generator=None, save_path=None, save_every=100, grad_sync=None, on_epoch=None):
+    """The epoch loop of exp_plas.main() (exp_plas.py:233-292).  `data`: the dict of `data.load_plas_mat` (encoded x_train
+    [n, N, 1], y_train [n, N, 4, T], x_test, y_test, pos [1, N, 2], t [T]); everything is moved to the model's device.
+
+    The train collate (`random_collate_fn`, :51-85) permutes the T timesteps of every sample on its own: `time_orders[ep]`
+    [ntrain, T] replays recorded permutations, row i for the i-th sample IN THE EPOCH'S ORDER; otherwise they are drawn
+    from `generator`.  Per batch `plas_train_step` (T model calls with T optimizer steps), then scheduler.step() ONCE
+    (:255; the caller builds OneCycleLR(max_lr=lr, epochs=epochs, steps_per_epoch=ceil(ntrain / batch_size))).  The test
+    pass runs the timesteps in order and keeps the summed step losses and the loss of the whole trajectory.
+
+    Returns one dict per epoch: train_step = sum / ntrain / T, test_step = sum / ntest / T, test_full = sum / ntest
+    (:279-282).  One host synchronisation per epoch; `epoch_orders`, `save_path` / `save_every`, `grad_sync`, `on_epoch`:
+    as fit_ns."""
+    loss_fn = loss_fn or TestLoss(size_average=False)
+    dev, train, test, positions, t = _plas_setup(model, data)
+    ntrain, ntest, T = len(train), len(test), t.numel()
+    history = []
+    for ep in range(epochs):
+        model.train()
+        acc = torch.zeros(3, dtype=torch.float64, device=dev)
+        seen = 0
+        for fx, yy in _epoch_batches(train, batch_size, ep, epoch_orders, generator):
+            bsz = fx.shape[0]
+            if time_orders is not None:
+                perm = torch.as_tensor(time_orders[ep], dtype=torch.long)[seen:seen + bsz].to(dev)
+            else:
+                gdev = dev if generator is None else generator.device
+                perm = torch.rand(bsz, T, generator=generator, device=gdev).argsort(dim=1).to(dev)
+            seen += bsz
+            tim = t[perm]                                                        # [B, T]
+            yy = yy.gather(-1, perm[:, None, None, :].expand_as(yy))             # u[..., permuted_indices] per sample
+            acc[0] += plas_train_step(model, optimizer, positions(bsz), fx, tim, yy, max_grad_norm=max_grad_norm,
+                                      grad_sync=grad_sync, loss_fn=loss_fn)
+            if scheduler is not None:
+                scheduler.step()
+        model.eval()
+        _plas_test_pass(model, test, batch_size, positions, t, loss_fn, acc)
+        a = acc.tolist()
+        history.append(dict(train_step=a[0] / ntrain / T, test_step=a[1] / ntest / T, test_full=a[2] / ntest))
+        if on_epoch is not None:
+            on_epoch(ep, history[-1])
+        if save_path is not None and ep % save_every == 0:
+            _save_state(model, save_path)
+    if save_path is not None:
+        _save_state(model, save_path)
+    return history

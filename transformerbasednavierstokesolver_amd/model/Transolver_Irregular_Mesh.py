@@ -71,7 +71,5 @@ class Model(TransolverBase):
     def forward(self, x, fx, T=None):
         if self.unified_pos:
             x = self.get_grid(x, x.shape[0])
-        z = self._embed(x, fx, always_placeholder=True)
-        if T is not None:
-            z = self._add_time(z, T)
+        z = self._embed(x, fx, always_placeholder=True, T=T)
         return self._run_blocks(z)

@@ -88,16 +88,14 @@ class Model(TransolverBase):
         _refuse_bf16_storage(engine)
         return super().set_engine(engine)
 
-    def _embed_input(self, x, fx):
+    def _embed_input(self, x, fx, T=None):
         _refuse_bf16_storage(self.engine)
         if self.unified_pos:      # the coordinates in `x` are ignored (only the batch size is used)
             x = self.pos.expand(x.shape[0], -1, -1, -1).reshape(x.shape[0], self.H * self.W, self.ref ** 2)
-        return self._embed(x, fx, always_placeholder=False)
+        return self._embed(x, fx, always_placeholder=False, T=T)
 
     def forward(self, x, fx, T=None):
-        z = self._embed_input(x, fx)
-        if T is not None:
-            z = self._add_time(z, T)
+        z = self._embed_input(x, fx, T)
         return self._run_blocks(z)
 
     def encode(self, x, fx):

@@ -50,7 +50,5 @@ class Model(TransolverBase):
     def forward(self, x, fx, T=None):
         if self.unified_pos:      # the coordinates in `x` are ignored (only the batch size is used)
             x = self.pos.expand(x.shape[0], -1, -1, -1).reshape(x.shape[0], self.H * self.W, self.ref ** 2)
-        z = self._embed(x, fx, always_placeholder=False)
-        if T is not None:
-            z = self._add_time(z, T)
+        z = self._embed(x, fx, always_placeholder=False, T=T)
         return self._run_blocks(z)

@@ -118,18 +118,20 @@ class TransolverBase(nn.Module):
             nn.init.ones_(m.weight)
             nn.init.zeros_(m.bias)
 
-    def _embed(self, x, fx, always_placeholder):
-        if fx is not None:
-            z = self.preprocess(torch.cat((x, fx), -1))
-            return z + self.placeholder[None, None, :] if always_placeholder else z
-        return self.preprocess(x) + self.placeholder[None, None, :]
+    def _embed(self, x, fx, always_placeholder, T=None):
+        """preprocess(x [, fx]) + placeholder (without fx, or always for the irregular mesh) + time_fc(embedding of T):
+        the two broadcast adds are ONE launch (Fn.embed_bias), in the order h + placeholder, then + time vector."""
+        h = self.preprocess(x if fx is None else torch.cat((x, fx), -1))
+        placeholder = self.placeholder if (fx is None or always_placeholder) else None
+        return Fn.embed_bias(h, placeholder, None if T is None else self._time_vector(T))
 
-    def _add_time(self, z, T):
-        """T: [B,1].  The reference repeats the embedding over the N points before `time_fc`
+    def _time_vector(self, T):
+        """T: [B,1] -> [B, C].  The reference repeats the embedding over the N points before `time_fc`
         (…_2D.py:212-215); that is the same per-point linear map, so it is applied once and broadcast."""
         fc = self.time_fc
         emb = timestep_embedding(T, self.n_hidden)
-        return z + Fn.mlp(emb, None, 'silu', fc[0].weight, fc[0].bias, fc[2].weight, fc[2].bias, engine=self.engine)
+        tvec = Fn.mlp(emb, None, 'silu', fc[0].weight, fc[0].bias, fc[2].weight, fc[2].bias, engine=self.engine)
+        return tvec.reshape(T.shape[0], self.n_hidden)
 
     def set_engine(self, engine):
         """Select the GEMM engine ("f32" | "split" | "bf16" | 0 | 1 | 2 | None = environment default) for every

@@ -1072,3 +1072,92 @@ def darcy_loss_bwd(out_n, y_n, mean, std, norms, coef, dx, s):
     _lib.check(_L().pa2d_darcy_loss_bwd(_p(out_n), _p(y_n), _p(mean), _p(std), _p(norms), _p(coef), _p(dout), B, s,
                                         float(dx), _stream()), "darcy_loss_bwd")
     return dout
+
+
+def _strided_target(pred2d, y, mean, std):
+    """(B, L, element stride, batch stride) of the target `y` of a [B, L] prediction.  `y` may be any fp32 GPU view whose
+    element (b, i) lies at b * batch_stride + i * elem_stride of its storage: a contiguous [B, L], or a slice such as
+    yy[..., t:t+1] of [B, N, 4, T] (no reshape copy)."""
+    _chk(pred2d, mean, std)
+    if pred2d.dim() != 2 or not y.is_cuda or y.dtype != torch.float32 or y.shape[0] != pred2d.shape[0]:
+        raise ValueError("rel_l2_affine needs pred [B, L] and an fp32 GPU target of B samples")
+    if (mean is None) != (std is None) or (mean is not None and (mean.numel() != 1 or std.numel() != 1)):
+        raise ValueError("rel_l2_affine needs a scalar normaliser (mean and std of one element each) or none")
+    B, L = pred2d.shape
+    strides = uniform_strides(y)
+    if strides is None or y.numel() != B * L:
+        raise ValueError("the target is no uniformly strided view of L elements per sample")
+    return B, L, strides[0], strides[1]
+
+
+def uniform_strides(y):
+    """(element stride, batch stride) if sample b's elements, in row-major order of y.shape[1:], lie at
+    b * batch_stride + i * elem_stride with elem_stride >= 1; else None."""
+    es = None
+    expect = 1
+    for size, stride in zip(reversed(y.shape[1:]), reversed(y.stride()[1:])):
+        if size == 1:
+            continue
+        if es is None:
+            es = stride
+        if stride != es * expect or es < 1:
+            return None
+        expect *= size
+    return (1 if es is None else es), y.stride(0)
+
+
+def rel_l2_affine_fwd(pred2d, y, mean=None, std=None):
+    """Per-sample ||o - y|| / ||y|| of the decoded prediction o = pred std + mean and target y std + mean (mean / std:
+    one-element device tensors, None = identity).  Returns (dnorm, ynorm, ratio), each [B]."""
+    B, L, es, bs = _strided_target(pred2d, y, mean, std)
+    dn = torch.empty(B, dtype=torch.float32, device=pred2d.device)
+    yn, ratio = torch.empty_like(dn), torch.empty_like(dn)
+    nb = 4 * 2 * B * _lib.REL_L2_AFFINE_SPLIT
+    ws = _ws(nb, pred2d)
+    _lib.check(_L().pa2d_rel_l2_affine_fwd(_p(pred2d), _p(y), es, bs, _p(mean), _p(std), _p(dn), _p(yn), _p(ratio),
+                                           ws.data_ptr(), nb, B, L, _stream()), "rel_l2_affine_fwd")
+    return dn, yn, ratio
+
+
+def rel_l2_affine_bwd(pred2d, y, mean, std, dn, yn, gout):
+    """gout: per-sample upstream gradient [B].  Returns d pred [B, L]."""
+    B, L, es, bs = _strided_target(pred2d, y, mean, std)
+    _chk(dn, yn, gout)
+    if gout.numel() != B or dn.numel() != B or yn.numel() != B:
+        raise ValueError("dn, yn and gout must hold one value per sample")
+    dpred = torch.empty_like(pred2d)
+    _lib.check(_L().pa2d_rel_l2_affine_bwd(_p(pred2d), _p(y), es, bs, _p(mean), _p(std), _p(dn), _p(yn), _p(gout),
+                                           _p(dpred), B, L, _stream()), "rel_l2_affine_bwd")
+    return dpred
+
+
+def embed_bias_supported(h, placeholder, tvec):
+    """True where pa2d_embed_bias_* apply: fp32 GPU tensors, C % 4 == 0 and 16-byte aligned storage (the kernels move 16
+    bytes at a time)."""
+    ts = [t for t in (h, placeholder, tvec) if t is not None]
+    return (h.dim() == 3 and h.shape[-1] % 4 == 0
+            and all(t.is_cuda and t.dtype == torch.float32 and t.data_ptr() % 16 == 0 for t in ts))
+
+
+def embed_bias_fwd(h, placeholder=None, tvec=None, out=None):
+    """z[b, n, :] = (h[b, n, :] + placeholder[:]) + tvec[b, :]; h [B, N, C], placeholder [C], tvec [B, C] (either may be
+    None).  `out` may be h itself (in place)."""
+    _chk(h, placeholder, tvec, out)
+    B, N, C = h.shape
+    if (placeholder is not None and placeholder.numel() != C) or (tvec is not None and tuple(tvec.shape) != (B, C)):
+        raise ValueError("embed_bias needs placeholder [C] and tvec [B, C]")
+    z = torch.empty_like(h) if out is None else out
+    _lib.check(_L().pa2d_embed_bias_fwd(_p(h), _p(placeholder), _p(tvec), _p(z), B, N, C, _stream()), "embed_bias_fwd")
+    return z
+
+
+def embed_bias_bwd(dz, want_placeholder, want_tvec):
+    """dz [B, N, C] -> (dplaceholder [C] or None, dtvec [B, C] or None): the column sums, by a fixed-order reduction."""
+    _chk(dz)
+    B, N, C = dz.shape
+    dp = torch.empty(C, dtype=torch.float32, device=dz.device) if want_placeholder else None
+    dt = torch.empty(B, C, dtype=torch.float32, device=dz.device) if want_tvec else None
+    nb = 4 * _lib.EMBED_BIAS_CHUNKS * (B if want_tvec else 1) * C
+    ws = _ws(nb, dz)
+    _lib.check(_L().pa2d_embed_bias_bwd(_p(dz), _p(dp), _p(dt), ws.data_ptr(), nb, B, N, C, _stream()), "embed_bias_bwd")
+    return dp, dt

@@ -14,7 +14,8 @@ import numpy as np
 
 __all__ = ["darcy_batch", "DARCY_CONFIG", "make_config", "state_dict_spec", "synth_state_dict", "synth_state_dict_from_spec",
            "synth_ns_fields", "ns_batch",
-           "meshgrid_pos", "NS_CONFIG", "NS_SMALL_CONFIG", "TINY_CONFIG"]
+           "meshgrid_pos", "NS_CONFIG", "NS_SMALL_CONFIG", "TINY_CONFIG", "mesh_field_arrays", "elas_arrays", "plas_input",
+           "plas_output_sample"]
 
 
 def make_config(space_dim=2, n_layers=8, n_hidden=256, n_head=8, mlp_ratio=1, fun_dim=10, out_dim=1,
@@ -256,3 +257,53 @@ def darcy_batch(S, s=421, seed=0):
         u = np.real(np.fft.ifft2(np.fft.fft2(rng.standard_normal((s, s))) * (1.0 + k2 / 4.0) ** -1.5))
         sol[i] = (0.01 * u / u.std() + 0.02).ravel()
     return meshgrid_pos(S, s, s), coeff, sol
+
+
+# ------------------------------------------------------------------ stand-ins for the airfoil / pipe / elas / plas files
+def mesh_field_arrays(n, h, w, channels, channel, seed):
+    """(X, Y [n, h, w], Q [n, channels, h, w]) float32 shaped like NACA_Cylinder_{X,Y,Q}.npy (221 x 51, target channel 4) and
+    Pipe_{X,Y,Q}.npy (129 x 129, target channel 0): a smoothly deformed mesh per sample and a smooth O(1) field with a
+    non-zero mean on it in `channel`; the other channels hold other fields, so a wrong channel shows."""
+    rng = np.random.default_rng(seed)
+    i, j = np.meshgrid(np.linspace(0, 1, h, dtype=np.float32), np.linspace(0, 1, w, dtype=np.float32), indexing="ij")
+    a = rng.uniform(0.6, 1.4, (n, 1, 1)).astype(np.float32)
+    b = rng.uniform(-0.2, 0.2, (n, 1, 1)).astype(np.float32)
+    ph = rng.uniform(0, 2 * np.pi, (n, 1, 1)).astype(np.float32)
+    two_pi = np.float32(2 * np.pi)
+    X = i[None] * a + b * np.sin(two_pi * j)[None]
+    Y = j[None] * (2 - a) + b * np.cos(two_pi * i)[None]
+    q = np.sin(two_pi * (X * a + Y) + ph) + 0.5 * np.cos(two_pi * (X - Y) * a) + 0.7
+    Q = np.empty((n, channels, h, w), dtype=np.float32)
+    for c in range(channels):
+        Q[:, c] = q if c == channel else np.float32(c + 1) - q
+    return X.astype(np.float32), Y.astype(np.float32), Q
+
+
+def elas_arrays(samples, points, seed):
+    """(sigma [points, samples], XY [points, 2, samples]) float32 shaped like Random_UnitCell_{sigma,XY}_10.npy: scattered
+    points in the unit square and a smooth stress-like field O(100) on them."""
+    rng = np.random.default_rng(seed)
+    xy = rng.uniform(0, 1, (points, 2, samples))
+    a = rng.uniform(0.5, 2.0, (1, samples))
+    ph = rng.uniform(0, 2 * np.pi, (1, samples))
+    sigma = 150.0 + 80.0 * np.sin(2 * np.pi * a * xy[:, 0] + ph) * np.cos(2 * np.pi * xy[:, 1]) + 30.0 * xy[:, 0] * a
+    return sigma.astype(np.float32), xy.astype(np.float32)
+
+
+def plas_input(samples, seed, s1=101):
+    """'input' of plas_N987_T20.mat: [samples, s1] float32 die profiles."""
+    rng = np.random.default_rng(seed)
+    s = np.linspace(0, 1, s1)[None]
+    a, ph = rng.uniform(0.5, 1.5, (samples, 1)), rng.uniform(0, 2 * np.pi, (samples, 1))
+    return (a * np.sin(2 * np.pi * s + ph) + 0.5 * a + s).astype(np.float32)
+
+
+def plas_output_sample(index, seed, s1=101, s2=31, T=20):
+    """One sample of 'output' of plas_N987_T20.mat: [s1, s2, T, 4] float32 (mesh position and displacement growing with
+    time), a pure function of (seed, index) so that a few samples can be made without the other 980."""
+    rng = np.random.default_rng([seed, index])
+    i, j, t = np.meshgrid(np.linspace(0, 1, s1), np.linspace(0, 1, s2), np.linspace(0, 1, T), indexing="ij")
+    a, b, ph = rng.uniform(0.5, 1.5), rng.uniform(-0.3, 0.3), rng.uniform(0, 2 * np.pi)
+    du = a * t * np.sin(np.pi * i + ph) * (1 - j)
+    dv = b * t * np.cos(np.pi * j) * i
+    return np.stack([50.0 * i + du, 15.0 * j + dv, du, dv], axis=-1).astype(np.float32)

@@ -1,10 +1,12 @@
-"""Command line in place of the reference's exp_ns.py, ns_vorticity_unrolling.py and exp_darcy.py:
+"""Command line in place of the reference's exp_ns.py, ns_vorticity_unrolling.py, exp_darcy.py, exp_airfoil.py, exp_pipe.py,
+exp_elas.py and exp_plas.py:
 
     python -m transformerbasednavierstokesolver_amd.train --driver ns --model Transolver_Structured_Mesh_2D \\
         --n-hidden 256 --n-heads 8 --n-layers 8 --slice_num 32 --unified_pos 1 --ref 8 --batch-size 2 \\
         --data_path /data/fno --save_name ns_Transolver
 
-The flags and their defaults are the reference drivers' own, per driver (`--driver {ns,unrolled,darcy}` selects the table).
+The flags and their defaults are the reference drivers' own, per driver (`--driver {ns,unrolled,darcy,airfoil,pipe,elas,plas}`
+selects the table).
 Added: `--driver`, `--engine` (GEMM engine: f32 | split | bf16 | bf16s, default PA2D_GEMM / split), `--ntrain` / `--ntest`
 (the drivers' hard-coded module globals; exp_darcy already has --ntrain).  `--gpu` is the device index.  `--data_path` is
 honoured (exp_ns.py and ns_vorticity_unrolling.py ignore it for a hard-coded path): a `.mat` file, or the directory that
@@ -15,7 +17,14 @@ whatever --model says), the optimizer is `optim.FusedAdamW` (clip threshold --ma
 `OneCycleLR` over the whole run, the data a `data.ResidentDataset`, the loop `harness.fit_ns` / `fit_unrolled` /
 `fit_darcy` (fused Darcy loss).  The Darcy schedule spans max(500, --epochs) epochs: exp_darcy.py builds it from its module
 global `epochs = 500`, not from --epochs.  The state_dict goes to ./checkpoints/<save_name>.pt every 100 epochs and at the
-end; `--eval 1` loads it and prints the test metric (no plots)."""
+end; `--eval 1` loads it and prints the test metric (no plots).
+
+`--driver airfoil | pipe | elas | plas` (exp_airfoil.py, exp_pipe.py, exp_elas.py, exp_plas.py) have their own flag tables
+(`--downsamplex` / `--downsampley`; exp_elas has `--downsample` and `--ntrain`) and take `--data_path` as those scripts do:
+the folder of NACA_Cylinder_{X,Y,Q}.npy, the folder of Pipe_{X,Y,Q}.npy, the folder above elasticity/Meshes/, and the
+plas_N987_T20.mat file itself.  They run `harness.fit_static` / `fit_plas` with the fused decoded rel-L2 loss.  exp_elas.py
+builds its CosineAnnealingLR from an undefined global `epochs` and raises as shipped; here the schedule is
+CosineAnnealingLR(T_max=--epochs), stepped once per epoch as in that script."""
 from __future__ import annotations
 
 import argparse
@@ -23,12 +32,22 @@ import math
 import os
 import sys
 
-DRIVERS = ("ns", "unrolled", "darcy")
+DRIVERS = ("ns", "unrolled", "darcy", "airfoil", "pipe", "elas", "plas")
+STATIC_DRIVERS = ("airfoil", "pipe", "elas")
 # what differs between the three reference parsers / module globals
 _PER_DRIVER = {
     "ns": dict(epochs=30, gpu="0", downsample=1, save_name="ns_2d_UniPDE", ntrain=50, ntest=50),
     "unrolled": dict(epochs=5, gpu="0", downsample=1, save_name="ns_2d_UniPDE", ntrain=100, ntest=50),
     "darcy": dict(epochs=500, gpu="1", downsample=5, save_name="darcy_Transolver", ntrain=1000, ntest=200),
+}
+# exp_airfoil / exp_pipe / exp_elas / exp_plas: their sample counts are locals of main(), here --ntrain / --ntest
+_PER_BENCHMARK = {
+    "airfoil": dict(gpu="0", model="Transolver_2D", save_name="airfoil_Transolver", data_path="/data/fno/airfoil/naca",
+                    ntrain=1000, ntest=200),
+    "pipe": dict(gpu="0", model="Transolver_2D", save_name="pipe_UniPDE", data_path="/data/fno/pipe", ntrain=1000, ntest=200),
+    "elas": dict(gpu="1", model="Transolver_1D", save_name="elas_Transolver", data_path="/data/fno", ntrain=1000, ntest=200),
+    "plas": dict(gpu="0", model="Transolver_2D", save_name="plas_Transolver", data_path="/data/fno/plas_N987_T20.mat",
+                 ntrain=900, ntest=80),
 }
 DARCY_SCHEDULE_EPOCHS = 500
 T_IN = T = 10
@@ -38,7 +57,43 @@ NS_FILE = "NavierStokes_V1e-5_N1200_T20"
 DARCY_FILES = ("piececonst_r421_N1024_smooth1.mat", "piececonst_r421_N1024_smooth2.mat")
 
 
+def _benchmark_parser(driver):
+    d = _PER_BENCHMARK[driver]
+    p = argparse.ArgumentParser("Training Transformer")
+    p.add_argument("--lr", type=float, default=1e-3)
+    p.add_argument("--epochs", type=int, default=500)
+    p.add_argument("--weight_decay", type=float, default=1e-5)
+    p.add_argument("--model", type=str, default=d["model"])
+    p.add_argument("--n-hidden", type=int, default=64, help="hidden dim")
+    p.add_argument("--n-layers", type=int, default=3, help="layers")
+    p.add_argument("--n-heads", type=int, default=4)
+    p.add_argument("--batch-size", type=int, default=8)
+    p.add_argument("--gpu", type=str, default=d["gpu"], help="GPU index to use")
+    p.add_argument("--max_grad_norm", type=float, default=None)
+    if driver == "elas":
+        p.add_argument("--downsample", type=int, default=5)
+    else:
+        p.add_argument("--downsamplex", type=int, default=1)
+        p.add_argument("--downsampley", type=int, default=1)
+    p.add_argument("--mlp_ratio", type=int, default=1)
+    p.add_argument("--dropout", type=float, default=0.0)
+    p.add_argument("--ntrain", type=int, default=d["ntrain"])
+    p.add_argument("--unified_pos", type=int, default=0)
+    p.add_argument("--ref", type=int, default=8)
+    p.add_argument("--slice_num", type=int, default=32)
+    p.add_argument("--eval", type=int, default=0)
+    p.add_argument("--save_name", type=str, default=d["save_name"])
+    p.add_argument("--data_path", type=str, default=d["data_path"])
+    # not in the reference (--ntrain is exp_elas's only)
+    p.add_argument("--driver", choices=DRIVERS, default=driver)
+    p.add_argument("--engine", type=str, default=None, help="GEMM engine: f32 | split | bf16 | bf16s")
+    p.add_argument("--ntest", type=int, default=d["ntest"])
+    return p
+
+
 def build_parser(driver):
+    if driver in _PER_BENCHMARK:
+        return _benchmark_parser(driver)
     d = _PER_DRIVER[driver]
     p = argparse.ArgumentParser("Training Transolver" if driver == "darcy" else "Training Transformer")
     p.add_argument("--lr", type=float, default=1e-3)
@@ -187,8 +242,91 @@ def run_darcy(args):
                              save_path=_checkpoint(args), fused=True, grad_sync=opt.sync, on_epoch=line)
 
 
+def _load_static(args):
+    from . import data
+    if args.driver == "airfoil":
+        return data.load_airfoil_npy(args.data_path, args.ntrain, args.ntest, args.downsamplex, args.downsampley)
+    if args.driver == "pipe":
+        return data.load_pipe_npy(args.data_path, args.ntrain, args.ntest, args.downsamplex, args.downsampley)
+    return data.load_elas_npy(args.data_path, args.ntrain, args.ntest)
+
+
+def run_static(args):
+    """exp_airfoil / exp_pipe / exp_elas: fun_dim = 0 (the placeholder path), one model(x, None) call per batch."""
+    import torch
+    from . import harness, model_dict
+    from .optim import FusedAdamW
+    from .utils.testloss import FusedTestLoss
+    dev = _device(args)
+    d = _load_static(args)
+    kw = dict(space_dim=2, n_layers=args.n_layers, n_hidden=args.n_hidden, dropout=args.dropout, n_head=args.n_heads,
+              Time_Input=False, mlp_ratio=args.mlp_ratio, fun_dim=0, out_dim=1, slice_num=args.slice_num, ref=args.ref,
+              unified_pos=args.unified_pos)
+    if args.driver != "elas":                       # the irregular-mesh model has no H / W
+        kw.update(H=d["s1"], W=d["s2"])
+    model = model_dict.get_model(args).Model(**kw).to(dev)
+    if args.engine is not None:
+        model.set_engine(args.engine)
+    print(args)
+    print(f"Total Trainable Params: {sum(p.numel() for p in model.parameters() if p.requires_grad)}")
+    loss_fn = FusedTestLoss(size_average=False)
+    err_line = "rel_err : {}" if args.driver == "elas" else "rel_err:{}"
+    if args.eval:
+        model.load_state_dict(torch.load(_checkpoint(args), map_location=dev, weights_only=True), strict=True)
+        m = harness.evaluate_static(model, d, args.batch_size, loss_fn)
+        print(err_line.format(m["rel_err"]))
+        return m
+    per_epoch = args.driver == "elas"
+    if per_epoch:       # exp_elas.py:102 reads an undefined global `epochs`; T_max = --epochs is the evident intent
+        opt = FusedAdamW(model.parameters(), lr=args.lr, weight_decay=args.weight_decay, max_grad_norm=args.max_grad_norm)
+        sched = torch.optim.lr_scheduler.CosineAnnealingLR(opt, T_max=args.epochs)
+    else:
+        opt, sched = _optim(args, model, math.ceil(args.ntrain / args.batch_size), args.epochs, args.max_grad_norm)
+
+    def line(ep, m):
+        print("Epoch {} Train loss : {:.5f}".format(ep, m["train_loss"]))
+        print(err_line.format(m["rel_err"]), flush=True)
+
+    return harness.fit_static(model, opt, sched, d, epochs=args.epochs, batch_size=args.batch_size, loss_fn=loss_fn,
+                              save_path=_checkpoint(args), scheduler_per_epoch=per_epoch, grad_sync=opt.sync, on_epoch=line)
+
+
+def run_plas(args):
+    """exp_plas: Time_Input, fun_dim = 1, out_dim = 4 on the 101 x 31 mesh; T = 20 calls and optimizer steps per batch."""
+    import torch
+    from . import data, harness, model_dict
+    from .utils.testloss import FusedTestLoss
+    dev = _device(args)
+    d = data.load_plas_mat(args.data_path, args.ntrain, args.ntest)
+    model = model_dict.get_model(args).Model(
+        space_dim=2, n_hidden=args.n_hidden, n_layers=args.n_layers, Time_Input=True, n_head=args.n_heads, fun_dim=1,
+        out_dim=data.PLAS_DEFORMATION, mlp_ratio=args.mlp_ratio, slice_num=args.slice_num, unified_pos=args.unified_pos,
+        H=d["s1"], W=d["s2"]).to(dev)
+    if args.engine is not None:
+        model.set_engine(args.engine)
+    print(args)
+    print(f"Total Trainable Params: {sum(p.numel() for p in model.parameters() if p.requires_grad)}")
+    loss_fn = FusedTestLoss(size_average=False)
+    if args.eval:
+        # exp_plas.py:169 loads with strict=False; a checkpoint of this model has every key, so strict stays on
+        model.load_state_dict(torch.load(_checkpoint(args), map_location=dev, weights_only=True), strict=True)
+        m = harness.evaluate_plas(model, d, args.batch_size, loss_fn)
+        print("test_step_loss:{:.5f} , test_full_loss:{:.5f}".format(m["test_step"], m["test_full"]))
+        return m
+    opt, sched = _optim(args, model, math.ceil(args.ntrain / args.batch_size), args.epochs, args.max_grad_norm)
+    return harness.fit_plas(
+        model, opt, sched, d, epochs=args.epochs, batch_size=args.batch_size, loss_fn=loss_fn, save_path=_checkpoint(args),
+        grad_sync=opt.sync,
+        on_epoch=lambda ep, m: print("Epoch {} , train_step_loss:{:.5f} , test_step_loss:{:.5f} , test_full_loss:{:.5f}".format(
+            ep, m["train_step"], m["test_step"], m["test_full"]), flush=True))
+
+
 def main(argv=None):
     args = parse_args(argv)
+    if args.driver in STATIC_DRIVERS:
+        return run_static(args)
+    if args.driver == "plas":
+        return run_plas(args)
     if args.driver == "darcy":
         return run_darcy(args)
     return run_ns(args, unrolled=args.driver == "unrolled")
