@@ -31,12 +31,14 @@ __device__ __forceinline__ unsigned img_off(int row, int ch) {       // byte off
 // F32SRC: plain dW = A^T . B of a linear layer straight from the fp32 operands (no tap shift): each thread loads the 8
 // floats of its (row, 8-column piece) of both operands, splits them into the NT bf16 planes in registers and writes the
 // same LDS plane images; the column sums of A (the bias gradient) are accumulated from the registers of column tile 0.
-template <int NT, int KS, bool F32SRC = false>
+// MF16 (F32SRC, NT = 3, PA2D_MC_MFMA=16): v_mfma_f32_16x16x32_bf16 on 32-row K-steps read from two of THREE 16-row LDS slots
+// (3 x 24 KB, still two workgroups per CU); the pipeline is the one of gemm_mc_planes_big_kernel's MF16 form below.
+template <int NT, int KS, bool F32SRC = false, bool MF16 = false>
 __global__ __launch_bounds__(256, 2) void gemm_mc_planes_kernel(const MCPlanesParams p) {
     constexpr int PIMG = 4096;                       // one plane image of one K-step: 16 rows x 256 B
     constexpr int STAGE = 2 * NT * KS * PIMG;        // A planes then B planes, KS sub-images each
     constexpr int NP = 2 * NT * KS;                  // 16-byte pieces per thread and stage
-    __shared__ __attribute__((aligned(16))) unsigned char smem[2 * STAGE];
+    __shared__ __attribute__((aligned(16))) unsigned char smem[(MF16 ? 3 : 2) * STAGE];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int tiles_i = (p.Mi + 127) / 128, tiles_j = (p.Nj + 127) / 128;
@@ -148,6 +150,148 @@ __global__ __launch_bounds__(256, 2) void gemm_mc_planes_kernel(const MCPlanesPa
             *reinterpret_cast<u32x4*>(smem + (buf_) * STAGE + s_lds[s]) = rg[s];                          \
     }
     const bool do_cs = F32SRC && p.colsum != nullptr && tj == 0;
+
+    if constexpr (MF16) {
+        // see gemm_mc_planes_big_kernel: lane groups 0 / 1 read rows 0-7 / 8-15 of the step's first slot, groups 2 / 3 of its
+        // second; B (the layer input) is the MFMA's A operand, so an accumulator quad is four consecutive columns of dW
+        static_assert(NT == 3 && KS == 1 && F32SRC, "the 16x16x32 form is written for the split engine's linear weight gradient");
+        f32x4 acc[4][4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        const int kq = lane >> 4, q4 = (lane & 15) >> 2, pq = lane & 3;
+        unsigned fa[2], fb[2];                            // 16-column tile 0 of the wave; tile t is `^ (t << 5)`
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const int row = 8 * (kq & 1) + 4 * r + q4;
+            fa[r] = img_off(row, wm * 8 + (pq >> 1)) + 8u * (pq & 1);
+            fb[r] = img_off(row, wn * 8 + (pq >> 1)) + 8u * (pq & 1);
+        }
+        typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+#define MP16_FRAG(base_, t_, pl_)                                                                         \
+    __builtin_bit_cast(bf16x8, __builtin_shufflevector(                                                   \
+        __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(smem + ((base_[0] ^ ((unsigned)(t_) << 5)) + (pl_) * PIMG))), \
+        __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(smem + ((base_[1] ^ ((unsigned)(t_) << 5)) + (pl_) * PIMG))), \
+        0, 1, 2, 3, 4, 5, 6, 7))
+#define MP16_MMA(ib_, AF)                                                                                 \
+    _Pragma("unroll") for (int j = 0; j < 4; ++j) {       /* smallest terms first; (A plane, B plane) as the 32x32x16 form */ \
+        acc[ib_][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xf[j][1], AF[1], acc[ib_][j], 0, 0, 0);     \
+        acc[ib_][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xf[j][0], AF[2], acc[ib_][j], 0, 0, 0);     \
+        acc[ib_][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xf[j][2], AF[0], acc[ib_][j], 0, 0, 0);     \
+        acc[ib_][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xf[j][0], AF[1], acc[ib_][j], 0, 0, 0);     \
+        acc[ib_][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xf[j][1], AF[0], acc[ib_][j], 0, 0, 0);     \
+        acc[ib_][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xf[j][0], AF[0], acc[ib_][j], 0, 0, 0);     \
+    }
+        // staging in two parts: MP16_CONVERT splits the fp32 registers into the bf16 planes (and adds to the column sums) while
+        // the other waves still multiply, MP16_WRITE is the six 16-byte LDS stores alone -> only those sit between the barriers
+        bf16x8 pk[2][NT];
+#define MP16_CONVERT()                                                                                    \
+    _Pragma("unroll") for (int op = 0; op < 2; ++op) {                                                    \
+        const u32x4 u0_ = rg[op * 2], u1_ = rg[op * 2 + 1];                                               \
+        const float4 v0_ = make_float4(__uint_as_float(u0_.x), __uint_as_float(u0_.y), __uint_as_float(u0_.z), __uint_as_float(u0_.w)); \
+        const float4 v1_ = make_float4(__uint_as_float(u1_.x), __uint_as_float(u1_.y), __uint_as_float(u1_.z), __uint_as_float(u1_.w)); \
+        if (op == 0 && do_cs) {                                                                           \
+            cs[0] += v0_.x; cs[1] += v0_.y; cs[2] += v0_.z; cs[3] += v0_.w;                               \
+            cs[4] += v1_.x; cs[5] += v1_.y; cs[6] += v1_.z; cs[7] += v1_.w;                               \
+        }                                                                                                 \
+        bf16x4 h0_, m0_, l0_, h1_, m1_, l1_;                                                              \
+        split3(v0_, h0_, m0_, l0_);                                                                       \
+        split3(v1_, h1_, m1_, l1_);                                                                       \
+        pk[op][0] = __builtin_shufflevector(h0_, h1_, 0, 1, 2, 3, 4, 5, 6, 7);                            \
+        pk[op][1] = __builtin_shufflevector(m0_, m1_, 0, 1, 2, 3, 4, 5, 6, 7);                            \
+        pk[op][2] = __builtin_shufflevector(l0_, l1_, 0, 1, 2, 3, 4, 5, 6, 7);                            \
+    }
+#define MP16_WRITE(buf_)                                                                                  \
+    _Pragma("unroll") for (int op = 0; op < 2; ++op) _Pragma("unroll") for (int pl = 0; pl < NT; ++pl)    \
+        *reinterpret_cast<bf16x8*>(smem + (buf_) * STAGE + flds + (op * NT + pl) * PIMG) = pk[op][pl];
+        const int nst = c_end - c_begin, steps = (nst + 1) >> 1;
+        if (nst > 0) {
+            MP_LOAD(c_begin)
+            MP16_CONVERT()
+            MP16_WRITE(0)
+            MP_LOAD(c_begin + 1)
+            MP16_CONVERT()
+            MP16_WRITE(1)
+            if (steps > 1) { MP_LOAD(c_begin + 2) }
+        }
+        __syncthreads();
+        // step k (stages 2k, 2k+1 in slots P, Q; R free; the registers hold stage 2k+2 in flight): tile 0 | convert and write
+        // stage 2k+2 to R, load 2k+3 | tiles 1, 2 | convert 2k+3, load 2k+4 | barrier | write P | tile 3 | barrier: every load
+        // has half a step to land, as in the 32x32x16 form.  Each stage is converted exactly once (column sums).
+        int sp = 0, sq = 1, sr = 2;
+        for (int k = 0; k < steps; ++k) {
+            const bool has_next = k + 1 < steps;          // workgroup-uniform
+            const unsigned lo = (unsigned)((kq >> 1) ? sq : sp) * (unsigned)STAGE;     // this lane group's slot (a multiple of 4 KB)
+            const unsigned ua[2] = {fa[0] + lo, fa[1] + lo};
+            const unsigned ub[2] = {fb[0] + lo + NT * PIMG, fb[1] + lo + NT * PIMG};
+            bf16x8 xf[4][NT];
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int pl = 0; pl < NT; ++pl) xf[j][pl] = MP16_FRAG(ub, j, pl);
+            bf16x8 afc[NT], afn[NT];                      // A fragments one 16-row tile ahead of their MFMAs
+#pragma unroll
+            for (int pl = 0; pl < NT; ++pl) afc[pl] = MP16_FRAG(ua, 0, pl);
+#pragma unroll
+            for (int ib = 0; ib < 4; ++ib) {
+                if (ib < 3) {
+#pragma unroll
+                    for (int pl = 0; pl < NT; ++pl) afn[pl] = MP16_FRAG(ua, ib + 1, pl);
+                }
+                if (ib == 1 && has_next) {
+                    MP16_CONVERT()
+                    MP16_WRITE(sr)
+                    MP_LOAD(c_begin + 2 * k + 3)
+                }
+                if (ib == 3) {       // every LDS read of the step is done: P is free; the last tile's MFMAs cover its refill
+                    if (has_next) {
+                        MP16_CONVERT()
+                        if (k + 2 < steps) { MP_LOAD(c_begin + 2 * k + 4) }
+                    }
+                    __syncthreads();
+                    if (has_next) { MP16_WRITE(sp) }
+                }
+                MP16_MMA(ib, afc)
+#pragma unroll
+                for (int pl = 0; pl < NT; ++pl) afc[pl] = afn[pl];
+            }
+            __syncthreads();
+            const int t = sp;
+            sp = sr;
+            sr = sq;
+            sq = t;
+        }
+#undef MP16_CONVERT
+#undef MP16_WRITE
+#undef MP16_MMA
+#undef MP16_FRAG
+        if (do_cs) {       // as below: LDS is free after the last barrier
+            float* sm = reinterpret_cast<float*>(smem);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) sm[frow * 128 + fc8 * 8 + e] = cs[e];
+            __syncthreads();
+            if (tid < 128) {
+                float t = 0.f;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) t += sm[r * 128 + tid];
+                if (ti * 128 + tid < p.Mi) p.colsum[(size_t)split * p.Mi + ti * 128 + tid] = t;
+            }
+        }
+        // accumulator quad r = 0..3 of lane l: dW row ti*128 + wm*64 + ib*16 + (l & 15), columns tj*128 + wn*64 + j*16 +
+        // 4*(l >> 4) + r (Nj % 4 == 0, checked by the launcher: a quad is inside or outside as a whole)
+        float* out = p.slab + (size_t)split * p.Mi * p.Nj;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int col = tj * 128 + wn * 64 + j * 16 + 4 * kq;
+#pragma unroll
+            for (int ib = 0; ib < 4; ++ib) {
+                const int row = ti * 128 + wm * 64 + ib * 16 + (lane & 15);
+                if (row < p.Mi && col < p.Nj) *reinterpret_cast<f32x4*>(out + (size_t)row * p.Nj + col) = acc[ib][j];
+            }
+        }
+        return;
+    }
 
     f32x16 acc[2][2];
 #pragma unroll
@@ -276,7 +420,9 @@ int launch_mc_planes(const void* PA, const void* PB, int C, int Cin, int Mk, int
 // workgroup per CU.  The launch is ONE round of <= 256 workgroups (tiles x splits); workgroups are numbered so that each
 // XCD (blockIdx & 7) owns a contiguous range of (split, i-tile, j-tile): the 9+ workgroups that re-read the same dOut
 // rows and the same X rows (at different tap shifts) sit behind one L2.
-template <int NT, int KS>
+// MF16 (NT = 3; PA2D_MC_MFMA=32 turns it off): v_mfma_f32_16x16x32_bf16 on 32-row K-steps read from two of THREE 16-row LDS slots (144 KB);
+// same tile, plane images, transposed reads and bytes per MAC (see the branch below).
+template <int NT, int KS, bool MF16 = false>
 __global__ __launch_bounds__(512, 1) void gemm_mc_planes_big_kernel(const MCPlanesParams p, const int per_xcd) {
     constexpr int PIMG = 8192;                       // one plane image of one K-step: 16 rows x 512 B (256 bf16 columns)
     constexpr int STAGE = 2 * NT * KS * PIMG;        // dOut planes then X planes
@@ -347,6 +493,116 @@ __global__ __launch_bounds__(512, 1) void gemm_mc_planes_big_kernel(const MCPlan
         const int n0 = (c_begin * 16 + row16) % HW;
         ly = n0 / p.W;
         lx = n0 - ly * p.W;
+    }
+
+    if constexpr (MF16) {
+        // v_mfma_f32_16x16x32_bf16 on REAL 32-row K-steps: LDS holds THREE 16-row slots (3 x 48 KB), a K-step reads two of
+        // them.  Lane group kq = lane>>4 of a 16x16x32 operand holds k = 8kq .. 8kq+7, so groups 0 / 1 take rows 0-7 / 8-15
+        // of the step's first slot and groups 2 / 3 the same rows of its second slot: the same two transposed reads per
+        // fragment and the same bytes per MAC as the 32x32x16 form, no duplicated data.  X is the A operand (rows = columns
+        // j of dW), so a lane's accumulator quad is four consecutive j of one dOut channel: 16-byte stores.
+        // Pipeline of step k (stages 2k, 2k+1 in slots P, Q; slot R free; the register set holds stage 2k+2 in flight):
+        //   MFMAs of dOut tiles 0-3 | store the registers to R, load stage 2k+3 | tiles 4-6, tile 7's fragments | barrier |
+        //   store the registers to P, load stage 2k+4 | MFMAs of tile 7 | barrier;  next step: (R, P), Q free.
+        // A split with an odd chunk count ends on a half-empty step: the rows past c_end load as zeros (MB_LOAD).
+        static_assert(NT == 3 && KS == 1, "the 16x16x32 form is written for the split engine");
+        f32x4 acc[8][4];
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        const int kq = lane >> 4, q4 = (lane & 15) >> 2, pq = lane & 3;
+        // byte offset of this lane's address in a plane image for 16-column tile 0 of the wave; tile t is `^ (t << 5)`:
+        // the tile index sits in chunk bits 1..3, which the row swizzle XORs and nothing else touches
+        unsigned fa[2], fb[2];
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const int row = 8 * (kq & 1) + 4 * r + q4;
+            const unsigned swz = (unsigned)(((row & 3) << 2) | ((row >> 2) & 3));
+            fa[r] = 512u * row + 16u * ((unsigned)(wm * 16 + (pq >> 1)) ^ swz) + 8u * (pq & 1);
+            fb[r] = 512u * row + 16u * ((unsigned)(wn * 8 + (pq >> 1)) ^ swz) + 8u * (pq & 1);
+        }
+        typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+#define MB16_FRAG(base_, t_, pl_)                                                                         \
+    __builtin_bit_cast(bf16x8, __builtin_shufflevector(                                                   \
+        __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(smem + ((base_[0] ^ ((unsigned)(t_) << 5)) + (pl_) * PIMG))), \
+        __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(smem + ((base_[1] ^ ((unsigned)(t_) << 5)) + (pl_) * PIMG))), \
+        0, 1, 2, 3, 4, 5, 6, 7))
+#define MB16_MMA(ib_, AF)                                                                                 \
+    _Pragma("unroll") for (int j = 0; j < 4; ++j) {       /* smallest terms first; (dOut plane, X plane) as the 32x32x16 form */ \
+        acc[ib_][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xf[j][1], AF[1], acc[ib_][j], 0, 0, 0);     \
+        acc[ib_][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xf[j][0], AF[2], acc[ib_][j], 0, 0, 0);     \
+        acc[ib_][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xf[j][2], AF[0], acc[ib_][j], 0, 0, 0);     \
+        acc[ib_][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xf[j][0], AF[1], acc[ib_][j], 0, 0, 0);     \
+        acc[ib_][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xf[j][1], AF[0], acc[ib_][j], 0, 0, 0);     \
+        acc[ib_][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xf[j][0], AF[0], acc[ib_][j], 0, 0, 0);     \
+    }
+        const int nst = c_end - c_begin, steps = (nst + 1) >> 1;
+        if (nst > 0) {
+            MB_LOAD(c_begin, rg0)
+            MB_STORE(0, rg0)
+            MB_LOAD(c_begin + 1, rg0)
+            MB_STORE(1, rg0)
+            if (steps > 1) MB_LOAD(c_begin + 2, rg0)
+        }
+        __syncthreads();
+        int sp = 0, sq = 1, sr = 2;
+        for (int k = 0; k < steps; ++k) {
+            const unsigned lo = (unsigned)((kq >> 1) ? sq : sp) * (unsigned)STAGE;     // this lane group's slot
+            // slot offsets are multiples of 8 KB: adding them first commutes with the tile XOR of bits 5..7
+            const unsigned ua[2] = {fa[0] + lo, fa[1] + lo};
+            const unsigned ub[2] = {fb[0] + lo + NT * PIMG, fb[1] + lo + NT * PIMG};
+            bf16x8 xf[4][NT];
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int pl = 0; pl < NT; ++pl) xf[j][pl] = MB16_FRAG(ub, j, pl);
+            // dOut fragments one 16-row tile ahead of their MFMAs.  Stores and loads past the last step are harmless (free
+            // slots, out-of-range offsets) and keep the loop body free of branches.
+            bf16x8 afc[NT], afn[NT];
+#pragma unroll
+            for (int pl = 0; pl < NT; ++pl) afc[pl] = MB16_FRAG(ua, 0, pl);
+#pragma unroll
+            for (int ib = 0; ib < 8; ++ib) {
+                if (ib < 7) {
+#pragma unroll
+                    for (int pl = 0; pl < NT; ++pl) afn[pl] = MB16_FRAG(ua, ib + 1, pl);
+                }
+                if (ib == 4) {
+                    MB_STORE(sr, rg0)
+                    MB_LOAD(c_begin + 2 * k + 3, rg0)
+                }
+                if (ib == 7) {       // every LDS read of the step is done: P is free; the last tile's MFMAs cover its refill
+                    __syncthreads();
+                    MB_STORE(sp, rg0)
+                    MB_LOAD(c_begin + 2 * k + 4, rg0)
+                }
+                MB16_MMA(ib, afc)
+#pragma unroll
+                for (int pl = 0; pl < NT; ++pl) afc[pl] = afn[pl];
+            }
+            __syncthreads();
+            const int t = sp;
+            sp = sr;
+            sr = sq;
+            sq = t;
+        }
+#undef MB16_MMA
+#undef MB16_FRAG
+        // accumulator quad r = 0..3 of lane l: dW row (dOut channel) ti*256 + wm*128 + ib*16 + (l & 15), columns
+        // tj*256 + wn*64 + j*16 + 4*(l >> 4) + r (Nj % 32 == 0: a quad is inside or outside as a whole)
+        float* out = p.slab + (size_t)split * p.Mi * p.Nj;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int col = tj * 256 + wn * 64 + j * 16 + 4 * kq;
+            if (col >= p.Nj) continue;
+#pragma unroll
+            for (int ib = 0; ib < 8; ++ib) {
+                const int row = ti * 256 + wm * 128 + ib * 16 + (lane & 15);
+                if (row < p.Mi) *reinterpret_cast<f32x4*>(out + (size_t)row * p.Nj + col) = acc[ib][j];
+            }
+        }
+        return;
     }
 
     f32x16 acc[4][2];
@@ -490,7 +746,16 @@ int launch_mc_planes_big_raw(const void* PA, int Mi, const void* PB, int Cin, in
     const int per_xcd = ceil_div(wgs, 8);
     const dim3 grid(per_xcd * 8);
     // the LDS attribute is set on every launch: it is per device and the call is cheap
-    if (NT == 3) {
+    // 16x16x32 form (default; PA2D_MC_MFMA=32 goes back): 16-byte stores of accumulator quads need an aligned slab
+    if (NT == 3 && pa2d_env().mc_mfma16 && (reinterpret_cast<uintptr_t>(slab) & 15) == 0) {
+        const int smem = 3 * 2 * 3 * 1 * 8192;      // three 16-row slots
+        {
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_mc_planes_big_kernel<3, 1, true>),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+            if (e != hipSuccess) return (int)e;
+        }
+        hipLaunchKernelGGL((gemm_mc_planes_big_kernel<3, 1, true>), grid, dim3(512), smem, st, p, per_xcd);
+    } else if (NT == 3) {
         const int smem = 2 * 2 * 3 * 1 * 8192;
         {
             hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_mc_planes_big_kernel<3, 1>),
@@ -528,7 +793,12 @@ int launch_mc_f32src(const float* A, long long lda, int Mi, const float* B, long
     if (ab >= 0xFFFFFFF0ull || bb >= 0xFFFFFFF0ull) return PA2D_ERR_UNSUPPORTED;
     p.a_bytes = (unsigned)ab; p.b_bytes = (unsigned)bb;
     const dim3 grid(ceil_div(Mi, 128) * ceil_div(Nj, 128) * pl.splits);
-    if (NT == 3) hipLaunchKernelGGL((gemm_mc_planes_kernel<3, 1, true>), grid, dim3(256), 0, st, p);
+    // 16x16x32 form (default; PA2D_MC_MFMA=32 goes back).  Its three LDS slots allow two workgroups per CU where the 32x32x16
+    // form runs three and the kernel alone is ~10 % slower, but the step is faster with it (the chip is power-
+    // limited and the kernels that follow hold a higher clock)
+    if (NT == 3 && pa2d_env().mc_mfma16 && (Nj % 4) == 0 && (reinterpret_cast<uintptr_t>(slab) & 15) == 0)
+        hipLaunchKernelGGL((gemm_mc_planes_kernel<3, 1, true, true>), grid, dim3(256), 0, st, p);
+    else if (NT == 3) hipLaunchKernelGGL((gemm_mc_planes_kernel<3, 1, true>), grid, dim3(256), 0, st, p);
     else hipLaunchKernelGGL((gemm_mc_planes_kernel<1, 4, true>), grid, dim3(256), 0, st, p);
     PA2D_CHECK_LAUNCH();
     return PA2D_OK;
