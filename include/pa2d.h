@@ -391,6 +391,17 @@ int pa2d_sumsq(const float* g, long long n, float* out, void* ws, size_t ws_byte
 int pa2d_adamw_step(float* p, const float* g, float* m, float* v, long long n, double lr, double beta1,
                     double beta2, double eps, double weight_decay, int step_index, const float* gnorm_sq,
                     float max_norm, pa2d_stream_t stream);
+/* the values the AdamW kernel uses at one step, as one 32-byte row: out[8] = (lr / bias1, 1 - lr * weight_decay,
+ * 1 - beta1, beta2, 1 - beta2, sqrt(bias2), eps, max_norm), each evaluated in double and rounded to float once.
+ * HOST only (no stream, `out` is host memory); pa2d_adamw_step fills its kernel argument with it.
+ * step_index < 1 or out == NULL: PA2D_ERR_ARG */
+int pa2d_adamw_coefficients(double lr, double beta1, double beta2, double eps, double weight_decay, int step_index,
+                            float max_norm, float* out);
+/* pa2d_adamw_step with that row read from DEVICE memory (coef_dev: 8 floats, 16-byte aligned, PA2D_ERR_ARG otherwise;
+ * written by an earlier operation of the same stream).  Same per-element arithmetic as pa2d_adamw_step (one device
+ * function): equal results bit for bit.  No host work depends on the step, so the launch can sit in a hipGraph. */
+int pa2d_adamw_step_dev(float* p, const float* g, float* m, float* v, long long n, const float* coef_dev,
+                        const float* gnorm_sq, pa2d_stream_t stream);
 /* per-sample ||pred-y||, ||y|| and their ratio (utils/testloss.py:31-42), and the gradient w.r.t. pred:
  * dpred[b] = gout[b] * (pred_b - y_b) / (dnorm_b * ynorm_b); gout is the per-sample upstream gradient [B];
  * a sample with dnorm_b == 0 gets the zero sub-gradient (as torch.norm's backward), never inf/NaN */

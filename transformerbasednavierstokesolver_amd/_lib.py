@@ -104,6 +104,8 @@ SIGNATURES = {
     "pa2d_sumsq": (_i, [_f, _ll, _f, _f, _sz, _st]),
     "pa2d_adamw_step": (_i, [_f, _f, _f, _f, _ll, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _i, _f,
                              C.c_float, _st]),
+    "pa2d_adamw_coefficients": (_i, [C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _i, C.c_float, _f]),
+    "pa2d_adamw_step_dev": (_i, [_f, _f, _f, _f, _ll, _f, _f, _st]),
     "pa2d_rel_l2_fwd": (_i, [_f, _f, _f, _f, _f, _i, _ll, _st]),
     "pa2d_rel_l2_bwd": (_i, [_f, _f, _f, _f, _f, _f, _i, _ll, _st]),
     "pa2d_darcy_loss_workspace": (_sz, [_i, _i]),

@@ -1,10 +1,11 @@
 // the optimizer / loss side of one exp_ns iteration (exp_ns.py:198-218,
 // utils/testloss.py:31-42) over the SAME flat fp32 buffers the DDP gradient bucket uses:
 //   * pa2d_sumsq            : sum of squares of the flat gradient (for clip_grad_norm_, exp_ns.py:215-216)
-//   * pa2d_adamw_step       : one multi-tensor AdamW update (decoupled weight decay, bias correction) of
+//   * pa2d_adamw_step[_dev] : one multi-tensor AdamW update (decoupled weight decay, bias correction) of
 //                             the whole flat parameter buffer in ONE launch; lr and beta1 are the values
 //                             OneCycleLR computed for this step; the clip coefficient
-//                             min(1, max_norm / (||g|| + 1e-6)) is applied on the fly
+//                             min(1, max_norm / (||g|| + 1e-6)) is applied on the fly; _dev reads the
+//                             step's coefficients (pa2d_adamw_coefficients) from device memory
 //   * pa2d_rel_l2_fwd / bwd : sum_b ||pred_b - y_b||_2 / ||y_b||_2 and its gradient
 // All HBM-bound streaming kernels (16-byte accesses, wave-shuffle + LDS block reductions, second
 // deterministic pass instead of float atomics).
@@ -37,34 +38,36 @@ __global__ __launch_bounds__(256) void sumsq_partial_kernel(const float* __restr
     if (threadIdx.x == 0) partial[blockIdx.x] = t;
 }
 
-struct AdamParams {
-    float* p; const float* g; float* m; float* v;
-    long long n;
-    float lr, beta1, beta2, eps, step, decay, bias2_sqrt, max_norm, omb1, omb2;   // omb = 1 - beta, rounded from double
-    const float* gnorm_sq;   // device scalar (sum of squares of g) or null
+// The per-step coefficients, in the order pa2d_adamw_coefficients writes them: one 32-byte row.  pa2d_adamw_step passes the
+// row as a kernel argument, pa2d_adamw_step_dev reads it from device memory (a captured launch then never holds a
+// host scalar of the step).
+struct AdamCoef {
+    float step, decay, omb1, beta2, omb2, bias2_sqrt, eps, max_norm;   // lr/bias1, 1 - lr*wd, 1-beta1, ., 1-beta2, ...
 };
 
 // torch.optim.AdamW (foreach path) arithmetic: p *= 1 - lr*wd ; m = lerp(m, g, 1-b1) ; v = b2*v + (1-b2) g^2 ;
 // p -= (lr/bias1) * m / (sqrt(v)/sqrt(bias2) + eps)
-__global__ __launch_bounds__(256) void adamw_kernel(const AdamParams a) {
+// ONE body for both entry points: the same expressions contract to the same FMAs, so their results are equal bit for bit.
+__device__ __forceinline__ void adamw_body(float* ap, const float* ag, float* am, float* av, const long long n,
+                                           const AdamCoef c, const float* gnorm_sq) {
     float coef = 1.f;
-    if (a.gnorm_sq && a.max_norm > 0.f) {
-        const float c = a.max_norm / (sqrtf(*a.gnorm_sq) + 1e-6f);
-        coef = c < 1.f ? c : 1.f;
+    if (gnorm_sq && c.max_norm > 0.f) {
+        const float q = c.max_norm / (sqrtf(*gnorm_sq) + 1e-6f);
+        coef = q < 1.f ? q : 1.f;
     }
-    const float step = a.step, decay = a.decay, omb1 = a.omb1, omb2 = a.omb2;
-    const long long n4 = a.n >> 2;
-    float4* p4 = reinterpret_cast<float4*>(a.p);
-    const float4* g4 = reinterpret_cast<const float4*>(a.g);
-    float4* m4 = reinterpret_cast<float4*>(a.m);
-    float4* v4 = reinterpret_cast<float4*>(a.v);
+    const float step = c.step, decay = c.decay, omb1 = c.omb1, omb2 = c.omb2;
+    const long long n4 = n >> 2;
+    float4* p4 = reinterpret_cast<float4*>(ap);
+    const float4* g4 = reinterpret_cast<const float4*>(ag);
+    float4* m4 = reinterpret_cast<float4*>(am);
+    float4* v4 = reinterpret_cast<float4*>(av);
 #define ADAM1(P, G, M, V)                                        \
     {                                                            \
         const float g_ = (G) * coef;                             \
         (P) *= decay;                                            \
         (M) += omb1 * (g_ - (M));                                \
-        (V) = a.beta2 * (V) + omb2 * g_ * g_;                    \
-        (P) -= step * (M) / (sqrtf(V) / a.bias2_sqrt + a.eps);   \
+        (V) = c.beta2 * (V) + omb2 * g_ * g_;                    \
+        (P) -= step * (M) / (sqrtf(V) / c.bias2_sqrt + c.eps);   \
     }
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
         float4 p = p4[i], m = m4[i], v = v4[i];
@@ -73,8 +76,25 @@ __global__ __launch_bounds__(256) void adamw_kernel(const AdamParams a) {
         p4[i] = p; m4[i] = m; v4[i] = v;
     }
     if (blockIdx.x == 0)
-        for (long long i = (n4 << 2) + threadIdx.x; i < a.n; i += 256) ADAM1(a.p[i], a.g[i], a.m[i], a.v[i])
+        for (long long i = (n4 << 2) + threadIdx.x; i < n; i += 256) ADAM1(ap[i], ag[i], am[i], av[i])
 #undef ADAM1
+}
+
+struct AdamParams {
+    float* p; const float* g; float* m; float* v;
+    long long n;
+    AdamCoef c;
+    const float* gnorm_sq;   // device scalar (sum of squares of g) or null
+};
+
+__global__ __launch_bounds__(256) void adamw_kernel(const AdamParams a) {
+    adamw_body(a.p, a.g, a.m, a.v, a.n, a.c, a.gnorm_sq);
+}
+
+// the row comes from device memory: two 16-byte loads, uniform over the grid
+__global__ __launch_bounds__(256) void adamw_dev_kernel(float* p, const float* g, float* m, float* v, const long long n,
+                                                        const AdamCoef* row, const float* gnorm_sq) {
+    adamw_body(p, g, m, v, n, *row, gnorm_sq);
 }
 
 // one workgroup per sample: d = ||pred-y||, yn = ||y||, ratio = d / yn
@@ -135,23 +155,52 @@ int pa2d_sumsq(const float* g, long long n, float* out, void* ws, size_t ws_byte
     return pa2d_launch_reduce((const float*)ws, nb, 1, out, st);
 }
 
+// The 32-byte coefficient row of one AdamW step (AdamCoef's order): lr/bias1, 1 - lr*wd, 1-beta1, beta2, 1-beta2,
+// sqrt(bias2), eps, max_norm.  Host only.  Hyper-parameters travel as double and the bias corrections are evaluated in
+// double, like torch.optim.AdamW's Python scalars (a float powf is off by ~1e-5 relative at step 1); each value is rounded
+// to float once.
+int pa2d_adamw_coefficients(double lr, double beta1, double beta2, double eps, double weight_decay, int step_index,
+                            float max_norm, float* out) {
+    if (step_index < 1 || out == nullptr) return PA2D_ERR_ARG;
+    const double bias1 = 1.0 - pow(beta1, (double)step_index);
+    out[0] = (float)(lr / bias1);
+    out[1] = (float)(1.0 - lr * weight_decay);
+    out[2] = (float)(1.0 - beta1);
+    out[3] = (float)beta2;
+    out[4] = (float)(1.0 - beta2);                                   // 1 - float(beta2) would be off by 1e-5 relative
+    out[5] = (float)sqrt(1.0 - pow(beta2, (double)step_index));
+    out[6] = (float)eps;
+    out[7] = max_norm;
+    return PA2D_OK;
+}
+
+static_assert(sizeof(AdamCoef) == 8 * sizeof(float), "the coefficient row is 8 floats");
+
 // One AdamW step over flat buffers p/g/m/v of n floats (16-byte aligned).  step_index >= 1.
-// Hyper-parameters travel as double and the bias corrections are evaluated in double on the host, like
-// torch.optim.AdamW's Python scalars (a float powf is off by ~1e-5 relative at step 1).
 int pa2d_adamw_step(float* p, const float* g, float* m, float* v, long long n, double lr, double beta1, double beta2,
                     double eps, double weight_decay, int step_index, const float* gnorm_sq, float max_norm,
                     hipStream_t st) {
     if (step_index < 1 || ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15)) return PA2D_ERR_ARG;
     if (n <= 0) return PA2D_OK;
     AdamParams a;
-    a.p = p; a.g = g; a.m = m; a.v = v; a.n = n; a.lr = (float)lr; a.beta1 = (float)beta1; a.beta2 = (float)beta2;
-    a.eps = (float)eps; a.max_norm = max_norm; a.gnorm_sq = gnorm_sq;
-    a.omb1 = (float)(1.0 - beta1); a.omb2 = (float)(1.0 - beta2);      // 1 - float(beta2) would be off by 1e-5 relative
-    const double bias1 = 1.0 - pow(beta1, (double)step_index);
-    a.step = (float)(lr / bias1);
-    a.decay = (float)(1.0 - lr * weight_decay);
-    a.bias2_sqrt = (float)sqrt(1.0 - pow(beta2, (double)step_index));
+    a.p = p; a.g = g; a.m = m; a.v = v; a.n = n; a.gnorm_sq = gnorm_sq;
+    const int rc = pa2d_adamw_coefficients(lr, beta1, beta2, eps, weight_decay, step_index, max_norm, reinterpret_cast<float*>(&a.c));
+    if (rc != PA2D_OK) return rc;
     hipLaunchKernelGGL(adamw_kernel, dim3(stream_blocks(n)), dim3(256), 0, st, a);
+    PA2D_CHECK_LAUNCH();
+    return PA2D_OK;
+}
+
+// The same update with the row read from device memory (coef_dev: 8 floats, 16-byte aligned, written by an earlier
+// operation of the same stream): nothing on the host depends on the step, so the launch can be captured in a hipGraph.
+int pa2d_adamw_step_dev(float* p, const float* g, float* m, float* v, long long n, const float* coef_dev,
+                        const float* gnorm_sq, hipStream_t st) {
+    if (coef_dev == nullptr ||
+        ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v) | ((uintptr_t)coef_dev)) & 15))
+        return PA2D_ERR_ARG;
+    if (n <= 0) return PA2D_OK;
+    hipLaunchKernelGGL(adamw_dev_kernel, dim3(stream_blocks(n)), dim3(256), 0, st, p, g, m, v, n,
+                       reinterpret_cast<const AdamCoef*>(coef_dev), gnorm_sq);
     PA2D_CHECK_LAUNCH();
     return PA2D_OK;
 }

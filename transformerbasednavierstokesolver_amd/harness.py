@@ -10,6 +10,9 @@ made (tests/golden/G14-G16, tools/make_golden_drivers.py):
                                 (prediction-feedback loop, no grad)
   GraphedRollout                the same step captured once in a hipGraph (static buffers; the
                                 `torch.cat` window shift becomes an in-place roll)
+  GraphedCallStep               a whole one-call iteration (exp_darcy / exp_airfoil / exp_pipe / exp_elas / one time step
+                                of exp_plas) with its optimizer step in one hipGraph: fit_darcy / fit_static / fit_plas
+                                with graphed=True
   unrolled_train_iteration      ns_vorticity_unrolling.py:225-244 (look-ahead windows through the SOL
   / LookAheadCurriculum         wrapper, BPTT through n chained calls) and :216-223 (curriculum)
   central_diff / darcy_loss     exp_darcy.py:59-68, 209-234 (decode, rel-L2 + 0.1 x derivative loss,
@@ -259,6 +262,128 @@ class GraphedTrainStep:
         if self.sched is not None:
             self.sched.step()
         return self.loss, self.full
+
+
+def _graphed_refusals(who, optimizer, max_grad_norm):
+    """What every graphed loop asks for before it captures anything (also on a machine without a GPU)."""
+    from .optim import FusedAdamW
+    if max_grad_norm is not None:
+        raise ValueError(f"{who}(graphed=True) clips inside optim.FusedAdamW: build it with max_grad_norm=... and pass "
+                         "max_grad_norm=None here (a replayed batch would otherwise go unclipped)")
+    if not isinstance(optimizer, FusedAdamW):
+        raise TypeError(f"{who}(graphed=True) needs optim.FusedAdamW (persistent flat gradient bucket, staged step)")
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        raise NotImplementedError(f"{who}(graphed=True): the gradient all-reduce is not captured; run one rank, or eager")
+
+
+class GraphedCallStep:
+    """A WHOLE one-call iteration in one hipGraph: zero-grad, one model call, the loss, the backward and the optimizer
+    step (`FusedAdamW.step_staged`: the gradient norm and the AdamW launches, which read the step's coefficients from the
+    device row `optimizer.coef`).  Unlike GraphedTrainStep there is NO `ops.weights_frozen()` scope around the model call
+    and the backward, as there is none in darcy_train_step / static_train_step / plas_train_step: with one call per
+    iteration every weight pack is used once, so making the packs ahead only adds launches (measured on the MI355X, Darcy
+    85 x 85 at batch 4: 6.43 ms with the scope against 6.25 ms without), and without it the capture holds
+    exactly the launches of the eager step.
+
+    `static`: the iteration's input buffers, owned by this object (pointers and strides never change).  `body(model,
+    *static)` makes the model call and returns the loss parts, the first of which is differentiated; the parts come back
+    from every call as (static) device tensors.  One call = copy the batch into the static buffers (None keeps a buffer
+    as it is), `optimizer.stage_step()` (host: counts the step and queues the row of the CURRENT lr / beta1 behind the
+    previous replay), ONE replay, `scheduler.step()` (host arithmetic) where a scheduler is given.  No host
+    synchronisation.  The replay runs the kernels of the eager iteration in the same order on the same values: the
+    results are equal bit for bit, PROVIDED the static buffers show the loss kernels the strides and the 16-byte phase
+    of the eager batch (they choose vector or scalar summation from those): buffers are made by `clone()` of a batch.
+
+    The warm-up (side stream) takes real optimizer steps; parameters, both moments and `steps` are put back after it.
+    The parameters that received a gradient differ per driver (`placeholder` does without `fx`), so the optimizer's
+    active ranges are recorded at capture: every call compares them and raises RuntimeError if they have changed, and
+    likewise if parameter storage moved (GraphedRollout's check)."""
+
+    def __init__(self, model, optimizer, scheduler, static, body, warmup=2):
+        _graphed_refusals("GraphedCallStep", optimizer, None)
+        self.model, self.opt, self.sched, self.static, self.body = model, optimizer, scheduler, list(static), body
+        opt = optimizer
+        snap = [t.clone() for t in (opt.flat_p, opt.exp_avg, opt.exp_avg_sq)]
+        steps = opt.steps
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(warmup):           # sets kernel attributes, warms the allocator, marks the touched parameters
+                opt.stage_step()
+                self._iteration()
+        torch.cuda.current_stream().wait_stream(side)
+        self._restore(snap, steps)
+        self.ranges = opt.sync.active_ranges()
+        self.graph = torch.cuda.CUDAGraph()
+        opt.stage_step()                      # a valid row for the capture's own (never executed) launches to point at
+        with torch.cuda.graph(self.graph):
+            self.out = self._iteration()
+        self._restore(snap, steps)
+        opt.sync.release_untouched()          # what step() leaves behind; a replay changes no Python state
+        self._param_ptrs = [p.data_ptr() for p in model.parameters()]
+
+    def _restore(self, snap, steps):
+        opt = self.opt
+        with torch.no_grad():
+            for t, q in zip((opt.flat_p, opt.exp_avg, opt.exp_avg_sq), snap):
+                t.copy_(q)
+        opt.steps = steps
+
+    def _iteration(self):
+        self.opt.zero_grad()
+        parts = self.body(self.model, *self.static)
+        parts[0].backward()
+        self.opt.step_staged()
+        return tuple(p.detach() for p in parts)
+
+    def __call__(self, *batch):
+        if self.opt.sync.active_ranges() != self.ranges:
+            raise RuntimeError("the set of parameters with a gradient changed since this iteration was captured (its "
+                               "AdamW launches cover the ranges of then); re-capture")
+        if [p.data_ptr() for p in self.model.parameters()] != self._param_ptrs:
+            raise RuntimeError("parameter storage moved since this iteration was captured; re-capture")
+        with torch.no_grad():
+            for buf, t in zip(self.static, batch):
+                if t is not None:
+                    buf.copy_(t)
+        self.opt.stage_step()
+        self.graph.replay()
+        if self.sched is not None:
+            self.sched.step()
+        return self.out
+
+
+def _capturable_model(model, who):
+    if getattr(model, "unified_pos", False) and not hasattr(model, "pos"):
+        raise NotImplementedError(f"{who}(graphed=True): the irregular-mesh model with unified_pos builds its lattice from "
+                                  "host memory in every call, which a capture cannot hold")
+
+
+def _darcy_body(y_normalizer, dx, s):
+    def body(model, x, fx, y):
+        out = model(x, fx=fx.unsqueeze(-1)).squeeze(-1)
+        if not _darcy_fusable(out, y, y_normalizer, s):
+            raise ValueError("fit_darcy(graphed=True) needs the fused Darcy loss (fp32 CUDA tensors, a scalar fp32 "
+                             "normaliser, s <= 2048); this batch would take the torch path")
+        return darcy_loss(out, y, y_normalizer, dx, s, fused=True)
+    return body
+
+
+def _static_body(loss_fn, y_normalizer):
+    def body(model, x, y):
+        return (_rel_decoded(loss_fn, model(x, None).squeeze(-1), y, y_normalizer),)
+    return body
+
+
+def _plas_body(loss_fn):
+    """static = (x, fx, tim [B, 1], yy [B, N, 4, T]): the target is COLUMN 0 of yy, a stride-T view like the eager
+    yy[..., t:t+1] (a contiguous copy would take the loss kernels' vector path and other last bits)."""
+    def body(model, x, fx, tim, yy):
+        bsz = x.shape[0]
+        im = model(x, fx, T=tim)
+        return (_rel_decoded(loss_fn, im.reshape(bsz, -1), yy[..., 0:1], None),)
+    return body
 
 
 # ------------------------------------------------------------------------------ unrolled look-ahead training
@@ -722,7 +847,7 @@ def fit_unrolled(sol_model, optimizer, scheduler, train, test, *, epochs, batch_
 
 def fit_darcy(model, optimizer, scheduler, data, *, epochs, batch_size, max_grad_norm=None, loss_fn=None,
               epoch_orders=None, generator=None, save_path=None, save_every=100, fused=True, grad_sync=None,
-              on_epoch=None):
+              on_epoch=None, graphed=False):
     """The epoch loop of exp_darcy.main() (exp_darcy.py:205-268).  `data`: the dict `data.load_darcy_mat` returns
     (encoded x_train / y_train / x_test, the RAW y_test, both normalisers, s, dx); everything is moved to the model's
     device, the positions are `data.grid_positions(s)`.
@@ -735,19 +860,35 @@ def fit_darcy(model, optimizer, scheduler, data, *, epochs, batch_size, max_grad
 
     Quirk of the reference kept OUT of this function: exp_darcy builds its OneCycleLR with epochs=500 whatever
     --epochs says (its module global `epochs`), so a shorter run never leaves the warm-up.  The caller builds the
-    scheduler; pass OneCycleLR(..., epochs=500, ...) to reproduce the reference, or the real count not to."""
+    scheduler; pass OneCycleLR(..., epochs=500, ...) to reproduce the reference, or the real count not to.
+
+    `graphed=True` (CUDA, optim.FusedAdamW, one rank, the fused loss): full batches replay ONE GraphedCallStep, the whole
+    iteration with the optimizer step, bit-identical to the eager one; the short last batch runs eagerly on the same
+    moments, step count and scheduler.  Clips through the optimizer only: `max_grad_norm` together with it raises."""
+    if graphed:
+        _graphed_refusals("fit_darcy", optimizer, max_grad_norm)
+        _capturable_model(model, "fit_darcy")
+        if not fused:
+            raise ValueError("fit_darcy(graphed=True) captures the fused Darcy loss: leave fused=True")
     test_loss = loss_fn or TestLoss(size_average=False)
     dev, yn, train, test, positions = _darcy_setup(model, data)
     s, dx = data["s"], data["dx"]
     ntrain, ntest = len(train), len(test)
+    graph = None
     history = []
     for ep in range(epochs):
         model.train()
         acc = torch.zeros(3, dtype=torch.float64, device=dev)
         for fx, y in _epoch_batches(train, batch_size, ep, epoch_orders, generator):
-            _, l2, deriv = darcy_train_step(model, optimizer, scheduler, positions(fx.shape[0]), fx, y, yn, dx, s,
-                                            max_grad_norm=max_grad_norm, grad_sync=grad_sync, fused=fused,
-                                            loss_fn=loss_fn)
+            if graphed and fx.shape[0] == batch_size:
+                if graph is None:
+                    graph = GraphedCallStep(model, optimizer, scheduler, (positions(batch_size), fx.clone(), y.clone()),
+                                            _darcy_body(yn, dx, s))
+                _, l2, deriv = graph(None, fx, y)
+            else:
+                _, l2, deriv = darcy_train_step(model, optimizer, scheduler, positions(fx.shape[0]), fx, y, yn, dx, s,
+                                                max_grad_norm=max_grad_norm, grad_sync=grad_sync, fused=fused,
+                                                loss_fn=loss_fn)
             acc[0] += l2
             acc[1] += deriv
         model.eval()
@@ -826,7 +967,7 @@ def evaluate_static(model, data, batch_size, loss_fn=None):
 
 def fit_static(model, optimizer, scheduler, data, *, epochs, batch_size, max_grad_norm=None, loss_fn=None,
                epoch_orders=None, generator=None, save_path=None, save_every=100, scheduler_per_epoch=False, grad_sync=None,
-               on_epoch=None):
+               on_epoch=None, graphed=False):
     """The epoch loop of exp_airfoil.main() (:182-226), exp_pipe.main() (:199-249) and exp_elas.main() (:158-204).  `data`:
     the dict of `data.load_airfoil_npy` / `load_pipe_npy` / `load_elas_npy` (x_train [n, N, 2], y_train [n, N], x_test, the
     RAW y_test, y_normalizer or None); everything is moved to the model's device.
@@ -843,17 +984,28 @@ def fit_static(model, optimizer, scheduler, data, *, epochs, batch_size, max_gra
     `loss_fn`: a TestLoss(size_average=False)-like object; utils.testloss.FusedTestLoss runs the training loss on the
     decoded rel-L2 kernels.  Returns one dict per epoch: train_loss = sum / ntrain, rel_err = sum / ntest.  Accumulators
     stay on the device: ONE host synchronisation per epoch.  `epoch_orders`, `generator`, `save_path` / `save_every`,
-    `grad_sync`, `on_epoch`: as fit_ns."""
+    `grad_sync`, `on_epoch`: as fit_ns.  `graphed`: as fit_darcy (the loss inside the capture is `_rel_decoded` with the
+    normaliser or none; a per-epoch scheduler stays outside it)."""
+    if graphed:
+        _graphed_refusals("fit_static", optimizer, max_grad_norm)
+        _capturable_model(model, "fit_static")
     loss_fn = loss_fn or TestLoss(size_average=False)
     dev, yn, train, test = _static_setup(model, data)
     ntrain, ntest = len(train), len(test)
+    batch_sched = None if scheduler_per_epoch else scheduler
+    graph = None
     history = []
     for ep in range(epochs):
         model.train()
         acc = torch.zeros(2, dtype=torch.float64, device=dev)
         for x, y in _epoch_batches(train, batch_size, ep, epoch_orders, generator):
-            acc[0] += static_train_step(model, optimizer, None if scheduler_per_epoch else scheduler, x, y, yn,
-                                        max_grad_norm=max_grad_norm, grad_sync=grad_sync, loss_fn=loss_fn)
+            if graphed and x.shape[0] == batch_size:
+                if graph is None:
+                    graph = GraphedCallStep(model, optimizer, batch_sched, (x.clone(), y.clone()), _static_body(loss_fn, yn))
+                acc[0] += graph(x, y)[0]
+            else:
+                acc[0] += static_train_step(model, optimizer, batch_sched, x, y, yn, max_grad_norm=max_grad_norm,
+                                            grad_sync=grad_sync, loss_fn=loss_fn)
         if scheduler_per_epoch and scheduler is not None:
             scheduler.step()
         model.eval()
@@ -935,7 +1087,8 @@ def evaluate_plas(model, data, batch_size, loss_fn=None):
 
 
 def fit_plas(model, optimizer, scheduler, data, *, epochs, batch_size, max_grad_norm=None, loss_fn=None, epoch_orders=None,
-             time_orders=None, generator=None, save_path=None, save_every=100, grad_sync=None, on_epoch=None):
+             time_orders=None, generator=None, save_path=None, save_every=100, grad_sync=None, on_epoch=None,
+             graphed=False):
     """The epoch loop of exp_plas.main() (exp_plas.py:233-292).  `data`: the dict of `data.load_plas_mat` (encoded x_train
     [n, N, 1], y_train [n, N, 4, T], x_test, y_test, pos [1, N, 2], t [T]); everything is moved to the model's device.
 
@@ -947,10 +1100,19 @@ def fit_plas(model, optimizer, scheduler, data, *, epochs, batch_size, max_grad_
 
     Returns one dict per epoch: train_step = sum / ntrain / T, test_step = sum / ntest / T, test_full = sum / ntest
     (:279-282).  One host synchronisation per epoch; `epoch_orders`, `save_path` / `save_every`, `grad_sync`, `on_epoch`:
-    as fit_ns."""
+    as fit_ns.
+
+    `graphed=True` (requirements as fit_darcy): a full batch is T replays of ONE GraphedCallStep (model call with the
+    time input, raw rel-L2, backward, optimizer step).  The window fx is written once per batch; between replays only
+    the static time vector [B, 1] and column 0 of the static [B, N, 4, T] target are rewritten.  The scheduler steps once
+    per batch, as in the eager loop; short batches run eagerly."""
+    if graphed:
+        _graphed_refusals("fit_plas", optimizer, max_grad_norm)
+        _capturable_model(model, "fit_plas")
     loss_fn = loss_fn or TestLoss(size_average=False)
     dev, train, test, positions, t = _plas_setup(model, data)
     ntrain, ntest, T = len(train), len(test), t.numel()
+    graph = None
     history = []
     for ep in range(epochs):
         model.train()
@@ -966,8 +1128,19 @@ def fit_plas(model, optimizer, scheduler, data, *, epochs, batch_size, max_grad_
             seen += bsz
             tim = t[perm]                                                        # [B, T]
             yy = yy.gather(-1, perm[:, None, None, :].expand_as(yy))             # u[..., permuted_indices] per sample
-            acc[0] += plas_train_step(model, optimizer, positions(bsz), fx, tim, yy, max_grad_norm=max_grad_norm,
-                                      grad_sync=grad_sync, loss_fn=loss_fn)
+            if graphed and bsz == batch_size:
+                if graph is None:
+                    graph = GraphedCallStep(model, optimizer, None, (positions(bsz), fx.clone(), tim[:, :1].clone(), yy.clone()),
+                                            _plas_body(loss_fn))
+                graph.static[1].copy_(fx)                                        # the window: once per batch
+                total = 0
+                for k in range(T):
+                    graph.static[3][..., 0].copy_(yy[..., k])                    # the target column and the time: per replay
+                    total = total + graph(None, None, tim[:, k:k + 1], None)[0]
+                acc[0] += total
+            else:
+                acc[0] += plas_train_step(model, optimizer, positions(bsz), fx, tim, yy, max_grad_norm=max_grad_norm,
+                                          grad_sync=grad_sync, loss_fn=loss_fn)
             if scheduler is not None:
                 scheduler.step()
         model.eval()

@@ -1019,6 +1019,32 @@ def adamw_step(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step_index, gnor
                                     step_index, _p(gnorm_sq), max_norm, _stream()), "adamw_step")
 
 
+ADAMW_ROW = 8      # floats of one coefficient row (include/pa2d.h: pa2d_adamw_coefficients)
+
+
+def adamw_coefficients(lr, beta1, beta2, eps, weight_decay, step_index, max_norm=0.0, out=None):
+    """The row `adamw_step_dev` reads: (lr / bias1, 1 - lr wd, 1 - beta1, beta2, 1 - beta2, sqrt(bias2), eps, max_norm),
+    evaluated in double and rounded once by the library (the values `adamw_step` hands its kernel).  Host arithmetic
+    only.  `out`: a contiguous fp32 HOST tensor of 8 elements to fill (e.g. a pinned staging slot); else a new one."""
+    if out is None:
+        out = torch.empty(ADAMW_ROW, dtype=torch.float32)
+    if out.is_cuda or out.dtype != torch.float32 or out.numel() != ADAMW_ROW or not out.is_contiguous():
+        raise ValueError("adamw_coefficients fills a contiguous fp32 host tensor of 8 elements")
+    _lib.check(_L().pa2d_adamw_coefficients(float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
+                                            int(step_index), float(max_norm), out.data_ptr()), "adamw_coefficients")
+    return out
+
+
+def adamw_step_dev(p, g, m, v, coef, gnorm_sq=None):
+    """`adamw_step` with the step's coefficient row `coef` (fp32 [8], on the device, 16-byte aligned) read by the kernel:
+    no argument depends on the step, so the launch can be captured."""
+    _chk(p, g, m, v, coef, gnorm_sq)
+    if coef.numel() != ADAMW_ROW:
+        raise ValueError("adamw_step_dev needs a coefficient row of 8 floats")
+    _lib.check(_L().pa2d_adamw_step_dev(_p(p), _p(g), _p(m), _p(v), p.numel(), _p(coef), _p(gnorm_sq), _stream()),
+               "adamw_step_dev")
+
+
 def rel_l2_fwd(pred2d, y2d):
     _chk(pred2d, y2d)
     B, L = pred2d.shape

@@ -38,6 +38,7 @@ class FusedAdamW(torch.optim.Optimizer):
         self.exp_avg = torch.zeros_like(self.flat_p)
         self.exp_avg_sq = torch.zeros_like(self.flat_p)
         self.steps = 0
+        self.coef = None                # device row of the staged step's coefficients: made by the first stage_step()
 
     def zero_grad(self, set_to_none=False):
         """Always zeroes in place (the views must stay alive); `set_to_none` is accepted and ignored."""
@@ -56,6 +57,53 @@ class FusedAdamW(torch.optim.Optimizer):
                            float(g["weight_decay"]), self.steps, gn, float(self.max_grad_norm or 0.0))
         self.sync.release_untouched()
         return None
+
+    # ---- the step in two halves, for a captured iteration (harness.GraphedCallStep): the host half stages the step's
+    # coefficients on the device, the device half is launches only
+    STAGE_SLOTS = 32
+
+    def stage_step(self):
+        """Host half of a staged step: counts the step and puts its coefficient row (ops.adamw_coefficients of the param
+        group's CURRENT lr / betas, i.e. what the scheduler last wrote, and `max_grad_norm`) into the persistent device
+        tensor `self.coef`, on the current stream.
+
+        The host source of that copy is a small PINNED ring (STAGE_SLOTS rows) and the copy is asynchronous: a pinned
+        source is read by the DMA engine when the stream reaches the copy, so the row must not be rewritten before then.
+        Every slot therefore carries an event recorded right after its copy, and a slot is refilled only once that event
+        has completed.  The host waits there only if it has run STAGE_SLOTS steps ahead of the device, never otherwise
+        (a pageable source with a blocking `copy_` would be safe too, but it synchronises the host with the stream on
+        every step).  Stream order does the rest: the copy of step i + 1 is queued behind the launches of step i, which
+        read `self.coef`, and in front of those of step i + 1."""
+        g = self.param_groups[0]
+        if self.coef is None:
+            self.coef = torch.zeros(ops.ADAMW_ROW, dtype=torch.float32, device=self.flat_p.device)
+            self._ring = torch.zeros(self.STAGE_SLOTS, ops.ADAMW_ROW, dtype=torch.float32).pin_memory()
+            self._ring_done = [None] * self.STAGE_SLOTS
+            self._ring_next = 0
+        slot = self._ring_next
+        self._ring_next = (slot + 1) % self.STAGE_SLOTS
+        if self._ring_done[slot] is not None:
+            self._ring_done[slot].synchronize()          # returns at once unless the host is STAGE_SLOTS steps ahead
+        self.steps += 1
+        self._opt_called = True         # what torch's wrapped step() notes: the scheduler may step after a staged step
+        ops.adamw_coefficients(float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]),
+                               float(g["weight_decay"]), self.steps, float(self.max_grad_norm or 0.0),
+                               out=self._ring[slot])
+        self.coef.copy_(self._ring[slot], non_blocking=True)
+        ev = self._ring_done[slot] or torch.cuda.Event()
+        ev.record()
+        self._ring_done[slot] = ev
+
+    @torch.no_grad()
+    def step_staged(self):
+        """Device half: the gradient norm (when clipping) and one AdamW launch per active range, with the coefficients
+        read from `self.coef`.  Launches only, no Python state: it can be captured in a hipGraph; every replay then
+        applies whatever row `stage_step` staged before it.  The gradients must already be in the bucket (they are
+        after `zero_grad()` + backward; `step()`'s adoption of foreign `.grad` tensors has no place in a capture)."""
+        gn = ops.sumsq(self.sync.flat) if self.max_grad_norm is not None else None
+        for a, b in self.sync.active_ranges():
+            ops.adamw_step_dev(self.flat_p[a:b], self.sync.flat[a:b], self.exp_avg[a:b], self.exp_avg_sq[a:b],
+                               self.coef, gn)
 
     # ---- checkpointing: the moments and the step count round-trip like torch.optim.AdamW's state
     def state_dict(self):

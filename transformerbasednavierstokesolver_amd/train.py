@@ -8,7 +8,9 @@ exp_elas.py and exp_plas.py:
 The flags and their defaults are the reference drivers' own, per driver (`--driver {ns,unrolled,darcy,airfoil,pipe,elas,plas}`
 selects the table).
 Added: `--driver`, `--engine` (GEMM engine: f32 | split | bf16 | bf16s, default PA2D_GEMM / split), `--ntrain` / `--ntest`
-(the drivers' hard-coded module globals; exp_darcy already has --ntrain).  `--gpu` is the device index.  `--data_path` is
+(the drivers' hard-coded module globals; exp_darcy already has --ntrain), `--graphed` (0 | 1, default 0: every full batch
+replays its iteration from one hipGraph, `graphed=True` of the harness loops, results bit-identical to `--graphed 0`; the
+clip threshold is inside the optimizer either way; refused for `--driver unrolled`).  `--gpu` is the device index.  `--data_path` is
 honoured (exp_ns.py and ns_vorticity_unrolling.py ignore it for a hard-coded path): a `.mat` file, or the directory that
 holds NavierStokes_V1e-5_N1200_T20.mat (directly or in a folder of that name) / piececonst_r421_N1024_smooth{1,2}.mat.
 
@@ -123,11 +125,24 @@ def build_parser(driver):
     return p
 
 
+def command_line_parser(driver):
+    """`build_parser(driver)` (the reference's flag table with --driver / --engine / --ntrain / --ntest) plus the flags
+    that only steer how this project runs the same loop."""
+    p = build_parser(driver)
+    p.add_argument("--graphed", type=int, default=0, help="1: full batches replay the whole iteration from one hipGraph")
+    return p
+
+
 def parse_args(argv=None):
     pre = argparse.ArgumentParser(add_help=False)
     pre.add_argument("--driver", choices=DRIVERS, default="ns")
     driver = pre.parse_known_args(argv)[0].driver
-    return build_parser(driver).parse_args(argv)
+    parser = command_line_parser(driver)
+    args = parser.parse_args(argv)
+    if driver == "unrolled" and args.graphed:
+        parser.error("--graphed 1 is not available for --driver unrolled: its look-ahead curriculum changes the number of "
+                     "chained model calls from epoch to epoch, so there is no one iteration to capture")
+    return args
 
 
 def _find(data_path, names):
@@ -206,7 +221,7 @@ def run_ns(args, unrolled):
     opt, sched = _optim(args, model, steps, args.epochs, args.max_grad_norm)
     return harness.fit_ns(
         model, opt, sched, train, test, epochs=args.epochs, batch_size=args.batch_size, T=T, step=STEP, loss_fn=loss_fn,
-        save_path=_checkpoint(args), grad_sync=opt.sync,
+        save_path=_checkpoint(args), grad_sync=opt.sync, graphed=bool(args.graphed),
         on_epoch=lambda ep, m: print(
             "Epoch {} , train_step_loss:{:.5f} , train_full_loss:{:.5f} , test_step_loss:{:.5f} , test_full_loss:{:.5f}".format(
                 ep, m["train_step"], m["train_full"], m["test_step"], m["test_full"]), flush=True))
@@ -239,7 +254,8 @@ def run_darcy(args):
         print("rel_err:{}".format(m["rel_err"]), flush=True)
 
     return harness.fit_darcy(model, opt, sched, d, epochs=args.epochs, batch_size=args.batch_size, loss_fn=loss_fn,
-                             save_path=_checkpoint(args), fused=True, grad_sync=opt.sync, on_epoch=line)
+                             save_path=_checkpoint(args), fused=True, grad_sync=opt.sync, on_epoch=line,
+                             graphed=bool(args.graphed))
 
 
 def _load_static(args):
@@ -288,7 +304,8 @@ def run_static(args):
         print(err_line.format(m["rel_err"]), flush=True)
 
     return harness.fit_static(model, opt, sched, d, epochs=args.epochs, batch_size=args.batch_size, loss_fn=loss_fn,
-                              save_path=_checkpoint(args), scheduler_per_epoch=per_epoch, grad_sync=opt.sync, on_epoch=line)
+                              save_path=_checkpoint(args), scheduler_per_epoch=per_epoch, grad_sync=opt.sync, on_epoch=line,
+                              graphed=bool(args.graphed))
 
 
 def run_plas(args):
@@ -316,7 +333,7 @@ def run_plas(args):
     opt, sched = _optim(args, model, math.ceil(args.ntrain / args.batch_size), args.epochs, args.max_grad_norm)
     return harness.fit_plas(
         model, opt, sched, d, epochs=args.epochs, batch_size=args.batch_size, loss_fn=loss_fn, save_path=_checkpoint(args),
-        grad_sync=opt.sync,
+        grad_sync=opt.sync, graphed=bool(args.graphed),
         on_epoch=lambda ep, m: print("Epoch {} , train_step_loss:{:.5f} , test_step_loss:{:.5f} , test_full_loss:{:.5f}".format(
             ep, m["train_step"], m["test_step"], m["test_full"]), flush=True))
 
