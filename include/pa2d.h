@@ -61,7 +61,9 @@ enum pa2d_engine { PA2D_ENGINE_F32 = 0, PA2D_ENGINE_SPLIT = 1, PA2D_ENGINE_BF16 
 int pa2d_default_engine(void);
 /* Kernel-selection overrides (PA2D_CONV_HALO, PA2D_MC_BIG, PA2D_LIN_PANEL, ...: A/B timing and the parity tests that
  * force one of two equivalent kernels) and PA2D_GEMM are read from the environment ONCE, when the library is loaded;
- * pa2d_reload_env() reads them again (tests).  They never change the numerics contract of an entry point. */
+ * pa2d_reload_env() reads them again (tests).  They never change the numerics contract of an entry point.
+ * PA2D_CONV_AHEAD=0: the split engine's halo conv (16x16x32 MFMA consumers) runs the reference consumer loop instead of
+ * the one that reads its LDS fragments ahead of use; the two are bit-equal. */
 void pa2d_reload_env(void);
 
 /* ---- LayerNorm: nn.LayerNorm(C) of Transolver_block, model/Transolver_Structured_Mesh_2D.py:58,62,65,70-73 */

@@ -35,9 +35,11 @@ constexpr int HH = TH + 2, HWD = TW + 2, HROWS = HH * HWD;          // 10 x 34 =
 // FLOP/s at the clock the chip holds under that load (tools/probes/mfma_shape_probe.hip: 1905 vs 1730 TFLOP/s).  The weights
 // are the A operand there, so a lane's accumulator quad is four consecutive channels of one pixel: 16-byte stores.
 // Row pitch: an even number (14) of 16-byte slots keeps the 16-row fragment reads conflict-free (13 is the 32-row optimum).
-template <int NT, typename TO = float, int TPB = (NT == 1 ? 3 : 1), bool MF16 = false>
-__global__ __launch_bounds__(512, 1) void conv_halo_kernel(const KCParams p, const int tiles_x, const int tiles_y,
-                                                           const int nimg) {
+// AHEAD (MF16 only): the consumers read every MFMA fragment from LDS at least 12 MFMAs before its first use (the body of
+// conv_halo_kernel<3, float, 1, true>); AHEAD = false is the plain loop whose order the compiler chooses
+// (conv_halo_ref_kernel, env PA2D_CONV_AHEAD=0).  Same MFMA sequence per accumulator: bit-equal outputs.
+template <int NT, typename TO, int TPB, bool MF16, bool AHEAD>
+__device__ __forceinline__ void conv_halo_body(const KCParams& p, const int tiles_x, const int tiles_y, const int nimg) {
     constexpr int PITCHB = NT * 64 + (MF16 ? 32 : 16);
     constexpr int PIECES = NT * 4;                                   // 16-byte pieces per row and chunk
     constexpr int A_BYTES = HROWS * PITCHB;
@@ -175,6 +177,86 @@ __global__ __launch_bounds__(512, 1) void conv_halo_kernel(const KCParams p, con
         const unsigned b_frag = (unsigned)((wn * 64 + li) * PITCHB + kq * 16);
         __syncthreads();                                      // #0
         int tap = 0;
+        if constexpr (AHEAD) {
+            // Every fragment is read from LDS at least 12 MFMAs before its first use, in an order pinned with sched_barrier
+            // (left alone, the compiler issues a row block's reads right before its MFMAs and the next stage's weight
+            // fragments in one burst behind the barrier).  Per stage of 192 MFMAs, (ib, j) = the six MFMAs of acc[ib][j]:
+            //   blocks 0..5 column after column, each behind the read of the NEXT block's A fragments into the other of
+            //   a0 / a1;
+            //   read block 7 -> a1 | (6,0) (6,1) | end-of-stage barrier (MFMA 132; its wait has 12 MFMAs of cover; every
+            //   LDS read of the stage is complete, so at a chunk boundary the producers may replace the halo tile behind
+            //   it) | (7,0) | bf[0] <- next stage | (7,1) | bf[1] <- | (6,2) (6,3) | second barrier at a chunk boundary |
+            //   a0 <- block 0 of the next tap | (7,2) | bf[2] <- | (7,3) | bf[3] <-.
+            // LDS operations retire in order and the prologue issues its reads in the tail's order, so every s_waitcnt of
+            // the loop names exactly the reads it needs.  acc[ib][j] still sees (chunk, tap, six terms) in the reference order.
+            // OVER-READ: the last stage issues the reads of a stage that does not exist (the other weight slot, tap 0 of
+            // the halo tile).  They stay inside today's LDS allocation and nothing uses them; whoever shrinks or re-lays
+            // the LDS image has to keep those addresses inside it, or guard the tail's reads with sg + 1 < nst.
+            // The six terms of an accumulator are issued back to back, not interleaved with other accumulators as the
+            // compiler orders the reference loop: a 16x16x32 chain issues at the full rate (16 cycles per MFMA), and on
+            // this power-limited kernel the chained form measured 6 % faster than a trial build of this loop with the
+            // terms interleaved (1.048 against 1.114 ms per launch in the step, same job).
+            bf16x8 bf[4][NT], a0[NT], a1[NT];
+#define CH_PIN() __builtin_amdgcn_sched_barrier(0)
+#define CH_LDA(AF_, base_, ib_)                                                                            \
+    {                                                                                                      \
+        _Pragma("unroll") for (int q = 0; q < NT; ++q)                                                     \
+            AF_[q] = *reinterpret_cast<const bf16x8*>((base_) + ((ib_) >> 1) * (HWD * PITCHB) + ((ib_) & 1) * 16 * PITCHB + q * 64); \
+        CH_PIN();                                                                                          \
+    }
+#define CH_LDB(j_, base_)                                                                                  \
+    {                                                                                                      \
+        _Pragma("unroll") for (int q = 0; q < NT; ++q)                                                     \
+            bf[j_][q] = *reinterpret_cast<const bf16x8*>((base_) + (j_) * 16 * PITCHB + q * 64);          \
+        CH_PIN();                                                                                          \
+    }
+#define CH_T(ib_, j_, AF_, bq_, aq_) \
+    acc[ib_][j_] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[j_][bq_], AF_[aq_], acc[ib_][j_], 0, 0, 0);
+#define CH_MM(ib_, j_, AF_)     /* smallest terms first; weights = A operand (rows = channels) */          \
+    {                                                                                                      \
+        CH_T(ib_, j_, AF_, 1, 1) CH_T(ib_, j_, AF_, 0, 2) CH_T(ib_, j_, AF_, 2, 0)                         \
+        CH_T(ib_, j_, AF_, 0, 1) CH_T(ib_, j_, AF_, 1, 0) CH_T(ib_, j_, AF_, 0, 0)                         \
+        CH_PIN();                                                                                          \
+    }
+#define CH_BLOCK(ib_, AF_) CH_MM(ib_, 0, AF_) CH_MM(ib_, 1, AF_) CH_MM(ib_, 2, AF_) CH_MM(ib_, 3, AF_)
+            const unsigned char* af_base = a_s + a_frag + (-HWD - 1) * PITCHB;        // tap 0
+            const unsigned char* bf_base = b_s + b_frag;
+            CH_PIN();
+            CH_LDB(0, bf_base) CH_LDB(1, bf_base) CH_LDA(a0, af_base, 0) CH_LDB(2, bf_base) CH_LDB(3, bf_base)
+            for (int sg = 0; sg < nst; ++sg) {
+                const bool swap = tap == 8;
+                const int ntap = swap ? 0 : tap + 1;
+                const int ndy = ntap / 3 - 1, ndx = ntap - (ntap / 3) * 3 - 1;
+                const unsigned char* af_next = a_s + a_frag + (ndy * HWD + ndx) * PITCHB;
+                const unsigned char* bf_next = b_s + ((sg + 1) & 1) * B_STAGE + b_frag;
+                CH_PIN();
+                CH_LDA(a1, af_base, 1) CH_BLOCK(0, a0)
+                CH_LDA(a0, af_base, 2) CH_BLOCK(1, a1)
+                CH_LDA(a1, af_base, 3) CH_BLOCK(2, a0)
+                CH_LDA(a0, af_base, 4) CH_BLOCK(3, a1)
+                CH_LDA(a1, af_base, 5) CH_BLOCK(4, a0)
+                CH_LDA(a0, af_base, 6) CH_BLOCK(5, a1)
+                CH_LDA(a1, af_base, 7) CH_MM(6, 0, a0) CH_MM(6, 1, a0)
+                __syncthreads();                              // end of stage sg
+                CH_PIN();
+                CH_MM(7, 0, a1) CH_LDB(0, bf_next)
+                CH_MM(7, 1, a1) CH_LDB(1, bf_next)
+                CH_MM(6, 2, a0) CH_MM(6, 3, a0)
+                if (swap && sg + 1 < nst) __syncthreads();    // the producers swapped the halo tile in between
+                CH_PIN();
+                CH_LDA(a0, af_next, 0)
+                CH_MM(7, 2, a1) CH_LDB(2, bf_next)
+                CH_MM(7, 3, a1) CH_LDB(3, bf_next)
+                af_base = af_next;
+                tap = ntap;
+            }
+#undef CH_BLOCK
+#undef CH_MM
+#undef CH_T
+#undef CH_LDB
+#undef CH_LDA
+#undef CH_PIN
+        } else
         for (int sg = 0; sg < nst; ++sg) {
             const int dy = tap / 3 - 1, dx = tap - (tap / 3) * 3 - 1;
             const unsigned char* af_base = a_s + a_frag + (dy * HWD + dx) * PITCHB;
@@ -343,6 +425,17 @@ __global__ __launch_bounds__(512, 1) void conv_halo_kernel(const KCParams p, con
     }
 }
 
+template <int NT, typename TO = float, int TPB = (NT == 1 ? 3 : 1), bool MF16 = false>
+__global__ __launch_bounds__(512, 1) void conv_halo_kernel(const KCParams p, const int tiles_x, const int tiles_y,
+                                                           const int nimg) {
+    conv_halo_body<NT, TO, TPB, MF16, MF16>(p, tiles_x, tiles_y, nimg);
+}
+// the 16x16x32 consumers as the compiler orders them (PA2D_CONV_AHEAD=0): the A/B partner of conv_halo_kernel<3, float, 1, true>
+__global__ __launch_bounds__(512, 1) void conv_halo_ref_kernel(const KCParams p, const int tiles_x, const int tiles_y,
+                                                               const int nimg) {
+    conv_halo_body<3, float, 1, true, false>(p, tiles_x, tiles_y, nimg);
+}
+
 // 0 = never, 1 = when the launch fills the chip (default), 2 = always (tests): env PA2D_CONV_HALO=off|auto|force
 static int halo_policy() { return pa2d_env().conv_halo; }
 
@@ -365,12 +458,13 @@ int launch_conv_halo(const KCParams& p, hipStream_t st) {
     // the LDS attribute is set on every launch: it is per device and the call is cheap
     if (NT == 3 && pa2d_env().conv_mfma16 && (p.N % 4) == 0 && (p.ldc % 4) == 0) {      // 16-byte stores of accumulator quads
         const int smem16 = (HROWS + 2 * BN) * (3 * 64 + 32);
+        auto* const kern = pa2d_env().conv_ahead ? &conv_halo_kernel<3, float, 1, true> : &conv_halo_ref_kernel;
         {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo_kernel<3, float, 1, true>),
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                                hipFuncAttributeMaxDynamicSharedMemorySize, smem16);
             if (e != hipSuccess) return (int)e;
         }
-        hipLaunchKernelGGL((conv_halo_kernel<3, float, 1, true>), grid, dim3(512), smem16, st, p, tiles_x, tiles_y, nimg);
+        hipLaunchKernelGGL(kern, grid, dim3(512), smem16, st, p, tiles_x, tiles_y, nimg);
     } else if (NT == 3) {
         {
             hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo_kernel<3>),

@@ -25,6 +25,7 @@ static Pa2dEnv read_env() {
     v.lin_rowpanel = is("PA2D_LIN_ROWPANEL", "of") ? 0 : 1;
     v.lin_small_split = is("PA2D_LIN_SMALL_SPLIT", "of") ? 0 : 1;
     v.conv_mfma16 = num("PA2D_CONV_MFMA", 16) == 32 ? 0 : 1;
+    v.conv_ahead = num("PA2D_CONV_AHEAD", 1) == 0 ? 0 : 1;
     v.mc_mfma16 = num("PA2D_MC_MFMA", 16) == 32 ? 0 : 1;
     v.split_big = num("PA2D_SPLIT_BIG", 1);
     v.slice_map = is("PA2D_SLICE_MAP", "l") ? 0 : 1;

@@ -19,6 +19,8 @@
 // Workgroups are persistent (one per CU); the stage stream continues across rounds.
 #include "pa2d_gemm_common.h"
 #include <type_traits>
+// RP_SGB: how the fragment reads of sub-step s + 1 sit among the 24 MFMAs of sub-step s.  1 (built): one read behind every
+// four MFMAs; 0: the compiler's order; 2: all six pinned in front of the MFMAs.  Only 1 fits the registers.
 #ifndef RP_SGB
 #define RP_SGB 1
 #endif
@@ -229,6 +231,9 @@ __global__ __launch_bounds__(256, 1) void gemm_rowpanel_kernel(const KCParams p,
             for (int ks4 = 0; ks4 < 4; ++ks4) {
                 if (ks4 < 3) frag_read((ks4 + 1) & 1, cur, ks4 + 1);
                 else frag_read(0, nxt, 0);                   // written before the barrier below, by every wave
+#if RP_SGB == 2      // trial: the six reads as one burst ahead of the sub-step's MFMAs (cover >= 24, but 140 B of scratch)
+                __builtin_amdgcn_sched_barrier(0);
+#endif
                 const int ks = kc * 4 + ks4;
 #ifndef RP_NO_ANEXT
                 // the rows fetched for the next round: k-step ks - 4 is free once stage kc - 1 of the last pair is through

@@ -139,6 +139,7 @@ struct Pa2dEnv {
     int lin_dw_split;     // PA2D_LIN_DW_SPLIT=off -> 0
     int lin_panel;        // PA2D_LIN_PANEL=off -> 0
     int conv_mfma16;      // PA2D_CONV_MFMA=32 -> 0 (halo conv consumers back on v_mfma_f32_32x32x16_bf16)
+    int conv_ahead;       // PA2D_CONV_AHEAD=0 -> 0 (16x16x32 halo conv consumers back on the loop without hand-placed fragment reads)
     int mc_mfma16;        // PA2D_MC_MFMA=32 -> 0 (split-engine weight gradients back on v_mfma_f32_32x32x16_bf16 and 16-row K-steps)
     int lin_small_split;  // PA2D_LIN_SMALL_SPLIT=off -> 0 (small split-engine linears back on the exact-fp32 kernels)
     int lin_rowpanel;     // PA2D_LIN_ROWPANEL=off -> 0 (row-stationary linears back on the panel / per-tile kernels)
