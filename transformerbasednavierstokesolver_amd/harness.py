@@ -17,11 +17,29 @@ made (tests/golden/G14-G16, tools/make_golden_drivers.py):
   / LookAheadCurriculum         wrapper, BPTT through n chained calls) and :216-223 (curriculum)
   central_diff / darcy_loss     exp_darcy.py:59-68, 209-234 (decode, rel-L2 + 0.1 x derivative loss,
   / darcy_train_step            clip, step) — the large-N single-call iteration
-  fit_ns / fit_unrolled         exp_ns.py:184-257, ns_vorticity_unrolling.py:204-329, exp_darcy.py:205-268: the epoch loops
-  / fit_darcy, evaluate_*       (shuffled batches, per-epoch test pass, the drivers' metric normalisation, checkpoints)
+  static_train_step             exp_airfoil.py:187-199, exp_pipe.py:204-221, exp_elas.py:163-176 (one model(x, None) call, rel-L2
+                                of the decoded prediction and target)
+  plas_train_step               exp_plas.py:242-253 (per batch T time-conditioned calls, each with its own optimizer step)
+  fit_ns / fit_unrolled         exp_ns.py:184-257, ns_vorticity_unrolling.py:204-329, exp_darcy.py:205-268, exp_airfoil.py:
+  / fit_darcy / fit_static      182-226, exp_pipe.py:199-249, exp_elas.py:158-204, exp_plas.py:233-292: the epoch loops (shuffled
+  / fit_plas                    batches, per-epoch test pass, the drivers' metric normalisation, checkpoints).  Each is its
+                                setup, a per-batch closure and a metrics function around the one loop `_fit`; a loop with a
+                                graph mode picks replay or eager per batch through `_graphed_or_eager`
+  evaluate_ns / _darcy          the test pass of a loop alone, normalised like the loop's metrics
+  / _static / _plas
   autoencoder_train_step        auto_encoder.py:166-181 (the auto-encoder reconstructs its own input fx)
   sequensolver_train_step       SequenSolver.py:572-606 (Tout teacher-forced calls of the latent sequence model, window slid
   / sequensolver_rollout        with the true frame, summed rel-L2, one backward, step) and :613-630 (prediction feedback)
+  learnslice_train_step         LearnSlice.py:477-526 (slice weights from the frozen model's code: one optimizer step per frame)
+  slice_predictor_train_step    LearnSlice.py:929-962 and :861-913 (the conv slice predictors: Tout summed terms and one step;
+  / slice_predictor_rollout     the prediction-feedback evaluation)
+
+Every *_train_step, the body of fit_unrolled and GraphedTrainStep end in `_apply_step`: [grad_sync], [clip], optimizer.step(),
+[scheduler.step()].  zero_grad and backward stay in each function, because their place differs and is kept as the drivers have
+it: the Darcy, static and plasticity steps zero with set_to_none=False outside any `ops.weights_frozen()` scope (before the
+model call; plas after it), the others zero after the forward and inside the scope (train_step with its `set_to_none`
+argument, the rest with the optimizer's default); the sequence-model and slice steps clip the trainable parameters only, the
+others all of them.
 """
 from __future__ import annotations
 
@@ -131,6 +149,19 @@ def _train_iteration_folded(model, x, fx, yy, step, loss_fn):
     return loss, full, pred
 
 
+def _apply_step(optimizer, scheduler, params, max_grad_norm, grad_sync):
+    """The tail of every eager iteration, after its backward: [grad_sync()], [clip_grad_norm_ of `params`, any iterable,
+    read only when a threshold is given], optimizer.step(), [scheduler.step()].  zero_grad and backward stay with the
+    caller: where they stand relative to the forward and to an `ops.weights_frozen()` scope differs per driver."""
+    if grad_sync is not None:
+        grad_sync()
+    if max_grad_norm is not None:
+        torch.nn.utils.clip_grad_norm_(params, max_grad_norm)
+    optimizer.step()
+    if scheduler is not None:
+        scheduler.step()
+
+
 def train_step(model, optimizer, scheduler, x, fx, yy, step=1, max_grad_norm=None, grad_sync=None,
                set_to_none=False, loss_fn=None, fold_time=False):
     """One full exp_ns.py:191-218 iteration.  `grad_sync` (DDP): callable run between backward and
@@ -141,13 +172,7 @@ def train_step(model, optimizer, scheduler, x, fx, yy, step=1, max_grad_norm=Non
         loss, full, _ = train_iteration(model, x, fx, yy, step, loss_fn, fold_time)
         optimizer.zero_grad(set_to_none=set_to_none)
         loss.backward()
-    if grad_sync is not None:
-        grad_sync()
-    if max_grad_norm is not None:
-        torch.nn.utils.clip_grad_norm_(model.parameters(), max_grad_norm)
-    optimizer.step()
-    if scheduler is not None:
-        scheduler.step()
+    _apply_step(optimizer, scheduler, model.parameters(), max_grad_norm, grad_sync)
     return loss.detach(), full
 
 
@@ -257,15 +282,13 @@ class GraphedTrainStep:
         self.fx.copy_(fx)
         self.yy.copy_(yy)
         self.graph.replay()
-        self.opt.sync()                 # all-reduce(SUM) of the flat bucket when world_size > 1
-        self.opt.step()
-        if self.sched is not None:
-            self.sched.step()
+        _apply_step(self.opt, self.sched, (), None, self.opt.sync)      # all-reduce(SUM) of the flat bucket when world_size > 1
         return self.loss, self.full
 
 
-def _graphed_refusals(who, optimizer, max_grad_norm):
-    """What every graphed loop asks for before it captures anything (also on a machine without a GPU)."""
+def _graphed_refusals(who, optimizer, max_grad_norm, one_rank=True):
+    """What every graphed loop asks for before it captures anything (also on a machine without a GPU).  `one_rank=False`:
+    fit_ns, whose GraphedTrainStep leaves the all-reduce and the optimizer step outside the capture and so serves several ranks."""
     from .optim import FusedAdamW
     if max_grad_norm is not None:
         raise ValueError(f"{who}(graphed=True) clips inside optim.FusedAdamW: build it with max_grad_norm=... and pass "
@@ -273,7 +296,7 @@ def _graphed_refusals(who, optimizer, max_grad_norm):
     if not isinstance(optimizer, FusedAdamW):
         raise TypeError(f"{who}(graphed=True) needs optim.FusedAdamW (persistent flat gradient bucket, staged step)")
     import torch.distributed as dist
-    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+    if one_rank and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
         raise NotImplementedError(f"{who}(graphed=True): the gradient all-reduce is not captured; run one rank, or eager")
 
 
@@ -474,13 +497,7 @@ def darcy_train_step(model, optimizer, scheduler, x, fx, y, y_normalizer, dx, s,
     out = model(x, fx=fx.unsqueeze(-1)).squeeze(-1)
     loss, l2, deriv = darcy_loss(out, y, y_normalizer, dx, s, loss_fn=loss_fn, fused=fused)
     loss.backward()
-    if grad_sync is not None:
-        grad_sync()
-    if max_grad_norm is not None:
-        torch.nn.utils.clip_grad_norm_(model.parameters(), max_grad_norm)
-    optimizer.step()
-    if scheduler is not None:
-        scheduler.step()
+    _apply_step(optimizer, scheduler, model.parameters(), max_grad_norm, grad_sync)
     return loss.detach(), l2.detach(), deriv.detach()
 
 
@@ -495,13 +512,7 @@ def autoencoder_train_step(model, optimizer, scheduler, x, fx, max_grad_norm=Non
         loss = TestLoss(size_average=False)(im.reshape(bsz, -1), fx.reshape(bsz, -1))
         optimizer.zero_grad()
         loss.backward()
-    if grad_sync is not None:
-        grad_sync()
-    if max_grad_norm is not None:
-        torch.nn.utils.clip_grad_norm_(model.parameters(), max_grad_norm)
-    optimizer.step()
-    if scheduler is not None:
-        scheduler.step()
+    _apply_step(optimizer, scheduler, model.parameters(), max_grad_norm, grad_sync)
     return loss.detach()
 
 
@@ -529,13 +540,7 @@ def sequensolver_train_step(model, optimizer, scheduler, x, fx, yy, use_gt=True,
             full = loss_fn(torch.cat(preds, -1).reshape(bsz, -1), yy.reshape(bsz, -1))
         optimizer.zero_grad()
         loss.backward()
-    if grad_sync is not None:
-        grad_sync()
-    if max_grad_norm is not None:
-        torch.nn.utils.clip_grad_norm_([p for p in model.parameters() if p.requires_grad], max_grad_norm)
-    optimizer.step()
-    if scheduler is not None:
-        scheduler.step()
+    _apply_step(optimizer, scheduler, (p for p in model.parameters() if p.requires_grad), max_grad_norm, grad_sync)
     return loss.detach(), full
 
 
@@ -560,13 +565,7 @@ def learnslice_train_step(model, optimizer, scheduler, sequen_solver, x, fx, yy,
             loss = Fn.slice_mse(model.get_slice_weight(code, x, fx, use_vorticity=use_vorticity), target)
             optimizer.zero_grad()
             loss.backward()
-            if grad_sync is not None:
-                grad_sync()
-            if max_grad_norm is not None:
-                torch.nn.utils.clip_grad_norm_([p for p in model.parameters() if p.requires_grad], max_grad_norm)
-            optimizer.step()
-            if scheduler is not None:
-                scheduler.step()
+            _apply_step(optimizer, scheduler, (p for p in model.parameters() if p.requires_grad), max_grad_norm, grad_sync)
             losses.append(loss.detach())
             fx = torch.cat((fx[..., 1:], y), dim=-1)             # the ground truth enters the window
     return losses
@@ -603,13 +602,7 @@ def slice_predictor_train_step(model, optimizer, scheduler, sequen_solver, x, fx
             fx = torch.cat((fx[..., 1:], y), dim=-1)             # the ground truth enters the window
         optimizer.zero_grad()
         loss.backward()
-    if grad_sync is not None:
-        grad_sync()
-    if max_grad_norm is not None:
-        torch.nn.utils.clip_grad_norm_([p for p in model.parameters() if p.requires_grad], max_grad_norm)
-    optimizer.step()
-    if scheduler is not None:
-        scheduler.step()
+    _apply_step(optimizer, scheduler, (p for p in model.parameters() if p.requires_grad), max_grad_norm, grad_sync)
     return loss.detach()
 
 
@@ -657,6 +650,19 @@ def _device_of(model):
     return next(model.parameters()).device
 
 
+def _positions_cache(pos1):
+    """positions(bsz): the mesh `pos1` [1, N, 2] as ONE contiguous [bsz, N, 2] copy per batch size (full and short batch),
+    not one per sample."""
+    pos = {}
+
+    def positions(bsz):
+        if bsz not in pos:
+            pos[bsz] = pos1.expand(bsz, -1, -1).contiguous()
+        return pos[bsz]
+
+    return positions
+
+
 def _epoch_batches(dataset, batch_size, ep, epoch_orders, generator):
     """Shuffled batches with the short last batch kept (DataLoader(shuffle=True), drop_last=False); `epoch_orders[ep]`
     replays a recorded permutation instead."""
@@ -671,6 +677,52 @@ def _save_state(module, save_path):
     if folder:
         os.makedirs(folder, exist_ok=True)
     torch.save({k: v.detach().cpu() for k, v in module.state_dict().items()}, save_path)
+
+
+def _fit(model, *, epochs, n_acc, batches, train_batch, test_pass, metrics, on_epoch, save_path, save_every, save_module=None,
+         per_epoch=None):
+    """The epoch loop that the fit_* drivers share.  Each epoch: model.train(); a zeroed float64 accumulator `acc` [n_acc]
+    on the model's device; `train_batch(batch, acc)` for every batch of `batches(ep)`; `per_epoch()` where given (a
+    scheduler stepped per epoch); model.eval(); `test_pass(acc)`; ONE acc.tolist(), the epoch's only host synchronisation;
+    `metrics(a)` makes the epoch's dict of that list; `on_epoch(ep, dict)`; `save_module` (default: the model) is saved
+    when ep % save_every == 0, and once more after the last epoch.  Returns the list of the dicts."""
+    dev = _device_of(model)
+    save_module = model if save_module is None else save_module
+    history = []
+    for ep in range(epochs):
+        model.train()
+        acc = torch.zeros(n_acc, dtype=torch.float64, device=dev)
+        for batch in batches(ep):
+            train_batch(batch, acc)
+        if per_epoch is not None:
+            per_epoch()
+        model.eval()
+        test_pass(acc)
+        history.append(metrics(acc.tolist()))
+        if on_epoch is not None:
+            on_epoch(ep, history[-1])
+        if save_path is not None and ep % save_every == 0:
+            _save_state(save_module, save_path)
+    if save_path is not None:
+        _save_state(save_module, save_path)
+    return history
+
+
+def _graphed_or_eager(graphed, batch_size, build, replay, eager):
+    """run(*batch) of a loop with a graph mode.  A full batch (batch[0].shape[0] == batch_size) of a graphed loop goes to
+    `replay(graph, *batch)`, where `graph = build(*batch)` is made of the first full batch; every other batch, and every
+    batch of an eager loop, goes to `eager(*batch)`."""
+    graph = None
+
+    def run(*batch):
+        nonlocal graph
+        if not (graphed and batch[0].shape[0] == batch_size):
+            return eager(*batch)
+        if graph is None:
+            graph = build(*batch)
+        return replay(graph, *batch)
+
+    return run
 
 
 @torch.no_grad()
@@ -719,15 +771,7 @@ def _darcy_setup(model, data, want_train=True):
     yn = copy.copy(data["y_normalizer"]).to(dev)
     train = ResidentDataset(data["x_train"], data["y_train"], device=dev) if want_train else None
     test = ResidentDataset(data["x_test"], data["y_test"], device=dev)
-    pos1 = grid_positions(data["s"]).to(dev)
-    pos = {}
-
-    def positions(bsz):         # one [bsz, N, 2] copy per batch size (full and short batch), not one per sample
-        if bsz not in pos:
-            pos[bsz] = pos1.expand(bsz, -1, -1).contiguous()
-        return pos[bsz]
-
-    return dev, yn, train, test, positions
+    return dev, yn, train, test, _positions_cache(grid_positions(data["s"]).to(dev))
 
 
 def evaluate_darcy(model, data, batch_size, loss_fn=None):
@@ -761,40 +805,28 @@ def fit_ns(model, optimizer, scheduler, train, test, *, epochs, batch_size, T=10
     calls the optimizer's own `sync` (the same bucket), and clips through the optimizer only: `max_grad_norm` together
     with `graphed=True` raises.
     `on_epoch(ep, metrics)`: called after every epoch's synchronisation (progress lines of a command line)."""
-    if graphed and max_grad_norm is not None:
-        raise ValueError("fit_ns(graphed=True) clips inside optim.FusedAdamW: build it with max_grad_norm=... and pass "
-                         "max_grad_norm=None here (a replayed batch would otherwise go unclipped)")
+    if graphed:
+        _graphed_refusals("fit_ns", optimizer, max_grad_norm, one_rank=False)
     loss_fn = loss_fn or TestLoss(size_average=False)
-    dev = _device_of(model)
     ntrain, ntest, calls = len(train), len(test), T / step
-    graph = None
-    history = []
-    for ep in range(epochs):
-        model.train()
-        acc = torch.zeros(4, dtype=torch.float64, device=dev)
-        for x, fx, yy in _epoch_batches(train, batch_size, ep, epoch_orders, generator):
-            yy = yy[..., :T]
-            if graphed and x.shape[0] == batch_size:
-                if graph is None:
-                    graph = GraphedTrainStep(model, optimizer, scheduler, x, fx, yy, step=step, loss_fn=loss_fn)
-                loss, full = graph(x, fx, yy)
-            else:
-                loss, full = train_step(model, optimizer, scheduler, x, fx, yy, step=step, max_grad_norm=max_grad_norm,
-                                        grad_sync=grad_sync, loss_fn=loss_fn)
-            acc[0] += loss
-            acc[1] += full
-        model.eval()
-        _ns_test_pass(model, test, batch_size, T, step, loss_fn, acc)
-        a = acc.tolist()                                         # the epoch's only host synchronisation
-        history.append(dict(train_step=a[0] / ntrain / calls, train_full=a[1] / ntrain,
-                            test_step=a[2] / ntest / calls, test_full=a[3] / ntest))
-        if on_epoch is not None:
-            on_epoch(ep, history[-1])
-        if save_path is not None and ep % save_every == 0:
-            _save_state(model, save_path)
-    if save_path is not None:
-        _save_state(model, save_path)
-    return history
+    run = _graphed_or_eager(
+        graphed, batch_size,
+        lambda x, fx, yy: GraphedTrainStep(model, optimizer, scheduler, x, fx, yy, step=step, loss_fn=loss_fn),
+        lambda graph, x, fx, yy: graph(x, fx, yy),
+        lambda x, fx, yy: train_step(model, optimizer, scheduler, x, fx, yy, step=step, max_grad_norm=max_grad_norm,
+                                     grad_sync=grad_sync, loss_fn=loss_fn))
+
+    def train_batch(batch, acc):
+        x, fx, yy = batch
+        loss, full = run(x, fx, yy[..., :T])
+        acc[0] += loss
+        acc[1] += full
+
+    return _fit(model, epochs=epochs, n_acc=4, batches=lambda ep: _epoch_batches(train, batch_size, ep, epoch_orders, generator),
+                train_batch=train_batch, test_pass=lambda acc: _ns_test_pass(model, test, batch_size, T, step, loss_fn, acc),
+                metrics=lambda a: dict(train_step=a[0] / ntrain / calls, train_full=a[1] / ntrain,
+                                           test_step=a[2] / ntest / calls, test_full=a[3] / ntest),
+                on_epoch=on_epoch, save_path=save_path, save_every=save_every)
 
 
 def fit_unrolled(sol_model, optimizer, scheduler, train, test, *, epochs, batch_size, T=10, step=1, look_ahead=1,
@@ -811,38 +843,28 @@ def fit_unrolled(sol_model, optimizer, scheduler, train, test, *, epochs, batch_
     look_ahead = the epoch's look-ahead.  One host synchronisation per epoch.  Saves
     `sol_model.transolver_model.state_dict()` (ep % save_every == 0 and after the last epoch).  No graph mode."""
     loss_fn = loss_fn or TestLoss(size_average=False)
-    dev = _device_of(sol_model)
     ntest, calls = len(test), T / step
     curriculum = LookAheadCurriculum(epochs, look_ahead, max_look_ahead)
     inner = sol_model.transolver_model
     sol_model.n = look_ahead
-    history = []
-    for ep in range(epochs):
-        sol_model.train()
-        acc = torch.zeros(4, dtype=torch.float64, device=dev)
-        la = curriculum.update(ep)
-        for x, fx, yy in _epoch_batches(train, batch_size, ep, epoch_orders, generator):
-            with ops.weights_frozen():
-                loss = unrolled_train_iteration(sol_model, x, fx, yy[..., :T], la, step, loss_fn)
-                optimizer.zero_grad()
-                loss.backward()
-            if grad_sync is not None:
-                grad_sync()
-            optimizer.step()
-            if scheduler is not None:
-                scheduler.step()
-            acc[0] += loss.detach()
-        sol_model.eval()
-        _ns_test_pass(inner, test, batch_size, T, step, loss_fn, acc, full=False)
-        a = acc.tolist()
-        history.append(dict(train_step=a[0], test_step=a[2] / ntest / calls, look_ahead=la))
-        if on_epoch is not None:
-            on_epoch(ep, history[-1])
-        if save_path is not None and ep % save_every == 0:
-            _save_state(inner, save_path)
-    if save_path is not None:
-        _save_state(inner, save_path)
-    return history
+
+    def batches(ep):
+        curriculum.update(ep)                # before the epoch's first batch; curriculum.look_ahead then holds for the epoch
+        return _epoch_batches(train, batch_size, ep, epoch_orders, generator)
+
+    def train_batch(batch, acc):
+        x, fx, yy = batch
+        with ops.weights_frozen():
+            loss = unrolled_train_iteration(sol_model, x, fx, yy[..., :T], curriculum.look_ahead, step, loss_fn)
+            optimizer.zero_grad()
+            loss.backward()
+        _apply_step(optimizer, scheduler, (), None, grad_sync)           # this loop never clips
+        acc[0] += loss.detach()
+
+    return _fit(sol_model, epochs=epochs, n_acc=4, batches=batches, train_batch=train_batch,
+                test_pass=lambda acc: _ns_test_pass(inner, test, batch_size, T, step, loss_fn, acc, full=False),
+                metrics=lambda a: dict(train_step=a[0], test_step=a[2] / ntest / calls, look_ahead=curriculum.look_ahead),
+                on_epoch=on_epoch, save_path=save_path, save_every=save_every, save_module=inner)
 
 
 def fit_darcy(model, optimizer, scheduler, data, *, epochs, batch_size, max_grad_norm=None, loss_fn=None,
@@ -871,37 +893,26 @@ def fit_darcy(model, optimizer, scheduler, data, *, epochs, batch_size, max_grad
         if not fused:
             raise ValueError("fit_darcy(graphed=True) captures the fused Darcy loss: leave fused=True")
     test_loss = loss_fn or TestLoss(size_average=False)
-    dev, yn, train, test, positions = _darcy_setup(model, data)
+    _, yn, train, test, positions = _darcy_setup(model, data)
     s, dx = data["s"], data["dx"]
     ntrain, ntest = len(train), len(test)
-    graph = None
-    history = []
-    for ep in range(epochs):
-        model.train()
-        acc = torch.zeros(3, dtype=torch.float64, device=dev)
-        for fx, y in _epoch_batches(train, batch_size, ep, epoch_orders, generator):
-            if graphed and fx.shape[0] == batch_size:
-                if graph is None:
-                    graph = GraphedCallStep(model, optimizer, scheduler, (positions(batch_size), fx.clone(), y.clone()),
-                                            _darcy_body(yn, dx, s))
-                _, l2, deriv = graph(None, fx, y)
-            else:
-                _, l2, deriv = darcy_train_step(model, optimizer, scheduler, positions(fx.shape[0]), fx, y, yn, dx, s,
-                                                max_grad_norm=max_grad_norm, grad_sync=grad_sync, fused=fused,
-                                                loss_fn=loss_fn)
-            acc[0] += l2
-            acc[1] += deriv
-        model.eval()
-        _darcy_test_pass(model, test, batch_size, positions, yn, test_loss, acc)
-        a = acc.tolist()
-        history.append(dict(reg=a[1] / ntrain, train_loss=a[0] / ntrain, rel_err=a[2] / ntest))
-        if on_epoch is not None:
-            on_epoch(ep, history[-1])
-        if save_path is not None and ep % save_every == 0:
-            _save_state(model, save_path)
-    if save_path is not None:
-        _save_state(model, save_path)
-    return history
+    run = _graphed_or_eager(
+        graphed, batch_size,
+        lambda fx, y: GraphedCallStep(model, optimizer, scheduler, (positions(batch_size), fx.clone(), y.clone()),
+                                      _darcy_body(yn, dx, s)),
+        lambda graph, fx, y: graph(None, fx, y),
+        lambda fx, y: darcy_train_step(model, optimizer, scheduler, positions(fx.shape[0]), fx, y, yn, dx, s,
+                                       max_grad_norm=max_grad_norm, grad_sync=grad_sync, fused=fused, loss_fn=loss_fn))
+
+    def train_batch(batch, acc):
+        _, l2, deriv = run(*batch)
+        acc[0] += l2
+        acc[1] += deriv
+
+    return _fit(model, epochs=epochs, n_acc=3, batches=lambda ep: _epoch_batches(train, batch_size, ep, epoch_orders, generator),
+                train_batch=train_batch, test_pass=lambda acc: _darcy_test_pass(model, test, batch_size, positions, yn, test_loss, acc),
+                metrics=lambda a: dict(reg=a[1] / ntrain, train_loss=a[0] / ntrain, rel_err=a[2] / ntest),
+                on_epoch=on_epoch, save_path=save_path, save_every=save_every)
 
 
 # ------------------------------------------------------------------ exp_airfoil / exp_pipe / exp_elas: one call per batch
@@ -927,13 +938,7 @@ def static_train_step(model, optimizer, scheduler, x, y, y_normalizer=None, max_
     out = model(x, None).squeeze(-1)
     loss = _rel_decoded(loss_fn, out, y, y_normalizer)
     loss.backward()
-    if grad_sync is not None:
-        grad_sync()
-    if max_grad_norm is not None:
-        torch.nn.utils.clip_grad_norm_(model.parameters(), max_grad_norm)
-    optimizer.step()
-    if scheduler is not None:
-        scheduler.step()
+    _apply_step(optimizer, scheduler, model.parameters(), max_grad_norm, grad_sync)
     return loss.detach()
 
 
@@ -990,35 +995,24 @@ def fit_static(model, optimizer, scheduler, data, *, epochs, batch_size, max_gra
         _graphed_refusals("fit_static", optimizer, max_grad_norm)
         _capturable_model(model, "fit_static")
     loss_fn = loss_fn or TestLoss(size_average=False)
-    dev, yn, train, test = _static_setup(model, data)
+    _, yn, train, test = _static_setup(model, data)
     ntrain, ntest = len(train), len(test)
     batch_sched = None if scheduler_per_epoch else scheduler
-    graph = None
-    history = []
-    for ep in range(epochs):
-        model.train()
-        acc = torch.zeros(2, dtype=torch.float64, device=dev)
-        for x, y in _epoch_batches(train, batch_size, ep, epoch_orders, generator):
-            if graphed and x.shape[0] == batch_size:
-                if graph is None:
-                    graph = GraphedCallStep(model, optimizer, batch_sched, (x.clone(), y.clone()), _static_body(loss_fn, yn))
-                acc[0] += graph(x, y)[0]
-            else:
-                acc[0] += static_train_step(model, optimizer, batch_sched, x, y, yn, max_grad_norm=max_grad_norm,
-                                            grad_sync=grad_sync, loss_fn=loss_fn)
-        if scheduler_per_epoch and scheduler is not None:
-            scheduler.step()
-        model.eval()
-        _static_test_pass(model, test, batch_size, yn, loss_fn, acc)
-        a = acc.tolist()                                         # the epoch's only host synchronisation
-        history.append(dict(train_loss=a[0] / ntrain, rel_err=a[1] / ntest))
-        if on_epoch is not None:
-            on_epoch(ep, history[-1])
-        if save_path is not None and ep % save_every == 0:
-            _save_state(model, save_path)
-    if save_path is not None:
-        _save_state(model, save_path)
-    return history
+    run = _graphed_or_eager(
+        graphed, batch_size,
+        lambda x, y: GraphedCallStep(model, optimizer, batch_sched, (x.clone(), y.clone()), _static_body(loss_fn, yn)),
+        lambda graph, x, y: graph(x, y)[0],
+        lambda x, y: static_train_step(model, optimizer, batch_sched, x, y, yn, max_grad_norm=max_grad_norm,
+                                       grad_sync=grad_sync, loss_fn=loss_fn))
+
+    def train_batch(batch, acc):
+        acc[0] += run(*batch)
+
+    return _fit(model, epochs=epochs, n_acc=2, batches=lambda ep: _epoch_batches(train, batch_size, ep, epoch_orders, generator),
+                train_batch=train_batch, test_pass=lambda acc: _static_test_pass(model, test, batch_size, yn, loss_fn, acc),
+                metrics=lambda a: dict(train_loss=a[0] / ntrain, rel_err=a[1] / ntest),
+                on_epoch=on_epoch, save_path=save_path, save_every=save_every,
+                per_epoch=scheduler.step if scheduler_per_epoch and scheduler is not None else None)
 
 
 # ------------------------------------------------------------------ exp_plas: T time-conditioned calls and steps per batch
@@ -1036,11 +1030,7 @@ def plas_train_step(model, optimizer, x, fx, tim, yy, max_grad_norm=None, grad_s
         total = total + loss.detach()
         optimizer.zero_grad(set_to_none=False)
         loss.backward()
-        if grad_sync is not None:
-            grad_sync()
-        if max_grad_norm is not None:
-            torch.nn.utils.clip_grad_norm_(model.parameters(), max_grad_norm)
-        optimizer.step()
+        _apply_step(optimizer, None, model.parameters(), max_grad_norm, grad_sync)
     return total
 
 
@@ -1065,14 +1055,7 @@ def _plas_setup(model, data, want_train=True):
     dev = _device_of(model)
     train = ResidentDataset(data["x_train"], data["y_train"], device=dev) if want_train else None
     test = ResidentDataset(data["x_test"], data["y_test"], device=dev)
-    pos1, pos = data["pos"].to(dev), {}
-
-    def positions(bsz):
-        if bsz not in pos:
-            pos[bsz] = pos1.expand(bsz, -1, -1).contiguous()
-        return pos[bsz]
-
-    return dev, train, test, positions, data["t"].to(dev)
+    return dev, train, test, _positions_cache(data["pos"].to(dev)), data["t"].to(dev)
 
 
 def evaluate_plas(model, data, batch_size, loss_fn=None):
@@ -1112,11 +1095,8 @@ def fit_plas(model, optimizer, scheduler, data, *, epochs, batch_size, max_grad_
     loss_fn = loss_fn or TestLoss(size_average=False)
     dev, train, test, positions, t = _plas_setup(model, data)
     ntrain, ntest, T = len(train), len(test), t.numel()
-    graph = None
-    history = []
-    for ep in range(epochs):
-        model.train()
-        acc = torch.zeros(3, dtype=torch.float64, device=dev)
+
+    def batches(ep):       # (fx, yy, perm [B, T]): a batch's time permutations are drawn right after the batch itself
         seen = 0
         for fx, yy in _epoch_batches(train, batch_size, ep, epoch_orders, generator):
             bsz = fx.shape[0]
@@ -1126,31 +1106,33 @@ def fit_plas(model, optimizer, scheduler, data, *, epochs, batch_size, max_grad_
                 gdev = dev if generator is None else generator.device
                 perm = torch.rand(bsz, T, generator=generator, device=gdev).argsort(dim=1).to(dev)
             seen += bsz
-            tim = t[perm]                                                        # [B, T]
-            yy = yy.gather(-1, perm[:, None, None, :].expand_as(yy))             # u[..., permuted_indices] per sample
-            if graphed and bsz == batch_size:
-                if graph is None:
-                    graph = GraphedCallStep(model, optimizer, None, (positions(bsz), fx.clone(), tim[:, :1].clone(), yy.clone()),
-                                            _plas_body(loss_fn))
-                graph.static[1].copy_(fx)                                        # the window: once per batch
-                total = 0
-                for k in range(T):
-                    graph.static[3][..., 0].copy_(yy[..., k])                    # the target column and the time: per replay
-                    total = total + graph(None, None, tim[:, k:k + 1], None)[0]
-                acc[0] += total
-            else:
-                acc[0] += plas_train_step(model, optimizer, positions(bsz), fx, tim, yy, max_grad_norm=max_grad_norm,
-                                          grad_sync=grad_sync, loss_fn=loss_fn)
-            if scheduler is not None:
-                scheduler.step()
-        model.eval()
-        _plas_test_pass(model, test, batch_size, positions, t, loss_fn, acc)
-        a = acc.tolist()
-        history.append(dict(train_step=a[0] / ntrain / T, test_step=a[1] / ntest / T, test_full=a[2] / ntest))
-        if on_epoch is not None:
-            on_epoch(ep, history[-1])
-        if save_path is not None and ep % save_every == 0:
-            _save_state(model, save_path)
-    if save_path is not None:
-        _save_state(model, save_path)
-    return history
+            yield fx, yy, perm
+
+    def replay(graph, fx, tim, yy):
+        graph.static[1].copy_(fx)                                            # the window: once per batch
+        total = 0
+        for k in range(T):
+            graph.static[3][..., 0].copy_(yy[..., k])                        # the target column and the time: per replay
+            total = total + graph(None, None, tim[:, k:k + 1], None)[0]
+        return total
+
+    run = _graphed_or_eager(
+        graphed, batch_size,
+        lambda fx, tim, yy: GraphedCallStep(model, optimizer, None, (positions(batch_size), fx.clone(), tim[:, :1].clone(), yy.clone()),
+                                            _plas_body(loss_fn)),
+        replay,
+        lambda fx, tim, yy: plas_train_step(model, optimizer, positions(fx.shape[0]), fx, tim, yy, max_grad_norm=max_grad_norm,
+                                            grad_sync=grad_sync, loss_fn=loss_fn))
+
+    def train_batch(batch, acc):
+        fx, yy, perm = batch
+        tim = t[perm]                                                            # [B, T]
+        yy = yy.gather(-1, perm[:, None, None, :].expand_as(yy))                 # u[..., permuted_indices] per sample
+        acc[0] += run(fx, tim, yy)
+        if scheduler is not None:
+            scheduler.step()
+
+    return _fit(model, epochs=epochs, n_acc=3, batches=batches, train_batch=train_batch,
+                test_pass=lambda acc: _plas_test_pass(model, test, batch_size, positions, t, loss_fn, acc),
+                metrics=lambda a: dict(train_step=a[0] / ntrain / T, test_step=a[1] / ntest / T, test_full=a[2] / ntest),
+                on_epoch=on_epoch, save_path=save_path, save_every=save_every)
