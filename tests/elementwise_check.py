@@ -13,6 +13,9 @@ element instead:
   with a sentinel (all-ones bytes = NaN in fp32 and bf16, then 0x71 bytes = 1.2e30), asserts that every output tensor
   lives in such a buffer, that both results are finite and that they are bit-identical: an element a kernel never
   writes, or writes differently from run to run, fails.
+* `to_planes` / `unplane` / `check_canonical_planes`: the bf16 plane images of the operand-planes route
+  (tests/test_gpu_planes_elementwise.py), built and taken apart in plain torch, and the exact condition that an image
+  is the canonical hi / mid / lo split of the value it holds.
 
 The failure messages name the worst element with its row modulo 16 / 32 / 128, its column modulo 64 / 128, the count of
 violating elements, the residues mod 32 of the violating rows and, for convs (`hw=(H, W)`), the pixel and whether it
@@ -135,6 +138,61 @@ def check_rows(got, ref, tol, *, hw=None, label=""):
             f"{label}: {int(bad.sum())} of {rel.numel()} rows exceed rel-L2 {tol:.3g}; worst {where}: rel-L2 "
             f"{worst:.3g}; violating {_row_summary(bad.nonzero().flatten(), hw)}")
     return worst
+
+
+# ---------------------------------------------------------------------------------------------- bf16 plane images
+# The operand-planes route hands a [rows, C] fp32 tensor on as a byte image [row][C / 32][nt][32] bf16 (nt = 3: the exact
+# split p0 = bf16(x), p1 = bf16(x - p0), p2 = bf16(x - p0 - p1), round-to-nearest-even; nt = 1: bf16(x)): element
+# (row, c, plane q) sits at byte row * (C / 32) * nt * 64 + ((c >> 5) * nt + q) * 64 + (c & 31) * 2.
+def to_planes(x, nt):
+    """fp32 [rows, C] -> flat uint8 plane image (plain torch, CPU or GPU)."""
+    x = torch.as_tensor(x).detach().to(torch.float32)
+    rows, C = x.shape
+    assert C % 32 == 0 and nt in (1, 3), (C, nt)
+    planes, r = [], x
+    for q in range(nt):
+        p = r.bfloat16()
+        planes.append(p.view(rows, C // 32, 32))
+        if q + 1 < nt:
+            r = r - p.float()            # exact in fp32
+    return torch.stack(planes, 2).contiguous().view(torch.uint8).reshape(-1)
+
+
+def unplane(img, rows, C, nt):
+    """(planes [nt, rows, C] bf16, their fp64 sum [rows, C]) of a plane image."""
+    assert img.numel() * img.element_size() == rows * C * nt * 2, (img.numel(), rows, C, nt)
+    p = img.reshape(-1).view(torch.bfloat16).view(rows, C // 32, nt, 32).permute(2, 0, 1, 3).reshape(nt, rows, C)
+    return p, p.double().sum(0)
+
+
+def check_canonical_planes(img, rows, C, nt, *, label=""):
+    """Assert that the image is the canonical split of the value it holds: every plane finite and, for nt = 3,
+    to_planes(p0 + p1 + p2) == img bit for bit (the sum of a canonical split is an fp32 number, and the split of that
+    number is unique).  Exact, no tolerance: swapped planes, a plane in the wrong slot and a stale plane fail, and the
+    message names rows, channels and planes.  nt = 1: any finite bf16 is its own split, so finiteness only.  Returns
+    the fp64 sum [rows, C]."""
+    planes, total = unplane(img, rows, C, nt)
+    bad = ~torch.isfinite(planes.float())                                        # [nt, rows, C]
+    what = "not finite (never written?)"
+    if not bool(bad.any()) and nt > 1:
+        x = total.float()
+        x = torch.where(x == 0, planes[0].float(), x)                           # keeps the sign of a zero
+        want, _ = unplane(to_planes(x, nt), rows, C, nt)
+        bad = planes.view(torch.int16) != want.view(torch.int16)
+        what = "not the canonical split of their own sum"
+    if bool(bad.any()):
+        elem = bad.any(0)                                                        # [rows, C]
+        badrows = elem.any(1).nonzero().flatten()
+        row = int(badrows[0])
+        cols = elem[row].nonzero().flatten()
+        col = int(cols[0])
+        held = ", ".join(f"p{q} = {float(planes[q, row, col]):.9g}" for q in range(nt))
+        raise AssertionError(
+            f"{label}: {int(elem.sum())} of {rows * C} elements of the {nt}-plane image are {what} (planes "
+            f"{sorted(set(bad.any(2).any(1).nonzero().flatten().tolist()))}); first at {_where(row, col, None)}, 32-channel "
+            f"chunk {col >> 5} of {C // 32}: {held}; channels [{int(cols.min())} .. {int(cols.max())}] of that row; violating "
+            f"{_row_summary(badrows, None)}")
+    return total
 
 
 # ---------------------------------------------------------------------------------------------- poisoned outputs

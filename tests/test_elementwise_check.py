@@ -262,3 +262,173 @@ def test_every_bound_rejects_its_corruptions(gemm):
     for eng in ROW_TOL:
         with pytest.raises(AssertionError, match="row 33333"):
             check_rows(got, ref, ROW_TOL[eng], label=eng)
+
+
+# ---------------------------------------------------------------------------------------------- bf16 plane images
+# to_planes / unplane / check_canonical_planes (the operand-planes route, tests/test_gpu_planes_elementwise.py).
+def _wide(rows, C, seed):
+    g = torch.Generator().manual_seed(seed)
+    return torch.randn(rows, C, generator=g) * torch.exp(3 * torch.randn(rows, C, generator=g))
+
+
+@pytest.mark.parametrize("nt", [1, 3])
+@pytest.mark.parametrize("rows,C", [(37, 160), (5, 32), (64, 256)])
+def test_planes_round_trip(rows, C, nt):
+    from elementwise_check import check_canonical_planes, to_planes, unplane
+    x = _wide(rows, C, rows + C)
+    x[0, :4] = torch.tensor([0.0, -0.0, 1.0, -2.0 ** -100])
+    img = to_planes(x, nt)
+    assert img.dtype == torch.uint8 and img.numel() == rows * C * nt * 2
+    planes, total = unplane(img, rows, C, nt)
+    assert planes.shape == (nt, rows, C) and planes.dtype == torch.bfloat16
+    if nt == 3:      # the split is exact, and every plane is at most half a bf16 ulp of the one above it
+        assert torch.equal(total, x.double())
+        p = planes.double().abs()
+        assert bool((p[1] <= 2.0 ** -8 * p[0]).all()) and bool((p[2] <= 2.0 ** -8 * p[1]).all())
+    else:
+        assert torch.equal(total, x.bfloat16().double())
+    assert torch.equal(check_canonical_planes(img, rows, C, nt, label="clean"), total)
+    x[0, 1] = 0.0                        # the plane sum of a negative zero is +0: the check takes the sign from p0
+    assert torch.equal(to_planes(unplane(to_planes(x, nt), rows, C, nt)[1].float(), nt), to_planes(x, nt))
+
+
+@pytest.mark.parametrize("nt", [1, 3])
+def test_planes_byte_offsets(nt):
+    """element (row, c, plane q) at byte row (C/32) nt 64 + ((c >> 5) nt + q) 64 + (c & 31) 2: the kernels' formula"""
+    from elementwise_check import to_planes
+    rows, C = 11, 160
+    x = _wide(rows, C, 3)
+    img = to_planes(x, nt).view(torch.int16)           # 2-byte units
+    r = x.clone()
+    for q in range(nt):
+        p = r.bfloat16()
+        r = r - p.float()
+        row, c = torch.meshgrid(torch.arange(rows), torch.arange(C), indexing="ij")
+        off = row * (C // 32) * nt * 64 + ((c >> 5) * nt + q) * 64 + (c & 31) * 2
+        assert torch.equal(img[off // 2], p.view(torch.int16)), q
+
+
+def _canonical_fails(img, rows, C, nt, label):
+    from elementwise_check import check_canonical_planes
+    with pytest.raises(AssertionError) as e:
+        check_canonical_planes(img, rows, C, nt, label=label)
+    return str(e.value)
+
+
+def test_canonical_planes_rejects_swapped_stale_and_misplaced():
+    from elementwise_check import SENTINEL_BYTES, to_planes
+    rows, C, nt = 40, 160, 3
+    x = _wide(rows, C, 9)
+    img = to_planes(x, nt)
+    v = lambda t: t.view(rows, C // 32, nt, 64)        # [row][chunk][plane][64 bytes]
+    # mid and lo swapped in one chunk of one row: same plane sum, so a value comparison cannot see it
+    sw = img.clone()
+    v(sw)[17, 3, 1], v(sw)[17, 3, 2] = v(img)[17, 3, 2], v(img)[17, 3, 1]
+    msg = _canonical_fails(sw, rows, C, nt, "swapped")
+    assert "row 17 (" in msg and "chunk 3 of 5" in msg and "planes [1, 2]" in msg and "1 distinct rows [17 .. 17]" in msg, msg
+    lo, hi = (int(s) for s in msg.split("channels [")[1].split("]")[0].split(" .. "))
+    assert 96 <= lo <= hi < 128, msg
+    # ... everywhere
+    sw = img.clone()
+    v(sw)[:, :, 1], v(sw)[:, :, 2] = v(img)[:, :, 2], v(img)[:, :, 1]
+    assert f"{rows} distinct rows" in _canonical_fails(sw, rows, C, nt, "all swapped")
+    # mid written into the hi slot and hi into the mid slot
+    sw = img.clone()
+    v(sw)[5, 0, 0], v(sw)[5, 0, 1] = v(img)[5, 0, 1], v(img)[5, 0, 0]
+    assert "row 5 (" in _canonical_fails(sw, rows, C, nt, "hi / mid")
+    for byte in SENTINEL_BYTES:      # what `poisoned` leaves in an element no kernel wrote
+        # one stale row
+        st = img.clone()
+        v(st)[23] = byte
+        msg = _canonical_fails(st, rows, C, nt, "stale row")
+        assert "row 23 (" in msg and "col 0 (" in msg and "channels [0 .. 159]" in msg and "1 distinct rows" in msg, msg
+        # one stale plane of one chunk
+        st = img.clone()
+        v(st)[2, 4, 2] = byte
+        msg = _canonical_fails(st, rows, C, nt, "stale plane")
+        assert "row 2 (" in msg and "chunk 4 of 5" in msg, msg
+        # a head's chunk written at the neighbouring head's offset: its own place keeps the sentinel
+        mis = img.clone()
+        v(mis)[31, 2] = v(img)[31, 1]
+        v(mis)[31, 1] = byte
+        msg = _canonical_fails(mis, rows, C, nt, "misplaced chunk")
+        assert "row 31 (" in msg and "col 32 (" in msg and "chunk 1 of 5" in msg, msg
+        # a quarter chunk (D = 8: four heads share a chunk) at the neighbouring head's offset, in every plane
+        mis = img.clone()
+        v(mis)[8, 0, :, 16:32] = v(img)[8, 0, :, 0:16]
+        v(mis)[8, 0, :, 0:16] = byte
+        msg = _canonical_fails(mis, rows, C, nt, "misplaced head")
+        assert "row 8 (" in msg and "channels [0 .. 7]" in msg, msg
+    # one plane: any finite bf16 is canonical, an unwritten (NaN-sentinel) one is not; the 0x71 sentinel is left to
+    # `poisoned`, whose two runs differ in such an element
+    img1 = to_planes(x, 1)
+    st = img1.clone()
+    st.view(rows, C // 32, 1, 64)[23] = SENTINEL_BYTES[0]
+    assert "row 23 (" in _canonical_fails(st, rows, C, 1, "stale row, one plane")
+
+    def stale_op(x):
+        out = torch.empty(rows * C * 2, dtype=torch.uint8)
+        out.copy_(to_planes(x, 1))
+        out.view(rows, C * 2)[23] = torch.empty(C * 2, dtype=torch.uint8)      # never written
+        return out.view(torch.bfloat16)
+
+    with pytest.raises(AssertionError, match="unwritten|differs between two runs"):
+        poisoned(stale_op, x)
+
+
+def test_swapped_planes_fail_the_forward_bound():
+    """A GEMM that reads an image with mid and lo swapped keeps hi w2 + lo w1 + ... and loses mid w1: at most 2^-16 per
+    product.  Where the residuals of both operands have one sign (here: every value just below a bf16 tie) the lost terms
+    add up and TAU[("split", "fwd")] fires.  With residuals of random sign they average out, to about 4e-6 / sqrt(K) of the
+    scale: 5e-7 at a conv's K = 9 * 128 below, under the bound.  (On the MI355X the conv backward of chain case B, fed such
+    an image from a scratch build, reached 1.9e-6 on the data gradient and 2.4e-6 on dwx against 1.6e-6 / 1e-6: it fires, but
+    by too little to rely on.)  That is why the image itself is held to check_canonical_planes, which is exact."""
+    from elementwise_check import to_planes, unplane
+    rows, N, K = 64, 96, 9 * 32
+    g = torch.Generator().manual_seed(4)
+
+    def below_tie(*shape):      # 2^e (1 + k / 128 + f / 256), k < 16, f in [0.45, 0.5): mid = +f 2^(e - 8), > 1.6e-3 |x|
+        e = torch.randint(-2, 2, shape, generator=g).float()
+        k = torch.randint(0, 16, shape, generator=g).float()
+        f = 0.45 + 0.05 * torch.rand(shape, generator=g)
+        return (2.0 ** e * (1 + k / 128 + f / 256)).float()
+
+    a, w = below_tie(rows, K), below_tie(N, K) / 16
+    ref, scale = a.double() @ w.double().t(), a.double().abs() @ w.double().abs().t()
+    pw = _planes(w)
+
+    def gemm_from(img):
+        pa, _ = unplane(img, rows, K, 3)
+        out = torch.zeros(rows, N, dtype=torch.float64)
+        for i in range(3):
+            for j in range(3):
+                if i + j <= 2:
+                    out += pa[i].double() @ pw[j].double().t()
+        return out.float()
+
+    img = to_planes(a, 3)
+    tau = TAU[("split", "fwd")]
+    assert check_products(gemm_from(img), ref, scale, tau, label="clean image") < tau / 2
+    sw = img.clone()
+    v, v0 = sw.view(rows, K // 32, 3, 64), img.view(rows, K // 32, 3, 64)
+    v[:, :, 1], v[:, :, 2] = v0[:, :, 2], v0[:, :, 1]
+    assert torch.equal(unplane(sw, rows, K, 3)[1], unplane(img, rows, K, 3)[1])      # same plane sums
+    worst = check_products(gemm_from(sw), ref, scale, 1.0, label="swapped image")
+    print(f"swapped image, residuals of one sign: worst |err| / scale {worst:.3g}")
+    with pytest.raises(AssertionError, match="swapped image"):
+        check_products(gemm_from(sw), ref, scale, tau, label="swapped image")
+    # residuals of random sign at a conv's depth (K = 9 * 128): the same swap stays below the bound, and the image check
+    # is what rejects it
+    K2 = 9 * 128
+    a2 = torch.randn(rows, K2, generator=g)
+    w2 = torch.randn(N, K2, generator=g) * K2 ** -0.5
+    ref2, scale2 = a2.double() @ w2.double().t(), a2.double().abs() @ w2.double().abs().t()
+    sw2 = to_planes(a2, 3)
+    v = sw2.view(rows, K2 // 32, 3, 64)
+    v[:, :, 1], v[:, :, 2] = v[:, :, 2].clone(), v[:, :, 1].clone()
+    pa, pw2 = unplane(sw2, rows, K2, 3)[0], _planes(w2)
+    out = sum(pa[i].double() @ pw2[j].double().t() for i in range(3) for j in range(3) if i + j <= 2).float()
+    worst = check_products(out, ref2, scale2, 1.0, label="random signs")
+    print(f"swapped image, residuals of random sign, K = {K2}: worst |err| / scale {worst:.3g}")
+    assert worst < tau
+    _canonical_fails(sw2, rows, K2, 3, "swapped image, random signs")
