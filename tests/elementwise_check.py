@@ -16,6 +16,10 @@ element instead:
 * `to_planes` / `unplane` / `check_canonical_planes`: the bf16 plane images of the operand-planes route
   (tests/test_gpu_planes_elementwise.py), built and taken apart in plain torch, and the exact condition that an image
   is the canonical hi / mid / lo split of the value it holds.
+* `check_abs_rel(got, ref, a, r)`, `adamw_reference`, `exact_sum_probes` / `decode_probe_sum`, `flat_where`: the flat
+  streaming kernels of the step tail (tests/test_gpu_step_tail_elementwise.py): |got - ref| <= a + r |ref| per element with
+  a message that names the grid-stride trip or the scalar tail, the fp64 statement of one AdamW step with its scales, and
+  sums of powers of two that must come out exact and say which term was dropped or doubled when they do not.
 
 The failure messages name the worst element with its row modulo 16 / 32 / 128, its column modulo 64 / 128, the count of
 violating elements, the residues mod 32 of the violating rows and, for convs (`hw=(H, W)`), the pixel and whether it
@@ -28,6 +32,7 @@ the corruptions these values reject: see the docstrings of test_gpu_elementwise.
 from __future__ import annotations
 
 import contextlib
+import math
 
 import torch
 
@@ -266,3 +271,135 @@ def poisoned(fn, *args, **kwargs):
                                  f"{int(diff.sum())} elements (unwritten, or not deterministic); first at index "
                                  f"{_unravel(flat, tuple(a.shape))}")
     return out0
+
+
+# ---------------------------------------------------------------------------------------------- the step tail
+# The flat streaming kernels of the step tail (sum of squares, AdamW): 256 threads x one float4 = 1024 floats per workgroup
+# sweep, a grid of min(ceil(n / 1024), 2048) workgroups that strides over the float4 body in "trips" of grid * 1024 floats,
+# and a scalar tail of n % 4 floats done by workgroup 0 (csrc/pa2d_optim.hip: stream_blocks, adamw_body).
+SWEEP, MAX_BLOCKS = 1024, 2048
+FLAT_MODS = (4, 256, 1024)
+EPS32 = 2.0 ** -24          # half an ulp of 1: one fp32 rounding
+ULP32 = 2.0 ** -23          # the floor of every yardstick-derived bound
+
+
+def stream_grid(n):
+    return max(1, min(-(-n // SWEEP), MAX_BLOCKS))
+
+
+def stream_trips(n, grid=None, vec=4):
+    grid = stream_grid(n) if grid is None else grid
+    return -(-(n // vec) // (grid * 256))
+
+
+def flat_where(i, n, grid=None, vec=4):
+    """Which part of a flat streaming launch over n floats handles element i: the trip, workgroup and thread of the
+    body (256 threads x `vec` floats per workgroup sweep, `grid` workgroups per trip), or the scalar tail of n % vec
+    floats.  vec = 1: the element-per-thread kernels (act_bwd, rel_l2_bwd), which have no tail."""
+    grid = stream_grid(n) if grid is None else grid
+    nv = n // vec
+    s = f"index {i} (" + ", ".join(f"mod {m} = {i % m}" for m in FLAT_MODS) + "): "
+    if i >= vec * nv:
+        return s + f"scalar tail, element {i - vec * nv} of {n % vec} (workgroup 0)"
+    trip, r = divmod(i // vec, grid * 256)
+    return s + (f"{'float4 ' if vec == 4 else ''}body, trip {trip} of {stream_trips(n, grid, vec)}, workgroup {r // 256} of "
+                f"{grid}, thread {r % 256}" + (f", component {i % vec}" if vec > 1 else ""))
+
+
+def _flat_summary(idx, n, grid, vec):
+    """Where the violating elements of a flat launch sit: tail / trips / residues."""
+    out = [f"indices [{int(idx.min())} .. {int(idx.max())}]"]
+    if n is not None:
+        grid = stream_grid(n) if grid is None else grid
+        body = idx[idx < vec * (n // vec)]
+        out.append(f"{int((idx >= vec * (n // vec)).sum())} in the scalar tail")
+        trips = sorted(set(((body // vec) // (grid * 256)).tolist()))
+        out.append(f"{body.numel()} in the body, trips {trips[:8]}")
+    for m in FLAT_MODS:
+        res = sorted(set((idx % m).tolist()))
+        out.append(f"mod {m}: {res if len(res) <= 8 else f'{len(res)} residues'}")
+    return "; ".join(out)
+
+
+def check_abs_rel(got, ref, a, r, label="", *, n_flat=None, grid=None, vec=4):
+    """Assert |got - ref| <= a + r |ref| element by element (a, r: numbers or tensors of got's shape; a = tau * scale and
+    r = 0 gives a check_products-style bound).  Returns the worst |got - ref| / (a + r |ref|): the fraction of the bound
+    in use.  The tensors are read as flat; n_flat = n: they are the n floats of one flat streaming launch (grid, vec: see
+    flat_where), and the message names the trip or the tail of the worst element and of all violating ones."""
+    g = _d(got).reshape(-1)
+    rr = _d(ref).to(g.device).reshape(-1)
+    assert g.shape == rr.shape, (label, tuple(g.shape), tuple(rr.shape))
+    if g.numel() == 0:
+        return 0.0
+    a = torch.as_tensor(a, dtype=torch.float64, device=g.device).expand_as(_d(got)).reshape(-1) if torch.is_tensor(a) else a
+    r = torch.as_tensor(r, dtype=torch.float64, device=g.device).expand_as(_d(got)).reshape(-1) if torch.is_tensor(r) else r
+    bound = (a + r * rr.abs()) * torch.ones_like(g)
+    err = (g - rr).abs()
+    ratio = torch.where(err == 0, torch.zeros_like(err), err / bound.clamp_min(1e-300))     # 0 <= 0 holds
+    ratio = torch.where(torch.isfinite(g), ratio, torch.full_like(ratio, float("inf")))     # NaN compares false: count it
+    worst = float(ratio.max())
+    bad = ratio > 1.0
+    nbad = int(bad.sum())
+    if nbad:
+        i = int(ratio.argmax())
+        idx = bad.nonzero().flatten()
+        where = flat_where(i, n_flat, grid, vec) if n_flat is not None else \
+            f"index {i} (" + ", ".join(f"mod {m} = {i % m}" for m in FLAT_MODS) + ")"
+        raise AssertionError(
+            f"{label}: {nbad} of {g.numel()} elements exceed |got - ref| <= a + r |ref|; worst at {where}: got "
+            f"{float(g[i]):.9g}, ref {float(rr[i]):.9g}, bound {float(bound[i]):.4g}, |err| / bound = {worst:.3g}; violating "
+            f"{_flat_summary(idx, n_flat, grid, vec)}")
+    return worst
+
+
+def adamw_reference(p, g, m, v, lr, beta1, beta2, eps, wd, step, gnorm_sq=None, max_norm=0.0, dtype=torch.float64):
+    """One AdamW step as csrc/pa2d_optim.hip's adamw_body states it (torch.optim.AdamW with the clip coefficient
+    min(1, max_norm / (sqrt(gnorm_sq) + 1e-6)) applied to the gradient), on copies of the given state in `dtype`; the
+    hyper-parameters are Python floats (fp64), never a rounded coefficient row.  Returns (p, m, v) and the scales
+    (|p0| + step (beta1 |m0| + (1 - beta1) |g'|) / (sqrt(v) / sqrt(bias2) + eps), |m0| + |g'|, v0 + g'^2) one step's
+    rounding is measured against.  dtype=torch.float32 is the
+    yardstick: the same statement with every tensor operation rounded to fp32."""
+    p, g, m, v = (torch.as_tensor(t).detach().to(dtype) for t in (p, g, m, v))
+    coef = 1.0
+    if gnorm_sq is not None and max_norm > 0.0:
+        coef = min(1.0, max_norm / (math.sqrt(float(gnorm_sq)) + 1e-6))
+    gc = g * coef
+    bias1, bias2 = 1.0 - beta1 ** step, 1.0 - beta2 ** step
+    m1 = m + (1.0 - beta1) * (gc - m)
+    v1 = beta2 * v + (1.0 - beta2) * gc * gc
+    upd = (lr / bias1) * m1 / (v1.sqrt() / math.sqrt(bias2) + eps)
+    p1 = p * (1.0 - lr * wd) - upd
+    # the update on absolute values: where beta1 m0 and (1 - beta1) g' cancel in m1, the update keeps their rounding
+    upd_abs = (lr / bias1) * (beta1 * m.abs() + (1.0 - beta1) * gc.abs()) / (v1.sqrt() / math.sqrt(bias2) + eps)
+    return (p1, m1, v1), (p.abs() + upd_abs, m.abs() + gc.abs(), v + gc * gc)
+
+
+def exact_sum_probes(n, positions):
+    """fp32 [n], zero except 2^j at positions[j] (at most 12 distinct positions): the squares are 4^j, every subset sum of
+    them (and of doubled ones) is below 2^24 and so exact in fp32, and a sum of squares must equal sum_j 4^j bit for bit
+    in any order."""
+    assert len(positions) <= 12 and len(set(positions)) == len(positions) and all(0 <= q < n for q in positions), positions
+    x = torch.zeros(n, dtype=torch.float32)
+    for j, q in enumerate(positions):
+        x[q] = 2.0 ** j
+    return x
+
+
+def decode_probe_sum(got, positions, n=None, grid=None):
+    """Reads a sum of squares of exact_sum_probes(n, positions) digit by digit in base 4: digit j is how often probe j
+    was counted.  Returns (is exact, text naming every probe counted 0, 2 or 3 times and where it sits)."""
+    want = sum(4 ** j for j in range(len(positions)))
+    got = float(got)
+    if got == want:
+        return True, "exact"
+    if not (math.isfinite(got) and got == int(got) and 0 <= got < 4 ** (len(positions) + 1)):
+        return False, f"got {got!r}, want {want}: not a sum of the probes' squares"
+    k, notes = int(got), []
+    for j, q in enumerate(positions):
+        d = (k >> (2 * j)) & 3
+        if d != 1:
+            what = {0: "dropped", 2: "counted twice", 3: "counted three times"}[d]
+            notes.append(f"probe 2^{j} {what} at " + (flat_where(q, n, grid) if n is not None else f"index {q}"))
+    if k >> (2 * len(positions)):
+        notes.append(f"and {k >> (2 * len(positions))} x 4^{len(positions)} more than all probes hold")
+    return False, f"got {k}, want {want}: " + "; ".join(notes)
