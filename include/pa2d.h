@@ -371,6 +371,40 @@ int pa2d_wide_slice_weights_bwd(const float* x, long long ldx, const float* ws, 
                                 void* ws_buf, size_t ws_bytes, int rows, int D, int M, int clamp_temperature, int accumulate,
                                 pa2d_stream_t stream, void* ev_start, void* ev_stop);
 
+/* ---- fused block tail for no-grad forwards: ONE launch for what the default path runs as
+ * pa2d_deslice_fwd, pa2d_gemm_bias_act_fwd (to_out + residual), pa2d_layernorm_fwd (ln_2), two pa2d_gemm_bias_act_fwd
+ * (the MLP) and the next pa2d_layernorm_fwd (Physics_Attention.py:116-119, …_2D.py:69-75).  For the R = B*N rows
+ *   y   = deslice(xm, o[b], ws, bs, temperature, clamp)        as pa2d_deslice_fwd (clamp_temperature = 0: irregular mesh)
+ *   a   = y . wo^T + bo + fx                                    fx [R, C] of pitch ldfx: the block's input
+ *   h   = act(LN(a; g2, be2) . w1^T + b1)                       w1 [hidden, C]; act: any id of enum pa2d_act (no flag bits)
+ *   out = h . w2^T + b2 + a                                     w2 [C, hidden]; out [R, C], always written
+ *   xn  = LN(out; gn, bn)                                       only when gn / bn are given (both or neither); xn [R, C]
+ * C = heads * D.  xm rows have pitch ldx (the first C columns of the conv's [B, N, 2C] output: ldx = 2C); o [B, heads, M, D].
+ * y_dbg [R, C], a_dbg [R, C], h_dbg [R, hidden]: optional copies of the intermediate stages (NULL = not written; tests).
+ * Supported (pa2d_block_tail_supported returns 1, else pa2d_block_tail_fwd returns PA2D_ERR_UNSUPPORTED before it looks
+ * at a pointer): engine PA2D_ENGINE_SPLIT only — 3-plane bf16 splits of both operands, six MFMA terms, fp32 accumulation;
+ * the other engines are refused, never run on this arithmetic; C in {64, 128, 256}, D in {8, 16, 32, 64}, 1 <= M <= 128,
+ * hidden = r C with r in 1..4, any B*N (B = 0 is a no-op); an operand past 4 GiB returns PA2D_ERR_UNSUPPORTED.
+ * Weight images: the kernel reads wo, w1, w2 from fragment-order bf16 plane images, pa2d_block_tail_image_bytes(N, K) bytes
+ * each, made by pa2d_block_tail_weight_image(w [N, K] of pitch ldw, ...).  wimg_o / wimg_1 / wimg_2 may each be NULL: the
+ * call then makes that image from the fp32 weight in `ws` (pa2d_block_tail_workspace(C, hidden) bytes hold all three; one
+ * small launch each); with all three given, wo / w1 / w2 and ws may be NULL.  Pointers 16-byte aligned, ldx, ldfx % 4 == 0.
+ * pa2d_block_tail_lds_bytes: the dynamic LDS of the tallest panel the launch may choose (<= 160 KiB); 0 if unsupported.
+ * PA2D_TAIL_PANEL=16|32 forces the panel height (A/B timing; rows are independent, so the results are the same bits). */
+int pa2d_block_tail_supported(int C, int heads, int D, int M, int hidden, int act, int engine);
+size_t pa2d_block_tail_lds_bytes(int C, int heads, int D, int M, int hidden, int act, int engine);
+size_t pa2d_block_tail_image_bytes(int N, int K);
+int pa2d_block_tail_weight_image(const float* w, long long ldw, void* img, size_t img_bytes, int N, int K, int engine,
+                                 pa2d_stream_t stream);
+size_t pa2d_block_tail_workspace(int C, int hidden);
+int pa2d_block_tail_fwd(const float* xm, long long ldx, const float* o, const float* ws, const float* bs,
+                        const float* temperature, const float* fx, long long ldfx, const float* wo, const float* bo,
+                        const float* g2, const float* be2, const float* w1, const float* b1, const float* w2,
+                        const float* b2, const float* gn, const float* bn, float* out, float* xn, float* y_dbg,
+                        float* a_dbg, float* h_dbg, const void* wimg_o, const void* wimg_1, const void* wimg_2, void* wsp,
+                        size_t wsp_bytes, int B, int N, int heads, int D, int M, int hidden, int act, int clamp_temperature,
+                        int engine, float eps, pa2d_stream_t stream);
+
 /* ---- output head mlp2 = nn.Linear(C, out_dim), out_dim <= 8 (…_2D.py:66,73) */
 int pa2d_head_fwd(const float* xn, const float* w, const float* b, float* y, int rows, int C, int out_dim,
                   pa2d_stream_t stream);

@@ -21,6 +21,8 @@ D = 256 (SliceLearner) and D = 384 (the code-conditioned MLP's last layer), M = 
 slice_predictor_train_step (frozen SequenSolver T=10, layers=8, Tout=1; FusedAdamW) of VorticitySliceLearner and SliceLearner.
 The darcy_loss stages time harness.darcy_loss (exp_darcy.py's loss) at s = 85, B = 4 (scripts/Transolver_Darcy.sh) and
 s = 421, B = 2, forward alone and forward plus backward, through the fused kernels and through the torch path.
+The block_tail stage times the fused block tail (split engine) at the same shape, beside the five kernels it
+replaces (deslice, linear_bias_res, ln_fwd, linear_gelu, linear_bias_res, ln_fwd): useful GEMM TFLOP/s of the three linears.
 Usage: python tools/kbench.py [--only conv_fwd,linear_fwd,...] [--iters 10] [--B 32]"""
 import argparse
 import os
@@ -55,6 +57,7 @@ def main():
     ap.add_argument("--H", type=int, default=64)
     ap.add_argument("--W", type=int, default=64)
     ap.add_argument("--heads", type=int, default=8)
+    ap.add_argument("--MR", type=int, default=1, help="MLP ratio of the block_tail stage")
     ap.add_argument("--B3", type=int, default=1, help="batch of the conv3d_* stages (3x3x3 conv, S3^3 mesh, C channels)")
     ap.add_argument("--S3", type=int, default=32, help="edge of the cubic mesh of the conv3d_* stages")
     ap.add_argument("--AB", type=int, default=8, help="batch of the ae_* stages (auto_encoder.py's shape)")
@@ -114,6 +117,22 @@ def main():
                               2.0 * R * C * 4, "GB")
     tests["token_fwd"] = (lambda: ops.token_attn_fwd(spart, npart, wq, wk, wv), 0, "us")
     tests["deslice"] = (lambda: ops.deslice_fwd(xf, 2 * C, 0, o, ws, bs, temp, B, N, heads, D, M), 2.0 * R * C * 4, "GB")
+    # the fused block tail (ops.block_tail_fwd, split engine) beside the five kernels it replaces (deslice, linear_bias_res,
+    # ln_fwd, linear_gelu, linear_bias_res, ln_fwd): --MR is the MLP ratio; images made once, as inside a rollout
+    if E == ops.ENGINE_SPLIT and ops.block_tail_supported(C, heads, D, M, args.MR * C, "gelu", E):
+        hid = args.MR * C
+        w1, b1, w2 = rn(hid, C) * 0.06, rn(hid), rn(C, hid) * 0.06
+        tail = lambda: ops.block_tail_fwd(xf, 2 * C, 0, o, ws, bs, temp, res, w, bias, gamma, beta, w1, b1, w2, bias, gamma,
+                                          beta, B, N, heads, D, M, "gelu", engine=E)
+        tail_scope = ops._FrozenScope()          # holds the three weight images, made by the first (untimed) call
+
+        def tail_timed():
+            ops._frozen.append(tail_scope)
+            try:
+                return tail()
+            finally:
+                ops._frozen.pop()
+        tests["block_tail"] = (tail_timed, 2.0 * R * C * (C + 2 * hid), "TF")
     dy3 = dy2d.view(B, N, C)
     dopart, _ = ops.slice_scatter(xf, 2 * C, 0, dy3, C, 0, ws, bs, temp, B, N, heads, D, M, want_norm=False)
     ds, dn, *_ = ops.token_attn_bwd(s, nrm, wq, wk, wv, dopart)

@@ -96,6 +96,12 @@ class SequenSolver(nn.Module):
         self.mlp2 = nn.Linear(self.C, 1)
 
     # ---- engine
+    def set_fused_tail(self, flag=True):
+        """Accepted for interface parity with the Transolver models (harness.rollout(fused_tail=...)); this model has no
+        block tail of that shape, so the flag has no effect."""
+        self.fused_tail = bool(flag)
+        return self
+
     def set_engine(self, engine):
         """GEMM engine of the encoder and of this model's dense layers ("f32" | "split" | "bf16" | None = default); bf16
         storage ('bf16s') is refused, as for the encoder family.  The two SequenSolver stages are exact fp32 on every engine."""

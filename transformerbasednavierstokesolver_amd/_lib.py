@@ -96,6 +96,12 @@ SIGNATURES = {
     "pa2d_wide_slice_weights_bwd_workspace": (_sz, [_i, _i, _i]),
     "pa2d_wide_slice_weights_bwd": (_i, [_f, _ll, _f, _f, _f, _f, _f, _ll, _f, _f, _f, _f, _sz, _i, _i, _i, _i, _i, _st,
                                          _st, _st]),
+    "pa2d_block_tail_supported": (_i, [_i, _i, _i, _i, _i, _i, _i]),
+    "pa2d_block_tail_lds_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
+    "pa2d_block_tail_image_bytes": (_sz, [_i, _i]),
+    "pa2d_block_tail_weight_image": (_i, [_f, _ll, _f, _sz, _i, _i, _i, _st]),
+    "pa2d_block_tail_workspace": (_sz, [_i, _i]),
+    "pa2d_block_tail_fwd": (_i, [_f, _ll, _f, _f, _f, _f, _f, _ll] + [_f] * 18 + [_f, _sz] + [_i] * 9 + [C.c_float, _st]),
     "pa2d_head_fwd": (_i, [_f, _f, _f, _f, _i, _i, _i, _st]),
     "pa2d_head_bwd_workspace": (_sz, [_i, _i, _i]),
     "pa2d_head_bwd": (_i, [_f, _f, _f, _f, _f, _f, _f, _sz, _i, _i, _i, _i, _st]),

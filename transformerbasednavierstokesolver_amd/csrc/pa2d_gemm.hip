@@ -30,6 +30,7 @@ static Pa2dEnv read_env() {
     v.split_big = num("PA2D_SPLIT_BIG", 1);
     v.slice_map = is("PA2D_SLICE_MAP", "l") ? 0 : 1;
     v.default_engine = is("PA2D_GEMM", "f") ? 0 : (is("PA2D_GEMM", "b") ? 2 : 1);
+    v.tail_panel = num("PA2D_TAIL_PANEL", 0);
     return v;
 }
 static Pa2dEnv g_env = read_env();

@@ -146,6 +146,7 @@ struct Pa2dEnv {
     int split_big;        // PA2D_SPLIT_BIG=0 -> 0
     int slice_map;        // PA2D_SLICE_MAP=legacy -> 0
     int default_engine;   // PA2D_GEMM=f32|split|bf16 : what pa2d_default_engine() returns
+    int tail_panel;       // PA2D_TAIL_PANEL=16|32 : panel height of the fused block tail (0 = automatic)
 };
 const Pa2dEnv& pa2d_env();
 

@@ -303,6 +303,39 @@ class MLPBranchFn(Function):
         return (dfx.view(dout.shape),) + _ret(tl, (dg, db)) + (None, None) + _ret(tg, gw)
 
 
+def block_tail(fx, xn, P, H, W, heads, ln2_w, ln2_b, act, w1, b1, w2, b2, next_w=None, next_b=None, engine=None):
+    """One block of a no-grad forward on the fused tail: conv (or the stacked Linear of the irregular mesh), slice
+    scatter, token attention, then ops.block_tail_fwd — four library calls.  fx [B,N,C]: the residual stream; xn = ln_1(fx),
+    made by the previous block's tail (or by the caller for the first block); P: dict ATTN_KEYS -> tensors; next_w / next_b:
+    the LayerNorm that follows (the next block's ln_1, or ln_3).  Returns (fx', LN_next(fx') or None).  No autograd node:
+    raises if grad mode is on and an input requires a gradient."""
+    tensors = (fx, xn, ln2_w, ln2_b, w1, b1, w2, b2, next_w, next_b) + tuple(P.values())
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
+        raise RuntimeError("functional.block_tail has no backward: call it under torch.no_grad()")
+    B, N, C = fx.shape
+    D, M = C // heads, P["ws"].shape[0]
+    c = lambda t: None if t is None else t.detach().contiguous()
+    P = {k: c(v) for k, v in P.items()}
+    temp = P["temperature"].reshape(heads).contiguous()
+    structured = H is not None
+    Wm, depth = mesh_extent(W)
+    xn = c(xn)
+    if structured and depth is not None:
+        xf = ops.conv3x3x3x2_fwd(xn, P["wx"], P["bx"], P["wf"], P["bf"], H, Wm, depth, engine=engine)
+    elif structured:
+        xf = ops.conv3x3x2_fwd(xn, P["wx"], P["bx"], P["wf"], P["bf"], H, W, engine=engine)
+    else:
+        wcat, bcat = torch.cat((P["wx"], P["wf"]), 0), torch.cat((P["bx"], P["bf"]), 0)
+        xf = ops.linear_fwd(xn.view(B * N, C), wcat, bcat, engine=engine)[0].view(B, N, 2 * C)
+    spart, npart = ops.slice_scatter(xf, 2 * C, 0, xf, 2 * C, C, P["ws"], P["bs"], temp, B, N, heads, D, M,
+                                     clamp=structured, engine=engine)
+    _, _, o = ops.token_attn_fwd(spart, npart, P["wq"], P["wk"], P["wv"])
+    out, xnext, _ = ops.block_tail_fwd(xf, 2 * C, 0, o, P["ws"], P["bs"], temp, c(fx).view(B * N, C), P["wo"], P["bo"],
+                                       c(ln2_w), c(ln2_b), c(w1), c(b1), c(w2), c(b2), c(next_w), c(next_b), B, N, heads,
+                                       D, M, act, clamp=structured, engine=engine)
+    return out.view(B, N, C), None if xnext is None else xnext.view(B, N, C)
+
+
 def attn_branch(fx, ln_w, ln_b, H, W, heads, params, engine=None):
     return AttnBranchFn.apply(fx, ln_w, ln_b, H, W, heads, engine, *params)
 

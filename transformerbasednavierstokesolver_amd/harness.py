@@ -176,10 +176,30 @@ def train_step(model, optimizer, scheduler, x, fx, yy, step=1, max_grad_norm=Non
     return loss.detach(), full
 
 
+class _fused_tail_set:
+    """`with _fused_tail_set(model, flag):` the model's fused-tail switch (TransolverBase.set_fused_tail) is `flag` inside
+    and what it was afterwards; flag None leaves the model as it is."""
+
+    def __init__(self, model, flag):
+        self.model, self.flag = model, flag
+
+    def __enter__(self):
+        if self.flag is not None:
+            self.before = bool(getattr(self.model, "fused_tail", False))
+            self.model.set_fused_tail(self.flag)
+
+    def __exit__(self, *exc):
+        if self.flag is not None:
+            self.model.set_fused_tail(self.before)
+        return False
+
+
 @torch.no_grad()
-def rollout(model, x, fx, nsteps, step=1):
+def rollout(model, x, fx, nsteps, step=1, fused_tail=None):
+    """fused_tail: None = the model as it is; True / False = the model's fused block tail (set_fused_tail) on / off for
+    this call, restored afterwards."""
     frames = []
-    with ops.weights_frozen():
+    with _fused_tail_set(model, fused_tail), ops.weights_frozen():
         for _ in range(nsteps):
             im = model(x, fx=fx)
             frames.append(im)
@@ -192,9 +212,15 @@ class GraphedRollout:
 
     Static buffers: `x`, the input window `fx` [B,N,fun_dim] and the output `im`.  The window shift
     `fx = cat(fx[..., step:], im)` is done in place inside the graph, so shapes and pointers never
-    change.  Replays are bit-identical to the eager loop (same kernels, same order)."""
+    change.  Replays are bit-identical to the eager loop (same kernels, same order).
+    fused_tail: None = the model as it is; True / False = the model's fused block tail on / off for the capture (the
+    captured step keeps that route; the model's own flag is restored when the constructor returns)."""
 
-    def __init__(self, model, x, fx, step=1, warmup=2):
+    def __init__(self, model, x, fx, step=1, warmup=2, fused_tail=None):
+        with _fused_tail_set(model, fused_tail):
+            self._capture(model, x, fx, step, warmup)
+
+    def _capture(self, model, x, fx, step, warmup):
         self.model, self.step = model, step
         self.x = x.clone()
         self.fx = fx.clone()

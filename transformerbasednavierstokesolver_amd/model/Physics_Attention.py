@@ -16,6 +16,8 @@ from ._core import pad_contraction
 
 
 class Physics_Attention_Structured_Mesh_2D(nn.Module):
+    fused_tail_capable = True      # BlockBase.fused_route: de-slice .. to_out are the stages ops.block_tail_fwd fuses
+
     def __init__(self, dim, heads=8, dim_head=64, dropout=0., slice_num=64, H=101, W=31, kernel=3):
         super().__init__()
         inner_dim = dim_head * heads
@@ -65,6 +67,7 @@ class Physics_Attention_Structured_Mesh_3D(nn.Module):
     [C, C, 3, 3, 3]) and `forward(x[B,N,C]) -> [B,N,C]`, N = H*W*D with point n = (h*W + w)*D + d.  Both Conv3d
     projections run as one 27-tap implicit GEMM of libpa2d (pa2d_conv3x3x3x2_*); slice, token attention, de-slice and
     to_out are the kernels of the 2-D class.  The nn.Conv3d / nn.Linear sub-modules are parameter containers only."""
+    fused_tail_capable = True
 
     def __init__(self, dim, heads=8, dim_head=64, dropout=0., slice_num=32, H=32, W=32, D=32, kernel=3):
         super().__init__()

@@ -15,6 +15,11 @@ class SOL_Transolver_Structured_Mesh_2D(nn.Module):
         self.transolver_model = _structured.Model(*model_args, **model_kwargs)
         self.n, self.step = look_ahead, step
 
+    def set_fused_tail(self, flag=True):
+        """The inner model's switch (TransolverBase.set_fused_tail): no-grad forwards on the fused block tail."""
+        self.transolver_model.set_fused_tail(flag)
+        return self
+
     def forward(self, x, fx):
         prediction = None
         for _ in range(self.n):

@@ -12,6 +12,8 @@ from ._core import ACTIVATION, MLP, BlockBase, TransolverBase  # noqa: F401
 
 
 class Physics_Attention_Irregular_Mesh(nn.Module):
+    fused_tail_capable = True      # BlockBase.fused_route
+
     def __init__(self, dim, heads=8, dim_head=64, dropout=0., slice_num=64):
         super().__init__()
         if dim_head * heads != dim:

@@ -62,6 +62,7 @@ class BlockBase(nn.Module):
     def _assemble(self, attn, hidden_dim, act, mlp_ratio, last_layer, out_dim):
         self.last_layer = last_layer
         self.engine = None
+        self.fused_tail = False         # TransolverBase.set_fused_tail: no-grad forwards take ops.block_tail_fwd
         self.ln_1 = nn.LayerNorm(hidden_dim)
         self.Attn = attn
         self.ln_2 = nn.LayerNorm(hidden_dim)
@@ -70,8 +71,50 @@ class BlockBase(nn.Module):
             self.ln_3 = nn.LayerNorm(hidden_dim)
             self.mlp2 = nn.Linear(hidden_dim, out_dim)
 
+    def fused_route(self, fx):
+        """True when this call takes the fused tail (ops.block_tail_fwd): the flag is on, the block is in eval mode and no
+        autograd graph is being recorded, storage is fp32, the block is the plain 2-D / 3-D / irregular block with an
+        n_layers = 0 MLP, and the library has the shape.  Everything else is today's route, bit for bit."""
+        from .. import ops
+        attn, mlp = self.Attn, self.mlp
+        if not self.fused_tail or torch.is_grad_enabled() or fx.dtype != torch.float32 or fx.dim() != 3:
+            return False
+        if self.training or self.engine == ops.ENGINE_BF16S or len(mlp.linears):
+            return False
+        if not getattr(attn, "fused_tail_capable", False):      # the plain 2-D, 3-D and irregular attention declare it
+            return False
+        C = fx.shape[-1]
+        if C % attn.heads or mlp.linear_pre[0].weight.shape[1] != C:
+            return False
+        return ops.block_tail_supported(C, attn.heads, C // attn.heads, attn.in_project_slice.weight.shape[0],
+                                        mlp.n_hidden, mlp.act_name, self.engine)
+
+    def forward_fused(self, fx, xn=None, next_ln=None):
+        """The fused route: conv, slice scatter, token attention, tail.  xn = ln_1(fx) from the previous block's tail
+        (None: made here); next_ln: the next block's ln_1.  Returns (fx', LN(fx')) with LN = ln_3 on the last block,
+        next_ln otherwise (None without one)."""
+        attn, mlp = self.Attn, self.mlp
+        if xn is None:
+            xn = Fn.layer_norm(fx, self.ln_1.weight, self.ln_1.bias)
+        ln = self.ln_3 if self.last_layer else next_ln
+        pre, post = mlp.linear_pre[0], mlp.linear_post
+        P = dict(zip(Fn.ATTN_KEYS, attn.attention_parameters()))
+        return Fn.block_tail(fx, xn, P, getattr(attn, "H", None), getattr(attn, "mesh_w", getattr(attn, "W", None)),
+                             attn.heads, self.ln_2.weight, self.ln_2.bias, mlp.act_name, pre.weight, pre.bias, post.weight,
+                             post.bias, None if ln is None else ln.weight, None if ln is None else ln.bias,
+                             engine=self.engine)
+
+    def head(self, z):
+        """mlp2 on z = ln_3(fx)."""
+        if self.mlp2.out_features <= HEAD_KERNEL_MAX_OUT:
+            return Fn.head(z, self.mlp2.weight, self.mlp2.bias)          # fp32 out, whatever the storage type
+        return Fn.linear(z, self.mlp2.weight, self.mlp2.bias, None, engine=self.engine).float()
+
     def forward(self, fx):
         attn, mlp = self.Attn, self.mlp
+        if self.fused_tail and self.fused_route(fx):
+            fx, z = self.forward_fused(fx)
+            return self.head(z) if self.last_layer else fx
         if attn.training and attn.dropout.p > 0:
             raise NotImplementedError("dropout > 0 is not implemented in the HIP path; refusing to ignore it")
         # each residual branch (LayerNorm -> sub-layer -> + fx) is one autograd node
@@ -87,16 +130,14 @@ class BlockBase(nn.Module):
                                post.weight, post.bias, engine=self.engine)
         if not self.last_layer:
             return fx
-        z = Fn.layer_norm(fx, self.ln_3.weight, self.ln_3.bias)
-        if self.mlp2.out_features <= HEAD_KERNEL_MAX_OUT:
-            return Fn.head(z, self.mlp2.weight, self.mlp2.bias)          # fp32 out, whatever the storage type
-        return Fn.linear(z, self.mlp2.weight, self.mlp2.bias, None, engine=self.engine).float()
+        return self.head(Fn.layer_norm(fx, self.ln_3.weight, self.ln_3.bias))
 
 
 class TransolverBase(nn.Module):
     def _assemble(self, make_block, in_features, n_layers, n_hidden, Time_Input, act):
         self.Time_Input, self.n_hidden = Time_Input, n_hidden
         self.engine = None
+        self.fused_tail = False         # set_fused_tail
         self.preprocess = MLP(in_features, n_hidden * 2, n_hidden, n_layers=0, res=False, act=act)
         if Time_Input:
             self.time_fc = nn.Sequential(nn.Linear(n_hidden, n_hidden), nn.SiLU(), nn.Linear(n_hidden, n_hidden))
@@ -143,8 +184,27 @@ class TransolverBase(nn.Module):
                 m.engine = eng
         return self
 
+    def set_fused_tail(self, flag=True):
+        """Opt in to (or out of) the fused block tail for no-grad forwards of THIS model: each block then runs conv,
+        slice scatter, token attention and ONE launch for de-slice .. next LayerNorm (ops.block_tail_fwd).  Training,
+        bf16 storage, generic MLPs and shapes outside the kernel keep the default route; so do models whose blocks are
+        not the plain Transolver block (the flag is accepted and has no effect).  Default: off."""
+        self.fused_tail = bool(flag)
+        for m in self.modules():
+            if isinstance(m, (BlockBase, TransolverBase)):
+                m.fused_tail = bool(flag)
+        return self
+
     def _run_blocks(self, z):
         from .. import ops
+        blocks = list(self.blocks)
+        if self.fused_tail and blocks and all(
+                isinstance(b, BlockBase) and b.fused_tail and b.fused_route(z) for b in blocks) and blocks[-1].last_layer:
+            # each tail hands (fx, ln_1 of the next block) on: ln_1 runs once, in front of the first block
+            xn = None
+            for i, block in enumerate(blocks):
+                z, xn = block.forward_fused(z, xn, blocks[i + 1].ln_1 if i + 1 < len(blocks) else None)
+            return blocks[-1].head(xn)
         if self.engine == ops.ENGINE_BF16S:
             # bf16 storage: from here on every activation, saved tensor and inter-kernel gradient is bf16 (the cast is
             # the one fp32 -> bf16 boundary; its autograd node casts the gradient back for the fp32 input embedding)

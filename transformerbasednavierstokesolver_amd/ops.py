@@ -243,7 +243,8 @@ class _FrozenScope:
     def __init__(self):
         self.packs = {}
         self.packs1 = {}      # packs of the single 3x3 conv (pa2d_conv3x3_pack): (w ptr, B, H, W, C, direction, engine)
-        self.images = {}      # weight plane images of the row-stationary linear kernel: (w ptr, transposed, N, K, engine)
+        self.images = {}      # weight plane images of the row-stationary linear kernel: (w ptr, transposed, N, K, engine);
+        #                       transposed = "tail": the fused block tail's image of the same weight (block_tail_fwd)
 
     def refresh(self):
         """Re-pack every entry in place (same device pointers): called before replaying a hipGraph that was captured
@@ -253,7 +254,10 @@ class _FrozenScope:
         for (_, B, H, W, Cc, direction, eng), (w, pack) in self.packs1.items():
             _make_pack1(w, pack, B, H, W, Cc, direction, eng)
         for (_, transposed, N, K, eng), (w, img) in self.images.items():
-            _make_image(w, transposed, img, N, K, eng)
+            if transposed == "tail":      # fragment-order image of the fused block tail
+                _make_tail_image(w, img, N, K, eng)
+            else:
+                _make_image(w, transposed, img, N, K, eng)
 
 
 _frozen = []      # stack of active scopes
@@ -612,6 +616,71 @@ def deslice_fwd(xm, ldx, xm_off, o, ws_w, bs, temperature, B, N, heads, D, M, cl
                                      B, N, heads, D, M, int(clamp), *_slice_engine_args(engine, bf), _stream(), e0, e1),
                "deslice_fwd")
     return y
+
+
+# ---------------------------------------------------------------------------------------------- fused block tail
+def block_tail_supported(Cc, heads, D, M, hidden, act, engine=None):
+    """True where `block_tail_fwd` runs (include/pa2d.h: pa2d_block_tail_supported); a host-side query, no GPU needed.
+    bf16 storage has no fused tail."""
+    eng = resolve_engine(engine)
+    if eng == ENGINE_BF16S or act not in ACT_IDS:
+        return False
+    return bool(_L().pa2d_block_tail_supported(Cc, heads, D, M, hidden, ACT_IDS[act], eng))
+
+
+def _make_tail_image(w, img, N, K, eng):
+    _lib.check(_L().pa2d_block_tail_weight_image(_p(w), w.shape[1], img.data_ptr(), img.numel(), N, K, eng, _stream()),
+               "block_tail_weight_image")
+
+
+def _tail_image(w, eng):
+    """Image pointer for the active `weights_frozen()` scope (made once per weight, re-made by scope.refresh());
+    0 outside a scope: the call then makes the image in its workspace."""
+    if not _frozen:
+        return 0
+    N, K = w.shape
+    scope = _frozen[-1]
+    key = (w.data_ptr(), "tail", N, K, eng)
+    hit = scope.images.get(key)
+    if hit is None:
+        img = torch.empty(_L().pa2d_block_tail_image_bytes(N, K), dtype=torch.uint8, device=w.device)
+        _make_tail_image(w, img, N, K, eng)
+        hit = scope.images[key] = (w, img)
+    return hit[1].data_ptr()
+
+
+def block_tail_fwd(xm, ldx, xm_off, o, ws_w, bs, temperature, fx2d, wo, bo, g2, be2, w1, b1, w2, b2, gn, bn, B, N, heads,
+                   D, M, act, clamp=True, engine=None, debug=False, eps=LN_EPS):
+    """The row-local tail of a block in ONE launch (no-grad forwards): de-slice, to_out + residual `fx2d`, ln_2, the MLP
+    and its residual, and — when gn / bn are given — the LayerNorm that follows (the next block's ln_1, or ln_3).
+    Returns (out [B*N, C], xn [B*N, C] or None, debug), debug = (y, a, h) copies of the stages when asked for."""
+    _chk(o, ws_w, bs, temperature, fx2d, wo, bo, g2, be2, w1, b1, w2, b2, gn, bn)
+    if _chk_act(xm):
+        raise TypeError("the fused block tail has no bf16-storage variant")
+    eng = _abi_engine(engine)
+    Cc, hidden, rows = heads * D, w1.shape[0], B * N
+    if tuple(wo.shape) != (Cc, Cc) or tuple(w1.shape) != (hidden, Cc) or tuple(w2.shape) != (Cc, hidden):
+        raise ValueError("block_tail_fwd: weight shapes do not match heads * D and the hidden width")
+    if tuple(fx2d.shape) != (rows, Cc) or (gn is None) != (bn is None):
+        raise ValueError("block_tail_fwd: fx must be [B*N, C]; gn and bn go together")
+    dev = xm.device
+    out = torch.empty(rows, Cc, dtype=torch.float32, device=dev)
+    xn = torch.empty(rows, Cc, dtype=torch.float32, device=dev) if gn is not None else None
+    dbg = None
+    if debug:
+        dbg = (torch.empty(rows, Cc, dtype=torch.float32, device=dev), torch.empty(rows, Cc, dtype=torch.float32, device=dev),
+               torch.empty(rows, hidden, dtype=torch.float32, device=dev))
+    y_d, a_d, h_d = dbg if dbg is not None else (None, None, None)
+    imgs = (0, 0, 0)
+    if _L().pa2d_block_tail_supported(Cc, heads, D, M, hidden, ACT_IDS[act], eng):
+        imgs = tuple(_tail_image(w, eng) for w in (wo, w1, w2))
+    nb = 0 if all(imgs) else _L().pa2d_block_tail_workspace(Cc, hidden)
+    ws = _ws(nb, xm) if nb else None
+    _lib.check(_L().pa2d_block_tail_fwd(_p(xm, xm_off), ldx, _p(o), _p(ws_w), _p(bs), _p(temperature), _p(fx2d), Cc, _p(wo),
+                                        _p(bo), _p(g2), _p(be2), _p(w1), _p(b1), _p(w2), _p(b2), _p(gn), _p(bn), _p(out),
+                                        _p(xn), _p(y_d), _p(a_d), _p(h_d), *imgs, _p(ws), nb, B, N, heads, D, M, hidden,
+                                        ACT_IDS[act], int(clamp), eng, eps, _stream()), "block_tail_fwd")
+    return out, xn, dbg
 
 
 def slice_bwd_points(xf, dy, ws_w, bs, temperature, o, ds, dn, B, N, heads, D, M, clamp=True, into=None, engine=None):
