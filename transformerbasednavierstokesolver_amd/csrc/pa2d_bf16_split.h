@@ -1,5 +1,6 @@
 // The exact bf16 operand split and the bf16-MFMA helpers built on it (gfx950 / CDNA4): the one home of this code for the
-// v3 slice kernels (pa2d_slice3.hip, pa2d_slice3_bwd.hip) and the split-engine GEMMs (pa2d_gemm_common.h).
+// v3 slice kernels (pa2d_slice3.hip, pa2d_slice3_bwd.hip) and the split-engine GEMMs (pa2d_gemm_common.h), including the
+// two term orders (mfma_terms: slice kernels; split_terms: GEMMs and convs) and the transposed fragment read.
 //
 // An fp32 value is carried as up to three bf16 planes, x = p0 + p1 + p2 up to 2^-25 |x|; a product of two split operands
 // keeps the terms a[i] * b[j] with i + j <= 2 on v_mfma_f32_16x16x32_bf16 with fp32 accumulation: a 24-bit significand.
@@ -84,10 +85,38 @@ __device__ __forceinline__ f32x4 mfma_terms(const bf16x8 (&a)[NA], const bf16x8 
     return acc;
 }
 
-// two transposed LDS reads (ds_read_b64_tr_b16) = one 8-element MFMA fragment (elements 0..3 from `a0`, 4..7 from `a1`)
-__device__ __forceinline__ bf16x8 tr_frag(const unsigned char* a0, const unsigned char* a1) {
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)a0);
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)a1);
+// The split-engine GEMMs (pa2d_gemm_split / _panel / _mc / _mc_planes, pa2d_conv_halo) keep the same six terms in ANOTHER
+// order, (A plane, B plane) = (1,1) (2,0) (0,2) (1,0) (0,1) (0,0): still smallest first, but the three second-order terms
+// start with (1,1) where mfma_terms (order of the slice kernels: (2,0) (1,1) (0,2) ...) starts with (2,0).  Both orders
+// are older than this header and every result bit of an engine depends on its own, so neither moves: a new GEMM kernel of
+// the split engine uses split_terms, a new slice kernel mfma_terms.  NT = 1 (bf16 compute) is the one term (0,0).
+// The accumulator type selects the MFMA: f32x16 = v_mfma_f32_32x32x16_bf16 (a, b); f32x4 = v_mfma_f32_16x16x32_bf16 of the
+// transposed product, b as the instruction's first operand (an accumulator quad = four consecutive columns of B's side).
+// acc is a reference on purpose: returned by value, the compiler copies accumulators of the 256 x 256 weight-gradient kernel.
+__device__ __forceinline__ void mfma_ab(const bf16x8& a, const bf16x8& b, f32x16& acc) {
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0);
+}
+__device__ __forceinline__ void mfma_ab(const bf16x8& a, const bf16x8& b, f32x4& acc) {
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b, a, acc, 0, 0, 0);
+}
+template <int NT, typename ACC>
+__device__ __forceinline__ void split_terms(const bf16x8 (&a)[NT], const bf16x8 (&b)[NT], ACC& acc) {
+    if constexpr (NT == 3) {
+        mfma_ab(a[1], b[1], acc);
+        mfma_ab(a[2], b[0], acc);
+        mfma_ab(a[0], b[2], acc);
+        mfma_ab(a[1], b[0], acc);
+        mfma_ab(a[0], b[1], acc);
+    }
+    mfma_ab(a[0], b[0], acc);
+}
+
+// two transposed LDS reads (ds_read_b64_tr_b16) = one 8-element MFMA fragment (elements 0..3 from base + off0, 4..7 from
+// base + off1).  Base (stage / plane image) and the lane's two byte offsets are separate arguments: with complete pointers,
+// or with the plane folded into the offsets, the compiler emits other address arithmetic in the weight-gradient kernels.
+__device__ __forceinline__ bf16x8 tr_frag(const unsigned char* base, unsigned off0, unsigned off1) {
+    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + off0));
+    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + off1));
     const s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
     return __builtin_bit_cast(bf16x8, v);
 }

@@ -31,14 +31,13 @@ static size_t conv_planes_bytes(int engine, int M, int N, int Cin) {
     return (planes_bytes(M, Cin, engine == 2 ? 1 : 3) + 255) & ~(size_t)255;
 }
 
-// Weight-gradient kernel: 0 = fp32 operands (gather kernel), 1 = planes of dOut and X, 128 x 128 tiles, 2 = planes,
-// 256 x 256 tiles (one round of workgroups).  The planes kernels are 3x3 only.
-static int conv_dw_kind(const ConvDesc& d) {
-    if (d.src == SRC_BF16) return 2;
-    if (d.taps != 9 || conv_planes_bytes(d.engine, d.M, d.C, d.nk * d.C) == 0) return 0;
-    if (d.nk == 1) return (!pa2d_env().mc_big_off && d.C >= 256 && d.M >= 16 * 8 * 4) ? 2 : 0;      // Mi = C rows
-    if (mc_planes_big_applies(d.C, d.C, d.M)) return 2;
-    return (mc_planes_supported(d.C, d.C) && plan_mc(2 * d.C, 9 * d.C, d.M).big) ? 1 : 0;
+// The weight gradient dW[nk*C][taps*C] = dOut^T . im2col(X) as the dispatch sees it; planes: dout / x are plane images made here
+static MCDesc conv_wgrad(const ConvDesc& d, const void* dout, const void* x, bool planes) {
+    MCDesc w = {};
+    w.A = dout; w.lda = d.nk * d.C; w.B = x; w.ldb = d.C; w.Mi = d.nk * d.C; w.Nj = d.taps * d.C; w.Mk = d.M;
+    w.taps = d.taps; w.H = d.H; w.W = d.W; w.depth = d.depth; w.Cin = d.C; w.engine = d.engine;
+    w.src = d.src == SRC_BF16 ? MC_SRC_BF16 : (d.src == SRC_PLANES || planes) ? MC_SRC_PLANES : MC_SRC_F32;
+    return w;
 }
 
 // weight pack: fp32 pack (nk*C * taps*C floats) or 3 bf16 planes (1.5x)
@@ -52,8 +51,7 @@ static size_t conv_pack_bytes(int C, int taps, int nk) {
 // at the END of the workspace.  All sizes in bytes.
 struct ConvLayout {
     size_t pack, scratch, apl, xpl, total;
-    int dw;        // conv_dw_kind (backward)
-    MCPlan pl;     // split plan of the weight gradient (backward)
+    MCChoice wg;   // kernel and split plan of the weight gradient (backward)
 };
 static ConvLayout conv_layout(const ConvDesc& d, bool bwd) {
     ConvLayout L = {};
@@ -63,13 +61,12 @@ static ConvLayout conv_layout(const ConvDesc& d, bool bwd) {
         L.total = L.pack + L.apl;
         return L;
     }
-    L.dw = conv_dw_kind(d);
-    L.pl = L.dw == 2 ? plan_mc_planes_big(d.nk * d.C, 9 * d.C, d.M) : plan_mc(d.nk * d.C, d.taps * d.C, d.M);
-    const size_t sl = L.pl.slab_floats, cs = (size_t)colsum_blocks(d.M) * d.nk * d.C;
+    L.wg = plan_wgrad(conv_wgrad(d, nullptr, nullptr, false));
+    const size_t sl = L.wg.pl.slab_floats, cs = (size_t)colsum_blocks(d.M) * d.nk * d.C;
     L.scratch = (d.src != SRC_PLANES && cs > sl ? cs : sl) * sizeof(float);      // SRC_PLANES: no bias gradient here
     if (d.src == SRC_F32) {
         L.apl = conv_planes_bytes(d.engine, d.M, d.C, d.nk * d.C);
-        if (L.dw) L.xpl = (planes_bytes(d.M, d.C, conv_nt(d)) + 255) & ~(size_t)255;
+        if (L.wg.planes) L.xpl = (planes_bytes(d.M, d.C, conv_nt(d)) + 255) & ~(size_t)255;
     }
     L.total = L.pack + L.scratch + L.apl + L.xpl;
     return L;
@@ -149,7 +146,7 @@ static int conv_backward(const ConvDesc& d, const void* dout, const void* x, con
     const void* a = dout;                                          // dOut / X as the GEMMs read them
     const void* b = x;
     int rc;
-    if (L.apl && (dx || L.dw)) {      // someone reads the planes of dOut
+    if (L.apl && (dx || L.wg.planes)) {      // someone reads the planes of dOut
         rc = launch_split_planes((const float*)dout, NC, planes, M, NC, NT, st);
         if (rc) return rc;
         a = planes;
@@ -164,21 +161,16 @@ static int conv_backward(const ConvDesc& d, const void* dout, const void* x, con
                        ev_start, ev_stop);
         if (rc) return rc;
     }
-    if (L.dw) {      // both operands as planes, transposed LDS reads, no conversion in the GEMM
-        if (L.xpl) {
-            rc = launch_split_planes((const float*)x, C, xplanes, M, C, NT, st);
-            if (rc) return rc;
-            b = xplanes;
-        }
-        rc = L.dw == 2 ? launch_mc_planes_big_raw(a, NC, b, C, 9, M, d.H, d.W, scratch, L.pl, NT, st)
-                       : launch_mc_planes(a, b, C, C, M, d.H, d.W, scratch, L.pl, NT, st);
-    } else {
-        rc = launch_mc((const float*)dout, NC, NC, (const float*)x, C, d.taps * C, M, true, d.H, d.W, C, scratch, L.pl,
-                       d.engine, st, nullptr, d.taps, d.depth);
+    if (L.xpl) {      // the weight gradient reads both operands as planes
+        rc = launch_split_planes((const float*)x, C, xplanes, M, C, NT, st);
+        if (rc) return rc;
+        b = xplanes;
     }
+    rc = L.wg.planes ? launch_wgrad(conv_wgrad(d, a, b, true), L.wg, scratch, st)
+                     : launch_wgrad(conv_wgrad(d, dout, x, false), L.wg, scratch, st);
     if (rc) return rc;
     // slab rows [nk*C][taps][Cin] -> dw0 / dw1 [C][Cin][taps] (nk = 1: every row in the first half)
-    rc = launch_reduce(scratch, L.pl.splits, (long long)NC * d.taps * C, dw0, dw1, 1, C, C, st, accumulate, d.taps);
+    rc = launch_reduce(scratch, L.wg.pl.splits, (long long)NC * d.taps * C, dw0, dw1, 1, C, C, st, accumulate, d.taps);
     if (rc || d.src == SRC_PLANES) return rc;
     const int split = d.nk == 2 ? C : 0;      // columns >= split are db1's
     return d.src == SRC_BF16 ? launch_colsum_bf16(dout, NC, M, NC, db0, scratch, st, db1, split, accumulate)
@@ -344,8 +336,9 @@ int pa2d_conv3x3x2_planes_mask(int B, int H, int W, int C, int engine) {
     const ConvDesc d = conv2d(B, H, W, C, 2, engine, SRC_F32);
     int m = 0;
     if (conv_planes_bytes(engine, d.M, 2 * C, C)) m |= 1;
-    if (conv_dw_kind(d)) m |= 2;
-    if (conv_planes_bytes(engine, d.M, C, 2 * C) && conv_dw_kind(d)) m |= 4;
+    const bool wg_planes = plan_wgrad(conv_wgrad(d, nullptr, nullptr, false)).planes;
+    if (wg_planes) m |= 2;
+    if (conv_planes_bytes(engine, d.M, C, 2 * C) && wg_planes) m |= 4;
     return m;
 }
 

@@ -212,7 +212,7 @@ __device__ __forceinline__ void conv_halo_body(const KCParams& p, const int tile
     }
 #define CH_T(ib_, j_, AF_, bq_, aq_) \
     acc[ib_][j_] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[j_][bq_], AF_[aq_], acc[ib_][j_], 0, 0, 0);
-#define CH_MM(ib_, j_, AF_)     /* smallest terms first; weights = A operand (rows = channels) */          \
+#define CH_MM(ib_, j_, AF_)     /* split_terms(AF_, bf[j_], acc) spelt out; weights = A operand (rows = channels) */ \
     {                                                                                                      \
         CH_T(ib_, j_, AF_, 1, 1) CH_T(ib_, j_, AF_, 0, 2) CH_T(ib_, j_, AF_, 2, 0)                         \
         CH_T(ib_, j_, AF_, 0, 1) CH_T(ib_, j_, AF_, 1, 0) CH_T(ib_, j_, AF_, 0, 0)                         \
@@ -273,14 +273,7 @@ __device__ __forceinline__ void conv_halo_body(const KCParams& p, const int tile
                 for (int q = 0; q < NT; ++q)
                     af[q] = *reinterpret_cast<const bf16x8*>(af_base + (ib >> 1) * (HWD * PITCHB) + (ib & 1) * 16 * PITCHB + q * 64);
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {                 // smallest terms first; weights = A operand (rows = channels)
-                    acc[ib][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[j][1], af[1], acc[ib][j], 0, 0, 0);
-                    acc[ib][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[j][0], af[2], acc[ib][j], 0, 0, 0);
-                    acc[ib][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[j][2], af[0], acc[ib][j], 0, 0, 0);
-                    acc[ib][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[j][0], af[1], acc[ib][j], 0, 0, 0);
-                    acc[ib][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[j][1], af[0], acc[ib][j], 0, 0, 0);
-                    acc[ib][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[j][0], af[0], acc[ib][j], 0, 0, 0);
-                }
+                for (int j = 0; j < 4; ++j) split_terms(af, bf[j], acc[ib][j]);      // weights = the MFMA's A operand (rows = channels)
             }
             ++tap;
             __syncthreads();                                  // end of stage sg
@@ -360,16 +353,7 @@ __device__ __forceinline__ void conv_halo_body(const KCParams& p, const int tile
 #pragma unroll
                 for (int i = 0; i < TM; ++i)
 #pragma unroll
-                    for (int j = 0; j < TN; ++j) {
-                        if constexpr (NT == 3) {   // smallest terms first
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][1], bf[j][1], acc[i][j], 0, 0, 0);
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][2], bf[j][0], acc[i][j], 0, 0, 0);
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][0], bf[j][2], acc[i][j], 0, 0, 0);
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][1], bf[j][0], acc[i][j], 0, 0, 0);
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][0], bf[j][1], acc[i][j], 0, 0, 0);
-                        }
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][0], bf[j][0], acc[i][j], 0, 0, 0);
-                    }
+                    for (int j = 0; j < TN; ++j) split_terms(af[i], bf[j], acc[i][j]);
             }
         }
         __syncthreads();                                  // end of stage sg

@@ -274,10 +274,18 @@ int pa2d_gemm_bwd_data(const float* dy, long long lddy, const float* w, long lon
     return launch_kc(p, false, st);
 }
 
+// dw[N,K] = dy[M,N]^T . x[M,K] as the weight-gradient dispatch sees it
+static MCDesc linear_wgrad(const void* dy, long long lddy, const void* x, long long ldx, int M, int N, int K, MCSrc src,
+                           int engine) {
+    MCDesc d = {};
+    d.A = dy; d.lda = lddy; d.B = x; d.ldb = ldx; d.Mi = N; d.Nj = K; d.Mk = M;
+    d.taps = 1; d.H = 1; d.W = 1; d.depth = 1; d.Cin = K; d.src = src; d.engine = engine;
+    return d;
+}
+
 size_t pa2d_gemm_bwd_weight_workspace(int M, int N, int K, int engine) {
-    (void)engine;
-    const MCPlan pl = plan_mc(N, K, M);
-    return (pl.slab_floats + (size_t)pl.splits * N) * sizeof(float);      // [slabs | per-split column sums of dy]
+    const MCChoice c = plan_wgrad(linear_wgrad(nullptr, N, nullptr, K, M, N, K, MC_SRC_F32, engine));
+    return c.slab_bytes + (size_t)c.pl.splits * N * sizeof(float);      // [slabs | per-split column sums of dy]
 }
 
 // dw[N,K] (+)= dy[M,N]^T . x[M,K] ; db[N] (+)= column sums of dy (db may be NULL).  accumulate != 0: add to what dw / db
@@ -291,13 +299,13 @@ int pa2d_gemm_bwd_weight(const float* dy, long long lddy, const float* x, long l
         return rz ? rz : pa2d_zero(db, sizeof(float) * N, st);
     }
     if (ws_bytes < pa2d_gemm_bwd_weight_workspace(M, N, K, engine)) return PA2D_ERR_WORKSPACE;
-    const MCPlan pl = plan_mc(N, K, M);
+    MCDesc d = linear_wgrad(dy, lddy, x, ldx, M, N, K, MC_SRC_F32, engine);
+    const MCChoice c = plan_wgrad(d);
+    const MCPlan& pl = c.pl;
     // the bias gradient (column sums of dy) rides in the GEMM: the workgroups of column tile 0 sum the dy tiles they stage
     float* cs = db ? (float*)ws + pl.slab_floats : nullptr;
-    // bf16 engines: the same split plan on the transposed-read planes kernel, operands split while staging
-    const bool bfk = (engine == 1 || engine == 2) && pl.big && mc_f32src_applies(N, K, M, lddy, ldx);
-    int rc = bfk ? launch_mc_f32src(dy, lddy, N, x, ldx, K, M, (float*)ws, pl, engine == 2 ? 1 : 3, cs, st)
-                 : launch_mc(dy, lddy, N, x, ldx, K, M, false, 0, 0, 0, (float*)ws, pl, engine, st, cs);
+    d.colsum = cs;
+    int rc = launch_wgrad(d, c, (float*)ws, st);
     if (rc) return rc;
     rc = launch_reduce((const float*)ws, pl.splits, (long long)N * K, dw, nullptr, 0, 0, 0, st, accumulate);
     if (rc) return rc;
@@ -331,9 +339,9 @@ int pa2d_gemm_bwd_data_bf16(const void* dy, long long lddy, const float* w, long
 }
 
 size_t pa2d_gemm_bwd_weight_workspace_bf16(int M, int N, int K) {
-    const MCPlan pl = plan_mc_planes_big(N, K, M);
-    size_t a = pl.slab_floats, b = (size_t)colsum_blocks(M) * N;
-    return (a > b ? a : b) * sizeof(float);
+    const MCChoice c = plan_wgrad(linear_wgrad(nullptr, N, nullptr, K, M, N, K, MC_SRC_BF16, 2));
+    const size_t b = (size_t)colsum_blocks(M) * N * sizeof(float);      // the column-sum partials reuse the slabs' space
+    return c.slab_bytes > b ? c.slab_bytes : b;
 }
 
 // dw[N,K] (+)= dy[M,N]^T . x[M,K] (fp32), db[N] (+)= column sums of dy; dy, x bf16 and CONTIGUOUS (lddy == N, ldx == K)
@@ -347,8 +355,10 @@ int pa2d_gemm_bwd_weight_bf16(const void* dy, long long lddy, const void* x, lon
         return rz ? rz : pa2d_zero(db, sizeof(float) * N, st);
     }
     if (ws_bytes < pa2d_gemm_bwd_weight_workspace_bf16(M, N, K)) return PA2D_ERR_WORKSPACE;
-    const MCPlan pl = plan_mc_planes_big(N, K, M);
-    int rc = launch_mc_planes_big_raw(dy, N, x, K, 1, M, 1, 1, (float*)ws, pl, 1, st);
+    const MCDesc d = linear_wgrad(dy, lddy, x, ldx, M, N, K, MC_SRC_BF16, 2);
+    const MCChoice c = plan_wgrad(d);
+    const MCPlan& pl = c.pl;
+    int rc = launch_wgrad(d, c, (float*)ws, st);
     if (rc) return rc;
     rc = launch_reduce((const float*)ws, pl.splits, (long long)N * K, dw, nullptr, 0, 0, 0, st, accumulate);
     if (rc) return rc;

@@ -1,8 +1,9 @@
 // Internal declarations shared by the GEMM translation units of libpa2d (pa2d_gemm.hip = engine selection, launch_kc +
 // C ABI of the linears, pa2d_conv.hip = C ABI of the conv stages (host code only), pa2d_gemm_kc.hip = exact fp32 engine,
-// pa2d_gemm_split.hip = bf16 split / bf16 compute engines, pa2d_gemm_mc.hip = weight-gradient engine and the
-// deterministic reductions).  Split only so that the translation units compile in parallel; nothing here is part of
-// the C ABI.
+// pa2d_gemm_split.hip = bf16 split / bf16 compute engines, pa2d_gemm_mc.hip = weight-gradient dispatch (plan_wgrad,
+// launch_wgrad), its gather kernel and the deterministic reductions, pa2d_gemm_mc_planes.hip = the weight-gradient kernels
+// on plane images), and the leaf code the weight-gradient kernels share.  Split only so that the translation units compile
+// in parallel; nothing here is part of the C ABI.
 #pragma once
 #include "pa2d_internal.h"
 #include "pa2d_bf16_split.h"      // bf16x8 / bf16x4, split3
@@ -135,6 +136,76 @@ struct MCParams {
 struct MCPlan { int big; int splits; int chunks_per_split; size_t slab_floats; };
 struct KCTile { int bm, bn, bk; };
 
+// ---- leaf code of the weight-gradient kernels (pa2d_gemm_mc.hip, pa2d_gemm_mc_planes.hip), written once; the kernels keep
+// their own staging and pipelines.  Three of the four are macros because the kernels' code objects are pinned: the same
+// text as an inline function (arguments by reference or by value) changes the register allocation of some instantiation.
+// Workgroup -> (split, row tile, column tile) of the 64 x 64 / 128 x 128-tile kernels.  XCD-aware map (speed only): when
+// the split count is a multiple of 8, blocks b, b+8, ... (one XCD under round-robin dispatch) own a contiguous range of
+// splits = a contiguous range of rows m, so each XCD's L2 streams 1/8 of the operands instead of all of them.
+#define MC_DECODE(splits_, tiles_i_, tiles_j_, split_, ti_, tj_)                                          \
+    {                                                                                                     \
+        const int tiles = (tiles_i_) * (tiles_j_);                                                        \
+        if (((splits_) & 7) == 0) {                                                                       \
+            const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, q = (splits_) >> 3;                   \
+            split_ = xcd * q + slot / tiles;                                                              \
+            const int t = slot % tiles;                                                                   \
+            tj_ = t % (tiles_j_);                                                                         \
+            ti_ = t / (tiles_j_);                                                                         \
+        } else {                                                                                          \
+            tj_ = blockIdx.x % (tiles_j_);                                                                \
+            ti_ = (blockIdx.x / (tiles_j_)) % (tiles_i_);                                                 \
+            split_ = blockIdx.x / tiles;                                                                  \
+        }                                                                                                 \
+    }
+// 8 consecutive fp32 values of one operand row (two 16-byte loads u0_, u1_) -> their NT_ bf16 planes pk_[NT_]; add_cs_: also
+// added to the thread's eight column sums cs_ (the bias gradient rides on the dY tiles of column tile 0)
+#define MC_SPLIT_ROW8(NT_, u0_, u1_, add_cs_, cs_, pk_)                                                   \
+    {                                                                                                     \
+        const float4 v0_ = make_float4(__uint_as_float((u0_).x), __uint_as_float((u0_).y), __uint_as_float((u0_).z), __uint_as_float((u0_).w)); \
+        const float4 v1_ = make_float4(__uint_as_float((u1_).x), __uint_as_float((u1_).y), __uint_as_float((u1_).z), __uint_as_float((u1_).w)); \
+        if (add_cs_) {                                                                                    \
+            cs_[0] += v0_.x; cs_[1] += v0_.y; cs_[2] += v0_.z; cs_[3] += v0_.w;                           \
+            cs_[4] += v1_.x; cs_[5] += v1_.y; cs_[6] += v1_.z; cs_[7] += v1_.w;                           \
+        }                                                                                                 \
+        bf16x4 h0_, m0_, l0_, h1_, m1_, l1_;                                                              \
+        split3(v0_, h0_, m0_, l0_);                                                                       \
+        split3(v1_, h1_, m1_, l1_);                                                                       \
+        pk_[0] = __builtin_shufflevector(h0_, h1_, 0, 1, 2, 3, 4, 5, 6, 7);                               \
+        if constexpr ((NT_) == 3) {                                                                       \
+            pk_[1] = __builtin_shufflevector(m0_, m1_, 0, 1, 2, 3, 4, 5, 6, 7);                           \
+            pk_[2] = __builtin_shufflevector(l0_, l1_, 0, 1, 2, 3, 4, 5, 6, 7);                           \
+        }                                                                                                 \
+    }
+// Column-sum epilogue: the RPP threads that staged the same column left their sums in sm[RPP][BM] (LDS is free after the
+// last barrier of the K loop); thread c < BM adds them in row order and stores colsum[split][ti*BM + c].
+template <int BM, int RPP>
+__device__ __forceinline__ void mc_colsum_reduce(const float* sm, int tid, int ti, int split, int Mi, float* colsum) {
+    static_assert(BM <= 256, "one column per thread");
+    __syncthreads();
+    if (tid < BM) {
+        float t = 0.f;
+#pragma unroll
+        for (int r = 0; r < RPP; ++r) t += sm[r * BM + tid];
+        if (ti * BM + tid < Mi) colsum[(size_t)split * Mi + ti * BM + tid] = t;
+    }
+}
+// Slab epilogue of the TM_ x TN_ 32x32x16 accumulators acc[i][j] of a wave into `out` (the split's slab), ragged edges
+// guarded: register r of lane l is row row0 + i*32 + (r&3) + 8*(r>>2) (row0 includes 4*(l>>5)), column col0 + j*32 (col0
+// includes l & 31).  Uses out, row0, col0, acc and p.Mi / p.Nj of the kernel.  One tile goes to the helper BY VALUE.
+__device__ __forceinline__ void mc_store_tile(float* out, int Mi, int Nj, int row0, int col, const f32x16 acc) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int row = row0 + (r & 3) + 8 * (r >> 2);
+        if (row < Mi) out[(size_t)row * Nj + col] = acc[r];
+    }
+}
+#define MC_STORE_TILES(TM_, TN_)                                                                          \
+    _Pragma("unroll") for (int j = 0; j < (TN_); ++j) {                                                   \
+        const int col = col0 + j * 32;                                                                    \
+        if (col >= p.Nj) continue;                                                                        \
+        _Pragma("unroll") for (int i = 0; i < (TM_); ++i) mc_store_tile(out, p.Mi, p.Nj, row0 + i * 32, col, acc[i][j]); \
+    }
+
 // engine selection / tile choice (pa2d_gemm.hip)
 static inline bool engine_ok(int e) { return e >= 0 && e <= 2; }
 bool use_split(int engine, int N, bool im2col, int Cin);
@@ -166,32 +237,41 @@ int launch_kc_rowpanel(const KCParams& p, const void* img, hipStream_t st);
 // conv with the halo tile resident in LDS (pa2d_conv_halo.hip): used by launch_kc_split for pre-split im2col operands
 bool conv_halo_applies(const KCParams& p);
 int launch_conv_halo(const KCParams& p, hipStream_t st);
-// weight-gradient engine and reductions (pa2d_gemm_mc.hip)
-MCPlan plan_mc(int Mi, int Nj, int Mk);
-// taps = 27 (im2col): the 3x3x3 view of an image [B,H,W,depth,Cin], Nj = 27*Cin
-int launch_mc(const float* A, long long lda, int Mi, const float* B, long long ldb, int Nj, int Mk, bool im2col,
-              int H, int W, int Cin, float* slab, const MCPlan& pl, int engine, hipStream_t st, float* colsum = nullptr,
-              int taps = 9, int depth = 1);
+// ---- weight gradients (pa2d_gemm_mc.hip): dW[Mi][Nj] = sum_m A[m][Mi]^T . B[m (shifted by tap)][Cin], written as per-split
+// slabs [splits][Mi][Nj] that launch_reduce adds up.  One description, one planner, one launch for every caller: the
+// counterpart of launch_kc.
+enum MCSrc {
+    MC_SRC_F32,       // A, B: fp32 matrices with row pitches lda, ldb (elements)
+    MC_SRC_PLANES,    // plane images of the split engines ([row][32-channel chunk][plane][32] bf16), contiguous
+    MC_SRC_BF16       // bf16 storage: contiguous bf16 tensors = 1-plane images (engine 2)
+};
+enum MCKernel { MC_K_GATHER, MC_K_F32SRC, MC_K_PLANES128, MC_K_PLANES256 };      // see plan_wgrad
+struct MCDesc {
+    const void* A; long long lda;      // dY / dOut [Mk][Mi]
+    const void* B; long long ldb;      // X [Mk][Cin]
+    int Mi, Nj, Mk;                    // Nj = taps * Cin
+    int taps;                          // 1: plain dW of a linear layer; 9: 3x3 view of the image B [.,H,W,Cin]; 27: 3x3x3 view of
+    int H, W, depth, Cin;              // [.,H,W,depth,Cin] (taps 1: H = W = depth = 1, Cin = Nj)
+    MCSrc src;
+    int engine;                        // PA2D_ENGINE_*
+    float* colsum;                     // optional, MC_SRC_F32 with taps = 1: [splits][Mi] per-split column sums of A
+};
+struct MCChoice {
+    MCKernel kernel;
+    MCPlan pl;                         // the split plan; pl.splits slabs
+    size_t slab_bytes;
+    bool planes;                       // the kernel reads plane images: an MC_SRC_F32 caller splits BOTH operands first
+                                       // (launch_split_planes) and launches with src = MC_SRC_PLANES
+};
+MCChoice plan_wgrad(const MCDesc& d);
+int launch_wgrad(const MCDesc& d, const MCChoice& c, float* slab, hipStream_t st);
+// the planes kernels behind launch_wgrad (pa2d_gemm_mc_planes.hip)
+int launch_wgrad_planes(const MCDesc& d, const MCChoice& c, unsigned a_bytes, unsigned b_bytes, float* slab, hipStream_t st);
 // accumulate != 0: out += sum of slabs (gradient accumulation straight into the caller's buffer); mode 1 with taps = 27
 // un-packs [2C][27][Cin] into two [C][Cin][3][3][3] gradients
 int launch_reduce(const float* slab, int nslab, long long count, float* out, float* out2, int mode, int C, int Cin,
                   hipStream_t st, int accumulate = 0, int taps = 9);
 int pa2d_launch_reduce(const float* slab, int nslab, long long count, float* out, hipStream_t st);
-// weight gradient from pre-split planes (pa2d_gemm_mc_planes.hip)
-bool mc_planes_supported(int C, int Cin);
-int launch_mc_planes(const void* PA, const void* PB, int C, int Cin, int Mk, int H, int W, float* slab,
-                     const MCPlan& pl, int NT, hipStream_t st);
-// 256 x 256-tile variant (8 waves, one round of workgroups) and its own split plan
-bool mc_planes_big_applies(int C, int Cin, int Mk);
-MCPlan plan_mc_planes_big(int Mi, int Nj, int Mk);
-int launch_mc_planes_big(const void* PA, const void* PB, int C, int Cin, int Mk, int H, int W, float* slab,
-                         const MCPlan& pl, int NT, hipStream_t st);
-int launch_mc_planes_big_raw(const void* PA, int Mi, const void* PB, int Cin, int taps, int Mk, int H, int W, float* slab,
-                             const MCPlan& pl, int NT, hipStream_t st);
-// plain dW of a linear layer straight from fp32 operands on the 128 x 128 planes kernel (split while staging)
-bool mc_f32src_applies(int Mi, int Nj, int Mk, long long lda, long long ldb);
-int launch_mc_f32src(const float* A, long long lda, int Mi, const float* B, long long ldb, int Nj, int Mk, float* slab,
-                     const MCPlan& pl, int NT, float* colsum, hipStream_t st);
 int colsum_blocks(int M);
 int launch_colsum_bf16(const void* X, long long ld, int M, int N, float* out, float* partial, hipStream_t st,
                        float* out2 = nullptr, int split = 0, int accumulate = 0);

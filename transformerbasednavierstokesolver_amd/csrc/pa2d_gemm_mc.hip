@@ -1,4 +1,6 @@
-// Weight-gradient GEMM engine (contraction over the row index of both operands), slab / column-sum reductions.
+// Weight gradients (contraction over the row index of both operands): the one dispatch of every dW (plan_wgrad: kernel, split
+// plan and slab bytes from shapes and environment; launch_wgrad: checks, buffer extents, launch), the gather kernel on fp32
+// operands (the planes kernels are in pa2d_gemm_mc_planes.hip), slab / column-sum reductions.
 #include "pa2d_gemm_common.h"
 
 // ---------------------------------------------------------------------------------------------
@@ -32,24 +34,8 @@ __global__ __launch_bounds__(256, 2) void gemm_mc_kernel(const MCParams p) {
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int tiles_i = (p.Mi + BM - 1) / BM, tiles_j = (p.Nj + BN - 1) / BN;
-    // XCD-aware map (speed only): when the split count is a multiple of 8, blocks b, b+8, ... (one XCD
-    // under round-robin dispatch) own a contiguous range of splits = a contiguous range of rows m, so
-    // each XCD's L2 streams 1/8 of the operands instead of all of them.
     int tj, ti, split;
-    {
-        const int tiles = tiles_i * tiles_j;
-        if ((p.splits & 7) == 0) {
-            const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, q = p.splits >> 3;
-            split = xcd * q + slot / tiles;
-            const int t = slot % tiles;
-            tj = t % tiles_j;
-            ti = t / tiles_j;
-        } else {
-            tj = blockIdx.x % tiles_j;
-            ti = (blockIdx.x / tiles_j) % tiles_i;
-            split = blockIdx.x / tiles;
-        }
-    }
+    MC_DECODE(p.splits, tiles_i, tiles_j, split, ti, tj)
     const int wm = wave >> 1, wn = wave & 1;
 
     // the host plans in 16-row chunks; a K-step of BK rows covers BK/16 of them
@@ -155,16 +141,7 @@ __global__ __launch_bounds__(256, 2) void gemm_mc_kernel(const MCParams p) {
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
-                for (int j = 0; j < TN; ++j) {
-                    if constexpr (NT == 3) {   // smallest terms first
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][1], bf[j][1], acc[i][j], 0, 0, 0);
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][2], bf[j][0], acc[i][j], 0, 0, 0);
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][0], bf[j][2], acc[i][j], 0, 0, 0);
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][1], bf[j][0], acc[i][j], 0, 0, 0);
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][0], bf[j][1], acc[i][j], 0, 0, 0);
-                    }
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][0], bf[j][0], acc[i][j], 0, 0, 0);
-                }
+                for (int j = 0; j < TN; ++j) split_terms(af[i], bf[j], acc[i][j]);
         } else {
         // fragments of k-step kk+1 are fetched into the other register set before the MFMAs of
         // k-step kk issue, so the LDS latency hides behind 4 x 64 MFMA cycles
@@ -215,22 +192,13 @@ __global__ __launch_bounds__(256, 2) void gemm_mc_kernel(const MCParams p) {
     float* out = p.slab + (size_t)split * p.Mi * p.Nj;
     const int col0 = tj * BN + wn * WN + (lane & 31);
     const int row0 = ti * BM + wm * WM + 4 * (lane >> 5);
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-        const int col = col0 + j * 32;
-        if (col >= p.Nj) continue;
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = row0 + i * 32 + (r & 3) + 8 * (r >> 2);
-                if (row < p.Mi) out[(size_t)row * p.Nj + col] = acc[i][j][r];
-            }
-    }
+    MC_STORE_TILES(TM, TN)
 }
 
 
-MCPlan plan_mc(int Mi, int Nj, int Mk) {
+// ---------------------------------------------------------------------------------------------
+// Split plans.  plan_mc: the 64 x 64 / 128 x 128-tile kernels (several rounds of workgroups).
+static MCPlan plan_mc(int Mi, int Nj, int Mk) {
     MCPlan pl;
     if (Mk < 1) Mk = 1;       // empty contraction (batch 0): plan as one chunk, the entry points zero-fill instead
     pl.big = (Mi > 64 && Nj > 64) ? 1 : 0;
@@ -262,6 +230,46 @@ MCPlan plan_mc(int Mi, int Nj, int Mk) {
     pl.splits = ceil_div(total_chunks, pl.chunks_per_split);
     pl.slab_floats = (size_t)pl.splits * Mi * Nj;
     return pl;
+}
+
+// the 256 x 256-tile kernel: one round of <= 256 workgroups, splits = 256 / tiles (>= 8 K-steps of 16 rows per split)
+static MCPlan plan_mc_planes_big(int Mi, int Nj, int Mk) {
+    MCPlan pl;
+    if (Mk < 1) Mk = 1;
+    pl.big = 2;
+    const int tiles = ceil_div(Mi, 256) * ceil_div(Nj, 256);
+    const int total_chunks = ceil_div(Mk, 16);
+    int splits = 256 / tiles;
+    if (pa2d_env().mcb_splits > 0) splits = pa2d_env().mcb_splits;         // tuning knob PA2D_MCB_SPLITS
+    const int max_splits = total_chunks / 8 > 0 ? total_chunks / 8 : 1;
+    if (splits > max_splits) splits = max_splits;
+    if (splits < 1) splits = 1;
+    pl.chunks_per_split = ceil_div(total_chunks, splits);
+    pl.splits = ceil_div(total_chunks, pl.chunks_per_split);
+    pl.slab_floats = (size_t)pl.splits * Mi * Nj;
+    return pl;
+}
+
+// Which kernel computes this dW, on which split plan (shapes and environment only; no pointer of `d` is read).
+MCChoice plan_wgrad(const MCDesc& d) {
+    MCChoice c = {};
+    c.kernel = MC_K_GATHER;
+    if (d.src == MC_SRC_BF16) {
+        c.kernel = MC_K_PLANES256;                    // bf16 storage: the tensors are the 1-plane images
+    } else if (d.taps == 1) {
+        // linear layer on the bf16 engines: the 128 x 128 planes kernel, operands split while staging (PA2D_LIN_DW_SPLIT=off: never)
+        if ((d.engine == 1 || d.engine == 2) && pa2d_env().lin_dw_split && (d.Mi % 8) == 0 && (d.Nj % 8) == 0 && d.Mi > 64 &&
+            d.Nj > 64 && d.Mk >= 16 * 8 * 16 && (d.lda % 4) == 0 && (d.ldb % 4) == 0)
+            c.kernel = MC_K_F32SRC;
+    } else if (d.taps == 9 && use_split(d.engine, d.Cin, true, d.Mi)) {
+        // 3x3 conv whose data gradient reads dOut as planes: both operands as planes, transposed LDS reads
+        if (!pa2d_env().mc_big_off && (d.Cin % 32) == 0 && d.Mi >= 256 && d.Mk >= 16 * 8 * 4) c.kernel = MC_K_PLANES256;
+        else if (d.Mi == 2 * d.Cin && (d.Cin % 128) == 0) c.kernel = MC_K_PLANES128;      // written for the pair [Wx | Wf]
+    }
+    c.planes = c.kernel == MC_K_PLANES128 || c.kernel == MC_K_PLANES256;
+    c.pl = c.kernel == MC_K_PLANES256 ? plan_mc_planes_big(d.Mi, d.Nj, d.Mk) : plan_mc(d.Mi, d.Nj, d.Mk);
+    c.slab_bytes = c.pl.slab_floats * sizeof(float);
+    return c;
 }
 
 // out[idx] = sum_s slab[s][idx]; mode 1 additionally un-packs the conv weight gradient:
@@ -306,57 +314,57 @@ __global__ __launch_bounds__(256) void reduce_slabs_kernel(const float* __restri
     *dst = accumulate ? *dst + s : s;
 }
 
-int launch_mc(const float* A, long long lda, int Mi, const float* B, long long ldb, int Nj, int Mk,
-                     bool im2col, int H, int W, int Cin, float* slab, const MCPlan& pl, int engine, hipStream_t st,
-                     float* colsum, int taps, int depth) {
-    if ((Mi & 3) || (Nj & 3) || (lda & 3) || (ldb & 3)) return PA2D_ERR_ARG;
-    if (im2col && (Cin & 3)) return PA2D_ERR_UNSUPPORTED;
-    MCParams p;
-    p.A = A; p.lda = lda; p.Mi = Mi; p.B = B; p.ldb = ldb; p.Nj = Nj; p.slab = slab; p.Mk = Mk;
-    p.chunks_per_split = pl.chunks_per_split; p.splits = pl.splits; p.H = H; p.W = W; p.Cin = Cin;
-    p.colsum = colsum;
-    p.depth = depth;
-    {
-        const unsigned long long ab = ((unsigned long long)(Mk - 1) * lda + Mi) * 4ull;
-        const unsigned long long bb = ((unsigned long long)(Mk - 1) * ldb + (im2col ? Cin : Nj)) * 4ull;
-        if (ab >= 0xFFFFFFF0ull || bb >= 0xFFFFFFF0ull) return PA2D_ERR_UNSUPPORTED;
-        p.a_bytes = (unsigned)ab;
-        p.b_bytes = (unsigned)bb;
-    }
+// the variant ladder of gemm_mc_kernel (fp32 operands gathered through LDS); PA2D_MC_BK=32: 32-row K-steps of the exact kernel
+static void launch_mc_gather(const MCParams& p, const MCPlan& pl, bool im2col, int taps, int engine, hipStream_t st) {
     const int bm = pl.big ? 128 : 64;
-    const dim3 grid(ceil_div(Mi, bm) * ceil_div(Nj, bm) * pl.splits);
+    const dim3 grid(ceil_div(p.Mi, bm) * ceil_div(p.Nj, bm) * pl.splits);
     const bool bf = engine == 2;
-    const int mc_bk = pa2d_env().mc_bk;
+    const bool bk32 = pl.big && !bf && pa2d_env().mc_bk == 32 && (pl.chunks_per_split % 2) == 0;
+    const bool split = pl.big && im2col && engine == 1 && (p.Cin % 32) == 0;      // 6-term split, fp32 accuracy
+#define MC_GO(...) hipLaunchKernelGGL((gemm_mc_kernel<__VA_ARGS__>), grid, dim3(256), 0, st, p)
     if (im2col && taps == 27) {      // 3x3x3 conv weight gradient: the same variant choice on the 27-tap view
-        if (pl.big && !bf && mc_bk == 32 && (pl.chunks_per_split % 2) == 0)
-            hipLaunchKernelGGL((gemm_mc_kernel<128, 128, true, 0, 32, 27>), grid, dim3(256), 0, st, p);
-        else if (pl.big && engine == 1 && (Cin % 32) == 0)
-            hipLaunchKernelGGL((gemm_mc_kernel<128, 128, true, 3, 16, 27>), grid, dim3(256), 0, st, p);
-        else if (pl.big && bf)
-            hipLaunchKernelGGL((gemm_mc_kernel<128, 128, true, 1, 16, 27>), grid, dim3(256), 0, st, p);
-        else if (pl.big)
-            hipLaunchKernelGGL((gemm_mc_kernel<128, 128, true, 0, 16, 27>), grid, dim3(256), 0, st, p);
-        else
-            hipLaunchKernelGGL((gemm_mc_kernel<64, 64, true, 0, 16, 27>), grid, dim3(256), 0, st, p);
-        PA2D_CHECK_LAUNCH();
-        return PA2D_OK;
-    }
-    if (pl.big && !bf && mc_bk == 32 && (pl.chunks_per_split % 2) == 0) {
-        if (im2col) hipLaunchKernelGGL((gemm_mc_kernel<128, 128, true, 0, 32>), grid, dim3(256), 0, st, p);
-        else hipLaunchKernelGGL((gemm_mc_kernel<128, 128, false, 0, 32>), grid, dim3(256), 0, st, p);
-    } else if (pl.big && im2col && engine == 1 && (Cin % 32) == 0) {     // 6-term split, fp32 accuracy
-        hipLaunchKernelGGL((gemm_mc_kernel<128, 128, true, 3>), grid, dim3(256), 0, st, p);
-
+        if (bk32) MC_GO(128, 128, true, 0, 32, 27);
+        else if (split) MC_GO(128, 128, true, 3, 16, 27);
+        else if (pl.big && bf) MC_GO(128, 128, true, 1, 16, 27);
+        else if (pl.big) MC_GO(128, 128, true, 0, 16, 27);
+        else MC_GO(64, 64, true, 0, 16, 27);
+    } else if (bk32) {
+        if (im2col) MC_GO(128, 128, true, 0, 32); else MC_GO(128, 128, false, 0, 32);
+    } else if (split) {
+        MC_GO(128, 128, true, 3);
     } else if (pl.big && bf) {
-        if (im2col) hipLaunchKernelGGL((gemm_mc_kernel<128, 128, true, 1>), grid, dim3(256), 0, st, p);
-        else hipLaunchKernelGGL((gemm_mc_kernel<128, 128, false, 1>), grid, dim3(256), 0, st, p);
+        if (im2col) MC_GO(128, 128, true, 1); else MC_GO(128, 128, false, 1);
     } else if (pl.big) {
-        if (im2col) hipLaunchKernelGGL((gemm_mc_kernel<128, 128, true, 0>), grid, dim3(256), 0, st, p);
-        else hipLaunchKernelGGL((gemm_mc_kernel<128, 128, false, 0>), grid, dim3(256), 0, st, p);
+        if (im2col) MC_GO(128, 128, true, 0); else MC_GO(128, 128, false, 0);
     } else {
-        if (im2col) hipLaunchKernelGGL((gemm_mc_kernel<64, 64, true, 0>), grid, dim3(256), 0, st, p);
-        else hipLaunchKernelGGL((gemm_mc_kernel<64, 64, false, 0>), grid, dim3(256), 0, st, p);
+        if (im2col) MC_GO(64, 64, true, 0); else MC_GO(64, 64, false, 0);
     }
+#undef MC_GO
+}
+
+// The one dispatch of every weight gradient: shape checks of the chosen kernel, the 32-bit operand extents of the buffer
+// descriptors, the launch.  `c` = plan_wgrad(d); slab: c.slab_bytes.
+int launch_wgrad(const MCDesc& d, const MCChoice& c, float* slab, hipStream_t st) {
+    const bool im2col = d.taps != 1;
+    const int NT = d.engine == 2 ? 1 : 3;              // bf16 planes per operand
+    if (c.planes != (d.src != MC_SRC_F32)) return PA2D_ERR_ARG;
+    if (c.kernel == MC_K_GATHER) {
+        if ((d.Mi & 3) || (d.Nj & 3) || (d.lda & 3) || (d.ldb & 3)) return PA2D_ERR_ARG;
+        if (im2col && (d.Cin & 3)) return PA2D_ERR_UNSUPPORTED;
+    } else if (c.kernel == MC_K_PLANES256) {
+        if ((d.Mi & 31) || (d.Cin & 31) || (d.taps != 1 && d.taps != 9)) return PA2D_ERR_UNSUPPORTED;
+    }
+    const unsigned long long ab = c.planes ? (unsigned long long)d.Mk * (d.Mi / 32) * NT * 64
+                                           : ((unsigned long long)(d.Mk - 1) * d.lda + d.Mi) * 4ull;
+    const unsigned long long bb = c.planes ? (unsigned long long)d.Mk * (d.Cin / 32) * NT * 64
+                                           : ((unsigned long long)(d.Mk - 1) * d.ldb + d.Cin) * 4ull;
+    if (ab >= 0xFFFFFFF0ull || bb >= 0xFFFFFFF0ull) return PA2D_ERR_UNSUPPORTED;
+    if (c.kernel != MC_K_GATHER) return launch_wgrad_planes(d, c, (unsigned)ab, (unsigned)bb, slab, st);
+    MCParams p;
+    p.A = (const float*)d.A; p.lda = d.lda; p.Mi = d.Mi; p.B = (const float*)d.B; p.ldb = d.ldb; p.Nj = d.Nj; p.slab = slab;
+    p.Mk = d.Mk; p.chunks_per_split = c.pl.chunks_per_split; p.splits = c.pl.splits; p.H = d.H; p.W = d.W; p.Cin = d.Cin;
+    p.colsum = d.colsum; p.depth = d.depth; p.a_bytes = (unsigned)ab; p.b_bytes = (unsigned)bb;
+    launch_mc_gather(p, c.pl, im2col, d.taps, d.engine, st);
     PA2D_CHECK_LAUNCH();
     return PA2D_OK;
 }

@@ -26,6 +26,14 @@ __device__ __forceinline__ unsigned img_off(int row, int ch) {       // byte off
     return 256u * row + 16u * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3)));
 }
 
+// 16x16x32 forms: the fragment of the wave's 16-column tile t_ in plane image pl_, from the lane's two addresses base_ for tile 0
+// (tile t is `^ (t << 5)`).  Written on the builtins: through tr_frag the 256 x 256 kernel's address arithmetic changes.
+#define MC16_FRAG(base_, t_, pl_)                                                                         \
+    __builtin_bit_cast(bf16x8, __builtin_shufflevector(                                                   \
+        __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(smem + ((base_[0] ^ ((unsigned)(t_) << 5)) + (pl_) * PIMG))), \
+        __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(smem + ((base_[1] ^ ((unsigned)(t_) << 5)) + (pl_) * PIMG))), \
+        0, 1, 2, 3, 4, 5, 6, 7))
+
 // KS = 16-row K-steps per LDS stage (one barrier per stage): 1 for NT = 3 (24 MFMAs per wave and barrier, 48 KB of LDS),
 // 4 for NT = 1 (16 MFMAs per barrier instead of 4, 64 KB).
 // F32SRC: plain dW = A^T . B of a linear layer straight from the fp32 operands (no tap shift): each thread loads the 8
@@ -43,20 +51,7 @@ __global__ __launch_bounds__(256, 2) void gemm_mc_planes_kernel(const MCPlanesPa
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int tiles_i = (p.Mi + 127) / 128, tiles_j = (p.Nj + 127) / 128;
     int tj, ti, split;
-    {
-        const int tiles = tiles_i * tiles_j;
-        if ((p.splits & 7) == 0) {                   // XCD-contiguous split ranges, as in gemm_mc_kernel
-            const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, q = p.splits >> 3;
-            split = xcd * q + slot / tiles;
-            const int t = slot % tiles;
-            tj = t % tiles_j;
-            ti = t / tiles_j;
-        } else {
-            tj = blockIdx.x % tiles_j;
-            ti = (blockIdx.x / tiles_j) % tiles_i;
-            split = blockIdx.x / tiles;
-        }
-    }
+    MC_DECODE(p.splits, tiles_i, tiles_j, split, ti, tj)
     const int wm = wave >> 1, wn = wave & 1;
     const int total_chunks = (p.Mk + 15) / 16;
     const int c_begin = split * p.chunks_per_split;
@@ -128,22 +123,11 @@ __global__ __launch_bounds__(256, 2) void gemm_mc_planes_kernel(const MCPlanesPa
 #define MP_STORE(buf_)                                                                                    \
     if constexpr (F32SRC) {                                                                               \
         _Pragma("unroll") for (int ks = 0; ks < KS; ++ks) _Pragma("unroll") for (int op = 0; op < 2; ++op) { \
-            const u32x4 u0_ = rg[ks * 4 + op * 2], u1_ = rg[ks * 4 + op * 2 + 1];                         \
-            const float4 v0_ = make_float4(__uint_as_float(u0_.x), __uint_as_float(u0_.y), __uint_as_float(u0_.z), __uint_as_float(u0_.w)); \
-            const float4 v1_ = make_float4(__uint_as_float(u1_.x), __uint_as_float(u1_.y), __uint_as_float(u1_.z), __uint_as_float(u1_.w)); \
-            if (op == 0 && do_cs) {                                                                       \
-                cs[0] += v0_.x; cs[1] += v0_.y; cs[2] += v0_.z; cs[3] += v0_.w;                           \
-                cs[4] += v1_.x; cs[5] += v1_.y; cs[6] += v1_.z; cs[7] += v1_.w;                           \
-            }                                                                                             \
-            bf16x4 h0_, m0_, l0_, h1_, m1_, l1_;                                                          \
-            split3(v0_, h0_, m0_, l0_);                                                                   \
-            split3(v1_, h1_, m1_, l1_);                                                                   \
+            bf16x8 pk_[NT];                                                                               \
+            MC_SPLIT_ROW8(NT, rg[ks * 4 + op * 2], rg[ks * 4 + op * 2 + 1], op == 0 && do_cs, cs, pk_)   \
             unsigned char* d_ = smem + (buf_) * STAGE + flds;                                             \
-            *reinterpret_cast<bf16x8*>(d_ + ((op * NT + 0) * KS + ks) * PIMG) = __builtin_shufflevector(h0_, h1_, 0, 1, 2, 3, 4, 5, 6, 7); \
-            if (NT == 3) {                                                                                \
-                *reinterpret_cast<bf16x8*>(d_ + ((op * NT + 1) * KS + ks) * PIMG) = __builtin_shufflevector(m0_, m1_, 0, 1, 2, 3, 4, 5, 6, 7); \
-                *reinterpret_cast<bf16x8*>(d_ + ((op * NT + 2) * KS + ks) * PIMG) = __builtin_shufflevector(l0_, l1_, 0, 1, 2, 3, 4, 5, 6, 7); \
-            }                                                                                             \
+            _Pragma("unroll") for (int pl = 0; pl < NT; ++pl)                                             \
+                *reinterpret_cast<bf16x8*>(d_ + ((op * NT + pl) * KS + ks) * PIMG) = pk_[pl];             \
         }                                                                                                 \
     } else {                                                                                              \
         _Pragma("unroll") for (int s = 0; s < NP; ++s)                                                    \
@@ -168,40 +152,12 @@ __global__ __launch_bounds__(256, 2) void gemm_mc_planes_kernel(const MCPlanesPa
             fa[r] = img_off(row, wm * 8 + (pq >> 1)) + 8u * (pq & 1);
             fb[r] = img_off(row, wn * 8 + (pq >> 1)) + 8u * (pq & 1);
         }
-        typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-#define MP16_FRAG(base_, t_, pl_)                                                                         \
-    __builtin_bit_cast(bf16x8, __builtin_shufflevector(                                                   \
-        __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(smem + ((base_[0] ^ ((unsigned)(t_) << 5)) + (pl_) * PIMG))), \
-        __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(smem + ((base_[1] ^ ((unsigned)(t_) << 5)) + (pl_) * PIMG))), \
-        0, 1, 2, 3, 4, 5, 6, 7))
-#define MP16_MMA(ib_, AF)                                                                                 \
-    _Pragma("unroll") for (int j = 0; j < 4; ++j) {       /* smallest terms first; (A plane, B plane) as the 32x32x16 form */ \
-        acc[ib_][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xf[j][1], AF[1], acc[ib_][j], 0, 0, 0);     \
-        acc[ib_][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xf[j][0], AF[2], acc[ib_][j], 0, 0, 0);     \
-        acc[ib_][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xf[j][2], AF[0], acc[ib_][j], 0, 0, 0);     \
-        acc[ib_][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xf[j][0], AF[1], acc[ib_][j], 0, 0, 0);     \
-        acc[ib_][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xf[j][1], AF[0], acc[ib_][j], 0, 0, 0);     \
-        acc[ib_][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xf[j][0], AF[0], acc[ib_][j], 0, 0, 0);     \
-    }
+#define MP16_MMA(ib_, AF) _Pragma("unroll") for (int j = 0; j < 4; ++j) split_terms(AF, xf[j], acc[ib_][j]);
         // staging in two parts: MP16_CONVERT splits the fp32 registers into the bf16 planes (and adds to the column sums) while
         // the other waves still multiply, MP16_WRITE is the six 16-byte LDS stores alone -> only those sit between the barriers
         bf16x8 pk[2][NT];
 #define MP16_CONVERT()                                                                                    \
-    _Pragma("unroll") for (int op = 0; op < 2; ++op) {                                                    \
-        const u32x4 u0_ = rg[op * 2], u1_ = rg[op * 2 + 1];                                               \
-        const float4 v0_ = make_float4(__uint_as_float(u0_.x), __uint_as_float(u0_.y), __uint_as_float(u0_.z), __uint_as_float(u0_.w)); \
-        const float4 v1_ = make_float4(__uint_as_float(u1_.x), __uint_as_float(u1_.y), __uint_as_float(u1_.z), __uint_as_float(u1_.w)); \
-        if (op == 0 && do_cs) {                                                                           \
-            cs[0] += v0_.x; cs[1] += v0_.y; cs[2] += v0_.z; cs[3] += v0_.w;                               \
-            cs[4] += v1_.x; cs[5] += v1_.y; cs[6] += v1_.z; cs[7] += v1_.w;                               \
-        }                                                                                                 \
-        bf16x4 h0_, m0_, l0_, h1_, m1_, l1_;                                                              \
-        split3(v0_, h0_, m0_, l0_);                                                                       \
-        split3(v1_, h1_, m1_, l1_);                                                                       \
-        pk[op][0] = __builtin_shufflevector(h0_, h1_, 0, 1, 2, 3, 4, 5, 6, 7);                            \
-        pk[op][1] = __builtin_shufflevector(m0_, m1_, 0, 1, 2, 3, 4, 5, 6, 7);                            \
-        pk[op][2] = __builtin_shufflevector(l0_, l1_, 0, 1, 2, 3, 4, 5, 6, 7);                            \
-    }
+    _Pragma("unroll") for (int op = 0; op < 2; ++op) MC_SPLIT_ROW8(NT, rg[op * 2], rg[op * 2 + 1], op == 0 && do_cs, cs, pk[op])
 #define MP16_WRITE(buf_)                                                                                  \
     _Pragma("unroll") for (int op = 0; op < 2; ++op) _Pragma("unroll") for (int pl = 0; pl < NT; ++pl)    \
         *reinterpret_cast<bf16x8*>(smem + (buf_) * STAGE + flds + (op * NT + pl) * PIMG) = pk[op][pl];
@@ -229,15 +185,15 @@ __global__ __launch_bounds__(256, 2) void gemm_mc_planes_kernel(const MCPlanesPa
 #pragma unroll
             for (int j = 0; j < 4; ++j)
 #pragma unroll
-                for (int pl = 0; pl < NT; ++pl) xf[j][pl] = MP16_FRAG(ub, j, pl);
+                for (int pl = 0; pl < NT; ++pl) xf[j][pl] = MC16_FRAG(ub, j, pl);
             bf16x8 afc[NT], afn[NT];                      // A fragments one 16-row tile ahead of their MFMAs
 #pragma unroll
-            for (int pl = 0; pl < NT; ++pl) afc[pl] = MP16_FRAG(ua, 0, pl);
+            for (int pl = 0; pl < NT; ++pl) afc[pl] = MC16_FRAG(ua, 0, pl);
 #pragma unroll
             for (int ib = 0; ib < 4; ++ib) {
                 if (ib < 3) {
 #pragma unroll
-                    for (int pl = 0; pl < NT; ++pl) afn[pl] = MP16_FRAG(ua, ib + 1, pl);
+                    for (int pl = 0; pl < NT; ++pl) afn[pl] = MC16_FRAG(ua, ib + 1, pl);
                 }
                 if (ib == 1 && has_next) {
                     MP16_CONVERT()
@@ -265,18 +221,11 @@ __global__ __launch_bounds__(256, 2) void gemm_mc_planes_kernel(const MCPlanesPa
 #undef MP16_CONVERT
 #undef MP16_WRITE
 #undef MP16_MMA
-#undef MP16_FRAG
         if (do_cs) {       // as below: LDS is free after the last barrier
             float* sm = reinterpret_cast<float*>(smem);
 #pragma unroll
             for (int e = 0; e < 8; ++e) sm[frow * 128 + fc8 * 8 + e] = cs[e];
-            __syncthreads();
-            if (tid < 128) {
-                float t = 0.f;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) t += sm[r * 128 + tid];
-                if (ti * 128 + tid < p.Mi) p.colsum[(size_t)split * p.Mi + ti * 128 + tid] = t;
-            }
+            mc_colsum_reduce<128, 16>(sm, tid, ti, split, p.Mi, p.colsum);
         }
         // accumulator quad r = 0..3 of lane l: dW row ti*128 + wm*64 + ib*16 + (l & 15), columns tj*128 + wn*64 + j*16 +
         // 4*(l >> 4) + r (Nj % 4 == 0, checked by the launcher: a quad is inside or outside as a whole)
@@ -332,29 +281,13 @@ __global__ __launch_bounds__(256, 2) void gemm_mc_planes_kernel(const MCPlanesPa
         for (int t = 0; t < 2; ++t)
 #pragma unroll
             for (int pl = 0; pl < NT; ++pl) {
-                typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-                const s16x4 a0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(st + pl * KS * PIMG + fa[t][0]));
-                const s16x4 a1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(st + pl * KS * PIMG + fa[t][1]));
-                const s16x4 b0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(st + (NT + pl) * KS * PIMG + fb[t][0]));
-                const s16x4 b1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(st + (NT + pl) * KS * PIMG + fb[t][1]));
-                const s16x8 av = __builtin_shufflevector(a0, a1, 0, 1, 2, 3, 4, 5, 6, 7);
-                const s16x8 bv = __builtin_shufflevector(b0, b1, 0, 1, 2, 3, 4, 5, 6, 7);
-                af[t][pl] = __builtin_bit_cast(bf16x8, av);
-                bf[t][pl] = __builtin_bit_cast(bf16x8, bv);
+                af[t][pl] = tr_frag(st + pl * KS * PIMG, fa[t][0], fa[t][1]);
+                bf[t][pl] = tr_frag(st + (NT + pl) * KS * PIMG, fb[t][0], fb[t][1]);
             }
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                if constexpr (NT == 3) {   // smallest terms first
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][1], bf[j][1], acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][2], bf[j][0], acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][0], bf[j][2], acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][1], bf[j][0], acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][0], bf[j][1], acc[i][j], 0, 0, 0);
-                }
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][0], bf[j][0], acc[i][j], 0, 0, 0);
-            }
+            for (int j = 0; j < 2; ++j) split_terms(af[i], bf[j], acc[i][j]);
         }
         if (c + KS < c_end) { MP_STORE(buf ^ 1) }
         __syncthreads();
@@ -367,13 +300,7 @@ __global__ __launch_bounds__(256, 2) void gemm_mc_planes_kernel(const MCPlanesPa
             float* sm = reinterpret_cast<float*>(smem);
 #pragma unroll
             for (int e = 0; e < 8; ++e) sm[frow * 128 + fc8 * 8 + e] = cs[e];
-            __syncthreads();
-            if (tid < 128) {
-                float t = 0.f;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) t += sm[r * 128 + tid];
-                if (ti * 128 + tid < p.Mi) p.colsum[(size_t)split * p.Mi + ti * 128 + tid] = t;
-            }
+            mc_colsum_reduce<128, 16>(sm, tid, ti, split, p.Mi, p.colsum);
         }
     }
     float* out = p.slab + (size_t)split * p.Mi * p.Nj;
@@ -388,26 +315,6 @@ __global__ __launch_bounds__(256, 2) void gemm_mc_planes_kernel(const MCPlanesPa
                 const int row = row0 + i * 32 + (r & 3) + 8 * (r >> 2);
                 if (!F32SRC || (row < p.Mi && col0 + j * 32 < p.Nj)) out[(size_t)row * p.Nj + col0 + j * 32] = acc[i][j][r];
             }
-}
-
-bool mc_planes_supported(int C, int Cin) { return (C % 64) == 0 && (Cin % 128) == 0; }
-
-// PA: planes of dOut [Mk][2C], PB: planes of X [Mk][Cin] (both NT planes per 32-channel chunk); slab as launch_mc
-int launch_mc_planes(const void* PA, const void* PB, int C, int Cin, int Mk, int H, int W, float* slab,
-                     const MCPlan& pl, int NT, hipStream_t st) {
-    if (!mc_planes_supported(C, Cin) || !pl.big) return PA2D_ERR_UNSUPPORTED;
-    MCPlanesParams p;
-    p.PA = PA; p.chA = 2 * C / 32; p.PB = PB; p.chB = Cin / 32; p.slab = slab;
-    p.Mi = 2 * C; p.Nj = 9 * Cin; p.Mk = Mk; p.chunks_per_split = pl.chunks_per_split; p.splits = pl.splits;
-    p.H = H; p.W = W; p.Cin = Cin; p.taps = 9;
-    const unsigned long long ab = (unsigned long long)Mk * p.chA * NT * 64, bb = (unsigned long long)Mk * p.chB * NT * 64;
-    if (ab >= 0xFFFFFFF0ull || bb >= 0xFFFFFFF0ull) return PA2D_ERR_UNSUPPORTED;
-    p.a_bytes = (unsigned)ab; p.b_bytes = (unsigned)bb;
-    const dim3 grid((p.Mi / 128) * (p.Nj / 128) * pl.splits);
-    if (NT == 3) hipLaunchKernelGGL((gemm_mc_planes_kernel<3, 1>), grid, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((gemm_mc_planes_kernel<1, 4>), grid, dim3(256), 0, st, p);
-    PA2D_CHECK_LAUNCH();
-    return PA2D_OK;
 }
 
 // =============================================================================================================
@@ -522,21 +429,7 @@ __global__ __launch_bounds__(512, 1) void gemm_mc_planes_big_kernel(const MCPlan
             fa[r] = 512u * row + 16u * ((unsigned)(wm * 16 + (pq >> 1)) ^ swz) + 8u * (pq & 1);
             fb[r] = 512u * row + 16u * ((unsigned)(wn * 8 + (pq >> 1)) ^ swz) + 8u * (pq & 1);
         }
-        typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-#define MB16_FRAG(base_, t_, pl_)                                                                         \
-    __builtin_bit_cast(bf16x8, __builtin_shufflevector(                                                   \
-        __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(smem + ((base_[0] ^ ((unsigned)(t_) << 5)) + (pl_) * PIMG))), \
-        __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(smem + ((base_[1] ^ ((unsigned)(t_) << 5)) + (pl_) * PIMG))), \
-        0, 1, 2, 3, 4, 5, 6, 7))
-#define MB16_MMA(ib_, AF)                                                                                 \
-    _Pragma("unroll") for (int j = 0; j < 4; ++j) {       /* smallest terms first; (dOut plane, X plane) as the 32x32x16 form */ \
-        acc[ib_][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xf[j][1], AF[1], acc[ib_][j], 0, 0, 0);     \
-        acc[ib_][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xf[j][0], AF[2], acc[ib_][j], 0, 0, 0);     \
-        acc[ib_][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xf[j][2], AF[0], acc[ib_][j], 0, 0, 0);     \
-        acc[ib_][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xf[j][0], AF[1], acc[ib_][j], 0, 0, 0);     \
-        acc[ib_][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xf[j][1], AF[0], acc[ib_][j], 0, 0, 0);     \
-        acc[ib_][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xf[j][0], AF[0], acc[ib_][j], 0, 0, 0);     \
-    }
+#define MB16_MMA(ib_, AF) _Pragma("unroll") for (int j = 0; j < 4; ++j) split_terms(AF, xf[j], acc[ib_][j]);
         const int nst = c_end - c_begin, steps = (nst + 1) >> 1;
         if (nst > 0) {
             MB_LOAD(c_begin, rg0)
@@ -556,17 +449,17 @@ __global__ __launch_bounds__(512, 1) void gemm_mc_planes_big_kernel(const MCPlan
 #pragma unroll
             for (int j = 0; j < 4; ++j)
 #pragma unroll
-                for (int pl = 0; pl < NT; ++pl) xf[j][pl] = MB16_FRAG(ub, j, pl);
+                for (int pl = 0; pl < NT; ++pl) xf[j][pl] = MC16_FRAG(ub, j, pl);
             // dOut fragments one 16-row tile ahead of their MFMAs.  Stores and loads past the last step are harmless (free
             // slots, out-of-range offsets) and keep the loop body free of branches.
             bf16x8 afc[NT], afn[NT];
 #pragma unroll
-            for (int pl = 0; pl < NT; ++pl) afc[pl] = MB16_FRAG(ua, 0, pl);
+            for (int pl = 0; pl < NT; ++pl) afc[pl] = MC16_FRAG(ua, 0, pl);
 #pragma unroll
             for (int ib = 0; ib < 8; ++ib) {
                 if (ib < 7) {
 #pragma unroll
-                    for (int pl = 0; pl < NT; ++pl) afn[pl] = MB16_FRAG(ua, ib + 1, pl);
+                    for (int pl = 0; pl < NT; ++pl) afn[pl] = MC16_FRAG(ua, ib + 1, pl);
                 }
                 if (ib == 4) {
                     MB_STORE(sr, rg0)
@@ -588,7 +481,6 @@ __global__ __launch_bounds__(512, 1) void gemm_mc_planes_big_kernel(const MCPlan
             sq = t;
         }
 #undef MB16_MMA
-#undef MB16_FRAG
         // accumulator quad r = 0..3 of lane l: dW row (dOut channel) ti*256 + wm*128 + ib*16 + (l & 15), columns
         // tj*256 + wn*64 + j*16 + 4*(l >> 4) + r (Nj % 32 == 0: a quad is inside or outside as a whole)
         float* out = p.slab + (size_t)split * p.Mi * p.Nj;
@@ -637,30 +529,14 @@ __global__ __launch_bounds__(512, 1) void gemm_mc_planes_big_kernel(const MCPlan
     _Pragma("unroll") for (int ks = 0; ks < KS; ++ks) {                                                   \
         const unsigned char* st = smem + (buf_) * STAGE + ks * PIMG;                                      \
         bf16x8 af[4][NT], bf[2][NT];                                                                      \
-        typedef __attribute__((address_space(3))) s16x4 lds_s16x4;                                        \
         _Pragma("unroll") for (int pl = 0; pl < NT; ++pl) {                                               \
-            _Pragma("unroll") for (int t = 0; t < 4; ++t) {                                               \
-                const s16x4 a0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(st + pl * KS * PIMG + fa[t][0])); \
-                const s16x4 a1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(st + pl * KS * PIMG + fa[t][1])); \
-                af[t][pl] = __builtin_bit_cast(bf16x8, __builtin_shufflevector(a0, a1, 0, 1, 2, 3, 4, 5, 6, 7)); \
-            }                                                                                             \
-            _Pragma("unroll") for (int t = 0; t < 2; ++t) {                                               \
-                const s16x4 b0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(st + (NT + pl) * KS * PIMG + fb[t][0])); \
-                const s16x4 b1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(st + (NT + pl) * KS * PIMG + fb[t][1])); \
-                bf[t][pl] = __builtin_bit_cast(bf16x8, __builtin_shufflevector(b0, b1, 0, 1, 2, 3, 4, 5, 6, 7)); \
-            }                                                                                             \
+            _Pragma("unroll") for (int t = 0; t < 4; ++t)                                                 \
+                af[t][pl] = tr_frag(st + pl * KS * PIMG, fa[t][0], fa[t][1]);                             \
+            _Pragma("unroll") for (int t = 0; t < 2; ++t)                                                 \
+                bf[t][pl] = tr_frag(st + (NT + pl) * KS * PIMG, fb[t][0], fb[t][1]);                      \
         }                                                                                                 \
         _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                     \
-            _Pragma("unroll") for (int j = 0; j < 2; ++j) {                                               \
-                if constexpr (NT == 3) {   /* smallest terms first */                                     \
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][1], bf[j][1], acc[i][j], 0, 0, 0); \
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][2], bf[j][0], acc[i][j], 0, 0, 0); \
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][0], bf[j][2], acc[i][j], 0, 0, 0); \
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][1], bf[j][0], acc[i][j], 0, 0, 0); \
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][0], bf[j][1], acc[i][j], 0, 0, 0); \
-                }                                                                                         \
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][0], bf[j][0], acc[i][j], 0, 0, 0); \
-            }                                                                                             \
+            _Pragma("unroll") for (int j = 0; j < 2; ++j) split_terms(af[i], bf[j], acc[i][j]);           \
     }
     // write-after-barrier order: at the top of stage c the registers (loaded during stage c-KS) are stored into the
     // buffer that stage c-KS just released, the loads of stage c+2KS are issued at once, then the MFMAs of stage c run
@@ -687,119 +563,60 @@ __global__ __launch_bounds__(512, 1) void gemm_mc_planes_big_kernel(const MCPlan
     float* out = p.slab + (size_t)split * p.Mi * p.Nj;
     const int col0 = tj * 256 + wn * 64 + (lane & 31);
     const int row0 = ti * 256 + wm * 128 + 4 * (lane >> 5);
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int col = col0 + j * 32;
-        if (col >= p.Nj) continue;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = row0 + i * 32 + (r & 3) + 8 * (r >> 2);
-                if (row < p.Mi) out[(size_t)row * p.Nj + col] = acc[i][j][r];
-            }
-    }
+    MC_STORE_TILES(4, 2)
 }
 
-// one round of <= 256 workgroups: splits = 256 / tiles (>= 8 K-steps of 16 rows per split)
-MCPlan plan_mc_planes_big(int Mi, int Nj, int Mk) {
-    MCPlan pl;
-    if (Mk < 1) Mk = 1;
-    pl.big = 2;
-    const int tiles = ceil_div(Mi, 256) * ceil_div(Nj, 256);
-    const int total_chunks = ceil_div(Mk, 16);
-    int splits = 256 / tiles;
-    if (pa2d_env().mcb_splits > 0) splits = pa2d_env().mcb_splits;         // tuning knob PA2D_MCB_SPLITS
-    const int max_splits = total_chunks / 8 > 0 ? total_chunks / 8 : 1;
-    if (splits > max_splits) splits = max_splits;
-    if (splits < 1) splits = 1;
-    pl.chunks_per_split = ceil_div(total_chunks, splits);
-    pl.splits = ceil_div(total_chunks, pl.chunks_per_split);
-    pl.slab_floats = (size_t)pl.splits * Mi * Nj;
-    return pl;
-}
-
-// 0 = never, 1 = when the shape suits it (default), env PA2D_MC_BIG=off|auto
-bool mc_planes_big_applies(int C, int Cin, int Mk) {
-    if (pa2d_env().mc_big_off) return false;
-    return (C % 16) == 0 && (Cin % 32) == 0 && 2 * C >= 256 && 9 * Cin >= 256 && Mk >= 16 * 8 * 4;
-}
-
-int launch_mc_planes_big(const void* PA, const void* PB, int C, int Cin, int Mk, int H, int W, float* slab,
-                         const MCPlan& pl, int NT, hipStream_t st) {
-    return launch_mc_planes_big_raw(PA, 2 * C, PB, Cin, 9, Mk, H, W, slab, pl, NT, st);
-}
-
-// General form: slab[split][Mi][Nj] += A[m][Mi]^T . B[m (shifted by tap)][Cin]; taps = 9 -> Nj = 9*Cin (3x3 conv weight
-// gradient), taps = 1 -> Nj = Cin (plain dW = dY^T . X).  A, B: NT-plane images with Mi / Cin multiples of 32.
-int launch_mc_planes_big_raw(const void* PA, int Mi, const void* PB, int Cin, int taps, int Mk, int H, int W, float* slab,
-                             const MCPlan& pl, int NT, hipStream_t st) {
-    if ((Mi & 31) || (Cin & 31) || (taps != 1 && taps != 9)) return PA2D_ERR_UNSUPPORTED;
-    MCPlanesParams p;
-    p.PA = PA; p.chA = Mi / 32; p.PB = PB; p.chB = Cin / 32; p.slab = slab;
-    p.Mi = Mi; p.Nj = taps * Cin; p.Mk = Mk; p.chunks_per_split = pl.chunks_per_split; p.splits = pl.splits;
-    p.H = H; p.W = W; p.Cin = Cin; p.taps = taps;
-    const unsigned long long ab = (unsigned long long)Mk * p.chA * NT * 64, bb = (unsigned long long)Mk * p.chB * NT * 64;
-    if (ab >= 0xFFFFFFF0ull || bb >= 0xFFFFFFF0ull) return PA2D_ERR_UNSUPPORTED;
-    p.a_bytes = (unsigned)ab; p.b_bytes = (unsigned)bb;
-    const int wgs = ceil_div(p.Mi, 256) * ceil_div(p.Nj, 256) * pl.splits;
+// dynamic LDS above the 64 KB default: the attribute is set on every launch (it is per device and the call is cheap)
+template <typename K>
+static int launch_big(K kernel, int smem, const MCPlanesParams& p, int wgs, hipStream_t st) {
     const int per_xcd = ceil_div(wgs, 8);
-    const dim3 grid(per_xcd * 8);
-    // the LDS attribute is set on every launch: it is per device and the call is cheap
-    // 16x16x32 form (default; PA2D_MC_MFMA=32 goes back): 16-byte stores of accumulator quads need an aligned slab
-    if (NT == 3 && pa2d_env().mc_mfma16 && (reinterpret_cast<uintptr_t>(slab) & 15) == 0) {
-        const int smem = 3 * 2 * 3 * 1 * 8192;      // three 16-row slots
-        {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_mc_planes_big_kernel<3, 1, true>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-            if (e != hipSuccess) return (int)e;
-        }
-        hipLaunchKernelGGL((gemm_mc_planes_big_kernel<3, 1, true>), grid, dim3(512), smem, st, p, per_xcd);
-    } else if (NT == 3) {
-        const int smem = 2 * 2 * 3 * 1 * 8192;
-        {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_mc_planes_big_kernel<3, 1>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-            if (e != hipSuccess) return (int)e;
-        }
-        hipLaunchKernelGGL((gemm_mc_planes_big_kernel<3, 1>), grid, dim3(512), smem, st, p, per_xcd);
-    } else {
-        const int smem = 2 * 2 * 1 * 4 * 8192;      // NT = 1: four 16-row K-steps per stage (64 MFMAs per wave and barrier)
-        {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_mc_planes_big_kernel<1, 4>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-            if (e != hipSuccess) return (int)e;
-        }
-        hipLaunchKernelGGL((gemm_mc_planes_big_kernel<1, 4>), grid, dim3(512), smem, st, p, per_xcd);
-    }
-    PA2D_CHECK_LAUNCH();
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(kernel, dim3(per_xcd * 8), dim3(512), smem, st, p, per_xcd);
     return PA2D_OK;
 }
 
-// Plain dW = A^T . B of the bf16 engines straight from fp32 operands (A [Mk][lda] with Mi columns, B [Mk][ldb] with Nj
-// columns; Mi, Nj multiples of 8), 128 x 128 tiles on plan_mc's split plan; colsum (optional): [splits][Mi].
-bool mc_f32src_applies(int Mi, int Nj, int Mk, long long lda, long long ldb) {
-    return pa2d_env().lin_dw_split && (Mi % 8) == 0 && (Nj % 8) == 0 && Mi > 64 && Nj > 64 && Mk >= 16 * 8 * 16 && (lda % 4) == 0 && (ldb % 4) == 0;
-}
-
-int launch_mc_f32src(const float* A, long long lda, int Mi, const float* B, long long ldb, int Nj, int Mk, float* slab,
-                     const MCPlan& pl, int NT, float* colsum, hipStream_t st) {
-    if (!pl.big) return PA2D_ERR_UNSUPPORTED;
+// The kernels of this file behind launch_wgrad (which did the shape and extent checks):
+//   MC_K_PLANES128: planes of dOut [Mk][Mi = 2C] and X [Mk][Cin] (NT planes per 32-channel chunk), 3x3 taps;
+//   MC_K_PLANES256: slab[split][Mi][Nj] = A[m][Mi]^T . B[m (shifted by tap)][Cin]; taps = 9 -> Nj = 9*Cin, taps = 1 -> Nj = Cin
+//                   (plain dW = dY^T . X); Mi, Cin multiples of 32;
+//   MC_K_F32SRC:    plain dW straight from fp32 operands (A [Mk][lda] with Mi columns, B [Mk][ldb] with Nj columns; Mi, Nj
+//                   multiples of 8), 128 x 128 tiles; colsum (optional): [splits][Mi].
+// The 16x16x32 forms (default; PA2D_MC_MFMA=32 goes back) store accumulator quads with 16-byte stores: they need an aligned slab.
+int launch_wgrad_planes(const MCDesc& d, const MCChoice& c, unsigned a_bytes, unsigned b_bytes, float* slab, hipStream_t st) {
+    const int NT = d.engine == 2 ? 1 : 3;
+    const bool mf16 = NT == 3 && pa2d_env().mc_mfma16 && (reinterpret_cast<uintptr_t>(slab) & 15) == 0;
     MCPlanesParams p = {};
-    p.PA = A; p.PB = B; p.slab = slab; p.lda = lda; p.ldb = ldb; p.colsum = colsum;
-    p.Mi = Mi; p.Nj = Nj; p.Mk = Mk; p.chunks_per_split = pl.chunks_per_split; p.splits = pl.splits;
-    p.H = 1; p.W = 1; p.Cin = Nj; p.taps = 1; p.chA = 0; p.chB = 0;
-    const unsigned long long ab = ((unsigned long long)(Mk - 1) * lda + Mi) * 4ull, bb = ((unsigned long long)(Mk - 1) * ldb + Nj) * 4ull;
-    if (ab >= 0xFFFFFFF0ull || bb >= 0xFFFFFFF0ull) return PA2D_ERR_UNSUPPORTED;
-    p.a_bytes = (unsigned)ab; p.b_bytes = (unsigned)bb;
-    const dim3 grid(ceil_div(Mi, 128) * ceil_div(Nj, 128) * pl.splits);
-    // 16x16x32 form (default; PA2D_MC_MFMA=32 goes back).  Its three LDS slots allow two workgroups per CU where the 32x32x16
-    // form runs three and the kernel alone is ~10 % slower, but the step is faster with it (the chip is power-
-    // limited and the kernels that follow hold a higher clock)
-    if (NT == 3 && pa2d_env().mc_mfma16 && (Nj % 4) == 0 && (reinterpret_cast<uintptr_t>(slab) & 15) == 0)
-        hipLaunchKernelGGL((gemm_mc_planes_kernel<3, 1, true, true>), grid, dim3(256), 0, st, p);
-    else if (NT == 3) hipLaunchKernelGGL((gemm_mc_planes_kernel<3, 1, true>), grid, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((gemm_mc_planes_kernel<1, 4, true>), grid, dim3(256), 0, st, p);
+    p.PA = d.A; p.PB = d.B; p.slab = slab; p.a_bytes = a_bytes; p.b_bytes = b_bytes;
+    p.Mi = d.Mi; p.Nj = d.Nj; p.Mk = d.Mk; p.chunks_per_split = c.pl.chunks_per_split; p.splits = c.pl.splits;
+    p.H = d.H; p.W = d.W; p.Cin = d.Cin; p.taps = d.taps;
+    if (c.kernel == MC_K_PLANES256) {
+        p.chA = d.Mi / 32; p.chB = d.Cin / 32;
+        const int wgs = ceil_div(p.Mi, 256) * ceil_div(p.Nj, 256) * c.pl.splits;
+        int rc;
+        if (mf16) rc = launch_big(&gemm_mc_planes_big_kernel<3, 1, true>, 3 * 2 * 3 * 1 * 8192, p, wgs, st);      // three 16-row slots
+        else if (NT == 3) rc = launch_big(&gemm_mc_planes_big_kernel<3, 1>, 2 * 2 * 3 * 1 * 8192, p, wgs, st);
+        else rc = launch_big(&gemm_mc_planes_big_kernel<1, 4>, 2 * 2 * 1 * 4 * 8192, p, wgs, st);      // four 16-row K-steps per stage
+        if (rc) return rc;
+        PA2D_CHECK_LAUNCH();
+        return PA2D_OK;
+    }
+    if (!c.pl.big) return PA2D_ERR_UNSUPPORTED;
+    const dim3 grid(ceil_div(d.Mi, 128) * ceil_div(d.Nj, 128) * c.pl.splits);
+    if (c.kernel == MC_K_PLANES128) {
+        if ((d.Mi % 128) || (d.Cin % 128) || d.taps != 9) return PA2D_ERR_UNSUPPORTED;
+        p.chA = d.Mi / 32; p.chB = d.Cin / 32;
+        if (NT == 3) hipLaunchKernelGGL((gemm_mc_planes_kernel<3, 1>), grid, dim3(256), 0, st, p);
+        else hipLaunchKernelGGL((gemm_mc_planes_kernel<1, 4>), grid, dim3(256), 0, st, p);
+    } else {
+        // F32SRC.  The three LDS slots of the 16x16x32 form allow two workgroups per CU where the 32x32x16 form runs three and
+        // the kernel alone is ~10 % slower, but the step is faster with it (the chip is power-limited and the
+        // kernels that follow hold a higher clock)
+        p.lda = d.lda; p.ldb = d.ldb; p.colsum = d.colsum;
+        if (mf16 && (d.Nj % 4) == 0) hipLaunchKernelGGL((gemm_mc_planes_kernel<3, 1, true, true>), grid, dim3(256), 0, st, p);
+        else if (NT == 3) hipLaunchKernelGGL((gemm_mc_planes_kernel<3, 1, true>), grid, dim3(256), 0, st, p);
+        else hipLaunchKernelGGL((gemm_mc_planes_kernel<1, 4, true>), grid, dim3(256), 0, st, p);
+    }
     PA2D_CHECK_LAUNCH();
     return PA2D_OK;
 }

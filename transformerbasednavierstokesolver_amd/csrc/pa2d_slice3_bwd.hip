@@ -371,7 +371,7 @@ __global__ __launch_bounds__(256, MT == 8 ? 1 : 2) void slice_bwd3_kernel(const 
 #pragma unroll
                     for (int q = 0; q < 3; ++q) {
                         const unsigned char* a_ = img + (mat * 3 + q) * PIMG + trf + (unsigned)(u * 32 * RP * 2) + trc(dt);
-                        dst[q] = tr_frag(a_, a_ + 16 * RP * 2);
+                        dst[q] = tr_frag(a_, 0u, 16 * RP * 2);
                     }
                 };
                 rd_(0, fr_[0]);
