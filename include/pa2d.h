@@ -102,6 +102,20 @@ size_t pa2d_gemm_bwd_data_workspace(int N, int K, int engine);
 int pa2d_gemm_bwd_data(const float* dy, long long lddy, const float* w, long long ldw, const float* pre,
                        long long ldpre, int act, float* dx, long long lddx, const void* wimg, void* ws, size_t ws_bytes,
                        int M, int N, int K, int engine, pa2d_stream_t stream);
+/* Diagnostic (returns on the host): which kernel the library's one planner picks for a forward / data-gradient GEMM.
+ * kind 0 / 1: the linear above / its data gradient, (d0, d1, d2) = (M, N, K), contiguous operands, epi = 1 bias | 2 residual
+ * | 4 pre-activation stored (forward) or supplied (data gradient) | 8 output pitch % 4 != 0; kind 2 / 3: the conv below
+ * (nk kernels stacked, taps 9 or 27, depth 1 for 3x3) / its data gradient, (d0, d1, d2) = (B, H, W).  bf16_storage: the
+ * *_bf16 entry points (engine 2 whatever `engine` says); image: weight-image scratch is on offer.
+ * out[PA2D_ROUTE_FIELDS]: 0 return code of the launch's kernel choice, 1 family (0 exact fp32 tiles, 1 small split tiles,
+ * 2 bf16-engine tiles, 3 halo conv, 4 row-panel, 5 row-stationary), 2-4 tile bm, bn, bk, 5 bf16 planes per operand, 6 / 7
+ * halo conv on 16x16x32 MFMAs / with fragment reads placed ahead, 8 bf16 outputs, 9 epilogue variant of the persistent
+ * kernels (-1 none), 10 rows on the persistent kernel, 11-13 family, bm, bn of the tail (-1 none), 14 A is read as planes,
+ * 15 conv weight pack (0 none, 1 fp32 chunk 16, 2 fp32 chunk 32, 3 bf16 planes), 16 the kernel(s) read the fp32 B
+ * (data gradient: the transposed weight), 17 weight-image bytes. */
+#define PA2D_ROUTE_FIELDS 18
+int pa2d_gemm_route(int kind, int d0, int d1, int d2, int depth, int C, int nk, int taps, int act, int epi, int engine,
+                    int bf16_storage, int image, int* out);
 size_t pa2d_gemm_bwd_weight_workspace(int M, int N, int K, int engine);
 /* dw[N,K] (+)= dy[M,N]^T . x[M,K];  db[N] (+)= column sums of dy (db may be NULL) */
 int pa2d_gemm_bwd_weight(const float* dy, long long lddy, const float* x, long long ldx, float* dw, float* db,

@@ -1,7 +1,8 @@
 // C ABI of the conv stages (pa2d_conv3x3*; declared in include/pa2d.h).  Host code only: the kernels live in
 // pa2d_gemm_kc.hip / pa2d_gemm_split.hip / pa2d_conv_halo.hip (implicit GEMMs), pa2d_gemm_mc.hip / pa2d_gemm_mc_planes.hip
-// (weight gradients) and pa2d_gemm.hip (fp32 weight packs, launch_kc).  Every entry point does its own family's checks and
-// then runs ONE forward / ONE backward on a ConvDesc.
+// (weight gradients) and pa2d_gemm.hip (fp32 weight packs, plan_kc, launch_kc).  Every entry point does its own family's checks
+// and then runs ONE forward / ONE backward on a ConvDesc; which kernel a GEMM gets, hence its operand layout and weight pack,
+// is asked of plan_kc, never predicted here.
 #include "pa2d_gemm_common.h"
 
 // ---------------------------------------------------------------------------------------------
@@ -24,11 +25,21 @@ static ConvDesc conv2d(int B, int H, int W, int C, int nk, int engine, ConvSrc s
 }
 static int conv_nt(const ConvDesc& d) { return d.engine == 2 ? 1 : 3; }      // bf16 planes per operand
 
-// bf16 engines: bytes of the pre-split activation planes of a [rows, Cin] operand (0 when the engine selected for
-// this GEMM reads fp32 operands)
-static size_t conv_planes_bytes(int engine, int M, int N, int Cin) {
-    if (!use_split(engine, N, true, Cin)) return 0;
-    return (planes_bytes(M, Cin, engine == 2 ? 1 : 3) + 255) & ~(size_t)255;
+// The kernel plan_kc picks for the implicit GEMM [M, taps*Cin] x [taps*Cin, N]: direction 0 = forward (N = nk*C, Cin = C),
+// 1 = data gradient (N = C, Cin = nk*C), asked with planes on offer.  What follows from it here: whether A is read as
+// planes (c.a_planes), and the weight pack (c.pack, c.nt).
+static KCParams conv_kc_shape(const ConvDesc& d, int direction) {
+    const int N = direction ? d.C : d.nk * d.C, Cin = direction ? d.nk * d.C : d.C;
+    return kc_conv_shape(d.engine, d.src == SRC_BF16, d.M, N, Cin, d.taps, d.H, d.W, d.depth);
+}
+static KCChoice conv_plan(const ConvDesc& d, int direction) { return plan_kc(conv_kc_shape(d, direction), true); }
+
+// bf16 engines: bytes of the pre-split activation planes of the A operand [M, Cin] of that GEMM (0 when its kernel reads
+// fp32 operands)
+static size_t conv_planes_bytes(const ConvDesc& d, int direction) {
+    const KCChoice c = conv_plan(d, direction);
+    if (!c.a_planes) return 0;
+    return (planes_bytes(d.M, direction ? d.nk * d.C : d.C, c.nt) + 255) & ~(size_t)255;
 }
 
 // The weight gradient dW[nk*C][taps*C] = dOut^T . im2col(X) as the dispatch sees it; planes: dout / x are plane images made here
@@ -57,7 +68,7 @@ static ConvLayout conv_layout(const ConvDesc& d, bool bwd) {
     ConvLayout L = {};
     L.pack = conv_pack_bytes(d.C, d.taps, d.nk);
     if (!bwd) {
-        if (d.src == SRC_F32) L.apl = conv_planes_bytes(d.engine, d.M, d.nk * d.C, d.C);
+        if (d.src == SRC_F32) L.apl = conv_planes_bytes(d, 0);
         L.total = L.pack + L.apl;
         return L;
     }
@@ -65,35 +76,31 @@ static ConvLayout conv_layout(const ConvDesc& d, bool bwd) {
     const size_t sl = L.wg.pl.slab_floats, cs = (size_t)colsum_blocks(d.M) * d.nk * d.C;
     L.scratch = (d.src != SRC_PLANES && cs > sl ? cs : sl) * sizeof(float);      // SRC_PLANES: no bias gradient here
     if (d.src == SRC_F32) {
-        L.apl = conv_planes_bytes(d.engine, d.M, d.C, d.nk * d.C);
+        L.apl = conv_planes_bytes(d, 1);
         if (L.wg.planes) L.xpl = (planes_bytes(d.M, d.C, conv_nt(d)) + 255) & ~(size_t)255;
     }
     L.total = L.pack + L.scratch + L.apl + L.xpl;
     return L;
 }
 
-// Packed conv weights in the layout the engine selected for these dims wants (channel chunk = K-step of the tile, fp32
-// or bf16 planes by GEMM mode; bf16 storage: ALWAYS the 1-plane image, also at the narrow shapes the fp32-I/O engines
-// hand to the exact kernel).  direction 0: forward pack ([nk*C][taps*C]); 1: data-gradient pack ([C][taps*nk*C], taps
+// Packed conv weights in the layout the kernel planned for these dims stages (KCChoice::pack: fp32 with the channel chunk =
+// K-step of the tile, or bf16 planes; bf16 storage: ALWAYS the 1-plane image, also at the narrow shapes the fp32-I/O
+// engines hand to the exact kernel).  direction 0: forward pack ([nk*C][taps*C]); 1: data-gradient pack ([C][taps*nk*C], taps
 // flipped).  w1 = NULL for nk = 1.  A pack stays valid while the weights, the dims and the GEMM mode do not change.
 static int conv_pack(const ConvDesc& d, const float* w0, const float* w1, void* pack, int direction, hipStream_t st) {
-    const int N = direction ? d.C : d.nk * d.C, Cin = direction ? d.nk * d.C : d.C;
-    if (d.src == SRC_BF16 || use_split(d.engine, N, true, Cin))
-        return launch_repack_split(w0, w1, pack, direction, conv_nt(d), d.C, d.C, st, d.taps);
-    return launch_repack(w0, w1, (float*)pack, direction ? 2 : 1, 0, kc_tile(d.M, N, true, Cin).bk, d.C, d.C, st, d.taps);
+    const KCChoice c = conv_plan(d, direction);
+    if (c.pack == KC_PACK_PLANES) return launch_repack_split(w0, w1, pack, direction, c.nt, d.C, d.C, st, d.taps);
+    return launch_repack(w0, w1, (float*)pack, direction ? 2 : 1, 0, c.pack == KC_PACK_F32_32 ? 32 : 16, d.C, d.C, st, d.taps);
 }
 
 // The implicit GEMM [M, taps*Cin] x [taps*Cin, N]: direction 0 = forward (N = nk*C, Cin = C, biases b0 | b1 split at C),
-// 1 = data gradient (N = C, Cin = nk*C).  A: the operand as the GEMM reads it (apre: bf16 planes).
-static KCParams conv_kc_params(const ConvDesc& d, int direction, const void* A, bool apre, const void* pack, void* out,
+// 1 = data gradient (N = C, Cin = nk*C).  A: the operand as the planned kernel reads it (bf16 planes where it says so).
+static KCParams conv_kc_params(const ConvDesc& d, int direction, const void* A, const void* pack, void* out,
                                const float* b0, const float* b1) {
-    const int N = direction ? d.C : d.nk * d.C, Cin = direction ? d.nk * d.C : d.C;
-    KCParams p = {};
-    p.engine = d.engine; p.io_bf16 = d.src == SRC_BF16 ? 1 : 0; p.apre = apre ? 1 : 0;
-    p.A = (const float*)A; p.lda = Cin; p.B = (const float*)pack; p.ldb = d.taps * Cin; p.C = (float*)out; p.ldc = N;
+    KCParams p = conv_kc_shape(d, direction);
+    p.apre = plan_kc(p, true).a_planes ? 1 : 0;
+    p.A = (const float*)A; p.B = (const float*)pack; p.C = (float*)out;
     p.bias = b0; p.bias2 = b1; p.bias_split = d.C;
-    p.M = d.M; p.N = N; p.K = d.taps * Cin; p.H = d.H; p.W = d.W; p.Cin = Cin;
-    p.taps = d.taps; p.depth = d.depth;
     return p;
 }
 
@@ -117,7 +124,7 @@ static int conv_forward(const ConvDesc& d, const void* x, const float* w0, const
         if (rc) return rc;
         x = planes;
     }
-    return launch_kc(conv_kc_params(d, 0, x, L.apl || d.src != SRC_F32, prepacked, out, b0, b1), true, st, ev_start, ev_stop);
+    return launch_kc(conv_kc_params(d, 0, x, prepacked, out, b0, b1), true, st, ev_start, ev_stop);
 }
 
 // accumulate == 0 on an empty batch: the gradients are zero (NULL pointers are skipped)
@@ -157,8 +164,7 @@ static int conv_backward(const ConvDesc& d, const void* dout, const void* x, con
             if (rc) return rc;
             prepacked = ws;
         }
-        rc = launch_kc(conv_kc_params(d, 1, a, L.apl || d.src != SRC_F32, prepacked, dx, nullptr, nullptr), true, st,
-                       ev_start, ev_stop);
+        rc = launch_kc(conv_kc_params(d, 1, a, prepacked, dx, nullptr, nullptr), true, st, ev_start, ev_stop);
         if (rc) return rc;
     }
     if (L.xpl) {      // the weight gradient reads both operands as planes
@@ -335,10 +341,10 @@ int pa2d_conv3x3x2_planes_mask(int B, int H, int W, int C, int engine) {
     if (!engine_ok(engine) || B <= 0) return 0;
     const ConvDesc d = conv2d(B, H, W, C, 2, engine, SRC_F32);
     int m = 0;
-    if (conv_planes_bytes(engine, d.M, 2 * C, C)) m |= 1;
+    if (conv_planes_bytes(d, 0)) m |= 1;
     const bool wg_planes = plan_wgrad(conv_wgrad(d, nullptr, nullptr, false)).planes;
     if (wg_planes) m |= 2;
-    if (conv_planes_bytes(engine, d.M, C, 2 * C) && wg_planes) m |= 4;
+    if (conv_planes_bytes(d, 1) && wg_planes) m |= 4;
     return m;
 }
 

@@ -23,7 +23,7 @@
 #include "pa2d_gemm_common.h"
 
 namespace {
-constexpr int TH = 8, TW = 32, BM = TH * TW, BN = 128;
+constexpr int TH = KC_HALO_TH, TW = KC_HALO_TW, BM = TH * TW, BN = 128;      // 8 x 32 pixels (plan_kc counts these tiles)
 constexpr int HH = TH + 2, HWD = TW + 2, HROWS = HH * HWD;          // 10 x 34 = 340 halo pixels
 }
 
@@ -420,57 +420,19 @@ __global__ __launch_bounds__(512, 1) void conv_halo_ref_kernel(const KCParams p,
     conv_halo_body<3, float, 1, true, false>(p, tiles_x, tiles_y, nimg);
 }
 
-// 0 = never, 1 = when the launch fills the chip (default), 2 = always (tests): env PA2D_CONV_HALO=off|auto|force
-static int halo_policy() { return pa2d_env().conv_halo; }
-
-bool conv_halo_applies(const KCParams& p) {
-    const int pol = halo_policy();
-    if (p.taps == 27) return false;      // 3x3 halo only: the 3x3x3 conv never comes here
-    if (pol == 0 || !p.apre || (p.Cin % 32) != 0 || p.H <= 0 || p.W <= 0 || (p.M % (p.H * p.W)) != 0) return false;
-    const long long tiles = (long long)(p.M / (p.H * p.W)) * ceil_div(p.H, TH) * ceil_div(p.W, TW) * ceil_div(p.N, BN);
-    return pol == 2 || tiles >= 512;
-}
-
-// p.a_bytes / p.b_bytes must already describe the plane image and the weight pack (launch_kc_split fills them)
-int launch_conv_halo(const KCParams& p, hipStream_t st) {
-    const int NT = p.engine == 2 ? 1 : 3;
+// the variant plan_kc picked (KC_HALO: c.nt, c.mfma16, c.ahead, c.out_bf16); p.a_bytes / p.b_bytes describe the plane image
+// and the planes pack
+int launch_conv_halo(const KCParams& p, const KCChoice& c, hipStream_t st) {
     const int tiles_x = ceil_div(p.W, TW), tiles_y = ceil_div(p.H, TH), nimg = p.M / (p.H * p.W);
     const int tiles_m = nimg * tiles_y * tiles_x, tiles_n = ceil_div(p.N, BN);
     const dim3 grid(ceil_div(tiles_m, 8) * 8 * tiles_n);
-    const int pitch = NT * 64 + 16;
-    const int smem = HROWS * pitch + 2 * (NT == 1 ? 3 : 1) * BN * pitch;
-    // the LDS attribute is set on every launch: it is per device and the call is cheap
-    if (NT == 3 && pa2d_env().conv_mfma16 && (p.N % 4) == 0 && (p.ldc % 4) == 0) {      // 16-byte stores of accumulator quads
-        const int smem16 = (HROWS + 2 * BN) * (3 * 64 + 32);
-        auto* const kern = pa2d_env().conv_ahead ? &conv_halo_kernel<3, float, 1, true> : &conv_halo_ref_kernel;
-        {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, smem16);
-            if (e != hipSuccess) return (int)e;
-        }
-        hipLaunchKernelGGL(kern, grid, dim3(512), smem16, st, p, tiles_x, tiles_y, nimg);
-    } else if (NT == 3) {
-        {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo_kernel<3>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-            if (e != hipSuccess) return (int)e;
-        }
-        hipLaunchKernelGGL((conv_halo_kernel<3>), grid, dim3(512), smem, st, p, tiles_x, tiles_y, nimg);
-    } else if (p.io_bf16) {
-        {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo_kernel<1, bf16_t>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-            if (e != hipSuccess) return (int)e;
-        }
-        hipLaunchKernelGGL((conv_halo_kernel<1, bf16_t>), grid, dim3(512), smem, st, p, tiles_x, tiles_y, nimg);
-    } else {
-        {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo_kernel<1>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-            if (e != hipSuccess) return (int)e;
-        }
-        hipLaunchKernelGGL((conv_halo_kernel<1>), grid, dim3(512), smem, st, p, tiles_x, tiles_y, nimg);
-    }
-    PA2D_CHECK_LAUNCH();
-    return PA2D_OK;
+    const int pitch = c.nt * 64 + (c.mfma16 ? 32 : 16);
+    const int smem = (HROWS + 2 * (c.nt == 1 ? 3 : 1) * BN) * pitch;
+#define HALO_GO(kernel) return launch_lds(kernel, grid, dim3(512), smem, st, p, tiles_x, tiles_y, nimg)
+    if (c.mfma16 && c.ahead) HALO_GO((&conv_halo_kernel<3, float, 1, true>));
+    if (c.mfma16) HALO_GO(&conv_halo_ref_kernel);
+    if (c.nt == 3) HALO_GO(&conv_halo_kernel<3>);
+    if (c.out_bf16) HALO_GO((&conv_halo_kernel<1, bf16_t>));
+    HALO_GO(&conv_halo_kernel<1>);
+#undef HALO_GO
 }

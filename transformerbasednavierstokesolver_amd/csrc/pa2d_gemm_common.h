@@ -1,8 +1,9 @@
-// Internal declarations shared by the GEMM translation units of libpa2d (pa2d_gemm.hip = engine selection, launch_kc +
-// C ABI of the linears, pa2d_conv.hip = C ABI of the conv stages (host code only), pa2d_gemm_kc.hip = exact fp32 engine,
-// pa2d_gemm_split.hip = bf16 split / bf16 compute engines, pa2d_gemm_mc.hip = weight-gradient dispatch (plan_wgrad,
-// launch_wgrad), its gather kernel and the deterministic reductions, pa2d_gemm_mc_planes.hip = the weight-gradient kernels
-// on plane images), and the leaf code the weight-gradient kernels share.  Split only so that the translation units compile
+// Internal declarations shared by the GEMM translation units of libpa2d (pa2d_gemm.hip = engine selection, plan_kc + launch_kc
+// (KCParams -> KCChoice -> launch) + C ABI of the linears, pa2d_conv.hip = C ABI of the conv stages (host code only),
+// pa2d_gemm_kc.hip = exact fp32 engine, pa2d_gemm_split.hip = bf16 split / bf16 compute engines, pa2d_gemm_mc.hip =
+// weight-gradient dispatch (plan_wgrad, launch_wgrad), its gather kernel and the deterministic reductions,
+// pa2d_gemm_mc_planes.hip = the weight-gradient kernels on plane images), launch_lds (the one launch of a kernel with more
+// than 64 KB of LDS) and the leaf code the weight-gradient kernels share.  Split only so that the translation units compile
 // in parallel; nothing here is part of the C ABI.
 #pragma once
 #include "pa2d_internal.h"
@@ -31,7 +32,7 @@ struct KCParams {
     int apre;   // split engine: A already holds the NT bf16 planes of every 32-channel chunk (split_planes_kernel)
     int engine; // PA2D_ENGINE_* of this call (explicit per call: the library keeps no engine state)
     int aux_deriv; // PA2D_ACT_SAVE_DERIVATIVE: aux receives / holds act'(pre-activation) instead of the pre-activation
-    void* wimg;  // scratch for the weight plane image of the row-stationary linear kernel (rowpanel_image_bytes), or NULL
+    void* wimg;  // scratch for the weight plane image of the row-stationary linear kernel (KCChoice::wimg_bytes), or NULL
     const float* wsrc; long long wsn, wsk;   // the image's source: B[n][k] = wsrc[n * wsn + k * wsk]
     int io_bf16; // bf16-storage entry points: A (row-major [M][K] or the NHWC image), C, res and aux hold bf16; lda / ldc /
                  // ldres / ldaux stay in ELEMENTS; a bf16 A is read as pre-made 1-plane "planes" (apre = 1)
@@ -206,40 +207,79 @@ __device__ __forceinline__ void mc_store_tile(float* out, int Mi, int Nj, int ro
         _Pragma("unroll") for (int i = 0; i < (TM_); ++i) mc_store_tile(out, p.Mi, p.Nj, row0 + i * 32, col, acc[i][j]); \
     }
 
-// engine selection / tile choice (pa2d_gemm.hip)
+// dynamic LDS above the 64 KB default: the attribute is set on every launch (it is per device and the call is cheap)
+template <typename K, typename... Args>
+static inline int launch_lds(K kernel, dim3 grid, dim3 block, int smem, hipStream_t st, Args... args) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(kernel, grid, block, smem, st, args...);
+    return (int)hipGetLastError();
+}
+
 static inline bool engine_ok(int e) { return e >= 0 && e <= 2; }
-bool use_split(int engine, int N, bool im2col, int Cin);
-KCTile kc_tile(int M, int N, bool im2col, int Cin);
-// the one dispatch of every forward / data-gradient GEMM: checks, buffer extents, kernel choice; ev0 / ev1 go round it
+// ---- forward / data-gradient GEMMs (pa2d_gemm.hip): one description (KCParams), one planner, one launch for every caller.
+enum KCFamily {
+    KC_EXACT,          // gemm_kc_kernel: exact fp32 MFMA tiles
+    KC_SPLIT_SMALL,    // gemm_kc_split_kernel<64, 64>: small plain GEMMs of the split engine, operands split while staged
+    KC_SPLIT,          // gemm_kc_split_kernel: per-tile kernel of the bf16 engines (conv on planes; plain GEMMs of engine 2)
+    KC_HALO,           // conv_halo_kernel: 3x3 conv with the halo tile resident in LDS
+    KC_PANEL,          // gemm_panel_kernel: persistent row-panel kernel on the whole 256-row blocks
+    KC_ROWPANEL        // gemm_rowpanel_kernel: row-stationary kernel on the whole 128-row rounds (needs the weight image)
+};
+enum KCPack { KC_PACK_NONE, KC_PACK_F32_16, KC_PACK_F32_32, KC_PACK_PLANES };      // conv weight pack the kernel stages
+struct KCChoice {
+    int rc;                   // PA2D_OK, or what launch_kc answers: no kernel of the chosen family takes this request
+    KCFamily family;
+    int bm, bn, bk;           // workgroup tile and K-step (row-stationary: 128 rows x 64-column pairs, 64-k stages)
+    int nt;                   // bf16 planes per operand: 3 = exact split, 1 = bf16 compute, 0 = fp32 MFMAs
+    int mfma16, ahead;        // KC_HALO: 16x16x32 consumers, and their hand-placed fragment reads (else the reference loop)
+    int out_bf16;             // C / res / aux hold bf16
+    int mode;                 // KC_PANEL / KC_ROWPANEL: epilogue variant (0 bias + residual, 1 GELU (+ pre), 2 * GELU'(aux))
+    int head_rows;            // KC_PANEL / KC_ROWPANEL: the rows they take; the other M - head_rows (< bm) go to the kernel that
+    int tail_family, tail_bm, tail_bn;      // plan_kc picks for a GEMM of that many rows (-1: no tail)
+    bool a_planes;            // A is read as bf16 planes ([row][32-channel chunk][nt][32]; bf16 storage: the tensor itself)
+    KCPack pack;              // conv: the weight pack B must be (KC_PACK_PLANES: x nt)
+    bool reads_b;             // some row goes to a kernel that reads p.B (false: the weight image serves every row)
+    size_t wimg_bytes;        // plain GEMM: bytes of the weight image with which the row-stationary kernel can run (0: never)
+};
+#define PA2D_ROUTE_FIELDS 18      // ints in which pa2d_gemm_route reports a KCChoice (include/pa2d.h)
+// Which kernel runs this GEMM.  Shapes, flags, null-ness of pointers and pa2d_env() only: nothing is dereferenced or allocated.
+// Callers that only have a shape fill the shape fields and apre = 1 ("planes on offer") and read the answer.
+KCChoice plan_kc(const KCParams& p, bool im2col);
+// the one dispatch of every forward / data-gradient GEMM: checks, every buffer extent, plan_kc, one switch; ev0 / ev1 go round it
 int launch_kc(const KCParams& p_in, bool im2col, hipStream_t st, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+// shape fields of the conv implicit GEMM [M, taps*Cin] x [taps*Cin, N] on the image [., H, W, depth, Cin]; planes on offer
+static inline KCParams kc_conv_shape(int engine, bool io_bf16, int M, int N, int Cin, int taps, int H, int W, int depth) {
+    KCParams p = {};
+    p.engine = engine; p.io_bf16 = io_bf16 ? 1 : 0; p.apre = 1;
+    p.lda = Cin; p.ldb = (long long)taps * Cin; p.ldc = N;
+    p.M = M; p.N = N; p.K = taps * Cin; p.H = H; p.W = W; p.Cin = Cin; p.taps = taps; p.depth = depth;
+    return p;
+}
 // fp32 weight re-layouts: mode 0 = transpose, 1 / 2 = conv forward / data-gradient pack (w1 = NULL: one kernel in it)
 int launch_repack(const float* w0, const float* w1, float* dst, int mode, int N, int K, int C, int Cin, hipStream_t st,
                   int taps = 9);
-// exact fp32 engine (pa2d_gemm_kc.hip): launches the tile variant `t` on a filled-in KCParams
+// ---- the kernels behind launch_kc: plain launchers of the variant `c` names, on a KCParams whose extents are filled in
+// exact fp32 engine (pa2d_gemm_kc.hip)
 int launch_kc_f32(const KCParams& p, bool im2col, const KCTile& t, hipStream_t st);
-// bf16 engines (pa2d_gemm_split.hip)
-int launch_kc_split(KCParams& p, bool im2col, hipStream_t st);
-bool kc_split_small_applies(const KCParams& p, bool im2col);
-int launch_kc_split_small(const KCParams& p, hipStream_t st);
+// bf16 engines (pa2d_gemm_split.hip): KC_SPLIT and KC_SPLIT_SMALL
+int launch_kc_split(const KCParams& p, bool im2col, const KCChoice& c, hipStream_t st);
 size_t planes_bytes(long long rows, int C, int NT);
 int launch_split_planes(const float* src, long long ld, void* dst, long long rows, int C, int NT, hipStream_t st);
 // taps = 27: pack of the two [C, Cin, 3, 3, 3] kernels of the 3x3x3 conv (same row image, K-step kc = cic*27 + tap)
 int launch_repack_split(const float* w0, const float* w1, void* dst, int bwd, int NT, int C, int Cin, hipStream_t st,
                         int taps = 9);
-// persistent row-panel kernel for large-M plain GEMMs of the bf16 engines (pa2d_gemm_panel.hip)
-bool panel_applies(const KCParams& p, bool im2col);
-int launch_kc_panel(const KCParams& p, hipStream_t st);
-// row-stationary split-engine linears (pa2d_gemm_rowpanel.hip): need a weight plane image in caller scratch
-size_t rowpanel_image_bytes(int N, int K, int engine);
-bool rowpanel_applies(const KCParams& p);
+// persistent row-panel kernel for large-M plain GEMMs of the bf16 engines (pa2d_gemm_panel.hip); p.M % 256 == 0
+int launch_kc_panel(const KCParams& p, const KCChoice& c, hipStream_t st);
+// row-stationary split-engine linears (pa2d_gemm_rowpanel.hip) on the weight plane image p.wimg; p.M % 128 == 0
 int launch_pack_weight_image(const float* w, long long sn, long long sk, void* img, int N, int K, hipStream_t st);
-int launch_kc_rowpanel(const KCParams& p, const void* img, hipStream_t st);
-// conv with the halo tile resident in LDS (pa2d_conv_halo.hip): used by launch_kc_split for pre-split im2col operands
-bool conv_halo_applies(const KCParams& p);
-int launch_conv_halo(const KCParams& p, hipStream_t st);
+int launch_kc_rowpanel(const KCParams& p, const KCChoice& c, hipStream_t st);
+// conv with the halo tile resident in LDS (pa2d_conv_halo.hip); KC_HALO_TH x KC_HALO_TW pixels x 128 channels per workgroup
+constexpr int KC_HALO_TH = 8, KC_HALO_TW = 32;
+int launch_conv_halo(const KCParams& p, const KCChoice& c, hipStream_t st);
 // ---- weight gradients (pa2d_gemm_mc.hip): dW[Mi][Nj] = sum_m A[m][Mi]^T . B[m (shifted by tap)][Cin], written as per-split
 // slabs [splits][Mi][Nj] that launch_reduce adds up.  One description, one planner, one launch for every caller: the
-// counterpart of launch_kc.
+// counterpart of KCParams / plan_kc / launch_kc.
 enum MCSrc {
     MC_SRC_F32,       // A, B: fp32 matrices with row pitches lda, ldb (elements)
     MC_SRC_PLANES,    // plane images of the split engines ([row][32-channel chunk][plane][32] bf16), contiguous

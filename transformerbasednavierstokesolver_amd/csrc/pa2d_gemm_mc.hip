@@ -261,8 +261,9 @@ MCChoice plan_wgrad(const MCDesc& d) {
         if ((d.engine == 1 || d.engine == 2) && pa2d_env().lin_dw_split && (d.Mi % 8) == 0 && (d.Nj % 8) == 0 && d.Mi > 64 &&
             d.Nj > 64 && d.Mk >= 16 * 8 * 16 && (d.lda % 4) == 0 && (d.ldb % 4) == 0)
             c.kernel = MC_K_F32SRC;
-    } else if (d.taps == 9 && use_split(d.engine, d.Cin, true, d.Mi)) {
-        // 3x3 conv whose data gradient reads dOut as planes: both operands as planes, transposed LDS reads
+    } else if (d.taps == 9 && plan_kc(kc_conv_shape(d.engine, false, d.Mk, d.Cin, d.Mi, 9, d.H, d.W, 1), true).a_planes) {
+        // 3x3 conv whose data gradient (the GEMM [Mk, 9*Mi] x [9*Mi, Cin]) reads dOut as planes: both operands as planes,
+        // transposed LDS reads
         if (!pa2d_env().mc_big_off && (d.Cin % 32) == 0 && d.Mi >= 256 && d.Mk >= 16 * 8 * 4) c.kernel = MC_K_PLANES256;
         else if (d.Mi == 2 * d.Cin && (d.Cin % 128) == 0) c.kernel = MC_K_PLANES128;      // written for the pair [Wx | Wf]
     }

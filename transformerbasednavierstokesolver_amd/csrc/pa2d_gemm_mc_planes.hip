@@ -566,14 +566,10 @@ __global__ __launch_bounds__(512, 1) void gemm_mc_planes_big_kernel(const MCPlan
     MC_STORE_TILES(4, 2)
 }
 
-// dynamic LDS above the 64 KB default: the attribute is set on every launch (it is per device and the call is cheap)
 template <typename K>
 static int launch_big(K kernel, int smem, const MCPlanesParams& p, int wgs, hipStream_t st) {
     const int per_xcd = ceil_div(wgs, 8);
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(kernel, dim3(per_xcd * 8), dim3(512), smem, st, p, per_xcd);
-    return PA2D_OK;
+    return launch_lds(kernel, dim3(per_xcd * 8), dim3(512), smem, st, p, per_xcd);
 }
 
 // The kernels of this file behind launch_wgrad (which did the shape and extent checks):
@@ -597,9 +593,7 @@ int launch_wgrad_planes(const MCDesc& d, const MCChoice& c, unsigned a_bytes, un
         if (mf16) rc = launch_big(&gemm_mc_planes_big_kernel<3, 1, true>, 3 * 2 * 3 * 1 * 8192, p, wgs, st);      // three 16-row slots
         else if (NT == 3) rc = launch_big(&gemm_mc_planes_big_kernel<3, 1>, 2 * 2 * 3 * 1 * 8192, p, wgs, st);
         else rc = launch_big(&gemm_mc_planes_big_kernel<1, 4>, 2 * 2 * 1 * 4 * 8192, p, wgs, st);      // four 16-row K-steps per stage
-        if (rc) return rc;
-        PA2D_CHECK_LAUNCH();
-        return PA2D_OK;
+        return rc;
     }
     if (!c.pl.big) return PA2D_ERR_UNSUPPORTED;
     const dim3 grid(ceil_div(d.Mi, 128) * ceil_div(d.Nj, 128) * c.pl.splits);

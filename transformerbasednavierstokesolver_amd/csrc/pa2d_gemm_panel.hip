@@ -12,7 +12,8 @@
 //                          fp32 accumulate), then the epilogue straight from the accumulators.
 // Epilogues address elements as per-lane offset + SGPR row offset (no per-element address arithmetic); residual and
 // pre-activation operands are fetched in 32-load batches.  NT = 3: PA2D_ENGINE_SPLIT (fp32 accuracy), NT = 1: bf16
-// compute.  AF32 = false: A is a bf16 matrix (bf16-storage entry points), copied with 16-byte pieces.
+// compute.  AF32 = false (A is a bf16 matrix, copied with 16-byte pieces) and TO = bf16 are not built: plan_kc keeps bf16
+// storage on the per-tile kernels (see launch_kc_panel).
 // Phase ablation at B*N = 131072, N = K = 256, NT = 3 (ms): full 0.116; MFMAs alone 0.079 (0.056 + 0.023 epilogue =
 // the HBM write of C); loads + convert alone 0.062; loads alone 0.046; nothing but barriers and the epilogue 0.023.
 // The producers' VALU conversion and the consumers' MFMAs add up instead of overlapping (same finding as on the conv),
@@ -29,15 +30,9 @@ template <typename TO> __device__ __forceinline__ float ld_so(__amdgpu_buffer_rs
 template <> __device__ __forceinline__ float ld_so<float>(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
     return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
 }
-template <> __device__ __forceinline__ float ld_so<bf16_t>(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-    return bf16_bits_to_f32(__builtin_amdgcn_raw_buffer_load_b16(r, voff, soff, 0));
-}
 template <typename TO> __device__ __forceinline__ void st_so(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff, float v);
 template <> __device__ __forceinline__ void st_so<float>(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff, float v) {
     __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), r, voff, soff, 0);
-}
-template <> __device__ __forceinline__ void st_so<bf16_t>(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff, float v) {
-    __builtin_amdgcn_raw_buffer_store_b16(f32_to_bf16_bits(v), r, voff, soff, 0);
 }
 
 // MODE 0: out = acc + bias (+ res; the bias is preloaded into the accumulators, the residual is added in batches);
@@ -261,70 +256,34 @@ __global__ __launch_bounds__(512, 1) void gemm_panel_kernel(const KCParams p, co
 
 constexpr int PANEL_WGS_PER_XCD = 32;      // 256 CUs = 8 XCDs x 32: one persistent workgroup per CU
 
-template <int NT, bool AF32, typename TO, int MODE>
+template <int NT, int MODE>
 int launch_panel_m(const KCParams& p, hipStream_t st) {
     constexpr int PITCHB = NT * 64 + 16;
     // >= 96 KB even when the stages are small, so that two workgroups never share a CU while another CU idles
     const int smem = 2 * 384 * PITCHB > 96 * 1024 ? 2 * 384 * PITCHB : 96 * 1024;
-    {   // every launch: the attribute is per device, and the call is cheap
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_panel_kernel<NT, AF32, TO, MODE>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        if (e != hipSuccess) return (int)e;
-    }
     const int tiles_m = p.M / 256, tiles_n = ceil_div(p.N, 128);
     const int tmx = ceil_div(tiles_m, 8);
     int S = tmx * tiles_n;
     if (S > PANEL_WGS_PER_XCD) S = PANEL_WGS_PER_XCD;
-    hipLaunchKernelGGL((gemm_panel_kernel<NT, AF32, TO, MODE>), dim3(8 * S), dim3(512), smem, st, p, tmx, S);
-    PA2D_CHECK_LAUNCH();
-    return PA2D_OK;
+    return launch_lds(&gemm_panel_kernel<NT, true, float, MODE>, dim3(8 * S), dim3(512), smem, st, p, tmx, S);
 }
 
-int panel_mode(const KCParams& p) {
-    const bool gelu = p.act == ACT_GELU, has_res = p.res != nullptr;
-    if (p.epi == 0) return 0;
-    if (gelu && !has_res && (p.epi == (EPI_ACT | EPI_STORE_PRE) || p.epi == EPI_ACT)) return 1;
-    if (gelu && !has_res && p.epi == EPI_MUL_DACT && !p.bias) return 2;
-    return -1;
-}
-
-template <int NT, bool AF32, typename TO>
-int launch_panel_t(const KCParams& p, hipStream_t st) {
-    switch (panel_mode(p)) {
-        case 0: return launch_panel_m<NT, AF32, TO, 0>(p, st);
-        case 1: return launch_panel_m<NT, AF32, TO, 1>(p, st);
-        case 2: return launch_panel_m<NT, AF32, TO, 2>(p, st);
+template <int NT>
+int launch_panel_t(const KCParams& p, int mode, hipStream_t st) {
+    switch (mode) {
+        case 0: return launch_panel_m<NT, 0>(p, st);
+        case 1: return launch_panel_m<NT, 1>(p, st);
+        case 2: return launch_panel_m<NT, 2>(p, st);
         default: return PA2D_ERR_ARG;
     }
 }
 
 }  // namespace
 
-// Large-M plain GEMMs of the bf16 engines (fp32 storage: engines 1 / 2; bf16 storage: io_bf16).  PA2D_LIN_PANEL=off
-// sends them back to the per-tile kernels (A/B measurements).
-bool panel_applies(const KCParams& p, bool im2col) {
-    if (!pa2d_env().lin_panel || im2col) return false;
-    // (bf16 storage stays on the per-tile kernels: with one MFMA term and 2-byte operands the layer is a pure streaming
-    //  problem and two small workgroups per CU keep more bytes in flight than one persistent one: measured 131 vs 138
-    //  samples/s on the bf16-storage bench)
-    if (p.io_bf16 || (p.engine != 1 && p.engine != 2)) return false;
-    if ((p.K % 32) != 0 || p.N < 64) return false;
-    if (p.io_bf16 && (p.lda % 8) != 0) return false;
-    if (panel_mode(p) < 0) return false;
-    if (p.epi == EPI_ACT && p.aux) return false;
-    return (long long)(p.M / 256) * ceil_div(p.N, 128) >= 256;        // at least one tile per CU
-}
-
-// the first M - M % 256 rows (the caller runs the < 256-row tail on the per-tile kernels)
-
-int launch_kc_panel(const KCParams& p_in, hipStream_t st) {
-    KCParams p = p_in;
-    if (p.io_bf16) {
-        const unsigned long long ab = ((unsigned long long)(p.M - 1) * p.lda + p.K) * 2ull;      // A holds bf16
-        if (ab >= 0xFFFFFFF0ull) return PA2D_ERR_UNSUPPORTED;
-        p.a_bytes = (unsigned)ab;
-        return launch_panel_t<1, false, bf16_t>(p, st);
-    }
-    if (p.engine == 1) return launch_panel_t<3, true, float>(p, st);
-    return launch_panel_t<1, true, float>(p, st);
+// The whole 256-row blocks of a large-M plain GEMM of the bf16 engines, fp32 storage (plan_kc: KC_PANEL; c.nt planes, epilogue
+// c.mode); the caller runs the < 256-row tail on the per-tile kernels.  bf16 storage never comes here: with one MFMA term
+// and 2-byte operands the layer is a pure streaming problem and two small workgroups per CU keep more bytes in flight than
+// one persistent one (measured 131 vs 138 samples/s on the bf16-storage bench), so only AF32 = true, TO = float are built.
+int launch_kc_panel(const KCParams& p, const KCChoice& c, hipStream_t st) {
+    return c.nt == 3 ? launch_panel_t<3>(p, c.mode, st) : launch_panel_t<1>(p, c.mode, st);
 }

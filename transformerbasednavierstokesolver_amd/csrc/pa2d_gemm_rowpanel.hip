@@ -281,55 +281,25 @@ __global__ __launch_bounds__(256, 1) void gemm_rowpanel_kernel(const KCParams p,
 }
 
 template <int KS, int MODE, bool HAS_RES>
-int launch_rowpanel_t(const KCParams& p, const unsigned char* img, hipStream_t st) {
+int launch_rowpanel_t(const KCParams& p, hipStream_t st) {
     const int smem = RP_BIAS + RP_SLOTS * RP_STAGE;
-    {   // every launch: the attribute is per device, and the call is cheap
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_rowpanel_kernel<KS, MODE, HAS_RES>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        if (e != hipSuccess) return (int)e;
-    }
     const int rounds = p.M / 128;
     const unsigned img_bytes = (unsigned)((size_t)p.N * p.K * 6);
-    hipLaunchKernelGGL((gemm_rowpanel_kernel<KS, MODE, HAS_RES>), dim3(rounds < 256 ? rounds : 256), dim3(256), smem, st, p,
-                       img, img_bytes);
-    PA2D_CHECK_LAUNCH();
-    return PA2D_OK;
-}
-
-int rowpanel_mode(const KCParams& p) {
-    const bool gelu = p.act == ACT_GELU, has_res = p.res != nullptr;
-    if (p.epi == 0) return 0;
-    if (gelu && !has_res && (p.epi == (EPI_ACT | EPI_STORE_PRE) || p.epi == EPI_ACT)) return 1;
-    if (gelu && !has_res && p.epi == EPI_MUL_DACT && !p.bias) return 2;
-    return -1;
+    return launch_lds(&gemm_rowpanel_kernel<KS, MODE, HAS_RES>, dim3(rounds < 256 ? rounds : 256), dim3(256), smem, st, p,
+                      (const unsigned char*)p.wimg, img_bytes);
 }
 
 template <int KS>
-int launch_rowpanel_k(const KCParams& p, const unsigned char* img, hipStream_t st) {
-    switch (rowpanel_mode(p)) {
-        case 0: return p.res ? launch_rowpanel_t<KS, 0, true>(p, img, st) : launch_rowpanel_t<KS, 0, false>(p, img, st);
-        case 1: return launch_rowpanel_t<KS, 1, false>(p, img, st);
-        case 2: return launch_rowpanel_t<KS, 2, false>(p, img, st);
+int launch_rowpanel_k(const KCParams& p, int mode, hipStream_t st) {
+    switch (mode) {
+        case 0: return p.res ? launch_rowpanel_t<KS, 0, true>(p, st) : launch_rowpanel_t<KS, 0, false>(p, st);
+        case 1: return launch_rowpanel_t<KS, 1, false>(p, st);
+        case 2: return launch_rowpanel_t<KS, 2, false>(p, st);
         default: return PA2D_ERR_ARG;
     }
 }
 
 }  // namespace
-
-// bytes of the weight plane image of an [N, K] layer (0: the row-stationary kernel does not take this shape / engine)
-size_t rowpanel_image_bytes(int N, int K, int engine) {
-    if (engine != 1 || (K != 128 && K != 256) || N < 128 || N > 1024 || (N % 128) != 0) return 0;      // pairs of 64 columns, two in flight
-    return (size_t)N * K * 6;
-}
-
-bool rowpanel_applies(const KCParams& p) {
-    if (!pa2d_env().lin_rowpanel || p.io_bf16) return false;
-    if (rowpanel_image_bytes(p.N, p.K, p.engine) == 0) return false;
-    if (rowpanel_mode(p) < 0 || (p.epi == EPI_ACT && p.aux)) return false;
-    // 16-byte loads / stores of accumulator quads: every leading dimension a multiple of 4 elements
-    if ((p.lda & 3) || (p.ldc & 3) || (p.res && (p.ldres & 3)) || (p.aux && (p.ldaux & 3))) return false;
-    return p.M / 128 >= 256;                                     // at least one round per CU
-}
 
 // sn / sk: element strides of B[n][k] in `w` (forward: ldw, 1; data gradient: 1, ldw)
 int launch_pack_weight_image(const float* w, long long sn, long long sk, void* img, int N, int K, hipStream_t st) {
@@ -339,8 +309,8 @@ int launch_pack_weight_image(const float* w, long long sn, long long sk, void* i
     return PA2D_OK;
 }
 
-// the first M - M % 128 rows of p (the caller runs the tail on the per-tile kernels)
-int launch_kc_rowpanel(const KCParams& p, const void* img, hipStream_t st) {
-    if (p.K == 256) return launch_rowpanel_k<16>(p, (const unsigned char*)img, st);
-    return launch_rowpanel_k<8>(p, (const unsigned char*)img, st);
+// the whole 128-row rounds of p on the image p.wimg (plan_kc: KC_ROWPANEL, K in {128, 256}, epilogue c.mode); the caller runs
+// the tail on the per-tile kernels
+int launch_kc_rowpanel(const KCParams& p, const KCChoice& c, hipStream_t st) {
+    return p.K == 256 ? launch_rowpanel_k<16>(p, c.mode, st) : launch_rowpanel_k<8>(p, c.mode, st);
 }

@@ -270,115 +270,29 @@ __global__ __launch_bounds__(512, (BM + BN > 256) ? 1 : 2) void gemm_kc_split_ke
     kc_epilogue<TM, TN, IM2COL, TO>(p, acc, tile_m * BM + wm * WM + 4 * (lane >> 5), tile_n * BN + wn * WN + (lane & 31));
 }
 
-// Variants in use: conv (im2col) GEMMs always take pre-split activation planes (NT = 3: fp32-accurate split,
-// NT = 1: bf16 compute); plain GEMMs run only in bf16-compute mode and convert while staging.
-// Small plain GEMMs of the split engine (rollout / training at batch 1-4: a few thousand rows): 64 x 64 tiles so that
-// M = 4096, N = 256 still makes 256 workgroups, both operands split while staged.  The exact-fp32 kernel these launches
-// used to take spends 1024 matrix-pipe cycles per 32-deep K-step and wave (16 x v_mfma_f32_32x32x2_f32), this one 384.
-bool kc_split_small_applies(const KCParams& p, bool im2col) {
-    if (!pa2d_env().lin_small_split || im2col || p.io_bf16 || p.engine != 1) return false;
-    if ((p.K % 32) != 0 || p.K < 64 || p.N < 64 || p.M < 256) return false;
-    return (long long)ceil_div(p.M, 128) * ceil_div(p.N, 128) < 384;      // where kc_tile leaves the 128 x 128 tiles
-}
-int launch_kc_split_small(const KCParams& p, hipStream_t st) {
-    const int smem = 2 * (64 + 64) * 208;
-    {   // every launch: the attribute is per device, and the call is cheap
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_kc_split_kernel<64, 64, false, 3, false>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        if (e != hipSuccess) return (int)e;
+// Variants in use (plan_kc picks; KC_SPLIT_SMALL is the 64 x 64 one): conv (im2col) GEMMs always take pre-split activation
+// planes (NT = 3: fp32-accurate split on 256x128 / 128x128 / 64x128 tiles, NT = 1: bf16 compute on 128x128; 9 or 27 taps);
+// plain GEMMs run only in bf16-compute mode and convert while staging, except the small ones of the split engine.  bf16
+// storage: A is the bf16 tensor itself, the outputs are bf16.
+int launch_kc_split(const KCParams& p, bool im2col, const KCChoice& c, hipStream_t st) {
+    const int smem = 2 * (c.bm + c.bn) * (c.nt * 64 + 16);
+    const dim3 grid(ceil_div(ceil_div(p.M, c.bm), 8) * 8 * ceil_div(p.N, c.bn));
+#define SPLIT_GO(...) return launch_lds(&gemm_kc_split_kernel<__VA_ARGS__>, grid, dim3(512), smem, st, p)
+#define SPLIT_CONV(TAPS)                                          \
+    if (c.nt == 1) SPLIT_GO(128, 128, true, 1, true, float, TAPS); \
+    if (c.bm == 256) SPLIT_GO(256, 128, true, 3, true, float, TAPS); \
+    if (c.bm == 64) SPLIT_GO(64, 128, true, 3, true, float, TAPS); \
+    SPLIT_GO(128, 128, true, 3, true, float, TAPS)
+    if (c.family == KC_SPLIT_SMALL) SPLIT_GO(64, 64, false, 3, false);
+    if (!im2col) {
+        if (c.out_bf16) SPLIT_GO(128, 128, false, 1, true, bf16_t);
+        SPLIT_GO(128, 128, false, 1, false);
     }
-    const dim3 grid(ceil_div(ceil_div(p.M, 64), 8) * 8 * ceil_div(p.N, 64));
-    hipLaunchKernelGGL((gemm_kc_split_kernel<64, 64, false, 3, false>), grid, dim3(512), smem, st, p);
-    PA2D_CHECK_LAUNCH();
-    return PA2D_OK;
-}
-
-// 27-tap (3x3x3) conv on pre-split activation planes: the tile choice of the 9-tap conv below (256x128 where M % 256 == 0
-// and >= 512 tiles, 64x128 for small launches, else 128x128); the halo-in-LDS kernel is 2-D only and is never used here.
-template <int BM, int BN, int NT>
-static int launch_split27(const KCParams& p, int rows_per_tile, int tiles_n, hipStream_t st) {
-    const int smem = 2 * (BM + BN) * (NT * 64 + 16);
-    if (smem > 65536) {      // every launch: the attribute is per device, and the call is cheap
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_kc_split_kernel<BM, BN, true, NT, true, float, 27>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        if (e != hipSuccess) return (int)e;
-    }
-    const dim3 grid(ceil_div(ceil_div(p.M, rows_per_tile), 8) * 8 * tiles_n);
-    hipLaunchKernelGGL((gemm_kc_split_kernel<BM, BN, true, NT, true, float, 27>), grid, dim3(512), smem, st, p);
-    PA2D_CHECK_LAUNCH();
-    return PA2D_OK;
-}
-static int launch_conv3d_split(const KCParams& p, int tiles_m, int tiles_n, hipStream_t st) {
-    if (p.engine == 2) return launch_split27<128, 128, 1>(p, 128, tiles_n, st);
-    if (pa2d_env().split_big && (p.M % 256) == 0 && (long long)(p.M / 256) * tiles_n >= 512)
-        return launch_split27<256, 128, 3>(p, 256, tiles_n, st);
-    if ((long long)tiles_m * tiles_n < 256) return launch_split27<64, 128, 3>(p, 64, tiles_n, st);
-    return launch_split27<128, 128, 3>(p, 128, tiles_n, st);
-}
-
-int launch_kc_split(KCParams& p, bool im2col, hipStream_t st) {
-    const int tiles_m = ceil_div(p.M, 128), tiles_n = ceil_div(p.N, 128);
-    const bool bf = p.engine == 2;
-    const int planes = bf ? 1 : 3;
-    if (im2col) {
-        if (!p.apre) return PA2D_ERR_ARG;
-        const unsigned long long pb = (unsigned long long)p.M * (p.Cin / 32) * planes * 64;
-        if (pb >= 0xFFFFFFF0ull) return PA2D_ERR_UNSUPPORTED;
-        p.a_bytes = (unsigned)pb;
-        p.b_bytes = (unsigned)((size_t)p.N * (p.K / 32) * planes * 64);
-    } else if (!bf) {
-        return PA2D_ERR_ARG;
-    }
-    if (p.io_bf16) {          // bf16-storage entry points: A is the bf16 tensor itself, outputs are bf16
-        if (p.taps == 27) return PA2D_ERR_UNSUPPORTED;      // no bf16-storage 3x3x3 conv
-        if (!bf || (!im2col && (p.K % 32) != 0)) return PA2D_ERR_UNSUPPORTED;
-        if (!im2col) {
-            const unsigned long long ab = ((unsigned long long)(p.M - 1) * p.lda + p.K) * 2ull;
-            if (ab >= 0xFFFFFFF0ull) return PA2D_ERR_UNSUPPORTED;
-            p.a_bytes = (unsigned)ab;
-        }
-        if (im2col && conv_halo_applies(p)) return launch_conv_halo(p, st);
-        const dim3 g16(ceil_div(tiles_m, 8) * 8 * tiles_n);
-        if (im2col) hipLaunchKernelGGL((gemm_kc_split_kernel<128, 128, true, 1, true, bf16_t>), g16, dim3(512), 2 * 256 * 80, st, p);
-        else hipLaunchKernelGGL((gemm_kc_split_kernel<128, 128, false, 1, true, bf16_t>), g16, dim3(512), 2 * 256 * 80, st, p);
-        PA2D_CHECK_LAUNCH();
-        return PA2D_OK;
-    }
-    if (im2col && p.taps == 27) return launch_conv3d_split(p, tiles_m, tiles_n, st);
-    if (im2col && conv_halo_applies(p)) return launch_conv_halo(p, st);
-    const dim3 grid(ceil_div(tiles_m, 8) * 8 * tiles_n);
-    const int smem = 2 * (128 + 128) * (bf ? 80 : 208);
-    {   // every launch: the attribute is per device, and the call is cheap
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_kc_split_kernel<128, 128, true, 3, true>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (128 + 128) * 208);
-        if (e != hipSuccess) return (int)e;
-    }
-    if (pa2d_env().split_big && im2col && !bf && (p.M % 256) == 0 && (long long)(p.M / 256) * tiles_n >= 512) {
-        // 256x128 workgroup tile (128x64 per consumer wave): 25 % less L2->LDS staging and LDS reads per MFMA
-        const int smem_big = 2 * (256 + 128) * 208;
-        {
-            hipError_t eb = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_kc_split_kernel<256, 128, true, 3, true>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, smem_big);
-            if (eb != hipSuccess) return (int)eb;
-        }
-        const dim3 gbig(ceil_div(p.M / 256, 8) * 8 * tiles_n);
-        hipLaunchKernelGGL((gemm_kc_split_kernel<256, 128, true, 3, true>), gbig, dim3(512), smem_big, st, p);
-    } else if (im2col && !bf && (long long)tiles_m * tiles_n < 256) {
-        // small launches (rollout at batch 1: 32 x 4 tiles of 128 x 128 leave half of the 256 CUs idle): 64-row tiles
-        const int smem_s = 2 * (64 + 128) * 208;
-        {
-            hipError_t es = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_kc_split_kernel<64, 128, true, 3, true>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, smem_s);
-            if (es != hipSuccess) return (int)es;
-        }
-        const dim3 gs(ceil_div(ceil_div(p.M, 64), 8) * 8 * tiles_n);
-        hipLaunchKernelGGL((gemm_kc_split_kernel<64, 128, true, 3, true>), gs, dim3(512), smem_s, st, p);
-    } else
-    if (!im2col) hipLaunchKernelGGL((gemm_kc_split_kernel<128, 128, false, 1, false>), grid, dim3(512), smem, st, p);
-    else if (bf) hipLaunchKernelGGL((gemm_kc_split_kernel<128, 128, true, 1, true>), grid, dim3(512), smem, st, p);
-    else hipLaunchKernelGGL((gemm_kc_split_kernel<128, 128, true, 3, true>), grid, dim3(512), smem, st, p);
-    PA2D_CHECK_LAUNCH();
-    return PA2D_OK;
+    if (c.out_bf16) SPLIT_GO(128, 128, true, 1, true, bf16_t);
+    if (p.taps == 27) { SPLIT_CONV(27); }
+    SPLIT_CONV(9);
+#undef SPLIT_CONV
+#undef SPLIT_GO
 }
 
 // Activation pre-split for the bf16 engines: src [rows][ld >= C] fp32 -> dst [rows][C/32][NT][32] bf16 (NT = 3:

@@ -195,7 +195,7 @@ def linear_bwd_data(dy, w, pre=None, act=None, engine=None, pre_is_derivative=Fa
         eng = _abi_engine(engine)
         nimg = _L().pa2d_gemm_fwd_workspace(K, N, eng)     # the data gradient is a GEMM of output width K, contraction N
         img = _lin_image(w, 1, K, N, eng, nimg)
-        nb = K * N * 4 if img else _L().pa2d_gemm_bwd_data_workspace(N, K, eng)
+        nb = _L().pa2d_gemm_bwd_data_workspace(N, K, eng) - (nimg if img else 0)      # [transposed weight | image unless ready-made]
         ws = _ws(nb, dy)
         _lib.check(_L().pa2d_gemm_bwd_data(_p(dy), N, _p(w), K, _p(pre), K, ACT_IDS[act] | aflag, _p(dx), K, img, ws.data_ptr(), nb,
                                            M, N, K, eng, _stream()), "gemm_bwd_data")
