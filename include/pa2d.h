@@ -368,6 +368,17 @@ int pa2d_zscore_fwd(const float* x, long long ldx, float* y, double* stats, void
  * the forward.  sigma = 0 is outside the contract (the reference's autograd gives NaN there). */
 int pa2d_zscore_bwd(const float* dy, long long lddy, const float* y, const double* stats, float* dx, long long lddx, void* ws,
                     size_t ws_bytes, long long rows, int C, pa2d_stream_t stream);
+/* The same z-score over `groups` independent groups of ONE tensor of pitch ldx: group g owns the rows
+ * [g * rows_per_group, (g + 1) * rows_per_group) and has its own stats[g][2] = (mu, sigma).  One partial-sum launch and one
+ * map launch serve all groups (the group is a grid axis), with the partition of pa2d_zscore_* on rows_per_group rows inside
+ * every group: group g's y, stats and dx are BIT FOR BIT those of pa2d_zscore_fwd / _bwd on its rows alone (groups = 1 is
+ * that call).  C % 4, the pitch and the alignment as above; the 4 GiB extent covers the whole tensor; 1 <= groups <= 65535
+ * (else PA2D_ERR_ARG / PA2D_ERR_UNSUPPORTED); groups * rows_per_group = 0 is a no-op; a NULL operand is PA2D_ERR_ARG. */
+size_t pa2d_zscore_grouped_workspace(int groups, long long rows_per_group, int C);
+int pa2d_zscore_grouped_fwd(const float* x, long long ldx, float* y, double* stats, void* ws, size_t ws_bytes, int groups,
+                            long long rows_per_group, int C, pa2d_stream_t stream);
+int pa2d_zscore_grouped_bwd(const float* dy, long long lddy, const float* y, const double* stats, float* dx, long long lddx,
+                            void* ws, size_t ws_bytes, int groups, long long rows_per_group, int C, pa2d_stream_t stream);
 /* wide slice weights (SliceLearner.py:127-128: softmax(in_project_slice(x_mid) / clamp(temperature, .1, 5)); the last layer
  * of the code-conditioned predictor's MLP): sw[r, :] = softmax_m((x[r, :] . ws[m, :] + bs[m]) / t), x [rows, D] of pitch ldx,
  * ws [M, D], bs [M], t = temperature[0] (clamped to [0.1, 5] with clamp_temperature = 1), sw [rows, M].
@@ -429,6 +440,9 @@ int pa2d_head_bwd(const float* dy, const float* xn, const float* w, float* dxn, 
 /* ---- elementwise out = dy * act'(pre): backward of the activation of a generic Linear+act layer
  * (MLP hidden layers with n_layers > 0, …_2D.py:28,32-36; not used by the NS/Darcy configurations) */
 int pa2d_act_bwd(const float* dy, const float* pre, float* out, long long n, int act, pa2d_stream_t stream);
+/* elementwise out = act(pre), the function the GEMM epilogues apply: the activation of a layer whose per-sample bias row was
+ * added by the broadcast embedding add: the folded code-conditioned slice predictor */
+int pa2d_act_fwd(const float* pre, float* out, long long n, int act, pa2d_stream_t stream);
 
 /* ---- optimizer / loss side of the exp_ns iteration over flat fp32 buffers
  * (exp_ns.py:198-218: TestLoss rel-L2 sum, clip_grad_norm_, AdamW.step; lr/beta1 of the step come from

@@ -293,6 +293,17 @@ def main():
                                                    wbytes, "HBM")
             tests[f"wide_sw_bwd D={dd} B={sb}"] = (lambda a=wxx, w=wws, b=wbs, d=wds: ops.wide_slice_weights_bwd(a, w, b, ptemp, d),
                                                    4.0 * pr * (3 * dd + 2 * 16), "HBM")     # x (kernel + GEMM), dx, dsw, dl
+    if only & {"zscore_grouped"}:      # a folded iteration's z-score: 10 calls x 4096 rows x 256, one launch pair against ten
+        gx, gd = rn(10 * 4096, 256), rn(10 * 4096, 256)
+        gy, gst = ops.zscore_grouped_fwd(gx, 10)
+        parts = [(gx[k * 4096:(k + 1) * 4096], gd[k * 4096:(k + 1) * 4096]) + ops.zscore_fwd(gx[k * 4096:(k + 1) * 4096])
+                 for k in range(10)]
+        gbytes = 10 * 4096 * 256 * 4.0
+        tests["zscore_grouped fwd 10x4096x256"] = (lambda: ops.zscore_grouped_fwd(gx, 10), 3.0 * gbytes, "HBM")
+        tests["zscore_grouped fwd 10 ungrouped calls"] = (lambda: [ops.zscore_fwd(p[0]) for p in parts], 3.0 * gbytes, "HBM")
+        tests["zscore_grouped bwd 10x4096x256"] = (lambda: ops.zscore_grouped_bwd(gd, gy, gst), 5.0 * gbytes, "HBM")
+        tests["zscore_grouped bwd 10 ungrouped calls"] = (lambda: [ops.zscore_bwd(p[1], p[2], p[3]) for p in parts],
+                                                          5.0 * gbytes, "HBM")
     if only & {"slice_predictor_iter"}:
         from transformerbasednavierstokesolver_amd import harness
         from transformerbasednavierstokesolver_amd.SequenSolver import SequenSolver

@@ -33,6 +33,42 @@ REFERENCE_ENCODER = dict(space_dim=2, n_layers=8, n_hidden=32, dropout=0.0, n_he
 WEIGHT_PROJECTION_HIDDEN = 64
 
 
+def fold_calls(ncalls, B, N, T, point_width, token_width):
+    """How many teacher-forced calls fit in ONE folded call (the rule of harness._fold_group): the widest per-point tensor
+    (`point_width` floats on calls*B*N rows) and the widest per-token tensor (`token_width` floats on calls*B*T rows) must
+    stay under the 4 GiB extent of a buffer descriptor."""
+    from .harness import FOLD_MAX_BYTES
+    per_call = max(4 * point_width * B * N, 4 * token_width * B * T, 1)
+    return max(1, min(ncalls, FOLD_MAX_BYTES // per_call))
+
+
+def encode_table(model, spatial_pos, seq, nframes, want_slices=False):
+    """The first `nframes` frames of seq [B, N, >= nframes] through the frozen encoder ONCE, as one frame-major batch (cut
+    only where a folded encoder tensor would pass the 4 GiB extent): tokens [B, Head, nframes, dim] and, with
+    `want_slices`, every frame's slice weights [nframes*B, 1, N, M] in frame-major order.  The encoder's cached slice
+    weights are left as the last frame's [B, 1, N, M], as a frame-by-frame loop leaves them."""
+    from .harness import _fold_group
+    B, N = seq.shape[0], seq.shape[1]
+    with torch.no_grad():
+        frames = seq[..., :nframes].permute(2, 0, 1).reshape(nframes * B, N, 1)
+        chunk = _fold_group(model.encoder, B, N, nframes)
+        codes, slices = [], []
+        for f0 in range(0, nframes, chunk):
+            f = min(chunk, nframes - f0)
+            pos = spatial_pos.repeat(f, *([1] * (spatial_pos.dim() - 1)))
+            code = model.encoder.encode(pos, frames[f0 * B:(f0 + f) * B])
+            codes.append(code.reshape(f, B, model.Head, model.dim))
+            sw = model.encoder.get_attention_slice()
+            if want_slices:
+                slices.append(sw)
+        model.encoder.set_attention_slice(sw[-B:].contiguous())
+        code = codes[0] if len(codes) == 1 else torch.cat(codes, 0)
+        tokens = code.permute(1, 2, 0, 3).contiguous()
+    if not want_slices:
+        return tokens
+    return tokens, (slices[0] if len(slices) == 1 else torch.cat(slices, 0))
+
+
 class SequenSolver(nn.Module):
 
     def __init__(self, transolver_path, T, W, H, M, C, B, mlp_ratio=4, layers=5, act='gelu', dropout=0., *,
@@ -169,16 +205,56 @@ class SequenSolver(nn.Module):
         code = self._code(tokens)
         self.code = code
         if not use_gt:
-            if spatial_pos.dim() != 3 or spatial_pos.shape[-1] != 2:
-                raise ValueError("use_gt=False predicts the slice weights from the two point coordinates: spatial_pos "
-                                 f"must be [B, N, 2]; got {tuple(spatial_pos.shape)}")
-            wp = self.weight_projection
-            self.slice_weights = Fn.code_slice_weights(code.reshape(B, self.M, self.C), spatial_pos,
-                                                       wp.linear_pre[0].weight, wp.linear_pre[0].bias,
-                                                       wp.linears[0][0].weight, wp.linears[0][0].bias,
-                                                       wp.linear_post.weight, wp.linear_post.bias)
+            self.slice_weights = self._predicted_slice_weights(code, spatial_pos)
         decoded = self.decode(code)
         return Fn.head(Fn.layer_norm(decoded, self.ln_3.weight, self.ln_3.bias), self.mlp2.weight, self.mlp2.bias)
+
+    def _predicted_slice_weights(self, code, spatial_pos):
+        if spatial_pos.dim() != 3 or spatial_pos.shape[-1] != 2:
+            raise ValueError("use_gt=False predicts the slice weights from the two point coordinates: spatial_pos "
+                             f"must be [B, N, 2]; got {tuple(spatial_pos.shape)}")
+        wp = self.weight_projection
+        return Fn.code_slice_weights(code.reshape(code.shape[0], self.M, self.C), spatial_pos,
+                                     wp.linear_pre[0].weight, wp.linear_pre[0].bias,
+                                     wp.linears[0][0].weight, wp.linears[0][0].bias,
+                                     wp.linear_post.weight, wp.linear_post.bias)
+
+    def forward_windows(self, spatial_pos, seq, use_gt=True):
+        """The n = seq.shape[-1] - T teacher-forced calls of a training iteration in folded batches: seq [B, N, T + n] holds
+        TRUE frames, and column k of the result [B, N, n] is what forward(spatial_pos, seq[..., k:k+T],
+        seq[..., k+T:k+T+1], use_gt) returns.  Every frame is encoded ONCE (use_gt=True: all T + n, and call k decodes
+        with the cached slice weights of frame T + k, a contiguous block of the encoder's output; else T + n - 1 and the
+        code -> slice-weight stage on the folded batch); call k's tokens are frames k .. k+T-1 of that table and the blocks
+        run on n*B sequences.  `code`, `slice_weights` and the encoder's cached slice weights are left as the last call's.
+        n is cut into several folded calls where a folded tensor would pass the 4 GiB extent.  This model has no conv
+        slice predictor (the merged model's 512-float hidden layer): its widest per-point rows are the slice weights (M),
+        the point features (C + 2) and weight_projection's hidden layer, its widest per-token row the blocks' mlp_ratio*dim."""
+        self._refuse()
+        B, T = seq.shape[0], self.T
+        n = seq.shape[-1] - T
+        if n < 1:
+            raise ValueError(f"forward_windows needs seq [B, N, T + n] with n >= 1; got {tuple(seq.shape)} at T = {T}")
+        if use_gt:
+            tokens, slices = encode_table(self, spatial_pos, seq, T + n, want_slices=True)
+        else:
+            tokens = encode_table(self, spatial_pos, seq, T + n - 1)
+        ratio = self.mlp.linear_pre[0].weight.shape[0] / self.dim
+        group = fold_calls(n, B, self.N, T, max(self.M, self.C + 2, WEIGHT_PROJECTION_HIDDEN), int(ratio * self.dim))
+        outs = []
+        for k0 in range(0, n, group):
+            g = min(group, n - k0)
+            win = torch.cat([tokens[:, :, k:k + T] for k in range(k0, k0 + g)], 0)       # [g*B, Head, T, dim], call-major
+            code = self._code(self._blocks(win))
+            if use_gt:
+                sw = slices[(T + k0) * B:(T + k0 + g) * B]
+            else:
+                sw = self._predicted_slice_weights(code, spatial_pos.repeat(g, 1, 1))
+            decoded = Fn.deslice_weights(code, sw)
+            out = Fn.head(Fn.layer_norm(decoded, self.ln_3.weight, self.ln_3.bias), self.mlp2.weight, self.mlp2.bias)
+            outs.append(out.reshape(g, B, self.N))
+        self.code, self.slice_weights = code[-B:], sw[-B:]
+        out = outs[0] if len(outs) == 1 else torch.cat(outs, 0)
+        return out.permute(1, 2, 0)
 
     def solve_with_slice_learner(self, slice_learner_path, spatial_pos, fx, y, unified_pos=0, use_vorticity=0,
                                  use_previous_slice=False, learn_from_vort=False, use_code_for_vorticity=False, *,

@@ -32,7 +32,7 @@ import torch.nn as nn
 
 from . import functional as Fn
 from . import ops
-from .SequenSolver import REFERENCE_ENCODER
+from .SequenSolver import REFERENCE_ENCODER, encode_table, fold_calls
 from .SliceLearner import code_conditioned_slice_weights
 from .model import Transolver_Structured_Mesh2D_Encoder
 from .model._core import ACTIVATION, MLP  # noqa: F401  (the reference module defines both names)
@@ -205,16 +205,52 @@ class SequenSolver(nn.Module):
         decoded = self.decode(code)
         return Fn.head(Fn.layer_norm(decoded, self.ln_3.weight, self.ln_3.bias), self.mlp2.weight, self.mlp2.bias)
 
-    def forward_slice(self, x, fx, code):
-        """x [B, N, 64], fx [B, N, T], code [B, 1, M, C] -> slice weights [B, 1, N, M]."""
+    def forward_windows(self, spatial_pos, seq, use_gt=True):
+        """The n = seq.shape[-1] - T teacher-forced calls of a training iteration in folded batches: seq [B, N, T + n] holds
+        TRUE frames, and column k of the result [B, N, n] is what forward(spatial_pos, seq[..., k:k+T],
+        seq[..., k+T:k+T+1], use_gt) returns.  Every frame is encoded ONCE (use_gt=True: all T + n, so that the encoder's
+        cached slice weights end as the last target's; else T + n - 1); call k's tokens are frames k .. k+T-1 of that
+        table plus the positional table; the blocks run on n*B sequences and forward_slice on n*B windows with one set of
+        z-score statistics per call (groups = n).  `code`, `slice_weights` and the encoder's cached slice weights are left
+        as the last call's.  n is cut into several folded calls where a folded tensor would pass the 4 GiB extent."""
+        self._refuse()
+        B, T = seq.shape[0], self.T
+        n = seq.shape[-1] - T
+        if n < 1:
+            raise ValueError(f"forward_windows needs seq [B, N, T + n] with n >= 1; got {tuple(seq.shape)} at T = {T}")
+        nframes = T + n if use_gt else T + n - 1
+        tokens = encode_table(self, spatial_pos, seq, nframes)                         # [B, Head, nframes, dim]
+        ratio = self.mlp.linear_pre[0].weight.shape[0] / self.dim
+        group = fold_calls(n, B, self.N, T, max(2 * SLICE_HIDDEN, self.concatenated // 2), int(ratio * self.dim))
+        outs = []
+        for k0 in range(0, n, group):
+            g = min(group, n - k0)
+            with torch.no_grad():       # the tokens come from the frozen encoder
+                win = torch.cat([tokens[:, :, k:k + T] for k in range(k0, k0 + g)], 0)   # [g*B, Head, T, dim], call-major
+                win = self.add_positional_encoding(win)
+                fxw = torch.cat([seq[..., k:k + T] for k in range(k0, k0 + g)], 0)       # [g*B, N, T]
+                pos = spatial_pos.repeat(g, *([1] * (spatial_pos.dim() - 1)))
+            code = self._code(self._blocks(win))
+            sw = self.forward_slice(pos, fxw, code, groups=g)
+            decoded = Fn.deslice_weights(code, sw)
+            out = Fn.head(Fn.layer_norm(decoded, self.ln_3.weight, self.ln_3.bias), self.mlp2.weight, self.mlp2.bias)
+            outs.append(out.reshape(g, B, self.N))
+        self.code, self.slice_weights = code[-B:], sw[-B:]
+        out = outs[0] if len(outs) == 1 else torch.cat(outs, 0)
+        return out.permute(1, 2, 0)
+
+    def forward_slice(self, x, fx, code, groups=1):
+        """x [B, N, 64], fx [B, N, T], code [B, 1, M, C] -> slice weights [B, 1, N, M].  `groups` > 1: the batch is that
+        many folded calls of B / groups samples, each z-scored on its own (SliceLearner.code_conditioned_slice_weights)."""
         self._refuse()
         if fx is None:
             raise ValueError("forward_slice needs fx: the reference's fx=None path reads a placeholder it never creates")
         if x.shape[-1] + fx.shape[-1] != self.fundemental:
             raise ValueError(f"forward_slice takes {SLICE_POS_FEATURES} positional features and T = {self.T} frames per "
                              f"point; got {x.shape[-1]} and {fx.shape[-1]}")
+        folded = {} if groups == 1 else dict(groups=groups)      # an unfolded call is made exactly as it always was
         return code_conditioned_slice_weights(x, fx, code, self.preprocess, self.in_project_x, self.in_project_slice,
-                                              self.temperature, self.H, self.W, self.M, self.C, self.engine)
+                                              self.temperature, self.H, self.W, self.M, self.C, self.engine, **folded)
 
     def get_code(self, spatial_pos, fx, y):
         """The code without the positional encoding, as the reference's get_code."""

@@ -102,12 +102,18 @@ class SliceLearner(_EngineMixin, nn.Module):
         return sw.reshape(B, 1, N, sw.shape[-1])
 
 
-def code_conditioned_slice_weights(x, fx, code, preprocess, in_project_x, in_project_slice, temperature, H, W, M, C, engine):
+def code_conditioned_slice_weights(x, fx, code, preprocess, in_project_x, in_project_slice, temperature, H, W, M, C, engine,
+                                   groups=1):
     """The reference's `LearnSlice.forward_from_vorticity` / merged `SequenSolver.forward_slice` over the caller's own
     sub-modules (the ONE implementation behind VorticitySliceLearner.forward and SequenSolverMerged.forward_slice):
     x [B, N, 64 or 2], fx [B, N, T], code [B, 1, M, C] or None -> slice weights [B, 1, N, M].  `preprocess` and
     `in_project_slice` are MLPs of model/_core.py, `in_project_x` a Conv2d(n_hidden, n_hidden, 3, 1, 1), `temperature` one
-    scalar (a Parameter or a plain tensor)."""
+    scalar (a Parameter or a plain tensor).
+
+    `groups` > 1: the batch holds `groups` independent calls of B / groups consecutive samples each (a time-folded
+    iteration).  Both z-scores are then taken per group (functional.zscore(groups=...)), and the per-sample code term of the
+    first layer is added to ONE row GEMM by the broadcast-add kernel (functional.embed_bias) before the activation.
+    groups = 1 is the path as it was, per-sample loop included."""
     z = preprocess(torch.cat((x, fx), -1))
     B, N, nh = z.shape
     if N != H * W:
@@ -121,13 +127,20 @@ def code_conditioned_slice_weights(x, fx, code, preprocess, in_project_x, in_pro
     else:
         if code.numel() != B * M * C:
             raise ValueError(f"need a code [B, 1, M, C] = {(B, 1, M, C)}; got {tuple(code.shape)}")
-        zc = Fn.zscore(code.reshape(B, M * C))
-        zx = Fn.zscore(x_mid)
+        if groups < 1 or B % groups:
+            raise ValueError(f"groups = {groups} must divide the batch of {B}")
+        zc = Fn.zscore(code.reshape(B, M * C), groups)
+        zx = Fn.zscore(x_mid, groups)
         # first layer on cat(z(x_mid), z(code)) without the concatenation: the code term is one row per sample
         # (the two column blocks of the weight are cut out once per forward, not once per sample)
         w1x, w1c = first.weight[:, :nh].contiguous(), first.weight[:, nh:].contiguous()
         tb = Fn.linear(zc, w1c, first.bias, None, engine=eng)                             # [B, hidden]
-        if B == 1:      # every use in the reference: no per-sample pieces to put together
+        if groups > 1:  # a folded batch: ONE GEMM over all rows, the per-sample rows added by the broadcast-add kernel
+            if tb.is_cuda and tb.shape[-1] % 4:      # Fn.embed_bias would take its torch expression: a missing kernel is an error
+                raise NotImplementedError(f"the folded slice predictor needs a hidden width that is a multiple of 4 "
+                                          f"(pa2d_embed_bias); got {tb.shape[-1]}")
+            h = Fn.activation(Fn.embed_bias(Fn.linear(zx, w1x, None, None, engine=eng), None, tb), act)
+        elif B == 1:    # every use in the reference: no per-sample pieces to put together
             h = Fn.linear(zx, w1x, tb[0], act, engine=eng)
         else:
             h = torch.stack([Fn.linear(zx[b], w1x, tb[b], act, engine=eng) for b in range(B)])

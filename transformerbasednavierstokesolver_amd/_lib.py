@@ -93,6 +93,9 @@ SIGNATURES = {
     "pa2d_zscore_workspace": (_sz, [_ll, _i]),
     "pa2d_zscore_fwd": (_i, [_f, _ll, _f, _f, _f, _sz, _ll, _i, _st]),
     "pa2d_zscore_bwd": (_i, [_f, _ll, _f, _f, _f, _ll, _f, _sz, _ll, _i, _st]),
+    "pa2d_zscore_grouped_workspace": (_sz, [_i, _ll, _i]),
+    "pa2d_zscore_grouped_fwd": (_i, [_f, _ll, _f, _f, _f, _sz, _i, _ll, _i, _st]),
+    "pa2d_zscore_grouped_bwd": (_i, [_f, _ll, _f, _f, _f, _ll, _f, _sz, _i, _ll, _i, _st]),
     "pa2d_wide_slice_weights_fwd": (_i, [_f, _ll, _f, _f, _f, _f, _i, _i, _i, _i, _st, _st, _st]),
     "pa2d_wide_slice_weights_bwd_workspace": (_sz, [_i, _i, _i]),
     "pa2d_wide_slice_weights_bwd": (_i, [_f, _ll, _f, _f, _f, _f, _f, _ll, _f, _f, _f, _f, _sz, _i, _i, _i, _i, _i, _st,
@@ -107,6 +110,7 @@ SIGNATURES = {
     "pa2d_head_bwd_workspace": (_sz, [_i, _i, _i]),
     "pa2d_head_bwd": (_i, [_f, _f, _f, _f, _f, _f, _f, _sz, _i, _i, _i, _i, _st]),
     "pa2d_act_bwd": (_i, [_f, _f, _f, _ll, _i, _st]),
+    "pa2d_act_fwd": (_i, [_f, _f, _ll, _i, _st]),
     "pa2d_sumsq_workspace": (_sz, [_ll]),
     "pa2d_sumsq": (_i, [_f, _ll, _f, _f, _sz, _st]),
     "pa2d_adamw_step": (_i, [_f, _f, _f, _f, _ll, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _i, _f,

@@ -297,6 +297,12 @@ __global__ void act_bwd_kernel(const float* __restrict__ dy, const float* __rest
         out[i] = dy[i] * act_bwd(act, pre[i]);
 }
 
+// out = act(pre)   (elementwise; the activation of a layer whose bias was added by another kernel, e.g. a per-sample row)
+__global__ void act_fwd_kernel(const float* __restrict__ pre, float* __restrict__ out, long long n, int act) {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+        out[i] = act_fwd(act, pre[i]);
+}
+
 static int row_blocks(int rows) {
     int b = ceil_div(rows, 64);
     if (b > 1024) b = 1024;
@@ -453,6 +459,16 @@ int pa2d_act_bwd(const float* dy, const float* pre, float* out, long long n, int
     long long blocks = ceil_div_ll(n, 256);
     if (blocks > 8192) blocks = 8192;
     hipLaunchKernelGGL(act_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, st, dy, pre, out, n, act);
+    PA2D_CHECK_LAUNCH();
+    return PA2D_OK;
+}
+
+int pa2d_act_fwd(const float* pre, float* out, long long n, int act, hipStream_t st) {
+    if (n <= 0) return PA2D_OK;
+    if (!pre || !out) return PA2D_ERR_ARG;
+    long long blocks = ceil_div_ll(n, 256);
+    if (blocks > 8192) blocks = 8192;
+    hipLaunchKernelGGL(act_fwd_kernel, dim3((unsigned)blocks), dim3(256), 0, st, pre, out, n, act);
     PA2D_CHECK_LAUNCH();
     return PA2D_OK;
 }

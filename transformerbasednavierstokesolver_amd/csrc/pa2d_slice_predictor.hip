@@ -30,6 +30,8 @@ __device__ __forceinline__ double block_sum_f64(double v, double* red) {
 // z-score.  Pass 1: workgroup b sums its fixed range of float4 elements in fp64 (products of two floats are exact there):
 // forward (sum x, sum x^2), backward (sum dy, sum dy*y) -> part[b][2].  Pass 2: every workgroup adds the partial records in
 // the same fixed order, so all of them hold the same statistics, and maps its own range.
+// Grouped form: blockIdx.y is a group of `rows` consecutive rows with its own partial records, statistics and ranges; every
+// base below is moved to the group once, so a group runs the arithmetic of an ungrouped launch on its rows alone.
 constexpr int Z_V4_PER_BLOCK = NT * 16;      // pass 1: float4 elements per workgroup (until 1024 workgroups)
 constexpr int Z_MAP_V4 = NT * 8;             // pass 2: float4 elements per workgroup
 static int zscore_blocks(long long n4) {
@@ -42,6 +44,9 @@ __global__ __launch_bounds__(NT) void zscore_partial_kernel(const float* __restr
                                                            const float* __restrict__ b, long long n4, int q4,
                                                            long long per, double* __restrict__ part) {
     __shared__ double red[4];
+    a += (long long)blockIdx.y * (n4 / q4) * lda;
+    if (BWD) b += (long long)blockIdx.y * n4 * 4;
+    part += 2 * (size_t)blockIdx.y * gridDim.x;
     const long long begin = (long long)blockIdx.x * per;
     const long long end = begin + per < n4 ? begin + per : n4;
     double s = 0.0, q = 0.0;
@@ -76,6 +81,10 @@ __global__ __launch_bounds__(NT) void zscore_fwd_kernel(const float* __restrict_
                                                        double* __restrict__ stats, const double* __restrict__ part, int nb,
                                                        long long n4, int q4) {
     __shared__ double red[4];
+    x += (long long)blockIdx.y * (n4 / q4) * ldx;
+    y += (long long)blockIdx.y * n4 * 4;
+    stats += 2 * blockIdx.y;
+    part += 2 * (size_t)blockIdx.y * nb;
     double S, Q;
     zscore_totals(part, nb, red, S, Q);
     const double n = (double)n4 * 4.0;
@@ -111,6 +120,11 @@ __global__ __launch_bounds__(NT) void zscore_bwd_kernel(const float* __restrict_
                                                        float* __restrict__ dx, long long lddx,
                                                        const double* __restrict__ part, int nb, long long n4, int q4) {
     __shared__ double red[4];
+    dy += (long long)blockIdx.y * (n4 / q4) * lddy;
+    y += (long long)blockIdx.y * n4 * 4;
+    dx += (long long)blockIdx.y * (n4 / q4) * lddx;
+    stats += 2 * blockIdx.y;
+    part += 2 * (size_t)blockIdx.y * nb;
     double S, Q;
     zscore_totals(part, nb, red, S, Q);
     const double n = (double)n4 * 4.0;
@@ -138,6 +152,15 @@ static int zscore_check(long long rows, int C, long long ld) {
     if (ld < C || (ld & 3)) return PA2D_ERR_ARG;
     if (((unsigned long long)(rows - 1) * ld + C) * 4ull >= 0xFFFFFFF0ull) return PA2D_ERR_UNSUPPORTED;
     return PA2D_OK;
+}
+
+constexpr int Z_MAX_GROUPS = 65535;           // the group is a grid axis
+// `groups` groups of `rpg` rows in one tensor of pitch ld: the shape contract of zscore_check, the extent over ALL rows
+static int zscore_grouped_check(int groups, long long rpg, int C, long long ld) {
+    if (C <= 0 || (C & 3)) return PA2D_ERR_UNSUPPORTED;
+    if (groups < 1 || rpg < 0) return PA2D_ERR_ARG;
+    if (groups > Z_MAX_GROUPS || rpg > (long long)0x7FFFFFFF) return PA2D_ERR_UNSUPPORTED;
+    return zscore_check((long long)groups * rpg, C, ld);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -396,6 +419,53 @@ int pa2d_zscore_bwd(const float* dy, long long lddy, const float* y, const doubl
     PA2D_CHECK_LAUNCH();
     hipLaunchKernelGGL(zscore_bwd_kernel, dim3((unsigned)ceil_div_ll(n4, Z_MAP_V4)), dim3(NT), 0, st, dy, lddy, y, stats, dx,
                        lddx, (const double*)ws, nb, n4, q4);
+    PA2D_CHECK_LAUNCH();
+    return PA2D_OK;
+}
+
+size_t pa2d_zscore_grouped_workspace(int groups, long long rows_per_group, int C) {
+    if (groups < 1 || groups > Z_MAX_GROUPS) return 0;
+    return (size_t)groups * pa2d_zscore_workspace(rows_per_group, C);
+}
+
+int pa2d_zscore_grouped_fwd(const float* x, long long ldx, float* y, double* stats, void* ws, size_t ws_bytes, int groups,
+                            long long rows_per_group, int C, void* stream) {
+    const int rc = zscore_grouped_check(groups, rows_per_group, C, ldx);
+    if (rc) return rc;
+    if (rows_per_group <= 0) return PA2D_OK;
+    if (!x || !y || ((uintptr_t)x & 15) || ((uintptr_t)y & 15) || !stats) return PA2D_ERR_ARG;
+    if (!ws || ws_bytes < pa2d_zscore_grouped_workspace(groups, rows_per_group, C)) return PA2D_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const int q4 = C / 4;
+    const long long n4 = rows_per_group * q4;      // per group: the partition of an ungrouped call on its rows
+    const int nb = zscore_blocks(n4);
+    hipLaunchKernelGGL((zscore_partial_kernel<false>), dim3(nb, groups), dim3(NT), 0, st, x, ldx, (const float*)nullptr, n4,
+                       q4, ceil_div_ll(n4, nb), (double*)ws);
+    PA2D_CHECK_LAUNCH();
+    hipLaunchKernelGGL(zscore_fwd_kernel, dim3((unsigned)ceil_div_ll(n4, Z_MAP_V4), groups), dim3(NT), 0, st, x, ldx, y,
+                       stats, (const double*)ws, nb, n4, q4);
+    PA2D_CHECK_LAUNCH();
+    return PA2D_OK;
+}
+
+int pa2d_zscore_grouped_bwd(const float* dy, long long lddy, const float* y, const double* stats, float* dx, long long lddx,
+                            void* ws, size_t ws_bytes, int groups, long long rows_per_group, int C, void* stream) {
+    int rc = zscore_grouped_check(groups, rows_per_group, C, lddy);
+    if (!rc) rc = zscore_grouped_check(groups, rows_per_group, C, lddx);
+    if (rc) return rc;
+    if (rows_per_group <= 0) return PA2D_OK;
+    if (!dy || !y || !dx || ((uintptr_t)dy & 15) || ((uintptr_t)y & 15) || ((uintptr_t)dx & 15) || !stats)
+        return PA2D_ERR_ARG;
+    if (!ws || ws_bytes < pa2d_zscore_grouped_workspace(groups, rows_per_group, C)) return PA2D_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const int q4 = C / 4;
+    const long long n4 = rows_per_group * q4;
+    const int nb = zscore_blocks(n4);
+    hipLaunchKernelGGL((zscore_partial_kernel<true>), dim3(nb, groups), dim3(NT), 0, st, dy, lddy, y, n4, q4,
+                       ceil_div_ll(n4, nb), (double*)ws);
+    PA2D_CHECK_LAUNCH();
+    hipLaunchKernelGGL(zscore_bwd_kernel, dim3((unsigned)ceil_div_ll(n4, Z_MAP_V4), groups), dim3(NT), 0, st, dy, lddy, y,
+                       stats, dx, lddx, (const double*)ws, nb, n4, q4);
     PA2D_CHECK_LAUNCH();
     return PA2D_OK;
 }

@@ -45,6 +45,20 @@ def split_ns_trajectories(u, ntrain, ntest, T_in=10, T=10, r=1):
                 test_a=cut(te, 0, T_in), test_u=cut(te, T_in, T_in + T))
 
 
+def split_ns_all_frames(u, ntrain, ntest):
+    """The split the auto-encoder trains on (auto_encoder.py:81-88): u [S, H, W, F] -> train [ntrain*F, H*W, 1] of the
+    first `ntrain` trajectories and test [ntest*F, H*W, 1] of the LAST `ntest`.  As in the script, [n, H*W, F] is RESHAPED
+    to [n*F, H*W, 1] (no transpose): sample i*F + j is the j-th run of H*W consecutive values of trajectory i's
+    point-major, frame-minor memory."""
+    u = np.asarray(u)
+
+    def frames(block):
+        flat = block.reshape(block.shape[0], -1, block.shape[-1])
+        return torch.from_numpy(np.ascontiguousarray(flat.reshape(flat.shape[0] * flat.shape[-1], flat.shape[1], 1)))
+
+    return dict(h=u.shape[1], train=frames(u[:ntrain]), test=frames(u[-ntest:]))
+
+
 def load_ns_mat(path, ntrain, ntest, T_in=10, T=10, r=1, key="u"):
     import scipy.io as scio
     return split_ns_trajectories(scio.loadmat(path)[key], ntrain, ntest, T_in, T, r)
@@ -79,6 +93,18 @@ def grid_positions(h, w=None):
     w = h if w is None else w
     xx, yy = np.meshgrid(np.linspace(0, 1, w), np.linspace(0, 1, h))
     return torch.tensor(np.c_[xx.ravel(), yy.ravel()], dtype=torch.float).unsqueeze(0)
+
+
+def unified_positions(h, w=None, ref=8):
+    """[1, h*w, ref*ref] float32: the `unified_pos` point input that the SequenSolver scripts' train() builds with their
+    get_grid(): the Euclidean distance of mesh point (i/(h-1), j/(w-1)) to the lattice point (k/(ref-1), l/(ref-1)),
+    feature index k*ref + l; linspace in float64, arithmetic in float32 (SliceLearner.get_grid is the same table)."""
+    w = h if w is None else w
+    axis = lambda n: torch.tensor(np.linspace(0, 1, n), dtype=torch.float)
+    rows, cols, lat = axis(h), axis(w), axis(ref)
+    dr2 = (rows[:, None] - lat[None, :]) ** 2
+    dc2 = (cols[:, None] - lat[None, :]) ** 2
+    return torch.sqrt(dr2[:, None, :, None] + dc2[None, :, None, :]).reshape(1, h * w, ref * ref).contiguous()
 
 
 class ResidentDataset:

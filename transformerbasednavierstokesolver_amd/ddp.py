@@ -123,10 +123,12 @@ class FlatGradSync:
                 p.grad = None
 
     def active_ranges(self):
-        """Contiguous [start, stop) float ranges of the flat buffer covered by touched parameters."""
+        """Contiguous [start, stop) float ranges of the flat buffer covered by touched parameters.  A parameter frozen after
+        the bucket was built (requires_grad switched off, e.g. SequenSolver.freeze_attention()) is left out from then on:
+        no step, no weight decay, no momentum, as torch.optim.AdamW leaves a parameter whose gradient is None."""
         runs = []
         for i, p in enumerate(self.params):
-            if not self.touched[i]:
+            if not self.touched[i] or not p.requires_grad:
                 continue
             a = self.offsets[i]
             b = self.offsets[i + 1] if i + 1 < len(self.params) else self.total

@@ -372,6 +372,24 @@ def linear(x, w, b, act, engine=None):
     return LinearFn.apply(x, act, engine, w, b)
 
 
+class ActivationFn(Function):
+    """act(x) element-wise with the function of the GEMM epilogues (ops.act_fwd / ops.act_bwd)."""
+
+    @staticmethod
+    def forward(ctx, x, act):
+        pre = x.detach().contiguous()
+        ctx.saved, ctx.act = pre, act
+        return ops.act_fwd(pre, act)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return ops.act_bwd(dy.contiguous(), ctx.saved, ctx.act), None
+
+
+def activation(x, act):
+    return x if act is None else ActivationFn.apply(x, act)
+
+
 def layer_norm(x, gamma, beta):
     return LayerNormFn.apply(x, gamma, beta)
 
@@ -820,6 +838,21 @@ class ZScoreFn(Function):
         return ops.zscore_bwd(_constant_pitch(dy), y, stats)
 
 
+class GroupedZScoreFn(Function):
+    """ZScoreFn over `groups` runs of consecutive leading entries, one set of statistics each (pa2d_zscore_grouped_*)."""
+
+    @staticmethod
+    def forward(ctx, x, groups):
+        y, stats = ops.zscore_grouped_fwd(_constant_pitch(x.detach()), groups)
+        ctx.saved = (y, stats)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        y, stats = ctx.saved
+        return ops.zscore_grouped_bwd(_constant_pitch(dy), y, stats), None
+
+
 class WideSliceWeightsFn(Function):
     """sw [..., M] = softmax((x . Ws^T + bs) / clamp(temperature, 0.1, 5)) for rows of 16..512 features
     (pa2d_wide_slice_weights_*); the weights are recomputed in the backward, never saved."""
@@ -848,8 +881,14 @@ def conv3x3(xn, H, W, w, b, engine=None):
     return Conv3x3Fn.apply(xn, H, W, engine, w, b)
 
 
-def zscore(x):
-    return ZScoreFn.apply(x)
+def zscore(x, groups=1):
+    """groups > 1: x.shape[0] is cut into `groups` runs of consecutive entries, each z-scored on its own (what `groups`
+    separate calls on those runs give, bit for bit, in one pair of launches); groups = 1 is the whole-tensor node."""
+    if groups == 1:
+        return ZScoreFn.apply(x)
+    if groups < 1 or x.dim() < 2 or x.shape[0] % groups:
+        raise ValueError(f"groups = {groups} must divide the leading dimension of {tuple(x.shape)}")
+    return GroupedZScoreFn.apply(x, groups)
 
 
 def wide_slice_weights(x, temperature, ws, bs):

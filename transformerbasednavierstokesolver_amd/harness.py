@@ -30,6 +30,9 @@ made (tests/golden/G14-G16, tools/make_golden_drivers.py):
   autoencoder_train_step        auto_encoder.py:166-181 (the auto-encoder reconstructs its own input fx)
   sequensolver_train_step       SequenSolver.py:572-606 (Tout teacher-forced calls of the latent sequence model, window slid
   / sequensolver_rollout        with the true frame, summed rel-L2, one backward, step) and :613-630 (prediction feedback)
+                                (fold_time=True: the Tout calls as ONE model.forward_windows call, every frame encoded once)
+  fit_autoencoder               auto_encoder.py:160-210, SequenSolver.py:572-640, SequenSolverMerged.py:454-523: the epoch
+  / fit_sequensolver            loops of the latent-sequence family on `_fit`, with the scripts' own metric divisors
   learnslice_train_step         LearnSlice.py:477-526 (slice weights from the frozen model's code: one optimizer step per frame)
   slice_predictor_train_step    LearnSlice.py:929-962 and :861-913 (the conv slice predictors: Tout summed terms and one step;
   / slice_predictor_rollout     the prediction-feedback evaluation)
@@ -542,7 +545,8 @@ def autoencoder_train_step(model, optimizer, scheduler, x, fx, max_grad_norm=Non
     return loss.detach()
 
 
-def sequensolver_train_step(model, optimizer, scheduler, x, fx, yy, use_gt=True, max_grad_norm=None, grad_sync=None):
+def sequensolver_train_step(model, optimizer, scheduler, x, fx, yy, use_gt=True, max_grad_norm=None, grad_sync=None,
+                            fold_time=False):
     """One SequenSolver.py:581-606 iteration of the latent sequence model (SequenSolver.SequenSolver): Tout = yy.shape[-1]
     teacher-forced calls model(x, fx, y, use_gt) on the window fx [B, N, T], which slides on with the TRUE frame y; the
     TestLoss(size_average=False) terms are summed, then zero_grad, one backward, [grad_sync], [clip], step, [scheduler].
@@ -551,19 +555,29 @@ def sequensolver_train_step(model, optimizer, scheduler, x, fx, yy, use_gt=True,
     gradient bucket.  With FusedAdamW pass `grad_sync=optimizer.sync` and put the clip threshold in the optimizer.
     The merged model (SequenSolverMerged.SequenSolver) has the same call signature and the same loop in its reference
     file, which runs it with use_gt=False (x is then the 64-wide unified encoding [B, N, 64]).
+    `fold_time`: the windows hold ground truth only, so the Tout calls do not depend on each other; True makes ONE
+    `model.forward_windows(x, cat(fx, yy), use_gt)` call (every frame encoded once, the blocks and the slice predictor on
+    Tout*B folded samples, per-call z-score statistics), the same per-call loss terms summed in call order and the same
+    full loss.  Teacher forcing only: `sequensolver_rollout` feeds predictions back and cannot fold.
     Returns (summed step loss [detached], full loss of the Tout predictions against yy)."""
     loss_fn = TestLoss(size_average=False)
     bsz = x.shape[0]
     with ops.weights_frozen():
         loss, preds = 0, []
-        for t in range(yy.shape[-1]):
-            y = yy[..., t:t + 1]
-            im = model(x, fx, y, use_gt=use_gt)
-            loss = loss + loss_fn(im.reshape(bsz, -1), y.reshape(bsz, -1))
-            preds.append(im)
-            fx = torch.cat((fx[..., 1:], y), dim=-1)             # the ground truth enters the window
+        if fold_time:
+            pred = model.forward_windows(x, torch.cat((fx, yy), dim=-1), use_gt=use_gt)      # [B, N, Tout]
+            for t in range(yy.shape[-1]):
+                loss = loss + loss_fn(pred[..., t].reshape(bsz, -1), yy[..., t].reshape(bsz, -1))
+        else:
+            for t in range(yy.shape[-1]):
+                y = yy[..., t:t + 1]
+                im = model(x, fx, y, use_gt=use_gt)
+                loss = loss + loss_fn(im.reshape(bsz, -1), y.reshape(bsz, -1))
+                preds.append(im)
+                fx = torch.cat((fx[..., 1:], y), dim=-1)             # the ground truth enters the window
+            pred = torch.cat(preds, -1)
         with torch.no_grad():
-            full = loss_fn(torch.cat(preds, -1).reshape(bsz, -1), yy.reshape(bsz, -1))
+            full = loss_fn(pred.reshape(bsz, -1), yy.reshape(bsz, -1))
         optimizer.zero_grad()
         loss.backward()
     _apply_step(optimizer, scheduler, (p for p in model.parameters() if p.requires_grad), max_grad_norm, grad_sync)
@@ -1162,3 +1176,126 @@ def fit_plas(model, optimizer, scheduler, data, *, epochs, batch_size, max_grad_
                 test_pass=lambda acc: _plas_test_pass(model, test, batch_size, positions, t, loss_fn, acc),
                 metrics=lambda a: dict(train_step=a[0] / ntrain / T, test_step=a[1] / ntest / T, test_full=a[2] / ntest),
                 on_epoch=on_epoch, save_path=save_path, save_every=save_every)
+
+
+# ------------------------------------------------------------------------------ latent-sequence family: epoch loops
+def fit_autoencoder(model, optimizer, scheduler, data, *, epochs, batch_size, ntrain, ntest, T=10, step=1, max_grad_norm=None,
+                    epoch_orders=None, generator=None, save_path=None, save_name=None, save_every=100, grad_sync=None,
+                    on_epoch=None):
+    """The epoch loop of auto_encoder.main() (auto_encoder.py:160-210) on `data` = data.split_ns_all_frames(...): every
+    frame of every trajectory is one sample [n*F, N, 1], and the loss of a batch is TestLoss(size_average=False) of
+    model(x, fx) against the input fx itself (`autoencoder_train_step`); the test pass is the same loss under no_grad.
+
+    Returns one dict per epoch with the script's metrics, unrounded and with ITS divisors (auto_encoder.py:199):
+    train_step = sum / ntrain / (T / step), test_step = sum / ntest / (T / step), where ntrain / ntest count TRAJECTORIES
+    (the script's globals), not frames.  One host synchronisation per epoch.  The state_dict is written when
+    ep % save_every == 0 (the script: 100) and after the last epoch, to `save_path`, or, as the script names it, to
+    sequential_checkpoints/<save_name>.pt.  `epoch_orders`, `generator`, `grad_sync`, `on_epoch` as fit_ns."""
+    from .data import ResidentDataset, grid_positions
+    if save_path is None and save_name is not None:
+        save_path = os.path.join("sequential_checkpoints", save_name + ".pt")
+    dev = _device_of(model)
+    train, test = ResidentDataset(data["train"], device=dev), ResidentDataset(data["test"], device=dev)
+    positions = _positions_cache(grid_positions(data["h"]).to(dev))
+    loss_fn, calls = TestLoss(size_average=False), T / step
+
+    def train_batch(batch, acc):
+        fx, = batch
+        acc[0] += autoencoder_train_step(model, optimizer, scheduler, positions(fx.shape[0]), fx, max_grad_norm=max_grad_norm,
+                                         grad_sync=grad_sync)
+
+    @torch.no_grad()
+    def test_pass(acc):
+        for fx, in test.batches(batch_size):
+            bsz = fx.shape[0]
+            acc[1] += loss_fn(model(positions(bsz), fx=fx).reshape(bsz, -1), fx.reshape(bsz, -1))
+
+    return _fit(model, epochs=epochs, n_acc=2, batches=lambda ep: _epoch_batches(train, batch_size, ep, epoch_orders, generator),
+                train_batch=train_batch, test_pass=test_pass,
+                metrics=lambda a: dict(train_step=a[0] / ntrain / calls, test_step=a[1] / ntest / calls),
+                on_epoch=on_epoch, save_path=save_path, save_every=save_every)
+
+
+# what the two reference files' train() loops differ in
+SEQUENSOLVER_LOOPS = {
+    # SequenSolver.py:572-640.  `if ep > 5: model.freeze_attention(); use_gt = False` sets a flag the calls never read: they
+    # pass use_gt=True throughout.  `test_l2_step += ...` and `test_l2_full = ...` (:629-630) stand AFTER the loop over the
+    # test batches, so both metrics are the LAST test batch's alone.
+    "plain": dict(train_use_gt=True, freeze_after=5, last_test_batch_only=True, first_frame=False),
+    # SequenSolverMerged.py:454-523: no freeze, both test sums accumulated, and the loss of the first predicted frame
+    "merged": dict(train_use_gt=False, freeze_after=None, last_test_batch_only=False, first_frame=True),
+}
+
+
+def fit_sequensolver(model, optimizer, scheduler, pos, train, test, *, epochs, batch_size=1, variant=None, Tin=None,
+                     fold_time=False, max_grad_norm=None, epoch_orders=None, generator=None, save_path=None, save_every=None,
+                     grad_sync=None, on_epoch=None, **loop):
+    """The epoch loop of the reference's SequenSolver.py / SequenSolverMerged.py train().  `pos` [1, N, P]: the point input of
+    every sample (the coordinates, or the 64 unified distances); `train` / `test`: data.ResidentDataset of (fx [n, N, Tin],
+    yy [n, N, Tout]) on the model's device.  `variant` "plain" | "merged" picks SEQUENSOLVER_LOOPS (default: by the model's
+    class); single entries can be overridden by keyword.
+
+    Each epoch: model.train(); from ep > freeze_after on, model.freeze_attention() (the frozen tensors then stop moving
+    with torch.optim.AdamW, whose zero_grad leaves them without a gradient, and with optim.FusedAdamW, whose active ranges
+    leave out parameters that no longer require a gradient); shuffled batches through `sequensolver_train_step(use_gt=
+    train_use_gt, fold_time=fold_time)`; model.eval() and `sequensolver_rollout(use_gt=True)` (prediction feedback) on
+    every test batch.
+
+    Returns one dict per epoch, divided as the scripts divide: train_step = sum / ntrain / Tin, train_full = sum / ntrain,
+    test_step = sum / ntest / Tin, test_full = sum / ntest (+ test_first = the first predicted frame's loss / ntest with
+    first_frame).  With last_test_batch_only the two test sums are the last test batch's alone, as the plain script
+    computes them.  One host synchronisation per epoch.  The scripts save once, after the last epoch: `save_every` None
+    does that; `epoch_orders`, `generator`, `grad_sync`, `on_epoch`, `save_path` as fit_ns."""
+    if variant is None:
+        variant = "merged" if hasattr(model, "sequential_head") else "plain"
+    unknown = set(loop) - set(SEQUENSOLVER_LOOPS[variant])
+    if unknown:
+        raise TypeError(f"fit_sequensolver got unexpected keywords {sorted(unknown)}")
+    cfg = dict(SEQUENSOLVER_LOOPS[variant], **loop)
+    ntrain, ntest = len(train), len(test)
+    Tin = model.T if Tin is None else Tin
+    positions = _positions_cache(pos.to(_device_of(model)))
+    loss_fn = TestLoss(size_average=False)
+
+    def batches(ep):
+        if cfg["freeze_after"] is not None and ep > cfg["freeze_after"]:
+            model.freeze_attention()
+        return _epoch_batches(train, batch_size, ep, epoch_orders, generator)
+
+    def train_batch(batch, acc):
+        fx, yy = batch
+        loss, full = sequensolver_train_step(model, optimizer, scheduler, positions(fx.shape[0]), fx, yy,
+                                             use_gt=cfg["train_use_gt"], max_grad_norm=max_grad_norm, grad_sync=grad_sync,
+                                             fold_time=fold_time)
+        acc[0] += loss
+        acc[1] += full
+
+    @torch.no_grad()
+    def test_pass(acc):
+        last = None
+        for fx, yy in test.batches(batch_size):
+            bsz = fx.shape[0]
+            pred, loss, full = sequensolver_rollout(model, positions(bsz), fx, yy, use_gt=True)
+            last = (loss, full)
+            if not cfg["last_test_batch_only"]:
+                acc[2] += loss
+                acc[3] += full
+            if cfg["first_frame"]:
+                acc[4] += loss_fn(pred[..., 0].reshape(bsz, -1), yy[..., 0].reshape(bsz, -1))
+        if cfg["last_test_batch_only"] and last is not None:
+            acc[2] += last[0]
+            acc[3] += last[1]
+
+    def metrics(a):
+        m = dict(train_step=a[0] / ntrain / Tin, train_full=a[1] / ntrain, test_step=a[2] / ntest / Tin,
+                 test_full=a[3] / ntest)
+        if cfg["first_frame"]:
+            m["test_first"] = a[4] / ntest
+        return m
+
+    history = _fit(model, epochs=epochs, n_acc=5, batches=batches, train_batch=train_batch, test_pass=test_pass,
+                   metrics=metrics, on_epoch=on_epoch, save_path=save_path if save_every is not None else None,
+                   save_every=save_every)
+    if save_path is not None and save_every is None:
+        _save_state(model, save_path)
+    return history

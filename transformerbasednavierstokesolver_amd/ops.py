@@ -977,6 +977,43 @@ def zscore_bwd(dy, y, stats):
     return dx
 
 
+def _group_rows(rows, groups):
+    if groups < 1 or rows % groups:
+        raise ValueError(f"groups = {groups} must divide the {rows} rows")
+    return rows // groups
+
+
+def zscore_grouped_fwd(x, groups):
+    """The z-score of zscore_fwd over `groups` groups of consecutive rows of x [..., C], each with its own statistics, in
+    one pair of launches; returns (y contiguous, stats fp64 [groups, 2] = mu, sigma).  Group g equals zscore_fwd on its rows
+    alone, bit for bit."""
+    rows, Cc, ldx = _rows_view(x)
+    rpg = _group_rows(rows, groups)
+    y = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    stats = torch.empty(groups, 2, dtype=torch.float64, device=x.device)
+    nb = _L().pa2d_zscore_grouped_workspace(groups, rpg, Cc)
+    ws = _ws(nb, x)
+    _lib.check(_L().pa2d_zscore_grouped_fwd(_p(x), ldx, _p(y), _p(stats), ws.data_ptr(), nb, groups, rpg, Cc, _stream()),
+               "zscore_grouped_fwd")
+    return y, stats
+
+
+def zscore_grouped_bwd(dy, y, stats):
+    """dx (contiguous) from dy (rows may be strided), the grouped forward's y and statistics [groups, 2]."""
+    _chk(y)
+    rows, Cc, lddy = _rows_view(dy)
+    if dy.shape != y.shape or stats.dtype != torch.float64 or stats.dim() != 2 or stats.shape[1] != 2:
+        raise ValueError("need dy of y's shape and the grouped forward's fp64 statistics [groups, 2]")
+    groups = stats.shape[0]
+    rpg = _group_rows(rows, groups)
+    dx = torch.empty(y.shape, dtype=torch.float32, device=y.device)
+    nb = _L().pa2d_zscore_grouped_workspace(groups, rpg, Cc)
+    ws = _ws(nb, y)
+    _lib.check(_L().pa2d_zscore_grouped_bwd(_p(dy), lddy, _p(y), _p(stats), _p(dx), Cc, ws.data_ptr(), nb, groups, rpg, Cc,
+                                            _stream()), "zscore_grouped_bwd")
+    return dx
+
+
 def wide_slice_weights_fwd(x, ws_w, bs, temperature, clamp=True):
     """x [..., D] (rows may be strided) -> sw [..., M] = softmax_m((x . ws^T + bs) / t), t = temperature (one scalar)."""
     _chk(ws_w, bs, temperature)
@@ -1069,6 +1106,13 @@ def act_bwd(dy, pre, act):
     _chk(dy, pre)
     out = torch.empty_like(dy)
     _lib.check(_L().pa2d_act_bwd(_p(dy), _p(pre), _p(out), dy.numel(), ACT_IDS[act], _stream()), "act_bwd")
+    return out
+
+
+def act_fwd(pre, act):
+    _chk(pre)
+    out = torch.empty_like(pre)
+    _lib.check(_L().pa2d_act_fwd(_p(pre), _p(out), pre.numel(), ACT_IDS[act], _stream()), "act_fwd")
     return out
 
 
