@@ -525,6 +525,26 @@ int pa2d_embed_bias_fwd(const float* h, const float* placeholder, const float* t
 int pa2d_embed_bias_bwd(const float* dz, float* dplaceholder, float* dtvec, void* ws, size_t ws_bytes, int B, int N,
                         int C, pa2d_stream_t stream);
 
+/* ==== first layer of the previous-slice predictor (reference LearnSlice.py:125-134: the MLP over
+ * cat(slice weights [M], flattened code [M C]); the concatenation is never formed).
+ *   h0[b, n, :] = act( sum_m sw[b, n, m] wsw[:, m] + tb[b, :] )
+ * sw [B, N, M] slice weights (data), wsw [H, M] the first M columns of the layer's weight (contiguous), tb [B, H] the
+ * per-sample row code[b] . Wtok^T + bias (a row GEMM of the caller), h0 [B, N, H]; act: the activation id of the GEMM
+ * epilogues.  Exact fp32 FMAs, m ascending from tb.  One launch for any B.
+ * bwd: recomputes the pre-activation from sw, wsw, tb; dpre = dh0 act'(pre);
+ *   dwsw[h, m] = sum_{b, n} dpre[b, n, h] sw[b, n, m],   dtb[b, h] = sum_n dpre[b, n, h]
+ * by one partial record per (sample, chunk of rows) and a fixed-order finish (two calls give the same bits; no float
+ * atomics).  Both outputs are overwritten (zero-filled when B N == 0).  ws: pa2d_prev_slice_entry_workspace bytes.
+ * M outside 1..64 or H % 4 != 0: PA2D_ERR_UNSUPPORTED; so is any tensor of 4 GiB or more (the buffer addressing covers
+ * 32 bits) and B * ceil(N / 64) > 262140.  NULL pointers (with B N > 0) and wsw, tb, h0, dh0, ws not 16-byte aligned:
+ * PA2D_ERR_ARG. */
+size_t pa2d_prev_slice_entry_workspace(int B, int N, int M, int H);
+int pa2d_prev_slice_entry_fwd(const float* sw, const float* wsw, const float* tb, float* h0, int B, int N, int M, int H,
+                              int act, pa2d_stream_t stream);
+int pa2d_prev_slice_entry_bwd(const float* dh0, const float* sw, const float* wsw, const float* tb, float* dwsw,
+                              float* dtb, void* ws, size_t ws_bytes, int B, int N, int M, int H, int act,
+                              pa2d_stream_t stream);
+
 /* ==== operand-planes interface of the bf16 engines (fp32 storage; PA2D_ENGINE_SPLIT: 3 planes, PA2D_ENGINE_BF16: 1).
  * The conv GEMMs of these engines stage their activation operand as a bf16 plane image [row][C/32][NT][32].  By default
  * pa2d_conv3x3x2_fwd/bwd make it from the fp32 tensor in a pre-pass; with the entry points below the PRODUCER of the

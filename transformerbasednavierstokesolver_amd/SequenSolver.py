@@ -256,6 +256,37 @@ class SequenSolver(nn.Module):
         out = outs[0] if len(outs) == 1 else torch.cat(outs, 0)
         return out.permute(1, 2, 0)
 
+    def code_windows(self, spatial_pos, seq):
+        """Everything the slice trainers take from this frozen model for the n = seq.shape[-1] - T teacher-forced calls of
+        an iteration, computed ONCE: seq [B, N, T + n] holds TRUE frames.  One `encode_table(..., T + n, want_slices=True)`
+        pass encodes every frame once, and the blocks run on the folded windows (cut by `fold_calls`, as
+        `forward_windows`); all under no_grad and ops.weights_frozen().  Returns
+
+          codes  [n, B, 1, M, C]   codes[k] is what get_code(spatial_pos, seq[..., k:k+T], .) returns;
+          slices [(T + n) * B, 1, N, M]   the encoder's slice weights of every frame, frame-major: frame f is the block
+                                   slices[f*B:(f+1)*B].
+
+        Call k reads its code codes[k], its target (the slice weights of frame T + k) and its previous slice (frame
+        T + k - 1: what get_last_slice_weight gives on window k).  The encoder's cached slice weights are left as the eager
+        loops' last call leaves them (the last window's last frame, T + n - 2); `code` and `slice_weights`, which those
+        loops never write, are not touched."""
+        self._refuse()
+        B, T = seq.shape[0], self.T
+        n = seq.shape[-1] - T
+        if n < 1:
+            raise ValueError(f"code_windows needs seq [B, N, T + n] with n >= 1; got {tuple(seq.shape)} at T = {T}")
+        with torch.no_grad(), ops.weights_frozen():
+            tokens, slices = encode_table(self, spatial_pos, seq, T + n, want_slices=True)
+            ratio = self.mlp.linear_pre[0].weight.shape[0] / self.dim
+            group = fold_calls(n, B, self.N, T, max(self.M, self.C + 2, WEIGHT_PROJECTION_HIDDEN), int(ratio * self.dim))
+            codes = []
+            for k0 in range(0, n, group):
+                g = min(group, n - k0)
+                win = torch.cat([tokens[:, :, k:k + T] for k in range(k0, k0 + g)], 0)   # [g*B, Head, T, dim], call-major
+                codes.append(self._code(self._blocks(win)).reshape(g, B, self.Head, self.M, self.C))
+            self.encoder.set_attention_slice(slices[(T + n - 2) * B:(T + n - 1) * B].contiguous())
+        return (codes[0] if len(codes) == 1 else torch.cat(codes, 0)), slices
+
     def solve_with_slice_learner(self, slice_learner_path, spatial_pos, fx, y, unified_pos=0, use_vorticity=0,
                                  use_previous_slice=False, learn_from_vort=False, use_code_for_vorticity=False, *,
                                  decode_with_learned=False):

@@ -178,6 +178,12 @@ class VorticitySliceLearner(_EngineMixin, nn.Module):
         self.temperature = nn.Parameter(torch.ones([1, 1, 1, 1]) * 0.5)
 
     def forward(self, x, fx, code=None):
+        return self.forward_folded(x, fx, code, 1)
+
+    def forward_folded(self, x, fx, code=None, groups=1):
+        """forward on a batch that holds `groups` independent calls of B / groups consecutive samples each (a time-folded
+        iteration): the z-scores stay per call (code_conditioned_slice_weights).  groups = 1 is forward itself, the call as
+        it was.  (A method of its own, not a keyword of forward, whose parameter list is the reference's.)"""
         if fx is None:
             raise ValueError("forward_from_vorticity needs fx: the reference's fx=None path reads a placeholder that its "
                              "LearnSlice never creates")
@@ -185,7 +191,70 @@ class VorticitySliceLearner(_EngineMixin, nn.Module):
             raise ValueError(f"built with use_code_for_vorticity={self.use_code_for_vorticity}: in_project_slice takes "
                              f"{self.concatenated} features, so the code must be " +
                              ("given" if self.use_code_for_vorticity else "None"))
-        return code_conditioned_slice_weights(x, fx, code, self.preprocess, self.in_project_x, self.in_project_slice,
-                                              self.temperature, self.H, self.W, self.M, self.C, self.engine)
+        args = (x, fx, code, self.preprocess, self.in_project_x, self.in_project_slice, self.temperature, self.H, self.W,
+                self.M, self.C, self.engine)
+        if groups == 1:         # the call as it was, argument list included: tests/test_sequensolver_merged_host.py replaces
+            #                     the function by a stand-in of the former signature, which has no `groups`
+            return code_conditioned_slice_weights(*args)
+        return code_conditioned_slice_weights(*args, groups=groups)
 
     forward_from_vorticity = forward
+
+
+# PreviousSliceLearner takes the fused first layer (functional.prev_slice_entry, pa2d_prev_slice_entry_*) by default only if
+# its measured median lies outside the three-op route's range at n*B = 10 folded samples (the rule of DESIGN 4.17).
+# Measured on the MI355X, forward plus backward, ms, median (min .. max) of 9: three-op 1.045 (1.038 .. 1.056), fused
+# 0.451 (0.444 .. 0.458): outside, below.  `fused_entry = False` on a module selects the three-op route.
+FUSED_ENTRY_DEFAULT = True
+
+
+class PreviousSliceLearner(_EngineMixin, nn.Module):
+    """The previous-slice predictor: forward(prev_slice_weight, token) is the reference's `LearnSlice.forward_previous_slice`
+    (LearnSlice.py:125-134).  prev_slice_weight [B, 1, N, M] (the encoder's slice weights of the window's last frame, data),
+    token [B, 1, M, C] (the code) -> the RAW output of `weight_projection_form_slice` [B, 1, N, M]: no softmax, as in the
+    reference.  Any B (the reference's reshape is B = 1).
+
+    The sub-module carries the reference's name, `weight_projection_form_slice = MLP(M + M C, 4 (M + M C), M, 1)`, so a
+    reference LearnSlice state_dict loads with strict=False and no missing key.  Initialisation is PyTorch's default, as in
+    the reference.  C, M and act (keyword-only; the reference hard-codes 32, 16 and 'gelu') are the extension.
+
+    The [B, N, M + M C] concatenation is never formed.  The first M columns of linear_pre's weight multiply the point's
+    slice weights; the other M C columns multiply the flattened token, in (m, c) order, which is the same for all N points:
+        h0 = act(sw . Wsw^T + tb[b]),   tb = token.reshape(B, M C) . Wtok^T + bias    [B, H], H = 4 (M + M C)
+        h1 = act(h0 . W1^T + b1) + h0,  out = h1 . Wpost^T + bpost
+    tb and the two later layers are functional.linear on this module's engine; h0 is functional.prev_slice_entry:
+    `fused_entry` True takes the fused kernels (exact fp32; one launch forward), False the row GEMM + broadcast add + activation."""
+
+    def __init__(self, *, C=32, M=16, act='gelu'):
+        super().__init__()
+        self.C, self.M = C, M
+        self.engine = None
+        self.fused_entry = FUSED_ENTRY_DEFAULT
+        self.concatenated = M + M * C                                                     # reference :66
+        self.weight_projection_form_slice = MLP(self.concatenated, self.concatenated * 4, M, 1, act=act)
+
+    def forward(self, prev_slice_weight, token):
+        _refuse_bf16_storage(self.engine)
+        M, C = self.M, self.C
+        if prev_slice_weight.dim() != 4 or prev_slice_weight.shape[1] != 1 or prev_slice_weight.shape[-1] != M:
+            raise ValueError(f"need the previous slice weights [B, 1, N, M = {M}]; got {tuple(prev_slice_weight.shape)}")
+        B, _, N, _ = prev_slice_weight.shape
+        if token.numel() != B * M * C:
+            raise ValueError(f"need a token [B, 1, M, C] = {(B, 1, M, C)}; got {tuple(token.shape)}")
+        mlp = self.weight_projection_form_slice
+        first, hidden, last = mlp.linear_pre[0], mlp.linears[0][0], mlp.linear_post
+        act, eng = mlp.act_name, self.engine
+        # the two column blocks of the first layer's weight are cut out once per forward
+        wsw, wtok = first.weight[:, :M].contiguous(), first.weight[:, M:]
+        tok = token.reshape(B, M * C)
+        pad = (-M * C) % 4                       # the row GEMM loads 16 bytes at a time along the contraction
+        if pad:
+            tok, wtok = nn.functional.pad(tok, (0, pad)), nn.functional.pad(wtok, (0, pad))
+        tb = Fn.linear(tok, wtok.contiguous(), first.bias, None, engine=eng)                  # [B, H]
+        h0 = Fn.prev_slice_entry(prev_slice_weight.reshape(B, N, M), wsw, tb, act, fused=self.fused_entry, engine=eng)
+        y = Fn.linear(h0, hidden.weight, hidden.bias, act, engine=eng)
+        h1 = y + h0 if mlp.res else y
+        out = Fn.linear(h1, last.weight, last.bias, None, engine=eng)
+        return out.reshape(B, 1, N, M)
+
+    forward_previous_slice = forward

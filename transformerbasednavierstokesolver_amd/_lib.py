@@ -126,6 +126,9 @@ SIGNATURES = {
     "pa2d_rel_l2_affine_bwd": (_i, [_f, _f, _ll, _ll, _f, _f, _f, _f, _f, _f, _i, _ll, _st]),
     "pa2d_embed_bias_fwd": (_i, [_f, _f, _f, _f, _i, _i, _i, _st]),
     "pa2d_embed_bias_bwd": (_i, [_f, _f, _f, _f, _sz, _i, _i, _i, _st]),
+    "pa2d_prev_slice_entry_workspace": (_sz, [_i, _i, _i, _i]),
+    "pa2d_prev_slice_entry_fwd": (_i, [_f, _f, _f, _f, _i, _i, _i, _i, _i, _st]),
+    "pa2d_prev_slice_entry_bwd": (_i, [_f, _f, _f, _f, _f, _f, _f, _sz, _i, _i, _i, _i, _i, _st]),
 }
 REL_L2_AFFINE_SPLIT = 64     # PA2D_REL_L2_AFFINE_SPLIT
 EMBED_BIAS_CHUNKS = 64       # PA2D_EMBED_BIAS_CHUNKS

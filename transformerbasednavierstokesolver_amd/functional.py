@@ -894,3 +894,43 @@ def zscore(x, groups=1):
 def wide_slice_weights(x, temperature, ws, bs):
     """x [..., D] -> [..., M]; temperature holds one scalar (any shape), clamped to [0.1, 5]."""
     return WideSliceWeightsFn.apply(x, temperature, ws, bs)
+
+
+class PrevSliceEntryFn(Function):
+    """h0 = act(sw . wsw^T + tb[:, None, :]) in one launch (ops.prev_slice_entry_fwd): the first layer of the previous-slice
+    predictor.  Backward (ops.prev_slice_entry_bwd): one kernel (M > 16: ceil(M / 16) grid slices of it, each reading dh0) and
+    the two fixed-order sums of its partial records.  The backward recomputes the pre-activation; gradients of wsw and tb only (sw is data)."""
+
+    @staticmethod
+    def forward(ctx, sw, wsw, tb, act):
+        sw, wsw, tb = sw.detach().contiguous(), wsw.detach().contiguous(), tb.detach().contiguous()
+        ctx.saved, ctx.act = (sw, wsw, tb), act
+        return ops.prev_slice_entry_fwd(sw, wsw, tb, act)
+
+    @staticmethod
+    def backward(ctx, dh0):
+        sw, wsw, tb = ctx.saved
+        src = dh0.contiguous()
+        if src.data_ptr() % 16:          # a view at an odd offset: the kernel reads 16 bytes at a time
+            src = src.clone()
+        dwsw, dtb = ops.prev_slice_entry_bwd(src, sw, wsw, tb, ctx.act)
+        return None, dwsw, dtb, None
+
+
+def prev_slice_entry(sw, wsw, tb, act, fused=True, engine=None):
+    """First layer of the previous-slice predictor without the [B, N, M + M C] concatenation: sw [B, N, M] (the points'
+    slice weights, data), wsw [H, M] (the weight columns that multiply them), tb [B, H] (the code columns' product plus the
+    bias, one row per sample) -> act(sw . wsw^T + tb[b]) [B, N, H].
+    fused=True: pa2d_prev_slice_entry_* (one launch forward; one kernel and two record sums backward), exact fp32.  fused=False: the three-op route the other
+    predictors take for a per-sample row — the row GEMM on `engine`, the broadcast add, the activation."""
+    if sw.requires_grad:
+        raise ValueError("prev_slice_entry takes the slice weights as data: no gradient flows to `sw` "
+                         "(detach it, as the trainers' frozen encoder does)")
+    if fused:
+        return PrevSliceEntryFn.apply(sw, wsw, tb, act)
+    rem = wsw.shape[1] % 4                      # the GEMMs load 16 bytes at a time along the contraction
+    if rem:
+        sw, wsw = torch.nn.functional.pad(sw, (0, 4 - rem)), torch.nn.functional.pad(wsw, (0, 4 - rem))
+    if tb.shape[-1] % 4:
+        raise NotImplementedError(f"prev_slice_entry needs a hidden width that is a multiple of 4; got {tb.shape[-1]}")
+    return activation(embed_bias(linear(sw, wsw, None, None, engine=engine), None, tb), act)

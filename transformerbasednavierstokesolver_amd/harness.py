@@ -584,8 +584,32 @@ def sequensolver_train_step(model, optimizer, scheduler, x, fx, yy, use_gt=True,
     return loss.detach(), full
 
 
+def _fold_table(sequen_solver, x, fx, yy):
+    """The frozen sequence model's part of a teacher-forced slice-trainer iteration, computed once
+    (`SequenSolver.code_windows` on the T + Tout true frames): (seq [B, N, T + Tout], codes [Tout, B, 1, M, C],
+    slices [(T + Tout) * B, 1, N, M] frame-major).  Call k: code codes[k], target frame T + k, previous slice frame
+    T + k - 1, window seq[..., k:k+T]."""
+    if fx.shape[-1] != sequen_solver.T:
+        raise ValueError(f"the window holds {fx.shape[-1]} frames; the sequence model reads T = {sequen_solver.T}")
+    seq = torch.cat((fx, yy), dim=-1)
+    codes, slices = sequen_solver.code_windows(x, seq)
+    return seq, codes, slices
+
+
+def _slice_fold_group(model, ncalls, bsz, npoints):
+    """How many calls of a slice predictor fit in ONE folded forward: its widest per-point row (the previous-slice
+    predictor's 4 (M + M C) hidden layer; the conv predictors' preprocess hidden 2 n_hidden or first-layer input) times
+    the folded row count stays under the 4 GiB extent of a buffer descriptor (SequenSolver.fold_calls)."""
+    from .SequenSolver import fold_calls
+    if hasattr(model, "weight_projection_form_slice"):
+        width = model.weight_projection_form_slice.n_hidden
+    else:
+        width = max(2 * model.n_hidden, getattr(model, "concatenated", model.n_hidden))
+    return fold_calls(ncalls, bsz, npoints, 1, width, 1)
+
+
 def learnslice_train_step(model, optimizer, scheduler, sequen_solver, x, fx, yy, use_vorticity, max_grad_norm=None,
-                          grad_sync=None):
+                          grad_sync=None, fold_time=False):
     """The LearnSlice.py:477-526 loop over one batch: for each of the Tout = yy.shape[-1] output frames y, the target is
     the frozen encoder's slice weights of y, the code comes from `sequen_solver.get_code` on the window fx [B, N, T]
     (no gradient: the sequence model is frozen), the loss is functional.slice_mse of
@@ -593,8 +617,23 @@ def learnslice_train_step(model, optimizer, scheduler, sequen_solver, x, fx, yy,
     F.mse_loss), then zero_grad, backward, [grad_sync], [clip], step, [scheduler]: ONE optimizer step PER FRAME, and the
     window slides on with the true frame.  The reference makes N calls of the MLP per step; here a step is one forward and
     one backward launch.  Works with torch.optim.AdamW and with `optim.FusedAdamW` (pass `grad_sync=optimizer.sync`).
+    `fold_time=True`: targets and codes of all Tout frames come from ONE `sequen_solver.code_windows` call (every frame
+    encoded once); the optimizer still steps once per frame, on window k = cat(fx, yy)[..., k:k+T].
     Returns the list of the Tout detached step losses."""
     losses = []
+    params = lambda: (p for p in model.parameters() if p.requires_grad)
+    if fold_time:
+        T, B = fx.shape[-1], x.shape[0]
+        with ops.weights_frozen():
+            seq, codes, slices = _fold_table(sequen_solver, x, fx, yy)
+            for k in range(yy.shape[-1]):
+                target = slices[(T + k) * B:(T + k + 1) * B]
+                loss = Fn.slice_mse(model.get_slice_weight(codes[k], x, seq[..., k:k + T], use_vorticity=use_vorticity), target)
+                optimizer.zero_grad()
+                loss.backward()
+                _apply_step(optimizer, scheduler, params(), max_grad_norm, grad_sync)
+                losses.append(loss.detach())
+        return losses
     with ops.weights_frozen():            # the sequence model's weights; LearnSlice's go through no packed GEMM
         for t in range(yy.shape[-1]):
             y = yy[..., t:t + 1]
@@ -622,28 +661,121 @@ def _predict_slices(model, sequen_solver, x, fx):
     return model(x, fx), code
 
 
-def slice_predictor_train_step(model, optimizer, scheduler, sequen_solver, x, fx, yy, max_grad_norm=None, grad_sync=None):
+def _folded_terms(pred, target, ncalls):
+    """sum over the calls, in call order, of F.mse_loss(pred of call k, target of call k): pred, target [ncalls*B, 1, N, M]
+    call-major."""
+    B = pred.shape[0] // ncalls
+    loss = 0
+    for k in range(ncalls):
+        loss = loss + Fn.slice_mse(pred[k * B:(k + 1) * B], target[k * B:(k + 1) * B]) / (B * pred.shape[2])
+    return loss
+
+
+def slice_predictor_train_step(model, optimizer, scheduler, sequen_solver, x, fx, yy, max_grad_norm=None, grad_sync=None,
+                               fold_time=False):
     """One LearnSlice.py:929-962 iteration (train_from_vorticity) of a conv slice predictor (SliceLearner.SliceLearner or
     SliceLearner.VorticitySliceLearner): for each of the Tout = yy.shape[-1] output frames y, the target is the frozen
     encoder's slice weights of y, the code comes from `sequen_solver.get_code` on the window fx [B, N, T] (no gradient), the
     term is F.mse_loss(model's slice weights, target) (the mean over ALL elements: functional.slice_mse scaled by 1 / (B N)),
     and the window slides on with the true frame; the Tout terms are summed, then zero_grad, ONE backward, [grad_sync],
     [clip], step, [scheduler].  Works with torch.optim.AdamW and with `optim.FusedAdamW` (pass `grad_sync=optimizer.sync`).
-    Returns the detached summed loss."""
+    `fold_time=True`: the windows hold ground truth only, so everything frozen comes from ONE `sequen_solver.code_windows`
+    call and the predictor runs ONE forward on the Tout*B folded samples, call-major (cut where a folded tensor would pass
+    the 4 GiB extent); the code-conditioned predictor's z-scores stay per call (`groups`).  The same terms, summed in call
+    order.  Returns the detached summed loss."""
     loss = 0
     with ops.weights_frozen():
-        for t in range(yy.shape[-1]):
-            y = yy[..., t:t + 1]
-            with torch.no_grad():
-                sequen_solver.encoder.encode(x, y)
-                target = sequen_solver.encoder.get_attention_slice()
-            pred, _ = _predict_slices(model, sequen_solver, x, fx)
-            loss = loss + Fn.slice_mse(pred, target) / (pred.shape[0] * pred.shape[2])
-            fx = torch.cat((fx[..., 1:], y), dim=-1)             # the ground truth enters the window
+        if fold_time:
+            T, B, n = fx.shape[-1], x.shape[0], yy.shape[-1]
+            seq, codes, slices = _fold_table(sequen_solver, x, fx, yy)
+            group = _slice_fold_group(model, n, B, x.shape[1])
+            for k0 in range(0, n, group):
+                g = min(group, n - k0)
+                wins = torch.cat([seq[..., k:k + T] for k in range(k0, k0 + g)], 0)            # [g*B, N, T], call-major
+                xs = x.repeat(g, *([1] * (x.dim() - 1)))
+                if hasattr(model, "use_code_for_vorticity"):
+                    code = codes[k0:k0 + g].reshape(g * B, *codes.shape[2:]) if model.use_code_for_vorticity else None
+                    pred = model.forward_folded(xs, wins, code, groups=g)
+                else:
+                    pred = model(xs, wins)
+                loss = loss + _folded_terms(pred, slices[(T + k0) * B:(T + k0 + g) * B], g)
+        else:
+            for t in range(yy.shape[-1]):
+                y = yy[..., t:t + 1]
+                with torch.no_grad():
+                    sequen_solver.encoder.encode(x, y)
+                    target = sequen_solver.encoder.get_attention_slice()
+                pred, _ = _predict_slices(model, sequen_solver, x, fx)
+                loss = loss + Fn.slice_mse(pred, target) / (pred.shape[0] * pred.shape[2])
+                fx = torch.cat((fx[..., 1:], y), dim=-1)             # the ground truth enters the window
         optimizer.zero_grad()
         loss.backward()
     _apply_step(optimizer, scheduler, (p for p in model.parameters() if p.requires_grad), max_grad_norm, grad_sync)
     return loss.detach()
+
+
+def previous_slice_train_step(model, optimizer, scheduler, sequen_solver, x, fx, yy, max_grad_norm=None, grad_sync=None,
+                              fold_time=False):
+    """One LearnSlice.py:722-755 iteration (train_from_previous) of SliceLearner.PreviousSliceLearner: for each of the
+    Tout = yy.shape[-1] output frames y, the target is the frozen encoder's slice weights of y, the code comes from
+    `sequen_solver.get_code` on the window fx [B, N, T], the previous slice is the encoder's slice weights of the window's
+    LAST frame (`get_last_slice_weight`), the term is F.mse_loss(model(previous slice, code), target) (functional.slice_mse
+    scaled by 1 / (B N)), and the window slides on with the true frame; the Tout terms are summed, then zero_grad, ONE
+    backward, [grad_sync], [clip], step, [scheduler].
+    `fold_time=True`: targets, codes and previous slices come from ONE `sequen_solver.code_windows` call (previous slice of
+    call k = frame T + k - 1 of its table) and the predictor runs ONE forward on the Tout*B folded samples, call-major; the
+    same terms, summed in call order.  Returns the detached summed loss."""
+    loss = 0
+    with ops.weights_frozen():
+        if fold_time:
+            T, B, n = fx.shape[-1], x.shape[0], yy.shape[-1]
+            _, codes, slices = _fold_table(sequen_solver, x, fx, yy)
+            group = _slice_fold_group(model, n, B, x.shape[1])
+            for k0 in range(0, n, group):
+                g = min(group, n - k0)
+                pred = model(slices[(T - 1 + k0) * B:(T - 1 + k0 + g) * B], codes[k0:k0 + g].reshape(g * B, *codes.shape[2:]))
+                loss = loss + _folded_terms(pred, slices[(T + k0) * B:(T + k0 + g) * B], g)
+        else:
+            for t in range(yy.shape[-1]):
+                y = yy[..., t:t + 1]
+                with torch.no_grad():
+                    sequen_solver.encoder.encode(x, y)
+                    target = sequen_solver.encoder.get_attention_slice()
+                    code = sequen_solver.get_code(x, fx, y)
+                    prev = sequen_solver.get_last_slice_weight(x, fx)
+                new_slice = model(prev, code)
+                loss = loss + Fn.slice_mse(new_slice, target) / (new_slice.shape[0] * new_slice.shape[2])
+                fx = torch.cat((fx[..., 1:], y), dim=-1)             # the ground truth enters the window
+        optimizer.zero_grad()
+        loss.backward()
+    _apply_step(optimizer, scheduler, (p for p in model.parameters() if p.requires_grad), max_grad_norm, grad_sync)
+    return loss.detach()
+
+
+def _decode_step(sequen_solver, slice_weights, code):
+    """The rollouts' feedback: decode `code` with `slice_weights` (left in sequen_solver.slice_weights) and apply
+    mlp2(ln_3(.)) -> [B, N, 1]."""
+    sequen_solver.slice_weights = slice_weights.contiguous()
+    decoded = sequen_solver.decode(code)
+    return Fn.head(Fn.layer_norm(decoded, sequen_solver.ln_3.weight, sequen_solver.ln_3.bias),
+                   sequen_solver.mlp2.weight, sequen_solver.mlp2.bias)
+
+
+@torch.no_grad()
+def previous_slice_rollout(model, sequen_solver, x, fx, nsteps):
+    """The evaluation loop of train_from_previous (LearnSlice.py:663-706) without its prints and plots: every step takes the
+    code of the frozen sequence model on the window fx [B, N, T], the encoder's slice weights of the window's last frame,
+    the predictor's RAW output for them, decodes the code with THAT output (set as sequen_solver.slice_weights), applies
+    mlp2(ln_3(.)) and feeds the prediction back into the window.  No ground truth is used.  Returns [B, N, nsteps]."""
+    preds = []
+    with ops.weights_frozen():
+        for _ in range(nsteps):
+            code = sequen_solver.get_code(x, fx, None)
+            prev = sequen_solver.get_last_slice_weight(x, fx)
+            pred = _decode_step(sequen_solver, model(prev, code), code)
+            preds.append(pred)
+            fx = torch.cat((fx[..., 1:], pred), dim=-1)
+    return torch.cat(preds, -1)
 
 
 @torch.no_grad()
@@ -1299,3 +1431,118 @@ def fit_sequensolver(model, optimizer, scheduler, pos, train, test, *, epochs, b
     if save_path is not None and save_every is None:
         _save_state(model, save_path)
     return history
+
+
+# ------------------------------------------------------------------------------ slice learners: epoch loops
+SLICE_LEARNER_KINDS = ("learnslice", "vorticity", "previous")
+
+
+def slice_learner_kind(model):
+    """The trainer a slice learner belongs to, by its class: LearnSlice.LearnSlice -> "learnslice" (train, :472-588),
+    SliceLearner.SliceLearner / VorticitySliceLearner -> "vorticity" (train_from_vorticity, :924-1006),
+    SliceLearner.PreviousSliceLearner -> "previous" (train_from_previous, :717-793)."""
+    if hasattr(model, "weight_projection_form_slice"):
+        return "previous"
+    if hasattr(model, "in_project_x"):
+        return "vorticity"
+    if hasattr(model, "weight_projection"):
+        return "learnslice"
+    raise TypeError(f"{type(model).__name__} is none of the slice learners (LearnSlice, SliceLearner, VorticitySliceLearner, "
+                    "PreviousSliceLearner)")
+
+
+@torch.no_grad()
+def slice_learner_test_loss(kind, model, sequen_solver, x, fx, yy, use_vorticity=0):
+    """The loss of ONE test batch as the `kind`'s script computes it inside its epoch loop, summed over the Tout frames
+    (the caller divides).  Every frame: the target is the encoder's slice weights of the true frame y, the code comes from
+    the window.
+      "learnslice" (:544-586): functional.slice_mse of get_slice_weight; the code is decoded with the TARGET slice
+                   weights and the prediction enters the window.
+      "vorticity"  (:975-1004): F.mse_loss of the predictor's slice weights; the code is decoded with the PREDICTED
+                   weights and the prediction enters the window.
+      "previous"   (:768-791): F.mse_loss of the predictor's raw output; the window NEVER slides (the script does not update
+                   fx in this loop), so code and previous slice are the first window's on every frame and only the target
+                   changes: both are computed once."""
+    loss = 0
+    with ops.weights_frozen():
+        code = prev = None
+        for t in range(yy.shape[-1]):
+            y = yy[..., t:t + 1]
+            sequen_solver.encoder.encode(x, y)
+            target = sequen_solver.encoder.get_attention_slice()
+            if kind == "previous":
+                if code is None:
+                    code = sequen_solver.get_code(x, fx, y)
+                    prev = sequen_solver.get_last_slice_weight(x, fx)
+                    new_slice = model(prev, code)
+                loss = loss + Fn.slice_mse(new_slice, target) / (new_slice.shape[0] * new_slice.shape[2])
+                continue
+            if kind == "learnslice":
+                code = sequen_solver.get_code(x, fx, y)
+                loss = loss + Fn.slice_mse(model.get_slice_weight(code, x, fx, use_vorticity=use_vorticity), target)
+                used = target
+            elif kind == "vorticity":
+                used, code = _predict_slices(model, sequen_solver, x, fx)
+                loss = loss + Fn.slice_mse(used, target) / (used.shape[0] * used.shape[2])
+            else:
+                raise ValueError(f"kind must be one of {SLICE_LEARNER_KINDS}; got {kind!r}")
+            fx = torch.cat((fx[..., 1:], _decode_step(sequen_solver, used, code)), dim=-1)
+    return loss
+
+
+def fit_slice_learner(model, optimizer, scheduler, sequen_solver, pos, train, test, *, epochs, batch_size=1, kind=None,
+                      fold_time=False, use_vorticity=None, max_grad_norm=None, epoch_orders=None, generator=None,
+                      save_path=None, save_every=1, grad_sync=None, on_epoch=None):
+    """The epoch loops of the reference's three slice trainers in LearnSlice.py, on the frozen `sequen_solver`.  `pos`
+    [1, N, P]: the point input of every sample; `train` / `test`: data.ResidentDataset of (fx [n, N, Tin], yy [n, N, Tout])
+    on the model's device.  `kind` "learnslice" | "vorticity" | "previous" picks the loop (default: by the model's class,
+    `slice_learner_kind`); `use_vorticity` (learnslice only) defaults to the model's own flag.
+
+    Each epoch: model.train(); shuffled batches through `learnslice_train_step` / `slice_predictor_train_step` /
+    `previous_slice_train_step` with `fold_time`; model.eval(); `slice_learner_test_loss` on every test batch.  Returns one
+    dict per epoch (train, test), each script's own figures with ITS divisors and quirks:
+      learnslice  train = sum over batches of (sum of the Tout step losses / Tout) / len(train batches);
+                  test = sum over test batches of (loss / Tout) / len(TRAIN batches): the script divides its test sum by
+                  len(train_loader) (:587).  The scheduler steps once per frame, inside the step function.
+      vorticity   train = the sum of the batch losses, undivided (:955-963); test = sum / len(test batches) (:1006).
+      previous    train = the sum of the batch losses, undivided (:750-756); test = the sum, undivided (:791-793), of a test
+                  pass whose window never slides.
+    One host synchronisation per epoch.  The scripts save after every epoch: `save_every` = 1 does that (and `_fit` writes
+    once more after the last epoch); `epoch_orders`, `generator`, `grad_sync`, `on_epoch`, `save_path` as fit_ns."""
+    kind = slice_learner_kind(model) if kind is None else kind
+    if kind not in SLICE_LEARNER_KINDS:
+        raise ValueError(f"kind must be one of {SLICE_LEARNER_KINDS}; got {kind!r}")
+    if use_vorticity is None:
+        use_vorticity = getattr(model, "use_vorticity", 0)
+    sequen_solver.eval()
+    positions = _positions_cache(pos.to(_device_of(model)))
+    ntrain_batches = -(-len(train) // batch_size)
+    ntest_batches = -(-len(test) // batch_size)
+    common = dict(max_grad_norm=max_grad_norm, grad_sync=grad_sync, fold_time=fold_time)
+
+    def train_batch(batch, acc):
+        fx, yy = batch
+        x = positions(fx.shape[0])
+        if kind == "learnslice":
+            losses = learnslice_train_step(model, optimizer, scheduler, sequen_solver, x, fx, yy, use_vorticity, **common)
+            acc[0] += torch.stack(losses).sum() / yy.shape[-1]
+        elif kind == "vorticity":
+            acc[0] += slice_predictor_train_step(model, optimizer, scheduler, sequen_solver, x, fx, yy, **common)
+        else:
+            acc[0] += previous_slice_train_step(model, optimizer, scheduler, sequen_solver, x, fx, yy, **common)
+
+    def test_pass(acc):
+        for fx, yy in test.batches(batch_size):
+            loss = slice_learner_test_loss(kind, model, sequen_solver, positions(fx.shape[0]), fx, yy, use_vorticity)
+            acc[1] += loss / yy.shape[-1] if kind == "learnslice" else loss
+
+    def metrics(a):
+        if kind == "learnslice":
+            return dict(train=a[0] / ntrain_batches, test=a[1] / ntrain_batches)
+        if kind == "vorticity":
+            return dict(train=a[0], test=a[1] / ntest_batches)
+        return dict(train=a[0], test=a[1])
+
+    return _fit(model, epochs=epochs, n_acc=2, batches=lambda ep: _epoch_batches(train, batch_size, ep, epoch_orders, generator),
+                train_batch=train_batch, test_pass=test_pass, metrics=metrics, on_epoch=on_epoch, save_path=save_path,
+                save_every=save_every)

@@ -1300,3 +1300,57 @@ def embed_bias_bwd(dz, want_placeholder, want_tvec):
     ws = _ws(nb, dz)
     _lib.check(_L().pa2d_embed_bias_bwd(_p(dz), _p(dp), _p(dt), ws.data_ptr(), nb, B, N, C, _stream()), "embed_bias_bwd")
     return dp, dt
+
+
+PREV_SLICE_MAX_M = 64       # widest slice row of pa2d_prev_slice_entry_* (include/pa2d.h)
+PREV_SLICE_FWD_ROWS = 64    # rows of one forward chunk (the backward's chunks are longer), and
+PREV_SLICE_MAX_UNITS = 4 * 65535      # the (sample, chunk) units of one launch: four per workgroup on a 65535-long grid axis
+_EXTENT = 1 << 32           # bytes the kernels' buffer addressing covers
+
+
+def _prev_slice_entry_shapes(sw, wsw, tb, act):
+    """(B, N, M, H) of sw [B, N, M], wsw [H, M], tb [B, H]; raises on what pa2d_prev_slice_entry_* refuse."""
+    _chk(sw, wsw, tb)
+    if act not in ACT_IDS:
+        raise ValueError(f"unknown activation {act!r}")
+    if sw.dim() != 3 or wsw.dim() != 2 or tb.dim() != 2:
+        raise ValueError(f"prev_slice_entry needs sw [B, N, M], wsw [H, M], tb [B, H]; got {tuple(sw.shape)}, "
+                         f"{tuple(wsw.shape)}, {tuple(tb.shape)}")
+    (B, N, M), H = sw.shape, wsw.shape[0]
+    if wsw.shape[1] != M or tuple(tb.shape) != (B, H):
+        raise ValueError(f"prev_slice_entry needs sw [B, N, M], wsw [H, M], tb [B, H]; got {tuple(sw.shape)}, "
+                         f"{tuple(wsw.shape)}, {tuple(tb.shape)}")
+    if not 1 <= M <= PREV_SLICE_MAX_M:
+        raise ValueError(f"prev_slice_entry handles 1 <= M <= {PREV_SLICE_MAX_M} slice weights per point; got {M}")
+    if H % 4:
+        raise ValueError(f"prev_slice_entry needs a hidden width that is a multiple of 4; got {H}")
+    if 4 * max(B * N * H, B * N * M, B * H, H * M) >= _EXTENT:
+        raise ValueError("prev_slice_entry: a tensor of 4 GiB or more is outside the kernels' buffer addressing")
+    if B * -(-N // PREV_SLICE_FWD_ROWS) > PREV_SLICE_MAX_UNITS:
+        raise ValueError(f"prev_slice_entry: B * ceil(N / {PREV_SLICE_FWD_ROWS}) = {B * -(-N // PREV_SLICE_FWD_ROWS)} row chunks "
+                         f"are more than the {PREV_SLICE_MAX_UNITS} one launch's grid holds")
+    return B, N, M, H
+
+
+def prev_slice_entry_fwd(sw, wsw, tb, act):
+    """h0[b, n, :] = act(sum_m sw[b, n, m] wsw[:, m] + tb[b, :]) in one launch: sw [B, N, M], wsw [H, M], tb [B, H]."""
+    B, N, M, H = _prev_slice_entry_shapes(sw, wsw, tb, act)
+    h0 = torch.empty(B, N, H, dtype=torch.float32, device=sw.device)
+    _lib.check(_L().pa2d_prev_slice_entry_fwd(_p(sw), _p(wsw), _p(tb), _p(h0), B, N, M, H, ACT_IDS[act], _stream()),
+               "prev_slice_entry_fwd")
+    return h0
+
+
+def prev_slice_entry_bwd(dh0, sw, wsw, tb, act):
+    """dh0 [B, N, H] -> (dwsw [H, M], dtb [B, H]) with the pre-activation recomputed; fixed-order reductions."""
+    B, N, M, H = _prev_slice_entry_shapes(sw, wsw, tb, act)
+    _chk(dh0)
+    if tuple(dh0.shape) != (B, N, H):
+        raise ValueError(f"prev_slice_entry_bwd needs dh0 {(B, N, H)}; got {tuple(dh0.shape)}")
+    dwsw = torch.empty(H, M, dtype=torch.float32, device=sw.device)
+    dtb = torch.empty(B, H, dtype=torch.float32, device=sw.device)
+    nb = _L().pa2d_prev_slice_entry_workspace(B, N, M, H)
+    ws = _ws(nb, sw)
+    _lib.check(_L().pa2d_prev_slice_entry_bwd(_p(dh0), _p(sw), _p(wsw), _p(tb), _p(dwsw), _p(dtb), ws.data_ptr(), nb, B, N,
+                                              M, H, ACT_IDS[act], _stream()), "prev_slice_entry_bwd")
+    return dwsw, dtb
