@@ -215,6 +215,37 @@ int pa2d_token_attn_bwd(const float* s, const float* nrm, const float* wq, const
                         const float* dopart, float* ds, float* dn, float* dwq, float* dwk, float* dwv, void* ws,
                         size_t ws_bytes, int BH, int nchunk, int M, int D, int accumulate, pa2d_stream_t stream);
 
+/* ---- training-mode dropout (Physics_Attention.py:51,110,282 and the Dropout of `to_out`, :28,85,257).
+ * Masks come from Philox4x32-10 evaluated INSIDE the kernels (csrc/pa2d_philox.h); none is written or saved, the
+ * backward evaluates the same function again.  A draw is (seed, offset, n), both 64-bit: element e < n takes word e & 3 of
+ * philox(counter = (lo32(offset + e/4), hi32(offset + e/4), 0, 0), key = (lo32(seed), hi32(seed))) and is KEPT iff that word
+ * >= thresh.  The caller passes thresh = floor(p * 2^32) and scale = (float)(1 / (1 - p)); no kernel computes with p.
+ * A draw of n elements uses the counters offset .. offset + ceil(n / 4) - 1.
+ *
+ * pa2d_dropout_keep_host: HOST only; keep[i] = 1 iff element first + i of the draw is kept, i < count. */
+int pa2d_dropout_keep_host(unsigned long long seed, unsigned long long offset, unsigned long long first,
+                           unsigned long long count, unsigned thresh, unsigned char* keep);
+/* out[e] = (res ? res[e] : 0) + (keep(e) ? z[e] * scale : 0), e < n; res may be NULL; product and sum round separately.
+ * Flat and grid-stride, one Philox evaluation per four consecutive elements; 16-byte accesses where z, res and out are
+ * 16-byte aligned, element by element otherwise (4-byte alignment is required: PA2D_ERR_ARG).  One trip of the grid
+ * covers PA2D_DROPOUT_TRIP elements.  Forward: z = to_out(y), res = fx, element index (b N + n) C + c; backward:
+ * z = dout, res = NULL gives the gradient entering to_out. */
+#define PA2D_DROPOUT_TRIP (2048 * 256 * 4)
+int pa2d_dropout_residual(const float* z, const float* res, float* out, long long n, unsigned thresh, float scale,
+                          unsigned long long seed, unsigned long long offset, pa2d_stream_t stream);
+/* pa2d_token_attn_fwd / _bwd with dropout on the attention matrix after the softmax: At = A (.) keep * scale, o = At V;
+ * element ((bh M + m) M + n) of a draw of BH*M*M elements.  Backward: dV = At^T dO, dA = (dO V^T) (.) keep * scale,
+ * dP = A (.) (dA - rowsum(dO (.) O)) with the UNDROPPED A (recomputed in the kernel).  Same limits as the entry points
+ * above; thresh = 0, scale = 1 gives their results bit for bit. */
+int pa2d_token_attn_fwd_dropout(const float* spart, const float* npart, const float* wq, const float* wk,
+                                const float* wv, float* s, float* nrm, float* o, int BH, int nchunk, int M, int D,
+                                unsigned thresh, float scale, unsigned long long seed, unsigned long long offset,
+                                pa2d_stream_t stream);
+int pa2d_token_attn_bwd_dropout(const float* s, const float* nrm, const float* wq, const float* wk, const float* wv,
+                                const float* dopart, float* ds, float* dn, float* dwq, float* dwk, float* dwv, void* ws,
+                                size_t ws_bytes, int BH, int nchunk, int M, int D, int accumulate, unsigned thresh,
+                                float scale, unsigned long long seed, unsigned long long offset, pa2d_stream_t stream);
+
 /* ---- de-slice: out_x = slice_weights . out_slice_token, written directly as [B,N,(h d)]
  * (Physics_Attention.py:116-117); slice weights are recomputed from x_mid, never stored. */
 int pa2d_deslice_fwd(const float* xm, long long ldx, const float* o, const float* ws, const float* bs,

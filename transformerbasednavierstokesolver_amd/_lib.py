@@ -16,6 +16,8 @@ _f = C.c_void_p      # const float* / float* (device pointers travel as integers
 _i = C.c_int
 _ll = C.c_longlong
 _sz = C.c_size_t
+_u32 = C.c_uint
+_u64 = C.c_ulonglong
 _st = C.c_void_p     # hipStream_t
 
 # name -> (restype, argtypes); mirrors include/pa2d.h one to one
@@ -60,6 +62,11 @@ SIGNATURES = {
     "pa2d_token_attn_fwd": (_i, [_f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _st]),
     "pa2d_token_attn_bwd_workspace": (_sz, [_i, _i]),
     "pa2d_token_attn_bwd": (_i, [_f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _sz, _i, _i, _i, _i, _i, _st]),
+    "pa2d_dropout_keep_host": (_i, [_u64, _u64, _u64, _u64, _u32, _f]),
+    "pa2d_dropout_residual": (_i, [_f, _f, _f, _ll, _u32, C.c_float, _u64, _u64, _st]),
+    "pa2d_token_attn_fwd_dropout": (_i, [_f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _u32, C.c_float, _u64, _u64, _st]),
+    "pa2d_token_attn_bwd_dropout": (_i, [_f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _sz, _i, _i, _i, _i, _i, _u32,
+                                        C.c_float, _u64, _u64, _st]),
     "pa2d_deslice_fwd": (_i, [_f, _ll, _f, _f, _f, _f, _f, _ll, _i, _i, _i, _i, _i, _i, _i, _st, _st, _st]),
     "pa2d_slice_bwd_workspace": (_sz, [_i, _i, _i, _i, _i]),
     "pa2d_slice_bwd_points": (_i, [_f, _ll, _f, _ll, _f, _ll, _f, _f, _f, _f, _f, _f, _f, _ll, _f, _ll, _f, _f, _f,

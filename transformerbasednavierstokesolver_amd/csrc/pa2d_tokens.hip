@@ -9,6 +9,7 @@
 //  * the per-chunk partial sums of the slice scatter are fetched with all loads of an element in
 //    flight (branch-free buffer loads) and added in a fixed order, so results stay deterministic.
 #include "pa2d_internal.h"
+#include "pa2d_philox.h"
 
 #define SLICE_EPS 1e-5f
 #define TOK_THREADS 512
@@ -95,12 +96,12 @@ __device__ __forceinline__ void load_weights(const TokLds& l, const float* wq, c
     }
 }
 
-// shared recompute from T (and the weights) in LDS: Q, K, V^T projections and A = softmax(Q K^T / sqrt(D));
-// rows and columns of A beyond M are exact zeros.
-__device__ __forceinline__ void tokens_forward_core(const TokLds& l, int M, int D, int tid) {
+// shared recompute from T (and the weights) in LDS: Q, K, V^T projections (tokens_project) and
+// A = softmax(Q K^T / sqrt(D)) (tokens_softmax); rows and columns of A beyond M are exact zeros.
+__device__ __forceinline__ void tokens_project(const TokLds& l, int M, int D, int tid) {
     const int P = l.P, PA = l.PA, M16 = l.Mp / 16, D16 = l.Dp / 16;
     const int lane = tid & 63, wave = tid >> 6;
-    float* const Q = l.Q; float* const Kk = l.K; float* const Vt = l.Vt; float* const A = l.A;
+    float* const Q = l.Q; float* const Kk = l.K; float* const Vt = l.Vt;
     lds_gemm(l.T, P, 1, l.Wq, P, 1, M16, D16, D, wave, lane, 0,
              [=](int m, int e, float v) { if (e < D) Q[m * P + e] = v; });
     lds_gemm(l.T, P, 1, l.Wk, P, 1, M16, D16, D, wave, lane, M16 * D16,
@@ -108,6 +109,11 @@ __device__ __forceinline__ void tokens_forward_core(const TokLds& l, int M, int 
     lds_gemm(l.Wv, P, 1, l.T, P, 1, D16, M16, D, wave, lane, 2 * M16 * D16,
              [=](int e, int m, float v) { Vt[e * PA + m] = v; });
     __syncthreads();
+}
+__device__ __forceinline__ void tokens_softmax(const TokLds& l, int M, int D, int tid) {
+    const int P = l.P, PA = l.PA, M16 = l.Mp / 16;
+    const int lane = tid & 63, wave = tid >> 6;
+    float* const Q = l.Q; float* const Kk = l.K; float* const A = l.A;
     const float scale = rsqrtf((float)D);
     lds_gemm(Q, P, 1, Kk, P, 1, M16, M16, D, wave, lane, 0,
              [=](int m, int n, float v) { A[m * PA + n] = v * scale; });
@@ -138,8 +144,38 @@ __device__ __forceinline__ void tokens_forward_core(const TokLds& l, int M, int 
     }
     __syncthreads();
 }
+__device__ __forceinline__ void tokens_forward_core(const TokLds& l, int M, int D, int tid) {
+    tokens_project(l, M, D, tid);
+    tokens_softmax(l, M, D, tid);
+}
 
-__global__ __launch_bounds__(TOK_THREADS) void token_attn_fwd_kernel(const TokParams p) {
+// Dropout on the attention matrix (Physics_Attention.py:110 `attn = dropout(softmax(...))`): element (m, n) of (b, h) is
+// element ((bh M + m) M + n) of the draw; the kernels get thresh = floor(p 2^32) and scale = fp32(1 / (1 - p)).
+struct TokDrop { unsigned thresh; float scale; unsigned long long seed, offset; };
+
+// A <- A (.) keep * scale in place, one Philox evaluation per group of four consecutive draw elements (a group may span
+// two rows, or two (b, h) when M * M is no multiple of 4: each workgroup writes only its own elements of it).
+__device__ __forceinline__ void tokens_drop_attention(const TokLds& l, int M, size_t bh, const TokDrop& d, int tid) {
+    const unsigned long long base = (unsigned long long)bh * M * M, end = base + (unsigned long long)M * M;
+    const unsigned long long g0 = base >> 2;
+    const int ngroups = (int)(((end + 3) >> 2) - g0);
+    for (int gi = tid; gi < ngroups; gi += TOK_THREADS) {
+        const Pa2dPhilox4 r = pa2d_dropout_words(d.seed, d.offset, g0 + gi);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const unsigned long long e = 4 * (g0 + gi) + j;
+            if (e >= base && e < end) {
+                const int i = (int)(e - base), m = i / M, n = i - m * M;
+                const float a = l.A[m * l.PA + n];
+                l.A[m * l.PA + n] = r.w[j] >= d.thresh ? a * d.scale : 0.f;
+            }
+        }
+    }
+    __syncthreads();
+}
+
+template <bool DROP>
+__device__ __forceinline__ void token_attn_fwd_body(const TokParams& p, const TokDrop& drop) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int M = p.M, D = p.D, tid = threadIdx.x;
     const TokLds l = carve(smem, M, D);
@@ -166,9 +202,16 @@ __global__ __launch_bounds__(TOK_THREADS) void token_attn_fwd_kernel(const TokPa
     }
     __syncthreads();
     tokens_forward_core(l, M, D, tid);
+    if (DROP) tokens_drop_attention(l, M, bh, drop, tid);
     float* const o = p.o + bh * M * D;
     lds_gemm(l.A, l.PA, 1, l.Vt, l.PA, 1, l.Mp / 16, l.Dp / 16, l.Mp, tid >> 6, tid & 63, 0,
              [=](int m, int d, float v) { if (m < M && d < D) o[m * D + d] = v; });
+}
+__global__ __launch_bounds__(TOK_THREADS) void token_attn_fwd_kernel(const TokParams p) {
+    token_attn_fwd_body<false>(p, TokDrop{});
+}
+__global__ __launch_bounds__(TOK_THREADS) void token_attn_fwd_dropout_kernel(const TokParams p, const TokDrop drop) {
+    token_attn_fwd_body<true>(p, drop);
 }
 
 struct TokBwdParams {
@@ -181,7 +224,13 @@ struct TokBwdParams {
 };
 static size_t tok_bwd_floats(int M, int D) { return tok_fwd_floats(M, D) + (size_t)3 * up16(M) * (D + 4) + up16(M); }
 
-__global__ __launch_bounds__(TOK_THREADS) void token_attn_bwd_kernel(const TokBwdParams p) {
+// DROP (Physics_Attention.py:110-111 with dropout p > 0, At = A (.) keep * scale): O = At V and dV = At^T dO need the
+// dropped matrix, dP = A (.) (dA - rowsum) the undropped one, also where keep = 0.  There is no LDS for both at M = 128,
+// so A is dropped in place for the two products and then made again from Q and K, which are still in LDS (the same code,
+// hence the same bits); dA = dAt (.) keep * scale is applied per element in the epilogue that forms dP.
+// rowsum(dA (.) A) = rowsum(dAt (.) At) = rowsum(dO (.) O) holds as before.
+template <bool DROP>
+__device__ __forceinline__ void token_attn_bwd_body(const TokBwdParams& p, const TokDrop& drop) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int M = p.M, D = p.D, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const TokLds l = carve(smem, M, D);
@@ -208,6 +257,7 @@ __global__ __launch_bounds__(TOK_THREADS) void token_attn_bwd_kernel(const TokBw
     }
     __syncthreads();
     tokens_forward_core(l, M, D, tid);
+    if (DROP) tokens_drop_attention(l, M, bh, drop, tid);
     // O = A V (for the softmax-backward row term) and dV[n][d] = sum_m A[m][n] dO[m][d]
     lds_gemm(A, PA, 1, l.Vt, PA, 1, M16, D16, Mp, wave, lane, 0,
              [=](int m, int d, float v) { if (d < D) G3[m * P + d] = v; });
@@ -220,9 +270,17 @@ __global__ __launch_bounds__(TOK_THREADS) void token_attn_bwd_kernel(const TokBw
         rsum[m] = g;
     }
     __syncthreads();
+    if (DROP) tokens_softmax(l, M, D, tid);      // the undropped A again
     // dA[m][n] = dO[m].V[n];  dP = A * (dA - rowsum), written over A (each element by the lane that read it)
     lds_gemm(G1, P, 1, l.Vt, 1, PA, M16, M16, D, wave, lane, 0,
-             [=](int m, int n, float v) { A[m * PA + n] *= (v - rsum[m]); });
+             [=](int m, int n, float v) {
+                 if (DROP) {
+                     const bool keep = m < M && n < M &&
+                         pa2d_dropout_keep(drop.seed, drop.offset, ((unsigned long long)bh * M + m) * M + n, drop.thresh);
+                     v = keep ? v * drop.scale : 0.f;
+                 }
+                 A[m * PA + n] *= (v - rsum[m]);
+             });
     __syncthreads();
     // dQ = scale * dP K (into G1: dO is dead), dK = scale * dP^T Q (into G3: O is dead)
     const float scale = rsqrtf((float)D);
@@ -271,40 +329,48 @@ __global__ __launch_bounds__(TOK_THREADS) void token_attn_bwd_kernel(const TokBw
         p.dn[bh * M + m] = -g / den;   // -(dT . S)/den^2 with S = T*den
     }
 }
-
-extern "C" {
-
-size_t pa2d_token_attn_lds_bytes(int M, int D, int backward) {
-    return sizeof(float) * (backward ? tok_bwd_floats(M, D) : tok_fwd_floats(M, D));
+__global__ __launch_bounds__(TOK_THREADS) void token_attn_bwd_kernel(const TokBwdParams p) {
+    token_attn_bwd_body<false>(p, TokDrop{});
+}
+__global__ __launch_bounds__(TOK_THREADS) void token_attn_bwd_dropout_kernel(const TokBwdParams p, const TokDrop drop) {
+    token_attn_bwd_body<true>(p, drop);
 }
 
-// spart/npart: partial sums from pa2d_slice_scatter ([B*heads, nchunk, ...]).
-// outputs: s (raw slice sums), nrm (slice norms), o (out_slice_token), all [B*heads, M, (D)].
-int pa2d_token_attn_fwd(const float* spart, const float* npart, const float* wq, const float* wk, const float* wv,
-                        float* s, float* nrm, float* o, int BH, int nchunk, int M, int D, hipStream_t st) {
+extern "C" size_t pa2d_token_attn_lds_bytes(int M, int D, int backward) {
+    return sizeof(float) * (backward ? tok_bwd_floats(M, D) : tok_fwd_floats(M, D));
+}
+extern "C" size_t pa2d_token_attn_bwd_workspace(int BH, int D) { return sizeof(float) * ((size_t)BH + 1) * 3 * D * D; }
+
+static int tok_lds_attribute(const void* kernel, size_t smem) {
+    if (smem <= 64 * 1024) return PA2D_OK;
+    return (int)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+}
+
+// drop == nullptr: the kernel without dropout
+static int token_attn_fwd_launch(const float* spart, const float* npart, const float* wq, const float* wk, const float* wv,
+                                 float* s, float* nrm, float* o, int BH, int nchunk, int M, int D, const TokDrop* drop,
+                                 hipStream_t st) {
     const size_t smem = pa2d_token_attn_lds_bytes(M, D, 0);
     if (smem > 160 * 1024 || M > 128 || (D & 3)) return PA2D_ERR_UNSUPPORTED;
     if (BH <= 0) return PA2D_OK;
-    if (smem > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&token_attn_fwd_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) return (int)e;
-    }
+    const int ra = tok_lds_attribute(drop ? reinterpret_cast<const void*>(&token_attn_fwd_dropout_kernel)
+                                          : reinterpret_cast<const void*>(&token_attn_fwd_kernel), smem);
+    if (ra) return ra;
     TokParams p;
     p.spart = spart; p.npart = npart; p.wq = wq; p.wk = wk; p.wv = wv; p.s = s; p.nrm = nrm; p.o = o;
     p.M = M; p.D = D; p.nchunk = nchunk;
-    hipLaunchKernelGGL(token_attn_fwd_kernel, dim3(BH), dim3(TOK_THREADS), smem, st, p);
+    if (drop)
+        hipLaunchKernelGGL(token_attn_fwd_dropout_kernel, dim3(BH), dim3(TOK_THREADS), smem, st, p, *drop);
+    else
+        hipLaunchKernelGGL(token_attn_fwd_kernel, dim3(BH), dim3(TOK_THREADS), smem, st, p);
     PA2D_CHECK_LAUNCH();
     return PA2D_OK;
 }
 
-size_t pa2d_token_attn_bwd_workspace(int BH, int D) { return sizeof(float) * ((size_t)BH + 1) * 3 * D * D; }
-// dwq/dwk/dwv (+)= (accumulate != 0: added to what they hold)
-
-// dopart: phase-A partials of dO = W^T dY.  Outputs ds, dn per (b,h) and fully reduced dwq/dwk/dwv [D,D].
-int pa2d_token_attn_bwd(const float* s, const float* nrm, const float* wq, const float* wk, const float* wv,
-                        const float* dopart, float* ds, float* dn, float* dwq, float* dwk, float* dwv, void* ws,
-                        size_t ws_bytes, int BH, int nchunk, int M, int D, int accumulate, hipStream_t st) {
+static int token_attn_bwd_launch(const float* s, const float* nrm, const float* wq, const float* wk, const float* wv,
+                                 const float* dopart, float* ds, float* dn, float* dwq, float* dwk, float* dwv, void* ws,
+                                 size_t ws_bytes, int BH, int nchunk, int M, int D, int accumulate, const TokDrop* drop,
+                                 hipStream_t st) {
     const size_t smem = pa2d_token_attn_lds_bytes(M, D, 1);
     if (smem > 160 * 1024 || M > 128 || (D & 3)) return PA2D_ERR_UNSUPPORTED;
     if (BH <= 0) {
@@ -315,15 +381,16 @@ int pa2d_token_attn_bwd(const float* s, const float* nrm, const float* wq, const
         return rz ? rz : pa2d_zero(dwv, wb, st);
     }
     if (ws_bytes < pa2d_token_attn_bwd_workspace(BH, D)) return PA2D_ERR_WORKSPACE;
-    if (smem > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&token_attn_bwd_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) return (int)e;
-    }
+    const int ra = tok_lds_attribute(drop ? reinterpret_cast<const void*>(&token_attn_bwd_dropout_kernel)
+                                          : reinterpret_cast<const void*>(&token_attn_bwd_kernel), smem);
+    if (ra) return ra;
     TokBwdParams p;
     p.s = s; p.nrm = nrm; p.wq = wq; p.wk = wk; p.wv = wv; p.dopart = dopart; p.ds = ds; p.dn = dn;
     p.dwpart = (float*)ws; p.M = M; p.D = D; p.nchunk = nchunk;
-    hipLaunchKernelGGL(token_attn_bwd_kernel, dim3(BH), dim3(TOK_THREADS), smem, st, p);
+    if (drop)
+        hipLaunchKernelGGL(token_attn_bwd_dropout_kernel, dim3(BH), dim3(TOK_THREADS), smem, st, p, *drop);
+    else
+        hipLaunchKernelGGL(token_attn_bwd_kernel, dim3(BH), dim3(TOK_THREADS), smem, st, p);
     PA2D_CHECK_LAUNCH();
     const long long dd = (long long)D * D;
     ReduceSegs segs;
@@ -331,6 +398,47 @@ int pa2d_token_attn_bwd(const float* s, const float* nrm, const float* wq, const
     segs.begin[0] = 0; segs.begin[1] = dd; segs.begin[2] = 2 * dd; segs.begin[3] = 3 * dd; segs.begin[4] = 3 * dd;
     segs.dst[0] = dwq; segs.dst[1] = dwk; segs.dst[2] = dwv; segs.dst[3] = nullptr;
     return pa2d_launch_reduce_segs((const float*)ws, BH, 3 * dd, segs, accumulate, st);
+}
+
+static TokDrop tok_drop(unsigned thresh, float scale, unsigned long long seed, unsigned long long offset) {
+    TokDrop d;
+    d.thresh = thresh; d.scale = scale; d.seed = seed; d.offset = offset;
+    return d;
+}
+
+extern "C" {
+
+// spart/npart: partial sums from pa2d_slice_scatter ([B*heads, nchunk, ...]).
+// outputs: s (raw slice sums), nrm (slice norms), o (out_slice_token), all [B*heads, M, (D)].
+int pa2d_token_attn_fwd(const float* spart, const float* npart, const float* wq, const float* wk, const float* wv,
+                        float* s, float* nrm, float* o, int BH, int nchunk, int M, int D, hipStream_t st) {
+    return token_attn_fwd_launch(spart, npart, wq, wk, wv, s, nrm, o, BH, nchunk, M, D, nullptr, st);
+}
+
+// dopart: phase-A partials of dO = W^T dY.  Outputs ds, dn per (b,h) and fully reduced dwq/dwk/dwv [D,D]
+// (accumulate != 0: added to what they hold).
+int pa2d_token_attn_bwd(const float* s, const float* nrm, const float* wq, const float* wk, const float* wv,
+                        const float* dopart, float* ds, float* dn, float* dwq, float* dwk, float* dwv, void* ws,
+                        size_t ws_bytes, int BH, int nchunk, int M, int D, int accumulate, hipStream_t st) {
+    return token_attn_bwd_launch(s, nrm, wq, wk, wv, dopart, ds, dn, dwq, dwk, dwv, ws, ws_bytes, BH, nchunk, M, D,
+                                 accumulate, nullptr, st);
+}
+
+// the same with dropout on the attention matrix: draw (seed, offset) of B*heads*M*M elements (pa2d_philox.h)
+int pa2d_token_attn_fwd_dropout(const float* spart, const float* npart, const float* wq, const float* wk, const float* wv,
+                                float* s, float* nrm, float* o, int BH, int nchunk, int M, int D, unsigned thresh,
+                                float scale, unsigned long long seed, unsigned long long offset, hipStream_t st) {
+    const TokDrop d = tok_drop(thresh, scale, seed, offset);
+    return token_attn_fwd_launch(spart, npart, wq, wk, wv, s, nrm, o, BH, nchunk, M, D, &d, st);
+}
+
+int pa2d_token_attn_bwd_dropout(const float* s, const float* nrm, const float* wq, const float* wk, const float* wv,
+                                const float* dopart, float* ds, float* dn, float* dwq, float* dwk, float* dwv, void* ws,
+                                size_t ws_bytes, int BH, int nchunk, int M, int D, int accumulate, unsigned thresh,
+                                float scale, unsigned long long seed, unsigned long long offset, hipStream_t st) {
+    const TokDrop d = tok_drop(thresh, scale, seed, offset);
+    return token_attn_bwd_launch(s, nrm, wq, wk, wv, dopart, ds, dn, dwq, dwk, dwv, ws, ws_bytes, BH, nchunk, M, D,
+                                 accumulate, &d, st);
 }
 
 }  // extern "C"

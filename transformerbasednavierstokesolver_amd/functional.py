@@ -37,13 +37,23 @@ def mesh_extent(W):
     return (W[0], W[1]) if isinstance(W, tuple) else (W, None)
 
 
-def attn_forward(xn, P, res, H, W, heads, engine=None, xn_planes=None, shape=None):
+def dropout_draws(p, B, N, C, heads, M):
+    """The two draws of one Physics-Attention layer in training mode with dropout p > 0, reserved from the package
+    generator IN THIS ORDER: the attention matrix (B*heads*M*M elements, Physics_Attention.py:110), then the output of
+    to_out (B*N*C, :28).  Each is the `drop` tuple (thresh, scale, seed, offset) of the ops.  Blocks reserve in model order."""
+    ts = ops.dropout_constants(p)
+    return ts + ops.dropout_reserve(B * heads * M * M), ts + ops.dropout_reserve(B * N * C)
+
+
+def attn_forward(xn, P, res, H, W, heads, engine=None, xn_planes=None, shape=None, drop=None):
     """xn [B,N,C] (already layer-normed).  P: dict of parameter tensors.  Returns (out, saved).
     H is None -> irregular-mesh variant (Physics_Attention.py:6-57): Linear projections, no
     temperature clamp; otherwise the structured-mesh variant (3x3 conv projections, clamp; W = (width, depth):
     the 3-D structured mesh, 3x3x3 conv projections, clamp).
     xn_planes (structured, bf16 engines): the LayerNorm output exists only as the conv's bf16 plane image
-    (ops.layernorm_fwd_planes); `xn` is then None and `shape` = (B, N, C)."""
+    (ops.layernorm_fwd_planes); `xn` is then None and `shape` = (B, N, C).
+    drop: `dropout_draws(...)` — the attention matrix is dropped inside the token kernel, and to_out runs WITHOUT the fused
+    residual so that out = res + dropout(to_out(y)) (one flat launch, ops.dropout_residual)."""
     B, N, C = xn.shape if xn is not None else shape
     D = C // heads
     M = P["ws"].shape[0]
@@ -63,23 +73,31 @@ def attn_forward(xn, P, res, H, W, heads, engine=None, xn_planes=None, shape=Non
         xf = ops.linear_fwd(xn.view(B * N, C), wcat, bcat, engine=engine)[0].view(B, N, 2 * C)
     spart, npart = ops.slice_scatter(xf, 2 * C, 0, xf, 2 * C, C, P["ws"], P["bs"], temp, B, N, heads, D, M,
                                      clamp=structured, engine=engine)
-    s, nrm, o = ops.token_attn_fwd(spart, npart, P["wq"], P["wk"], P["wv"])
+    s, nrm, o = ops.token_attn_fwd(spart, npart, P["wq"], P["wk"], P["wv"], **({} if drop is None else dict(drop=drop[0])))
     y = ops.deslice_fwd(xf, 2 * C, 0, o, P["ws"], P["bs"], temp, B, N, heads, D, M, clamp=structured, engine=engine)  # [B,N,C]
-    out, _ = ops.linear_fwd(y.view(B * N, C), P["wo"], P["bo"],
-                            res=None if res is None else res.reshape(B * N, C), engine=engine)
+    res2d = None if res is None else res.reshape(B * N, C)
+    if drop is None:
+        out, _ = ops.linear_fwd(y.view(B * N, C), P["wo"], P["bo"], res=res2d, engine=engine)
+    else:
+        z, _ = ops.linear_fwd(y.view(B * N, C), P["wo"], P["bo"], engine=engine)
+        out = ops.dropout_residual(z, res2d, drop[1])
     return out.view(B, N, C), (xn if xn_planes is None else xn_planes, xf, s, nrm, o, y, temp)
 
 
-def attn_backward(saved, P, dout, H, W, heads, need_dx=True, engine=None, targets=None, planes=False):
+def attn_backward(saved, P, dout, H, W, heads, need_dx=True, engine=None, targets=None, planes=False, drop=None):
     """`targets`: dict ATTN_KEYS -> gradient buffer to ADD into (structured meshes), or None (fresh tensors).
     `planes`: saved[0] is the plane image of the LayerNorm output; the slice backward then emits [dX | dF] as planes too
-    (plus the conv bias gradients) and the conv backward consumes both images directly."""
+    (plus the conv bias gradients) and the conv backward consumes both images directly.
+    `drop`: the forward's draws; the gradient entering to_out is dout with the output mask made again (the caller keeps
+    the undropped dout as the residual gradient)."""
     xn, xf, s, nrm, o, y, temp = saved
     B, N, C2 = xf.shape
     C = C2 // 2
     D = C // heads
     M = P["ws"].shape[0]
     d2 = dout.reshape(B * N, C)
+    if drop is not None:
+        d2 = ops.dropout_residual(d2, None, drop[1])
     structured = H is not None
     Wm, depth = mesh_extent(W)
     if planes and depth is not None:
@@ -90,7 +108,8 @@ def attn_backward(saved, P, dout, H, W, heads, need_dx=True, engine=None, target
     dwo, dbo = ops.linear_bwd_weight(d2, y.view(B * N, C), engine=engine, into=t("wo", "bo"))
     dopart, _ = ops.slice_scatter(xf, 2 * C, 0, dy, C, 0, P["ws"], P["bs"], temp, B, N, heads, D, M,
                                   want_norm=False, clamp=structured, engine=engine)
-    ds, dn, dwq, dwk, dwv = ops.token_attn_bwd(s, nrm, P["wq"], P["wk"], P["wv"], dopart, into=t("wq", "wk", "wv"))
+    ds, dn, dwq, dwk, dwv = ops.token_attn_bwd(s, nrm, P["wq"], P["wk"], P["wv"], dopart, into=t("wq", "wk", "wv"),
+                                               **({} if drop is None else dict(drop=drop[0])))
     if planes:
         dxfp, dbx, dbf, dws, dbs, dtemp = ops.slice_bwd_points_planes(xf, dy, P["ws"], P["bs"], temp, o, ds, dn, nrm, B, N, heads,
                                                                       D, M, engine, clamp=True,
@@ -247,7 +266,7 @@ class AttnBranchFn(Function):
     H / W: mesh geometry as for attn_forward (W = (width, depth) on the 3-D structured mesh)."""
 
     @staticmethod
-    def forward(ctx, fx, ln_w, ln_b, H, W, heads, engine, *params):
+    def forward(ctx, fx, ln_w, ln_b, H, W, heads, engine, dropout, *params):
         shp = fx.shape
         ctx.params, ctx.ln_params = params, (ln_w, ln_b)
         fx2d = fx.detach().reshape(-1, shp[-1]).contiguous()
@@ -256,12 +275,14 @@ class AttnBranchFn(Function):
         # bf16 engines on fp32 storage: LayerNorm writes the conv's operand planes directly (no fp32 xn, no pre-pass)
         ctx.planes = (H is not None and mesh_extent(W)[1] is None and fx2d.dtype == torch.float32 and len(shp) == 3
                       and ops.conv_planes_mask(shp[0], H, W, shp[2], engine) == 7)
+        # training-mode dropout p > 0: the layer's two draws, reserved here (attention, then output) and kept for the backward
+        ctx.drop = drop = dropout_draws(dropout, shp[0], shp[1], shp[2], heads, P["ws"].shape[0]) if dropout else None
         if ctx.planes:
             xnp, mean, rstd = ops.layernorm_fwd_planes(fx2d, ln_w, ln_b, engine)
-            out, saved = attn_forward(None, P, fx2d.view(shp), H, W, heads, engine, xn_planes=xnp, shape=tuple(shp))
+            out, saved = attn_forward(None, P, fx2d.view(shp), H, W, heads, engine, xn_planes=xnp, shape=tuple(shp), drop=drop)
         else:
             xn, mean, rstd = ops.layernorm_fwd(fx2d, ln_w, ln_b)
-            out, saved = attn_forward(xn.view(shp), P, fx2d.view(shp), H, W, heads, engine)
+            out, saved = attn_forward(xn.view(shp), P, fx2d.view(shp), H, W, heads, engine, drop=drop)
         ctx.P, ctx.saved, ctx.geom, ctx.ln = P, saved, (H, W, heads, engine), (fx2d, mean, rstd, ln_w)
         return out
 
@@ -271,11 +292,11 @@ class AttnBranchFn(Function):
         fx2d, mean, rstd, ln_w = ctx.ln
         dout = dout.contiguous()
         dxn, g = attn_backward(ctx.saved, ctx.P, dout, H, W, heads, need_dx=True, engine=engine,
-                               targets=_attn_targets(ctx.params, H is not None), planes=ctx.planes)
+                               targets=_attn_targets(ctx.params, H is not None), planes=ctx.planes, drop=ctx.drop)
         tl = grad_targets(ctx.ln_params)
         dfx, dg, db = ops.layernorm_bwd(dxn.reshape(fx2d.shape), fx2d, mean, rstd, ln_w, dres=dout.reshape(fx2d.shape),
                                         into=tl)
-        return (dfx.view(dout.shape),) + _ret(tl, (dg, db)) + (None, None, None, None) + _attn_grads(g)
+        return (dfx.view(dout.shape),) + _ret(tl, (dg, db)) + (None, None, None, None, None) + _attn_grads(g)
 
 
 class MLPBranchFn(Function):
@@ -336,8 +357,12 @@ def block_tail(fx, xn, P, H, W, heads, ln2_w, ln2_b, act, w1, b1, w2, b2, next_w
     return out.view(B, N, C), None if xnext is None else xnext.view(B, N, C)
 
 
-def attn_branch(fx, ln_w, ln_b, H, W, heads, params, engine=None):
-    return AttnBranchFn.apply(fx, ln_w, ln_b, H, W, heads, engine, *params)
+def attn_branch(fx, ln_w, ln_b, H, W, heads, params, engine=None, dropout=None):
+    """dropout: probability p in (0, 1) of training-mode dropout at the layer's two sites (None or 0: none, and the launches
+    of a model without dropout); fp32 storage only."""
+    if dropout and fx.dtype != torch.float32:
+        raise NotImplementedError("dropout > 0 is served for fp32 storage only")
+    return AttnBranchFn.apply(fx, ln_w, ln_b, H, W, heads, engine, dropout or None, *params)
 
 
 def mlp_branch(fx, ln_w, ln_b, act, w1, b1, w2, b2, engine=None):

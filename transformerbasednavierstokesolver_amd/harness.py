@@ -87,7 +87,9 @@ def train_iteration(model, x, fx, yy, step=1, loss_fn=None, fold_time=False):
     they run as ONE call on a batch of (T/step)*B windows: the same per-window outputs, the same summed
     loss and (up to fp32 summation order inside the weight-gradient reductions) the same gradients, with
     1/(T/step) of the launches, no per-call gradient accumulation and full tiles at the reference's small
-    batch sizes.  Not applicable to the prediction-feedback rollout."""
+    batch sizes.  Not applicable to the prediction-feedback rollout.
+    With training-mode dropout the folded call draws ONE larger mask per layer for all its windows where the loop draws one
+    per call: both are valid dropout, from different stretches of the generator, so the two routes are not bit-equal then."""
     loss_fn = loss_fn or TestLoss(size_average=False)
     T = yy.shape[-1]
     bsz = x.shape[0]
@@ -266,6 +268,20 @@ class GraphedRollout:
         return torch.cat(frames, -1)
 
 
+def training_dropout(model):
+    """Largest dropout probability that applies in a call of `model` as it stands: over its nn.Dropout members in training
+    mode (0.0 without one).  Host-side, no GPU."""
+    return max((float(m.p) for m in model.modules() if isinstance(m, torch.nn.Dropout) and m.training), default=0.0)
+
+
+def _refuse_graphed_dropout(model, who):
+    """The dropout kernels take the draw's (seed, offset) as launch constants, which a capture bakes in: every replay would
+    reuse one mask.  First check of every graph-capturing step, before anything touches the GPU."""
+    if training_dropout(model) > 0:
+        raise NotImplementedError(f"{who}: a model with training-mode dropout p > 0 cannot be captured (every replay would "
+                                  "draw the same mask); run the eager step, or set dropout=0")
+
+
 class GraphedTrainStep:
     """exp_ns iteration with the launch-bound part captured in ONE hipGraph.
 
@@ -280,6 +296,7 @@ class GraphedTrainStep:
 
     def __init__(self, model, optimizer, scheduler, x, fx, yy, step=1, loss_fn=None, warmup=3, fold_time=False):
         from .optim import FusedAdamW
+        _refuse_graphed_dropout(model, "GraphedTrainStep")
         self.fold_time = fold_time
         if not isinstance(optimizer, FusedAdamW):
             raise TypeError("GraphedTrainStep needs optim.FusedAdamW (persistent flat gradient bucket)")
@@ -353,6 +370,7 @@ class GraphedCallStep:
     likewise if parameter storage moved (GraphedRollout's check)."""
 
     def __init__(self, model, optimizer, scheduler, static, body, warmup=2):
+        _refuse_graphed_dropout(model, "GraphedCallStep")
         _graphed_refusals("GraphedCallStep", optimizer, None)
         self.model, self.opt, self.sched, self.static, self.body = model, optimizer, scheduler, list(static), body
         opt = optimizer

@@ -42,6 +42,8 @@ class Physics_Attention_Irregular_Mesh(nn.Module):
 
 
 class Transolver_block(BlockBase):
+    serves_dropout = True          # BlockBase.forward: training-mode dropout runs on the HIP kernels
+
     def __init__(self, num_heads, hidden_dim, dropout, act='gelu', mlp_ratio=4, last_layer=False, out_dim=1,
                  slice_num=32):
         super().__init__()

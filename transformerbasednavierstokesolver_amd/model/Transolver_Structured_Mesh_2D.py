@@ -10,6 +10,8 @@ from .Physics_Attention import Physics_Attention_Structured_Mesh_2D
 
 
 class Transolver_block(BlockBase):
+    serves_dropout = True          # BlockBase.forward: training-mode dropout runs on the HIP kernels
+
     def __init__(self, num_heads, hidden_dim, dropout, act='gelu', mlp_ratio=4, last_layer=False, out_dim=1,
                  slice_num=32, H=85, W=85):
         super().__init__()

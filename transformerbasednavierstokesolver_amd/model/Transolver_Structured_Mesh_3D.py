@@ -12,6 +12,8 @@ from .Physics_Attention import Physics_Attention_Structured_Mesh_3D
 
 
 class Transolver_block(BlockBase):
+    serves_dropout = True          # BlockBase.forward: training-mode dropout runs on the HIP kernels
+
     def __init__(self, num_heads, hidden_dim, dropout, act='gelu', mlp_ratio=4, last_layer=False, out_dim=1,
                  slice_num=32, H=32, W=32, D=32):
         super().__init__()
@@ -71,6 +73,10 @@ class Model(TransolverBase):
         # re-entrant form: the blocks' autograd nodes keep their saved tensors on ctx (not save_for_backward), which the
         # saved-tensor hooks of the non-re-entrant form never see; here the forward runs without a graph and is redone
         # inside the backward, so the activations of a block really are freed in between
+        if any(block.training_dropout() > 0 for block in self.blocks):
+            # the recomputation would reserve NEW draws: the gradient would belong to other masks than the loss
+            raise NotImplementedError("use_checkpoint with training-mode dropout > 0 is not implemented: the package's dropout "
+                                      "generator is not rewound for the recomputation; refusing to mix two sets of masks")
         for block in self.blocks:
             z = checkpoint.checkpoint(block, z, use_reentrant=True)
         return z

@@ -59,6 +59,15 @@ class MLP(nn.Module):
 class BlockBase(nn.Module):
     """pre-LN residual block: fx += Attn(LN1 fx); fx += MLP(LN2 fx); last block: head(LN3 fx)."""
 
+    # training-mode dropout p > 0 (on the attention matrix and after to_out, DESIGN §4.19) is served by the blocks that
+    # declare it: the 2-D, 3-D and irregular Transolver_block.  Every other block keeps refusing it.
+    serves_dropout = False
+
+    def training_dropout(self):
+        """p of the attention's dropout while it applies (the attention is in training mode), else 0."""
+        attn = self.Attn
+        return float(attn.dropout.p) if attn.training else 0.0
+
     def _assemble(self, attn, hidden_dim, act, mlp_ratio, last_layer, out_dim):
         self.last_layer = last_layer
         self.engine = None
@@ -78,6 +87,8 @@ class BlockBase(nn.Module):
         from .. import ops
         attn, mlp = self.Attn, self.mlp
         if not self.fused_tail or torch.is_grad_enabled() or fx.dtype != torch.float32 or fx.dim() != 3:
+            return False
+        if self.training_dropout() > 0:         # the tail has no dropout: such a call takes the served route or raises
             return False
         if self.training or self.engine == ops.ENGINE_BF16S or len(mlp.linears):
             return False
@@ -115,13 +126,19 @@ class BlockBase(nn.Module):
         if self.fused_tail and self.fused_route(fx):
             fx, z = self.forward_fused(fx)
             return self.head(z) if self.last_layer else fx
-        if attn.training and attn.dropout.p > 0:
-            raise NotImplementedError("dropout > 0 is not implemented in the HIP path; refusing to ignore it")
+        p = self.training_dropout()
+        if p > 0:
+            from .. import ops
+            if not self.serves_dropout:
+                raise NotImplementedError("dropout > 0 is not implemented in the HIP path for this block; refusing to ignore it")
+            if fx.dtype != torch.float32 or self.engine == ops.ENGINE_BF16S:
+                raise NotImplementedError("dropout > 0 is served for fp32 storage only; refusing to ignore it under bf16 storage")
+            ops.dropout_constants(p)            # p = 1 has no finite scale: ValueError before any kernel runs
         # each residual branch (LayerNorm -> sub-layer -> + fx) is one autograd node
         # mesh geometry: H, and W (2-D) or (W, D) (3-D attention's `mesh_w`); the irregular mesh has neither
         fx = Fn.attn_branch(fx, self.ln_1.weight, self.ln_1.bias, getattr(attn, "H", None),
                             getattr(attn, "mesh_w", getattr(attn, "W", None)), attn.heads, attn.attention_parameters(),
-                            engine=self.engine)
+                            engine=self.engine, dropout=p or None)
         pre, post = mlp.linear_pre[0], mlp.linear_post
         if mlp.linears or pre.weight.shape[1] % 4:      # generic MLP shapes keep the unfused route
             fx = mlp(Fn.layer_norm(fx, self.ln_2.weight, self.ln_2.bias), residual=fx)

@@ -582,18 +582,23 @@ def slice_scatter(xm, ldx, xm_off, v, ldv, v_off, ws_w, bs, temperature, B, N, h
     return spart, npart
 
 
-def token_attn_fwd(spart, npart, wq, wk, wv):
+def token_attn_fwd(spart, npart, wq, wk, wv, drop=None):
+    """`drop` = (thresh, scale, seed, offset): dropout on the attention matrix, a draw of BH*M*M elements."""
     _chk(spart, npart, wq, wk, wv)
     BH, nchunk, M, D = spart.shape
     s = torch.empty(BH, M, D, dtype=torch.float32, device=spart.device)
     nrm = torch.empty(BH, M, dtype=torch.float32, device=spart.device)
     o = torch.empty_like(s)
-    _lib.check(_L().pa2d_token_attn_fwd(_p(spart), _p(npart), _p(wq), _p(wk), _p(wv), _p(s), _p(nrm), _p(o), BH,
-                                        nchunk, M, D, _stream()), "token_attn_fwd")
+    args = (_p(spart), _p(npart), _p(wq), _p(wk), _p(wv), _p(s), _p(nrm), _p(o), BH, nchunk, M, D)
+    if drop is None:
+        _lib.check(_L().pa2d_token_attn_fwd(*args, _stream()), "token_attn_fwd")
+    else:
+        _lib.check(_L().pa2d_token_attn_fwd_dropout(*args, *_drop_args(drop), _stream()), "token_attn_fwd_dropout")
     return s, nrm, o
 
 
-def token_attn_bwd(s, nrm, wq, wk, wv, dopart, into=None):
+def token_attn_bwd(s, nrm, wq, wk, wv, dopart, into=None, drop=None):
+    """`drop`: the forward's draw; the kernel makes the mask again."""
     _chk(s, nrm, wq, wk, wv, dopart)
     BH, nchunk, M, D = dopart.shape
     ds = torch.empty_like(s)
@@ -601,10 +606,87 @@ def token_attn_bwd(s, nrm, wq, wk, wv, dopart, into=None):
     (dwq, dwk, dwv), acc = _grad_outputs(into, ((D, D), (D, D), (D, D)), s)
     nb = _L().pa2d_token_attn_bwd_workspace(BH, D)
     ws = _ws(nb, s)
-    _lib.check(_L().pa2d_token_attn_bwd(_p(s), _p(nrm), _p(wq), _p(wk), _p(wv), _p(dopart), _p(ds), _p(dn), _p(dwq),
-                                        _p(dwk), _p(dwv), ws.data_ptr(), nb, BH, nchunk, M, D, acc, _stream()),
-               "token_attn_bwd")
+    args = (_p(s), _p(nrm), _p(wq), _p(wk), _p(wv), _p(dopart), _p(ds), _p(dn), _p(dwq), _p(dwk), _p(dwv), ws.data_ptr(), nb,
+            BH, nchunk, M, D, acc)
+    if drop is None:
+        _lib.check(_L().pa2d_token_attn_bwd(*args, _stream()), "token_attn_bwd")
+    else:
+        _lib.check(_L().pa2d_token_attn_bwd_dropout(*args, *_drop_args(drop), _stream()), "token_attn_bwd_dropout")
     return ds, dn, dwq, dwk, dwv
+
+
+# ---------------------------------------------------------------------------------------------- training-mode dropout
+# Masks are never stored: a DRAW (seed, offset, n) names them (include/pa2d.h), the kernels evaluate Philox4x32-10 for it,
+# forward and backward alike.  The package keeps one generator: a 64-bit seed and the offset of the next draw.
+DROPOUT_TRIP = 2048 * 256 * 4        # elements one grid-stride trip of dropout_residual covers (PA2D_DROPOUT_TRIP)
+_MASK64 = (1 << 64) - 1
+_dropout = {"seed": None, "offset": 0, "torch_seed": None}
+
+
+def dropout_constants(p):
+    """(thresh, scale) the kernels take for dropout probability p: floor(p 2^32) and fp32(1 / (1 - p)).  Host arithmetic."""
+    p = float(p)
+    if p == 1.0:
+        raise ValueError("dropout p = 1 drops everything and has no finite scale 1 / (1 - p)")
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"dropout probability has to be in [0, 1); got {p}")
+    return int(p * 4294967296.0), float(torch.tensor(1.0 / (1.0 - p), dtype=torch.float64).to(torch.float32))
+
+
+def _dropout_latch():
+    """Without an explicit seed the generator follows torch's: it takes torch.initial_seed() at first use and again, with
+    offset 0, whenever that value has changed since (torch.manual_seed(s) with a new s; an explicit seed is dropped then)."""
+    ts = torch.initial_seed()
+    if _dropout["seed"] is None or ts != _dropout["torch_seed"]:
+        _dropout.update(seed=ts & _MASK64, offset=0, torch_seed=ts)
+
+
+def dropout_manual_seed(seed):
+    """Seed the package's dropout generator; the next draw starts at offset 0."""
+    _dropout.update(seed=int(seed) & _MASK64, offset=0, torch_seed=torch.initial_seed())
+
+
+def dropout_state():
+    """(seed, offset) of the next draw."""
+    _dropout_latch()
+    return _dropout["seed"], _dropout["offset"]
+
+
+def dropout_reserve(n):
+    """(seed, offset) of a draw of n elements; the generator moves on by the ceil(n / 4) counters the draw uses."""
+    _dropout_latch()
+    draw = (_dropout["seed"], _dropout["offset"])
+    _dropout["offset"] = (_dropout["offset"] + (int(n) + 3) // 4) & _MASK64
+    return draw
+
+
+def dropout_keep_host(seed, offset, first, count, thresh):
+    """uint8 [count] host tensor: 1 where element first + i of the draw (seed, offset) is kept.  Host code, no GPU."""
+    keep = torch.empty(int(count), dtype=torch.uint8)
+    _lib.check(_L().pa2d_dropout_keep_host(int(seed) & _MASK64, int(offset) & _MASK64, int(first), int(count), int(thresh),
+                                           keep.data_ptr()), "dropout_keep_host")
+    return keep
+
+
+def _drop_args(drop):
+    thresh, scale, seed, offset = drop
+    if not 0 <= int(thresh) < (1 << 32):
+        raise ValueError(f"dropout threshold {thresh} is not a 32-bit word")
+    return int(thresh), float(scale), int(seed) & _MASK64, int(offset) & _MASK64
+
+
+def dropout_residual(z, res, drop):
+    """out = (res or 0) + keep * z * scale over the flat tensor (element index = flat index of z); `drop` = (thresh, scale,
+    seed, offset).  z and res may be views at any 4-byte aligned address (the kernel then goes element by element)."""
+    for t in (z, res):
+        if t is not None and (not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous()):
+            raise ValueError("dropout_residual needs contiguous fp32 tensors on the GPU")
+    if res is not None and res.numel() != z.numel():
+        raise ValueError("dropout_residual: z and res differ in size")
+    out = torch.empty_like(z)
+    _lib.check(_L().pa2d_dropout_residual(_p(z), _p(res), _p(out), z.numel(), *_drop_args(drop), _stream()),
+               "dropout_residual")
+    return out
 
 
 def deslice_fwd(xm, ldx, xm_off, o, ws_w, bs, temperature, B, N, heads, D, M, clamp=True, engine=None):
