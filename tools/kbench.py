@@ -124,14 +124,12 @@ def main():
         w1, b1, w2 = rn(hid, C) * 0.06, rn(hid), rn(C, hid) * 0.06
         tail = lambda: ops.block_tail_fwd(xf, 2 * C, 0, o, ws, bs, temp, res, w, bias, gamma, beta, w1, b1, w2, bias, gamma,
                                           beta, B, N, heads, D, M, "gelu", engine=E)
-        tail_scope = ops._FrozenScope()          # holds the three weight images, made by the first (untimed) call
+        with ops.weights_frozen() as tail_scope:      # holds the three weight images, made by the first (untimed) call
+            pass
 
         def tail_timed():
-            ops._frozen.append(tail_scope)
-            try:
+            with ops.weights_frozen(tail_scope):
                 return tail()
-            finally:
-                ops._frozen.pop()
         tests["block_tail"] = (tail_timed, 2.0 * R * C * (C + 2 * hid), "TF")
     dy3 = dy2d.view(B, N, C)
     dopart, _ = ops.slice_scatter(xf, 2 * C, 0, dy3, C, 0, ws, bs, temp, B, N, heads, D, M, want_norm=False)

@@ -45,6 +45,80 @@ def dropout_draws(p, B, N, C, heads, M):
     return ts + ops.dropout_reserve(B * heads * M * M), ts + ops.dropout_reserve(B * N * C)
 
 
+def project_fwd(xn, P, geom, engine, xn_planes=None, shape=None):
+    """[x_mid | fx_mid] [B,N,2C] of xn [B,N,C] on the geometry geom = (H, W) of attn_forward: the 3x3 conv pair, the 3x3x3
+    pair of a 3-D mesh (W = (width, depth)), the pair on the operand planes `xn_planes` (xn is then None and shape =
+    (B, N, C)), or, H None, the two Linear(C, C) of the irregular mesh as ONE GEMM with the weights stacked along the output
+    dim.  Returns (xf, kept); kept = (the operand, the stacked weight or None, (B, N, C)) is what project_bwd takes."""
+    H, W = geom
+    B, N, C = shape = tuple(xn.shape) if xn is not None else shape
+    Wm, depth = mesh_extent(W)
+    wcat = None
+    if xn_planes is not None:
+        if depth is not None:
+            raise ValueError("the operand-planes route is 3x3 only; the 3-D mesh takes the fp32 operand")
+        xf = ops.conv3x3x2_fwd_planes(xn_planes, P["wx"], P["bx"], P["wf"], P["bf"], B, H, W, engine)
+    elif H is not None and depth is not None:
+        xf = ops.conv3x3x3x2_fwd(xn, P["wx"], P["bx"], P["wf"], P["bf"], H, Wm, depth, engine=engine)
+    elif H is not None:
+        xf = ops.conv3x3x2_fwd(xn, P["wx"], P["bx"], P["wf"], P["bf"], H, W, engine=engine)
+    else:   # the stacked weight is a temporary: a weights_frozen() scope gets no entry for it
+        wcat, bcat = torch.cat((P["wx"], P["wf"]), 0), torch.cat((P["bx"], P["bf"]), 0)
+        with ops.unscoped():
+            xf = ops.linear_fwd(xn.view(B * N, C), wcat, bcat, engine=engine)[0].view(B, N, 2 * C)
+    return xf, (xn if xn_planes is None else xn_planes, wcat, shape)
+
+
+def project_bwd(dxf, kept, P, geom, engine, need_dx, into, planes):
+    """Backward of project_fwd from dxf = [dX | dF] [B,N,2C] (`planes`: its plane image, beside the operand's).  `into`:
+    (dwx, dbx, dwf, dbf) buffers to add into, or None.  Returns (dxn or None, the gradients made here as a dict: wx, bx, wf,
+    bf; on the planes route wx and wf, the bias gradients come with the slice backward)."""
+    H, W = geom
+    xn, wcat, (B, N, C) = kept
+    Wm, depth = mesh_extent(W)
+    if planes:
+        dxn, dwx, dwf = ops.conv3x3x2_bwd_planes(dxf, xn, P["wx"], P["wf"], B, H, W, engine, need_dx=need_dx,
+                                                 into=None if into is None else (into[0], into[2]))
+        return dxn, dict(wx=dwx, wf=dwf)
+    if H is not None and depth is not None:
+        dxn, dwx, dbx, dwf, dbf = ops.conv3x3x3x2_bwd(dxf, xn, P["wx"], P["wf"], H, Wm, depth, need_dx=need_dx,
+                                                      engine=engine, into=into)
+    elif H is not None:
+        dxn, dwx, dbx, dwf, dbf = ops.conv3x3x2_bwd(dxf, xn, P["wx"], P["wf"], H, W, need_dx=need_dx, engine=engine,
+                                                    into=into)
+    else:
+        dxf2 = dxf.view(B * N, 2 * C)
+        dwcat, dbcat = ops.linear_bwd_weight(dxf2, xn.view(B * N, C), engine=engine)
+        dwx, dwf, dbx, dbf = dwcat[:C].contiguous(), dwcat[C:].contiguous(), dbcat[:C].contiguous(), dbcat[C:].contiguous()
+        dxn = None
+        if need_dx:
+            with ops.unscoped():
+                dxn = ops.linear_bwd_data(dxf2, wcat, engine=engine).view(B, N, C)
+    return dxn, dict(wx=dwx, bx=dbx, wf=dwf, bf=dbf)
+
+
+def _front(xn, P, geom, heads, engine, xn_planes=None, shape=None, drop=None):
+    """The front half of a Physics-Attention layer: projection, slice scatter, token attention (`drop`: the draw of the
+    attention matrix).  Returns (xf, kept, s, nrm, o, temp): kept as of project_fwd; s, nrm, o the slice tokens, their norms
+    and the attended tokens; temp the temperature as the kernels take it.  H None: no temperature clamp."""
+    xf, kept = project_fwd(xn, P, geom, engine, xn_planes=xn_planes, shape=shape)
+    B, N, C = kept[2]
+    D, M = C // heads, P["ws"].shape[0]
+    temp = P["temperature"].reshape(heads).contiguous()
+    spart, npart = ops.slice_scatter(xf, 2 * C, 0, xf, 2 * C, C, P["ws"], P["bs"], temp, B, N, heads, D, M,
+                                     clamp=geom[0] is not None, engine=engine)
+    s, nrm, o = ops.token_attn_fwd(spart, npart, P["wq"], P["wk"], P["wv"], **({} if drop is None else dict(drop=drop)))
+    return xf, kept, s, nrm, o, temp
+
+
+def _target_lookup(targets):
+    """t(*keys): the gradient buffers of `targets` (dict key -> buffer) under those keys, as the `into` of a backward op;
+    None without targets (the op then makes fresh tensors)."""
+    if targets is None:
+        return lambda *ks: None
+    return lambda *ks: tuple(targets[k] for k in ks)
+
+
 def attn_forward(xn, P, res, H, W, heads, engine=None, xn_planes=None, shape=None, drop=None):
     """xn [B,N,C] (already layer-normed).  P: dict of parameter tensors.  Returns (out, saved).
     H is None -> irregular-mesh variant (Physics_Attention.py:6-57): Linear projections, no
@@ -54,90 +128,55 @@ def attn_forward(xn, P, res, H, W, heads, engine=None, xn_planes=None, shape=Non
     (ops.layernorm_fwd_planes); `xn` is then None and `shape` = (B, N, C).
     drop: `dropout_draws(...)` — the attention matrix is dropped inside the token kernel, and to_out runs WITHOUT the fused
     residual so that out = res + dropout(to_out(y)) (one flat launch, ops.dropout_residual)."""
-    B, N, C = xn.shape if xn is not None else shape
-    D = C // heads
-    M = P["ws"].shape[0]
-    temp = P["temperature"].reshape(heads).contiguous()
-    structured = H is not None
-    Wm, depth = mesh_extent(W)
-    if xn_planes is not None:
-        if depth is not None:
-            raise ValueError("the operand-planes route is 3x3 only; the 3-D mesh takes the fp32 operand")
-        xf = ops.conv3x3x2_fwd_planes(xn_planes, P["wx"], P["bx"], P["wf"], P["bf"], B, H, W, engine)
-    elif structured and depth is not None:
-        xf = ops.conv3x3x3x2_fwd(xn, P["wx"], P["bx"], P["wf"], P["bf"], H, Wm, depth, engine=engine)    # [B,N,2C]
-    elif structured:
-        xf = ops.conv3x3x2_fwd(xn, P["wx"], P["bx"], P["wf"], P["bf"], H, W, engine=engine)    # [B,N,2C]
-    else:   # both Linear(C, C) projections as ONE GEMM with the weights stacked along the output dim
-        wcat, bcat = torch.cat((P["wx"], P["wf"]), 0), torch.cat((P["bx"], P["bf"]), 0)
-        xf = ops.linear_fwd(xn.view(B * N, C), wcat, bcat, engine=engine)[0].view(B, N, 2 * C)
-    spart, npart = ops.slice_scatter(xf, 2 * C, 0, xf, 2 * C, C, P["ws"], P["bs"], temp, B, N, heads, D, M,
-                                     clamp=structured, engine=engine)
-    s, nrm, o = ops.token_attn_fwd(spart, npart, P["wq"], P["wk"], P["wv"], **({} if drop is None else dict(drop=drop[0])))
-    y = ops.deslice_fwd(xf, 2 * C, 0, o, P["ws"], P["bs"], temp, B, N, heads, D, M, clamp=structured, engine=engine)  # [B,N,C]
+    xf, kept, s, nrm, o, temp = _front(xn, P, (H, W), heads, engine, xn_planes, shape, None if drop is None else drop[0])
+    B, N, C = kept[2]
+    y = ops.deslice_fwd(xf, 2 * C, 0, o, P["ws"], P["bs"], temp, B, N, heads, C // heads, P["ws"].shape[0],
+                        clamp=H is not None, engine=engine)                                    # [B,N,C]
     res2d = None if res is None else res.reshape(B * N, C)
     if drop is None:
         out, _ = ops.linear_fwd(y.view(B * N, C), P["wo"], P["bo"], res=res2d, engine=engine)
     else:
         z, _ = ops.linear_fwd(y.view(B * N, C), P["wo"], P["bo"], engine=engine)
         out = ops.dropout_residual(z, res2d, drop[1])
-    return out.view(B, N, C), (xn if xn_planes is None else xn_planes, xf, s, nrm, o, y, temp)
+    return out.view(B, N, C), (kept, xf, s, nrm, o, y, temp)
 
 
 def attn_backward(saved, P, dout, H, W, heads, need_dx=True, engine=None, targets=None, planes=False, drop=None):
     """`targets`: dict ATTN_KEYS -> gradient buffer to ADD into (structured meshes), or None (fresh tensors).
-    `planes`: saved[0] is the plane image of the LayerNorm output; the slice backward then emits [dX | dF] as planes too
-    (plus the conv bias gradients) and the conv backward consumes both images directly.
+    `planes`: the saved operand is the plane image of the LayerNorm output; the slice backward then emits [dX | dF] as planes
+    too (plus the conv bias gradients) and the conv backward consumes both images directly.
     `drop`: the forward's draws; the gradient entering to_out is dout with the output mask made again (the caller keeps
-    the undropped dout as the residual gradient)."""
-    xn, xf, s, nrm, o, y, temp = saved
-    B, N, C2 = xf.shape
-    C = C2 // 2
+    the undropped dout as the residual gradient).
+    Returns (dxn, dict ATTN_KEYS -> gradient); the dict is None where the gradients went into `targets`."""
+    kept, xf, s, nrm, o, y, temp = saved
+    B, N, C = kept[2]
     D = C // heads
     M = P["ws"].shape[0]
     d2 = dout.reshape(B * N, C)
     if drop is not None:
         d2 = ops.dropout_residual(d2, None, drop[1])
     structured = H is not None
-    Wm, depth = mesh_extent(W)
-    if planes and depth is not None:
+    if planes and mesh_extent(W)[1] is not None:
         raise ValueError("the operand-planes route is 3x3 only; the 3-D mesh takes the fp32 operand")
     T = targets if structured else None
-    t = (lambda *ks: tuple(T[k] for k in ks)) if T is not None else (lambda *ks: None)
+    t = _target_lookup(T)
     dy = ops.linear_bwd_data(d2, P["wo"], engine=engine)                                      # [B*N,C]
     dwo, dbo = ops.linear_bwd_weight(d2, y.view(B * N, C), engine=engine, into=t("wo", "bo"))
     dopart, _ = ops.slice_scatter(xf, 2 * C, 0, dy, C, 0, P["ws"], P["bs"], temp, B, N, heads, D, M,
                                   want_norm=False, clamp=structured, engine=engine)
     ds, dn, dwq, dwk, dwv = ops.token_attn_bwd(s, nrm, P["wq"], P["wk"], P["wv"], dopart, into=t("wq", "wk", "wv"),
                                                **({} if drop is None else dict(drop=drop[0])))
+    g = dict(wq=dwq, wk=dwk, wv=dwv, wo=dwo, bo=dbo)
     if planes:
-        dxfp, dbx, dbf, dws, dbs, dtemp = ops.slice_bwd_points_planes(xf, dy, P["ws"], P["bs"], temp, o, ds, dn, nrm, B, N, heads,
-                                                                      D, M, engine, clamp=True,
-                                                                      into=t("bx", "bf", "ws", "bs", "temperature"))
-        dxn, dwx, dwf = ops.conv3x3x2_bwd_planes(dxfp, xn, P["wx"], P["wf"], B, H, W, engine, need_dx=need_dx,
-                                                 into=t("wx", "wf"))
-        if T is not None:
-            return dxn, None
-        return dxn, dict(temperature=dtemp.view(1, heads, 1, 1), wx=dwx, bx=dbx, wf=dwf, bf=dbf, ws=dws, bs=dbs,
-                         wq=dwq, wk=dwk, wv=dwv, wo=dwo, bo=dbo)
-    dxf, dws, dbs, dtemp = ops.slice_bwd_points(xf, dy, P["ws"], P["bs"], temp, o, ds, dn, B, N, heads, D, M,
-                                                clamp=structured, into=t("ws", "bs", "temperature"), engine=engine)
-    if structured and depth is not None:
-        dxn, dwx, dbx, dwf, dbf = ops.conv3x3x3x2_bwd(dxf, xn, P["wx"], P["wf"], H, Wm, depth, need_dx=need_dx,
-                                                      engine=engine, into=t("wx", "bx", "wf", "bf"))
-    elif structured:
-        dxn, dwx, dbx, dwf, dbf = ops.conv3x3x2_bwd(dxf, xn, P["wx"], P["wf"], H, W, need_dx=need_dx, engine=engine,
-                                                    into=t("wx", "bx", "wf", "bf"))
+        dxf, g["bx"], g["bf"], dws, dbs, dtemp = ops.slice_bwd_points_planes(
+            xf, dy, P["ws"], P["bs"], temp, o, ds, dn, nrm, B, N, heads, D, M, engine, clamp=True,
+            into=t("bx", "bf", "ws", "bs", "temperature"))
     else:
-        dxf2, xn2 = dxf.view(B * N, 2 * C), xn.view(B * N, C)
-        dwcat, dbcat = ops.linear_bwd_weight(dxf2, xn2, engine=engine)
-        dwx, dwf, dbx, dbf = dwcat[:C].contiguous(), dwcat[C:].contiguous(), dbcat[:C].contiguous(), dbcat[C:].contiguous()
-        dxn = ops.linear_bwd_data(dxf2, torch.cat((P["wx"], P["wf"]), 0), engine=engine).view(B, N, C) if need_dx else None
-    if T is not None:
-        return dxn, None
-    grads = dict(temperature=dtemp.view(1, heads, 1, 1), wx=dwx, bx=dbx, wf=dwf, bf=dbf, ws=dws, bs=dbs,
-                 wq=dwq, wk=dwk, wv=dwv, wo=dwo, bo=dbo)
-    return dxn, grads
+        dxf, dws, dbs, dtemp = ops.slice_bwd_points(xf, dy, P["ws"], P["bs"], temp, o, ds, dn, B, N, heads, D, M,
+                                                    clamp=structured, into=t("ws", "bs", "temperature"), engine=engine)
+    dxn, gproj = project_bwd(dxf, kept, P, (H, W), engine, need_dx, t("wx", "bx", "wf", "bf"), planes)
+    g.update(gproj, temperature=dtemp.view(1, heads, 1, 1), ws=dws, bs=dbs)
+    return dxn, None if T is not None else g
 
 
 def _attn_targets(params, structured):
@@ -337,23 +376,10 @@ def block_tail(fx, xn, P, H, W, heads, ln2_w, ln2_b, act, w1, b1, w2, b2, next_w
     D, M = C // heads, P["ws"].shape[0]
     c = lambda t: None if t is None else t.detach().contiguous()
     P = {k: c(v) for k, v in P.items()}
-    temp = P["temperature"].reshape(heads).contiguous()
-    structured = H is not None
-    Wm, depth = mesh_extent(W)
-    xn = c(xn)
-    if structured and depth is not None:
-        xf = ops.conv3x3x3x2_fwd(xn, P["wx"], P["bx"], P["wf"], P["bf"], H, Wm, depth, engine=engine)
-    elif structured:
-        xf = ops.conv3x3x2_fwd(xn, P["wx"], P["bx"], P["wf"], P["bf"], H, W, engine=engine)
-    else:
-        wcat, bcat = torch.cat((P["wx"], P["wf"]), 0), torch.cat((P["bx"], P["bf"]), 0)
-        xf = ops.linear_fwd(xn.view(B * N, C), wcat, bcat, engine=engine)[0].view(B, N, 2 * C)
-    spart, npart = ops.slice_scatter(xf, 2 * C, 0, xf, 2 * C, C, P["ws"], P["bs"], temp, B, N, heads, D, M,
-                                     clamp=structured, engine=engine)
-    _, _, o = ops.token_attn_fwd(spart, npart, P["wq"], P["wk"], P["wv"])
+    xf, _, _, _, o, temp = _front(c(xn), P, (H, W), heads, engine)
     out, xnext, _ = ops.block_tail_fwd(xf, 2 * C, 0, o, P["ws"], P["bs"], temp, c(fx).view(B * N, C), P["wo"], P["bo"],
                                        c(ln2_w), c(ln2_b), c(w1), c(b1), c(w2), c(b2), c(next_w), c(next_b), B, N, heads,
-                                       D, M, act, clamp=structured, engine=engine)
+                                       D, M, act, clamp=H is not None, engine=engine)
     return out.view(B, N, C), None if xnext is None else xnext.view(B, N, C)
 
 
@@ -563,41 +589,30 @@ class EncodeFn(Function):
         P = dict(zip(ENC_KEYS, (p.detach().contiguous() for p in params)))
         xn = xn.detach().contiguous()
         B, N, C = xn.shape
-        D = C // heads
-        M = P["ws"].shape[0]
-        temp = P["temperature"].reshape(heads).contiguous()
-        xf = ops.conv3x3x2_fwd(xn, P["wx"], P["bx"], P["wf"], P["bf"], H, W, engine=engine)       # [B,N,2C]
-        spart, npart = ops.slice_scatter(xf, 2 * C, 0, xf, 2 * C, C, P["ws"], P["bs"], temp, B, N, heads, D, M,
-                                         clamp=True, engine=engine)
-        s, nrm, o = ops.token_attn_fwd(spart, npart, P["wq"], P["wk"], P["wv"])
-        ctx.P, ctx.saved, ctx.geom, ctx.params = P, (xn, xf, s, nrm, o, temp), (H, W, heads, engine), params
-        return o.view(B, heads, M, D), xf[:, :, :C]
+        xf, kept, s, nrm, o, temp = _front(xn, P, (H, W), heads, engine)                          # xf [B,N,2C]
+        ctx.P, ctx.saved, ctx.geom, ctx.params = P, (kept, xf, s, nrm, o, temp), (H, W, heads, engine), params
+        return o.view(B, heads, P["ws"].shape[0], C // heads), xf[:, :, :C]
 
     @staticmethod
     def backward(ctx, dcode, dxm):
         H, W, heads, engine = ctx.geom
         P = ctx.P
-        xn, xf, s, nrm, o, temp = ctx.saved
-        B, N, C = xn.shape
+        kept, xf, s, nrm, o, temp = ctx.saved
+        B, N, C = kept[2]
         D = C // heads
         M = P["ws"].shape[0]
         tg = grad_targets(ctx.params)
-        T = None if tg is None else dict(zip(ENC_KEYS, tg))
-        t = (lambda *ks: tuple(T[k] for k in ks)) if T is not None else (lambda *ks: None)
+        t = _target_lookup(None if tg is None else dict(zip(ENC_KEYS, tg)))
         dop = (dcode.contiguous() if dcode is not None else torch.zeros_like(o)).view(B * heads, 1, M, D)
         ds, dn, dwq, dwk, dwv = ops.token_attn_bwd(s, nrm, P["wq"], P["wk"], P["wv"], dop, into=t("wq", "wk", "wv"))
-        dy0 = torch.zeros(B, N, C, dtype=torch.float32, device=xn.device)
+        dy0 = torch.zeros(B, N, C, dtype=torch.float32, device=xf.device)
         dxf, dws, dbs, dtemp = ops.slice_bwd_points(xf, dy0, P["ws"], P["bs"], temp, o, ds, dn, B, N, heads, D, M,
                                                     clamp=True, into=t("ws", "bs", "temperature"), engine=engine)
         if dxm is not None:
             dxf[:, :, :C] += dxm
-        dxn, dwx, dbx, dwf, dbf = ops.conv3x3x2_bwd(dxf, xn, P["wx"], P["wf"], H, W, need_dx=ctx.needs_input_grad[0],
-                                                    engine=engine, into=t("wx", "bx", "wf", "bf"))
-        if T is not None:
-            return (dxn, None, None, None, None) + tuple(None for _ in ENC_KEYS)
-        g = dict(temperature=dtemp.view(1, heads, 1, 1), wx=dwx, bx=dbx, wf=dwf, bf=dbf, ws=dws, bs=dbs, wq=dwq, wk=dwk,
-                 wv=dwv)
-        return (dxn, None, None, None, None) + tuple(g[k] for k in ENC_KEYS)
+        dxn, g = project_bwd(dxf, kept, P, (H, W), engine, ctx.needs_input_grad[0], t("wx", "bx", "wf", "bf"), False)
+        g.update(temperature=dtemp.view(1, heads, 1, 1), ws=dws, bs=dbs, wq=dwq, wk=dwk, wv=dwv)
+        return (dxn, None, None, None, None) + tuple(None if tg is not None else g[k] for k in ENC_KEYS)
 
 
 class SliceWeightsFn(Function):
@@ -650,7 +665,8 @@ class ToOutTwiceFn(Function):
         shp = y.shape
         y2d = y.detach().reshape(-1, shp[-1]).contiguous()
         w2, b2 = 2.0 * w.detach(), 2.0 * b.detach()
-        out, _ = ops.linear_fwd(y2d, w2, b2, engine=engine)
+        with ops.unscoped():      # the doubled weight is a temporary: a weights_frozen() scope gets no entry for it
+            out, _ = ops.linear_fwd(y2d, w2, b2, engine=engine)
         ctx.saved, ctx.shp, ctx.engine = (y2d, w2), shp, engine
         return out.view(*shp[:-1], w.shape[0])
 
@@ -658,8 +674,10 @@ class ToOutTwiceFn(Function):
     def backward(ctx, dout):
         y2d, w2 = ctx.saved
         d2 = dout.reshape(-1, w2.shape[0]).contiguous()
-        dy = ops.linear_bwd_data(d2, w2, engine=ctx.engine).view(ctx.shp) if ctx.needs_input_grad[0] else None
-        dw = db = None
+        dy = dw = db = None
+        if ctx.needs_input_grad[0]:
+            with ops.unscoped():
+                dy = ops.linear_bwd_data(d2, w2, engine=ctx.engine).view(ctx.shp)
         if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
             dw, db = ops.linear_bwd_weight(d2, y2d, engine=ctx.engine)
             dw.mul_(2.0)

@@ -8,8 +8,16 @@ CPU path (the CPU restatement lives in oracle/ and is test infrastructure only).
 Parameter-gradient outputs: every backward op takes `into=` — a tuple of existing gradient buffers (the
 views of the flat gradient bucket) that the kernels ADD to (`accumulate = 1` in the C ABI); without it the
 op allocates fresh tensors and overwrites them.
+
+Weight packs and images: inside `weights_frozen()` everything derived from a weight (conv packs, GEMM weight images, the
+fused tail's images) is made once and kept in the scope's one table (`_scoped`); outside a scope each call derives it in its
+own workspace.  `weights_frozen(scope)` enters a kept scope again, with the entries it already holds.  Under `unscoped()` a
+call behaves as outside any scope: for calls on a temporary weight, which a scope would keep alive and never hit again.
 """
 from __future__ import annotations
+
+from types import MappingProxyType
+from typing import NamedTuple
 
 import torch
 
@@ -155,6 +163,13 @@ def layernorm_bwd(dy, x2d, mean, rstd, gamma, dres=None, into=None):
 ACT_SAVE_DERIVATIVE = 0x100      # include/pa2d.h: PA2D_ACT_SAVE_DERIVATIVE
 
 
+def _make_image(img, w, transposed, N, K, eng):
+    """Plane image of w for the row-stationary linear kernel; N, K: the GEMM's output width and contraction length (forward:
+    the layer's [N, K]; data gradient: [K, N])."""
+    _lib.check(_L().pa2d_gemm_weight_image(_p(w), w.shape[1], transposed, img.data_ptr(), img.numel(), N, K, eng, _stream()),
+               "gemm_weight_image")
+
+
 def linear_fwd(x2d, w, bias=None, res=None, act=None, want_pre=False, engine=None, save_derivative=False):
     """y = act(x . w^T + bias) (+ res); returns (y, pre) with pre = pre-activation if want_pre — or act'(pre-activation)
     with save_derivative (what `linear_bwd_data(..., pre_is_derivative=True)` multiplies by)."""
@@ -171,7 +186,8 @@ def linear_fwd(x2d, w, bias=None, res=None, act=None, want_pre=False, engine=Non
     else:
         eng = _abi_engine(engine)
         nb = _L().pa2d_gemm_fwd_workspace(N, K, eng)
-        img = _lin_image(w, 0, N, K, eng, nb)              # inside weights_frozen(): made once per weight
+        # inside weights_frozen(): the weight image is made once per weight (0 = the call makes it in its scratch)
+        img = _scoped(("image", w.data_ptr(), 0, N, K, eng), nb, _make_image, (w,), w, 0, N, K, eng)
         ws = _ws(nb, x2d) if (nb and not img) else None
         _lib.check(_L().pa2d_gemm_bias_act_fwd(_p(x2d), K, _p(w), w.shape[1], _p(bias), _p(res), N, _p(y), N, _p(pre), N,
                                                img, _p(ws), nb if ws is not None else 0, M, N, K, ACT_IDS[act] | aflag, eng,
@@ -194,7 +210,7 @@ def linear_bwd_data(dy, w, pre=None, act=None, engine=None, pre_is_derivative=Fa
     else:
         eng = _abi_engine(engine)
         nimg = _L().pa2d_gemm_fwd_workspace(K, N, eng)     # the data gradient is a GEMM of output width K, contraction N
-        img = _lin_image(w, 1, K, N, eng, nimg)
+        img = _scoped(("image", w.data_ptr(), 1, K, N, eng), nimg, _make_image, (w,), w, 1, K, N, eng)
         nb = _L().pa2d_gemm_bwd_data_workspace(N, K, eng) - (nimg if img else 0)      # [transposed weight | image unless ready-made]
         ws = _ws(nb, dy)
         _lib.check(_L().pa2d_gemm_bwd_data(_p(dy), N, _p(w), K, _p(pre), K, ACT_IDS[act] | aflag, _p(dx), K, img, ws.data_ptr(), nb,
@@ -233,44 +249,49 @@ def linear_bwd_weight(dy, x2d, want_bias=True, engine=None, into=None):
     return dw, db
 
 
-# ---------------------------------------------------------------------------------------------- conv weight packs
+# ---------------------------------------------------------------------------------------------- weights_frozen()
 class _FrozenScope:
-    """Book-keeping of one `weights_frozen()` scope: packs made inside it, keyed by (weights, dims, direction,
-    engine) — the pack layout depends on the engine, which is part of the key, so models on different engines
-    can share a scope.  The dims include the depth of a 3-D mesh (None for the 3x3 conv): a 2-D and a 3-D model in
-    one scope never share a pack."""
+    """Book-keeping of one `weights_frozen()` scope: ONE table of everything derived from a weight inside it (conv packs,
+    GEMM weight images, the fused tail's images), key -> (kept tensors, buffer, remake).  The key is the kind ("pack",
+    "pack1", "image"), the weights' addresses and all the layout depends on: the dims (with the depth of a 3-D mesh, None for
+    the 3x3 conv: a 2-D and a 3-D model in one scope never share a pack), the direction and the engine (so models on different
+    engines can share a scope).  The kept tensors are those weights (their addresses stay theirs); remake() derives the
+    buffer again, in place."""
 
     def __init__(self):
-        self.packs = {}
-        self.packs1 = {}      # packs of the single 3x3 conv (pa2d_conv3x3_pack): (w ptr, B, H, W, C, direction, engine)
-        self.images = {}      # weight plane images of the row-stationary linear kernel: (w ptr, transposed, N, K, engine);
-        #                       transposed = "tail": the fused block tail's image of the same weight (block_tail_fwd)
+        self.table = {}
 
     def refresh(self):
-        """Re-pack every entry in place (same device pointers): called before replaying a hipGraph that was captured
-        inside this scope, so the graph's conv launches always see the current weights."""
-        for (_, _, B, H, W, depth, Cc, direction, eng), (wx, wf, pack) in self.packs.items():
-            _make_pack(wx, wf, pack, B, H, W, Cc, direction, eng, depth)
-        for (_, B, H, W, Cc, direction, eng), (w, pack) in self.packs1.items():
-            _make_pack1(w, pack, B, H, W, Cc, direction, eng)
-        for (_, transposed, N, K, eng), (w, img) in self.images.items():
-            if transposed == "tail":      # fragment-order image of the fused block tail
-                _make_tail_image(w, img, N, K, eng)
-            else:
-                _make_image(w, transposed, img, N, K, eng)
+        """Re-make every entry in place (same device pointers): called before replaying a hipGraph that was captured
+        inside this scope, so the graph's launches always see the current weights."""
+        for _, _, remake in self.table.values():
+            remake()
+
+    def _view(self, kind):
+        return MappingProxyType({k[1:]: keep + (buf,) for k, (keep, buf, _) in self.table.items() if k[0] == kind})
+
+    # read-only views of the table, one per kind: the key without the kind -> (weights..., buffer)
+    packs = property(lambda self: self._view("pack"))      # (wx ptr, wf ptr, B, H, W, depth, C, direction, engine) -> (wx, wf, pack)
+    packs1 = property(lambda self: self._view("pack1"))    # single 3x3 conv: (w ptr, B, H, W, C, direction, engine) -> (w, pack)
+    images = property(lambda self: self._view("image"))    # (w ptr, transposed, N, K, engine) -> (w, image) of the row-stationary
+    #                                                        linear; transposed = "tail": the fused block tail's image of w
 
 
-_frozen = []      # stack of active scopes
+_frozen = []      # stack of active scopes; None: an `unscoped()` frame
 
 
 class weights_frozen:
     """Context manager declaring that no parameter changes inside it (the model calls + backward of one training
     iteration, a rollout).  Inside, the K-major pack of each layer's conv weights is built on first use and
     reused by later calls; outside a scope every conv call packs its weights itself (always correct, whatever
-    changed the weights).  `with weights_frozen() as scope:` exposes `scope.refresh()`."""
+    changed the weights).  `with weights_frozen() as scope:` exposes `scope.refresh()`; `weights_frozen(scope)` enters that
+    scope again, with the entries it already holds."""
+
+    def __init__(self, scope=None):
+        self.scope = scope
 
     def __enter__(self):
-        _frozen.append(_FrozenScope())
+        _frozen.append(_FrozenScope() if self.scope is None else self.scope)
         return _frozen[-1]
 
     def __exit__(self, *exc):
@@ -278,121 +299,133 @@ class weights_frozen:
         return False
 
 
-def _make_image(w, transposed, img, N, K, eng):
-    _lib.check(_L().pa2d_gemm_weight_image(_p(w), w.shape[1], transposed, img.data_ptr(), img.numel(), N, K, eng, _stream()),
-               "gemm_weight_image")
+class unscoped:
+    """Context manager under which every op behaves as outside any scope (a null frame on the stack): for calls on a
+    temporary weight (a concatenation, a scaled copy), which a scope would keep alive and re-make without ever hitting it."""
+
+    def __enter__(self):
+        _frozen.append(None)
+
+    def __exit__(self, *exc):
+        _frozen.pop()
+        return False
 
 
-def _lin_image(w, transposed, N, K, eng, nbytes):
-    """Image pointer for the active `weights_frozen()` scope (0 = let the GEMM call make it in its scratch): N, K are
-    the GEMM's output width and contraction length (forward: the layer's [N, K]; data gradient: [K, N])."""
-    if not _frozen or not nbytes:
+def _active():
+    """The scope that `_scoped` fills, or None (no scope, or under `unscoped()`)."""
+    return _frozen[-1] if _frozen else None
+
+
+def _scoped(key, nbytes, make, keep, *args):
+    """Device pointer of the buffer that `make(buffer, *args)` fills from the weights `keep`: made once per `key` in the
+    active scope and re-made by its refresh().  0 without a scope, or where the buffer has no bytes: the call then derives it
+    in its own workspace.  nbytes: a number, or a function that is asked for it only when the buffer has to be made."""
+    scope = _active()
+    if scope is None or nbytes == 0:
         return 0
-    scope = _frozen[-1]
-    key = (w.data_ptr(), transposed, N, K, eng)
-    hit = scope.images.get(key)
+    hit = scope.table.get(key)
     if hit is None:
-        img = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
-        _make_image(w, transposed, img, N, K, eng)
-        hit = scope.images[key] = (w, img)
+        buf = torch.empty(nbytes() if callable(nbytes) else nbytes, dtype=torch.uint8, device=keep[0].device)
+        make(buf, *args)
+        hit = scope.table[key] = (keep, buf, lambda: make(buf, *args))
     return hit[1].data_ptr()
 
 
-def _make_pack(wx, wf, pack, B, H, W, Cc, direction, eng, depth=None):
-    """eng = ENGINE_BF16S: the pack of the bf16-storage conv entry points (always the bf16 kernels' layout);
-    depth (not None): the 3x3x3 conv of a [B, H, W, depth] mesh."""
-    if depth is not None:
-        _lib.check(_L().pa2d_conv3x3x3x2_pack(_p(wx), _p(wf), pack.data_ptr(), pack.numel(), B, H, W, depth, Cc, direction,
-                                              eng, _stream()), "conv3x3x3x2_pack")
-    elif eng == ENGINE_BF16S:
-        _lib.check(_L().pa2d_conv3x3x2_pack_bf16(_p(wx), _p(wf), pack.data_ptr(), pack.numel(), Cc, direction, _stream()),
-                   "conv3x3x2_pack_bf16")
-    else:
-        _lib.check(_L().pa2d_conv3x3x2_pack(_p(wx), _p(wf), pack.data_ptr(), pack.numel(), B, H, W, Cc, direction, eng,
-                                            _stream()), "conv3x3x2_pack")
+# ---------------------------------------------------------------------------------------------- convs
+class _Conv(NamedTuple):
+    """One family of conv entry points of the C ABI, by the names of its symbols."""
+    nw: int             # weights per call: 1 (the single conv) or 2 (the x / fx pair, output [.., 2C])
+    depth: bool         # dims are (B, H, W, depth, C): the 3x3x3 conv of a [B, H, W, depth] mesh
+    bf16: bool          # has *_bf16 twins for bf16 storage (no engine argument; the bf16 kernels' pack layout, no dims)
+    planes: bool        # the operands arrive as bf16 plane images; the bias gradients are made elsewhere
+    pack_bytes: str
+    pack: str
+    fwd: str
+    bwd: str
+    fwd_ws: str         # workspace query of the forward (from planes: one pack) ...
+    bwd_ws: str         # ... and of the backward
 
 
-def _conv_pack(wx, wf, B, H, W, Cc, direction, eng, depth=None):
-    """Pack pointer for the active scope (0 = let the conv call pack into its workspace)."""
-    if not _frozen:
+def _conv_kind(stem, nw, depth=False, bf16=False, planes=False):
+    p, sfx = "pa2d_" + stem, "_planes" if planes else ""
+    return _Conv(nw, depth, bf16, planes, p + "_pack_bytes", p + "_pack", p + "_fwd" + sfx, p + "_bwd" + sfx,
+                 p + ("_pack_bytes" if planes else "_fwd_workspace"), p + "_workspace" + sfx)
+
+
+_PAIR = _conv_kind("conv3x3x2", 2, bf16=True)
+_SINGLE = _conv_kind("conv3x3", 1)        # in_project_x of the conv slice predictors: one Conv2d(C, C, 3, 1, 1), fp32 storage only
+_PAIR3D = _conv_kind("conv3x3x3x2", 2, depth=True)
+_PLANES = _conv_kind("conv3x3x2", 2, planes=True)      # shares the packs of _PAIR
+
+
+def _make_pack(pack, kind, weights, dims, direction, eng, b16):
+    name = kind.pack + "_bf16" if b16 else kind.pack
+    tail = (dims[-1], direction) if b16 else dims + (direction, eng)
+    _lib.check(getattr(_L(), name)(*[_p(w) for w in weights], pack.data_ptr(), pack.numel(), *tail, _stream()), name[5:])
+
+
+def _conv_pack(kind, weights, dims, direction, eng, b16):
+    """Pack pointer for the active scope (0 = let the conv call pack into its workspace).  b16: the pack of the
+    bf16-storage entry points (eng is ENGINE_BF16S then)."""
+    if _active() is None:
         return 0
-    scope = _frozen[-1]
-    key = (wx.data_ptr(), wf.data_ptr(), B, H, W, depth, Cc, direction, eng)
-    hit = scope.packs.get(key)
-    if hit is None:
-        nb = _L().pa2d_conv3x3x2_pack_bytes(Cc) if depth is None else _L().pa2d_conv3x3x3x2_pack_bytes(Cc)
-        pack = torch.empty(nb, dtype=torch.uint8, device=wx.device)
-        _make_pack(wx, wf, pack, B, H, W, Cc, direction, eng, depth)
-        hit = scope.packs[key] = (wx, wf, pack)
-    return hit[2].data_ptr()
+    if kind.nw == 1:
+        key = ("pack1", weights[0].data_ptr()) + dims + (direction, eng)
+    else:
+        key = ("pack", weights[0].data_ptr(), weights[1].data_ptr()) + dims[:3] + (dims[3] if kind.depth else None, dims[-1],
+                                                                                   direction, eng)
+    return _scoped(key, lambda: getattr(_L(), kind.pack_bytes)(dims[-1]), _make_pack, weights, kind, weights, dims, direction,
+                   eng, b16)
+
+
+def _conv_fwd(kind, x, wb, N, dims, eng):
+    """The forward of every conv kind: x [B, N, C] (or its plane image), wb = (w, b) per weight, dims = (B, H, W[, depth],
+    C), eng as resolved by the wrapper.  Returns [B, N, nw * C] of x's storage type (fp32 from planes)."""
+    L, Cc, b16 = _L(), dims[-1], kind.bf16 and eng == ENGINE_BF16S
+    sfx, eargs = ("_bf16", ()) if b16 else ("", (eng,))
+    out = torch.empty(dims[0], N, kind.nw * Cc, dtype=torch.float32 if kind.planes else x.dtype, device=x.device)
+    pre = _conv_pack(kind, wb[::2], dims, 0, eng, b16)
+    e0, e1 = _events("conv")
+    nb = getattr(L, kind.fwd_ws + sfx)(*((Cc,) if kind.planes else dims + eargs))
+    ws = _ws(nb, x)
+    name = kind.fwd + sfx
+    _lib.check(getattr(L, name)(_p(x), *[_p(t) for t in wb], _p(out), pre, ws.data_ptr(), nb, *dims, *eargs, _stream(), e0, e1),
+               name[5:])
+    return out
+
+
+def _conv_bwd(kind, dout, x, weights, N, dims, eng, need_dx, into):
+    """The backward of every conv kind: returns (dx [B, N, C] or None, then per weight dw, db — dw only from planes);
+    `into`: those parameter gradients' buffers, to accumulate into."""
+    L, Cc, b16 = _L(), dims[-1], kind.bf16 and eng == ENGINE_BF16S
+    sfx, eargs = ("_bf16", ()) if b16 else ("", (eng,))
+    dx = torch.empty(dims[0], N, Cc, dtype=torch.float32 if kind.planes else x.dtype, device=x.device) if need_dx else None
+    shapes = [w.shape for w in weights] if kind.planes else [s for w in weights for s in (w.shape, (Cc,))]
+    grads, acc = _grad_outputs(into, shapes, x)
+    pre = _conv_pack(kind, weights, dims, 1, eng, b16) if need_dx else 0
+    e0, e1 = _events("conv") if need_dx else (0, 0)
+    nb = getattr(L, kind.bwd_ws + sfx)(*dims, *eargs)
+    ws = _ws(nb, x)
+    name = kind.bwd + sfx
+    _lib.check(getattr(L, name)(_p(dout), _p(x), *[_p(w) for w in weights], _p(dx), *[_p(g) for g in grads], pre,
+                                ws.data_ptr(), nb, *dims, acc, *eargs, _stream(), e0, e1), name[5:])
+    return (dx,) + grads
 
 
 def conv3x3x2_fwd(xn, wx, bx, wf, bf, H, W, engine=None):
     """xn [B,N,C] -> [B,N,2C] = [x_mid | fx_mid]."""
     _chk(wx, bx, wf, bf)
-    b16 = _chk_act(xn)
+    eng = ENGINE_BF16S if _chk_act(xn) else _abi_engine(engine)
     B, N, Cc = xn.shape
-    eng = ENGINE_BF16S if b16 else _abi_engine(engine)
-    out = torch.empty(B, N, 2 * Cc, dtype=xn.dtype, device=xn.device)
-    pre = _conv_pack(wx, wf, B, H, W, Cc, 0, eng)
-    e0, e1 = _events("conv")
-    if b16:
-        nb = _L().pa2d_conv3x3x2_fwd_workspace_bf16(B, H, W, Cc)
-        ws = _ws(nb, xn)
-        _lib.check(_L().pa2d_conv3x3x2_fwd_bf16(_p(xn), _p(wx), _p(bx), _p(wf), _p(bf), _p(out), pre, ws.data_ptr(), nb,
-                                                B, H, W, Cc, _stream(), e0, e1), "conv3x3x2_fwd_bf16")
-        return out
-    nb = _L().pa2d_conv3x3x2_fwd_workspace(B, H, W, Cc, eng)
-    ws = _ws(nb, xn)
-    _lib.check(_L().pa2d_conv3x3x2_fwd(_p(xn), _p(wx), _p(bx), _p(wf), _p(bf), _p(out), pre, ws.data_ptr(), nb,
-                                       B, H, W, Cc, eng, _stream(), e0, e1), "conv3x3x2_fwd")
-    return out
+    return _conv_fwd(_PAIR, xn, (wx, bx, wf, bf), N, (B, H, W, Cc), eng)
 
 
 def conv3x3x2_bwd(dout, xn, wx, wf, H, W, need_dx=True, engine=None, into=None):
     """Returns (dxn, dwx, dbx, dwf, dbf); `into` = (dwx, dbx, dwf, dbf) buffers to accumulate into."""
     _chk(wx, wf)
-    b16 = _chk_act(dout, xn)
+    eng = ENGINE_BF16S if _chk_act(dout, xn) else _abi_engine(engine)
     B, N, Cc = xn.shape
-    eng = ENGINE_BF16S if b16 else _abi_engine(engine)
-    dxn = torch.empty_like(xn) if need_dx else None
-    (dwx, dbx, dwf, dbf), acc = _grad_outputs(into, (wx.shape, (Cc,), wf.shape, (Cc,)), xn)
-    pre = _conv_pack(wx, wf, B, H, W, Cc, 1, eng) if need_dx else 0
-    e0, e1 = _events("conv") if need_dx else (0, 0)
-    if b16:
-        nb = _L().pa2d_conv3x3x2_workspace_bf16(B, H, W, Cc)
-        ws = _ws(nb, xn)
-        _lib.check(_L().pa2d_conv3x3x2_bwd_bf16(_p(dout), _p(xn), _p(wx), _p(wf), _p(dxn), _p(dwx), _p(dbx), _p(dwf),
-                                                _p(dbf), pre, ws.data_ptr(), nb, B, H, W, Cc, acc, _stream(), e0, e1),
-                   "conv3x3x2_bwd_bf16")
-        return dxn, dwx, dbx, dwf, dbf
-    nb = _L().pa2d_conv3x3x2_workspace(B, H, W, Cc, eng)
-    ws = _ws(nb, xn)
-    _lib.check(_L().pa2d_conv3x3x2_bwd(_p(dout), _p(xn), _p(wx), _p(wf), _p(dxn), _p(dwx), _p(dbx), _p(dwf), _p(dbf),
-                                       pre, ws.data_ptr(), nb, B, H, W, Cc, acc, eng, _stream(), e0, e1),
-               "conv3x3x2_bwd")
-    return dxn, dwx, dbx, dwf, dbf
-
-
-# ---------------------------------------------------------------------------------------------- single 3x3 conv
-# in_project_x of the conv slice predictors (pa2d_conv3x3_*): one Conv2d(C, C, 3, 1, 1), fp32 storage only.
-def _make_pack1(w, pack, B, H, W, Cc, direction, eng):
-    _lib.check(_L().pa2d_conv3x3_pack(_p(w), pack.data_ptr(), pack.numel(), B, H, W, Cc, direction, eng, _stream()),
-               "conv3x3_pack")
-
-
-def _conv1_pack(w, B, H, W, Cc, direction, eng):
-    """Pack pointer for the active weights_frozen scope (0 = let the conv call pack into its workspace)."""
-    if not _frozen:
-        return 0
-    scope = _frozen[-1]
-    key = (w.data_ptr(), B, H, W, Cc, direction, eng)
-    hit = scope.packs1.get(key)
-    if hit is None:
-        pack = torch.empty(_L().pa2d_conv3x3_pack_bytes(Cc), dtype=torch.uint8, device=w.device)
-        _make_pack1(w, pack, B, H, W, Cc, direction, eng)
-        hit = scope.packs1[key] = (w, pack)
-    return hit[1].data_ptr()
+    return _conv_bwd(_PAIR, dout, xn, (wx, wf), N, (B, H, W, Cc), eng, need_dx, into)
 
 
 def _conv1_engine(engine, *acts):
@@ -408,14 +441,7 @@ def conv3x3_fwd(xn, w, b, H, W, engine=None):
     B, N, Cc = xn.shape
     if N != H * W or tuple(w.shape) != (Cc, Cc, 3, 3):
         raise ValueError(f"need xn [B, H*W, C] and w [C, C, 3, 3]; got {tuple(xn.shape)}, {tuple(w.shape)}, H*W = {H * W}")
-    out = torch.empty(B, N, Cc, dtype=torch.float32, device=xn.device)
-    pre = _conv1_pack(w, B, H, W, Cc, 0, eng)
-    nb = _L().pa2d_conv3x3_fwd_workspace(B, H, W, Cc, eng)
-    ws = _ws(nb, xn)
-    e0, e1 = _events("conv")
-    _lib.check(_L().pa2d_conv3x3_fwd(_p(xn), _p(w), _p(b), _p(out), pre, ws.data_ptr(), nb, B, H, W, Cc, eng, _stream(),
-                                     e0, e1), "conv3x3_fwd")
-    return out
+    return _conv_fwd(_SINGLE, xn, (w, b), N, (B, H, W, Cc), eng)
 
 
 def conv3x3_bwd(dout, xn, w, H, W, need_dx=True, engine=None, into=None):
@@ -424,15 +450,7 @@ def conv3x3_bwd(dout, xn, w, H, W, need_dx=True, engine=None, into=None):
     B, N, Cc = xn.shape
     if N != H * W or dout.shape != xn.shape:
         raise ValueError(f"need xn, dout [B, H*W, C]; got {tuple(xn.shape)}, {tuple(dout.shape)}")
-    dxn = torch.empty_like(xn) if need_dx else None
-    (dw, db), acc = _grad_outputs(into, (w.shape, (Cc,)), xn)
-    pre = _conv1_pack(w, B, H, W, Cc, 1, eng) if need_dx else 0
-    nb = _L().pa2d_conv3x3_workspace(B, H, W, Cc, eng)
-    ws = _ws(nb, xn)
-    e0, e1 = _events("conv") if need_dx else (0, 0)
-    _lib.check(_L().pa2d_conv3x3_bwd(_p(dout), _p(xn), _p(w), _p(dxn), _p(dw), _p(db), pre, ws.data_ptr(), nb, B, H, W, Cc,
-                                     acc, eng, _stream(), e0, e1), "conv3x3_bwd")
-    return dxn, dw, db
+    return _conv_bwd(_SINGLE, dout, xn, (w,), N, (B, H, W, Cc), eng, need_dx, into)
 
 
 def _conv3d_engine(engine, *acts):
@@ -450,14 +468,7 @@ def conv3x3x3x2_fwd(xn, wx, bx, wf, bf, H, W, depth, engine=None):
     B, N, Cc = xn.shape
     if N != H * W * depth:
         raise ValueError(f"conv3x3x3x2_fwd: N = {N} is not H*W*depth = {H}*{W}*{depth}")
-    out = torch.empty(B, N, 2 * Cc, dtype=xn.dtype, device=xn.device)
-    pre = _conv_pack(wx, wf, B, H, W, Cc, 0, eng, depth)
-    e0, e1 = _events("conv")
-    nb = _L().pa2d_conv3x3x3x2_fwd_workspace(B, H, W, depth, Cc, eng)
-    ws = _ws(nb, xn)
-    _lib.check(_L().pa2d_conv3x3x3x2_fwd(_p(xn), _p(wx), _p(bx), _p(wf), _p(bf), _p(out), pre, ws.data_ptr(), nb,
-                                         B, H, W, depth, Cc, eng, _stream(), e0, e1), "conv3x3x3x2_fwd")
-    return out
+    return _conv_fwd(_PAIR3D, xn, (wx, bx, wf, bf), N, (B, H, W, depth, Cc), eng)
 
 
 def conv3x3x3x2_bwd(dout, xn, wx, wf, H, W, depth, need_dx=True, engine=None, into=None):
@@ -468,16 +479,7 @@ def conv3x3x3x2_bwd(dout, xn, wx, wf, H, W, depth, need_dx=True, engine=None, in
     B, N, Cc = xn.shape
     if N != H * W * depth:
         raise ValueError(f"conv3x3x3x2_bwd: N = {N} is not H*W*depth = {H}*{W}*{depth}")
-    dxn = torch.empty_like(xn) if need_dx else None
-    (dwx, dbx, dwf, dbf), acc = _grad_outputs(into, (wx.shape, (Cc,), wf.shape, (Cc,)), xn)
-    pre = _conv_pack(wx, wf, B, H, W, Cc, 1, eng, depth) if need_dx else 0
-    e0, e1 = _events("conv") if need_dx else (0, 0)
-    nb = _L().pa2d_conv3x3x3x2_workspace(B, H, W, depth, Cc, eng)
-    ws = _ws(nb, xn)
-    _lib.check(_L().pa2d_conv3x3x3x2_bwd(_p(dout), _p(xn), _p(wx), _p(wf), _p(dxn), _p(dwx), _p(dbx), _p(dwf), _p(dbf),
-                                         pre, ws.data_ptr(), nb, B, H, W, depth, Cc, acc, eng, _stream(), e0, e1),
-               "conv3x3x3x2_bwd")
-    return dxn, dwx, dbx, dwf, dbf
+    return _conv_bwd(_PAIR3D, dout, xn, (wx, wf), N, (B, H, W, depth, Cc), eng, need_dx, into)
 
 
 # ---------------------------------------------------------------------------------------------- operand planes
@@ -508,34 +510,13 @@ def layernorm_fwd_planes(x2d, gamma, beta, engine, eps=LN_EPS):
 def conv3x3x2_fwd_planes(xn_planes, wx, bx, wf, bf, B, H, W, engine):
     """[x_mid | fx_mid] [B, H*W, 2C] fp32 from the plane image of the LayerNorm output."""
     _chk(wx, bx, wf, bf)
-    Cc = wx.shape[0]
-    eng = _abi_engine(engine)
-    out = torch.empty(B, H * W, 2 * Cc, dtype=torch.float32, device=wx.device)
-    pre = _conv_pack(wx, wf, B, H, W, Cc, 0, eng)
-    nb = _L().pa2d_conv3x3x2_pack_bytes(Cc)
-    ws = _ws(nb, wx)
-    e0, e1 = _events("conv")
-    _lib.check(_L().pa2d_conv3x3x2_fwd_planes(xn_planes.data_ptr(), _p(wx), _p(bx), _p(wf), _p(bf), _p(out), pre,
-                                              ws.data_ptr(), nb, B, H, W, Cc, eng, _stream(), e0, e1),
-               "conv3x3x2_fwd_planes")
-    return out
+    return _conv_fwd(_PLANES, xn_planes, (wx, bx, wf, bf), H * W, (B, H, W, wx.shape[0]), _abi_engine(engine))
 
 
 def conv3x3x2_bwd_planes(dout_planes, xn_planes, wx, wf, B, H, W, engine, need_dx=True, into=None):
     """(dxn, dwx, dwf) from plane images of dOut and X; `into` = (dwx, dwf) buffers to accumulate into."""
     _chk(wx, wf)
-    Cc = wx.shape[0]
-    eng = _abi_engine(engine)
-    dxn = torch.empty(B, H * W, Cc, dtype=torch.float32, device=wx.device) if need_dx else None
-    (dwx, dwf), acc = _grad_outputs(into, (wx.shape, wf.shape), wx)
-    nb = _L().pa2d_conv3x3x2_workspace_planes(B, H, W, Cc, eng)
-    ws = _ws(nb, wx)
-    pre = _conv_pack(wx, wf, B, H, W, Cc, 1, eng) if need_dx else 0
-    e0, e1 = _events("conv") if need_dx else (0, 0)
-    _lib.check(_L().pa2d_conv3x3x2_bwd_planes(dout_planes.data_ptr(), xn_planes.data_ptr(), _p(wx), _p(wf), _p(dxn), _p(dwx),
-                                              _p(dwf), pre, ws.data_ptr(), nb, B, H, W, Cc, acc, eng, _stream(), e0, e1),
-               "conv3x3x2_bwd_planes")
-    return dxn, dwx, dwf
+    return _conv_bwd(_PLANES, dout_planes, xn_planes, (wx, wf), H * W, (B, H, W, wx.shape[0]), _abi_engine(engine), need_dx, into)
 
 
 def slice_bwd_points_planes(xf, dy, ws_w, bs, temperature, o, ds, dn, nrm, B, N, heads, D, M, engine, clamp=True, into=None):
@@ -710,25 +691,9 @@ def block_tail_supported(Cc, heads, D, M, hidden, act, engine=None):
     return bool(_L().pa2d_block_tail_supported(Cc, heads, D, M, hidden, ACT_IDS[act], eng))
 
 
-def _make_tail_image(w, img, N, K, eng):
+def _make_tail_image(img, w, N, K, eng):
     _lib.check(_L().pa2d_block_tail_weight_image(_p(w), w.shape[1], img.data_ptr(), img.numel(), N, K, eng, _stream()),
                "block_tail_weight_image")
-
-
-def _tail_image(w, eng):
-    """Image pointer for the active `weights_frozen()` scope (made once per weight, re-made by scope.refresh());
-    0 outside a scope: the call then makes the image in its workspace."""
-    if not _frozen:
-        return 0
-    N, K = w.shape
-    scope = _frozen[-1]
-    key = (w.data_ptr(), "tail", N, K, eng)
-    hit = scope.images.get(key)
-    if hit is None:
-        img = torch.empty(_L().pa2d_block_tail_image_bytes(N, K), dtype=torch.uint8, device=w.device)
-        _make_tail_image(w, img, N, K, eng)
-        hit = scope.images[key] = (w, img)
-    return hit[1].data_ptr()
 
 
 def block_tail_fwd(xm, ldx, xm_off, o, ws_w, bs, temperature, fx2d, wo, bo, g2, be2, w1, b1, w2, b2, gn, bn, B, N, heads,
@@ -755,7 +720,11 @@ def block_tail_fwd(xm, ldx, xm_off, o, ws_w, bs, temperature, fx2d, wo, bo, g2, 
     y_d, a_d, h_d = dbg if dbg is not None else (None, None, None)
     imgs = (0, 0, 0)
     if _L().pa2d_block_tail_supported(Cc, heads, D, M, hidden, ACT_IDS[act], eng):
-        imgs = tuple(_tail_image(w, eng) for w in (wo, w1, w2))
+        def image(w):      # inside weights_frozen(): made once per weight, re-made by scope.refresh()
+            N, K = w.shape
+            return _scoped(("image", w.data_ptr(), "tail", N, K, eng), lambda: _L().pa2d_block_tail_image_bytes(N, K),
+                           _make_tail_image, (w,), w, N, K, eng)
+        imgs = tuple(image(w) for w in (wo, w1, w2))
     nb = 0 if all(imgs) else _L().pa2d_block_tail_workspace(Cc, hidden)
     ws = _ws(nb, xm) if nb else None
     _lib.check(_L().pa2d_block_tail_fwd(_p(xm, xm_off), ldx, _p(o), _p(ws_w), _p(bs), _p(temperature), _p(fx2d), Cc, _p(wo),
