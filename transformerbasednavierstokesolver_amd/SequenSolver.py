@@ -25,6 +25,8 @@ import torch.nn as nn
 
 from . import functional as Fn
 from . import ops
+from .LearnSlice import LearnSlice
+from .folding import _fold_group, fold_calls, groups, joined, windows
 from .model import Transolver_Structured_Mesh2D_Encoder
 from .model._core import ACTIVATION, MLP  # noqa: F401  (the reference module defines both names)
 
@@ -33,13 +35,24 @@ REFERENCE_ENCODER = dict(space_dim=2, n_layers=8, n_hidden=32, dropout=0.0, n_he
 WEIGHT_PROJECTION_HIDDEN = 64
 
 
-def fold_calls(ncalls, B, N, T, point_width, token_width):
-    """How many teacher-forced calls fit in ONE folded call (the rule of harness._fold_group): the widest per-point tensor
-    (`point_width` floats on calls*B*N rows) and the widest per-token tensor (`token_width` floats on calls*B*T rows) must
-    stay under the 4 GiB extent of a buffer descriptor."""
-    from .harness import FOLD_MAX_BYTES
-    per_call = max(4 * point_width * B * N, 4 * token_width * B * T, 1)
-    return max(1, min(ncalls, FOLD_MAX_BYTES // per_call))
+def load_frozen(source, build, *, strict, device=None, freeze=True):
+    """A checkpoint into a module that is then left in eval() with (`freeze`) no trainable parameter.  `source`: a
+    checkpoint file, a state_dict, None (nothing is loaded) or a module, which is returned untouched: the caller's own.
+    `build()` gives the module to load into; `device`: where it is moved after loading."""
+    if isinstance(source, nn.Module):
+        return source
+    module = build()
+    if source is not None:
+        if isinstance(source, (str, os.PathLike)):
+            source = torch.load(source, weights_only=True, map_location="cpu")
+        module.load_state_dict({k: torch.as_tensor(v) for k, v in source.items()}, strict=strict)
+    if device is not None:
+        module = module.to(device)
+    module.eval()
+    if freeze:
+        for param in module.parameters():
+            param.requires_grad = False
+    return module
 
 
 def encode_table(model, spatial_pos, seq, nframes, want_slices=False):
@@ -47,14 +60,11 @@ def encode_table(model, spatial_pos, seq, nframes, want_slices=False):
     only where a folded encoder tensor would pass the 4 GiB extent): tokens [B, Head, nframes, dim] and, with
     `want_slices`, every frame's slice weights [nframes*B, 1, N, M] in frame-major order.  The encoder's cached slice
     weights are left as the last frame's [B, 1, N, M], as a frame-by-frame loop leaves them."""
-    from .harness import _fold_group
     B, N = seq.shape[0], seq.shape[1]
     with torch.no_grad():
         frames = seq[..., :nframes].permute(2, 0, 1).reshape(nframes * B, N, 1)
-        chunk = _fold_group(model.encoder, B, N, nframes)
         codes, slices = [], []
-        for f0 in range(0, nframes, chunk):
-            f = min(chunk, nframes - f0)
+        for f0, f in groups(nframes, _fold_group(model.encoder, B, N, nframes)):
             pos = spatial_pos.repeat(f, *([1] * (spatial_pos.dim() - 1)))
             code = model.encoder.encode(pos, frames[f0 * B:(f0 + f) * B])
             codes.append(code.reshape(f, B, model.Head, model.dim))
@@ -62,18 +72,20 @@ def encode_table(model, spatial_pos, seq, nframes, want_slices=False):
             if want_slices:
                 slices.append(sw)
         model.encoder.set_attention_slice(sw[-B:].contiguous())
-        code = codes[0] if len(codes) == 1 else torch.cat(codes, 0)
-        tokens = code.permute(1, 2, 0, 3).contiguous()
+        tokens = joined(codes).permute(1, 2, 0, 3).contiguous()
     if not want_slices:
         return tokens
-    return tokens, (slices[0] if len(slices) == 1 else torch.cat(slices, 0))
+    return tokens, joined(slices)
 
 
-class SequenSolver(nn.Module):
+class _LatentSequence(nn.Module):
+    """What SequenSolver.SequenSolver and SequenSolverMerged.SequenSolver share.  Registration order is behaviour (the
+    state_dict's key order, the parameter order of an optimizer's bucket, the order construction draws from the RNG) and
+    the two interleave shared and own members differently, so a constructor calls the `_build_*` steps in its own order."""
+    WHAT = None                # _refuse's default subject
+    ENGINE_MODULES = ()        # the dense sub-modules that carry an `engine`
 
-    def __init__(self, transolver_path, T, W, H, M, C, B, mlp_ratio=4, layers=5, act='gelu', dropout=0., *,
-                 encoder_config=None):
-        super().__init__()
+    def _set_geometry(self, T, W, H, M, C, B, layers):
         self.T, self.W, self.H, self.M, self.C = T, W, H, M, C
         self.N = H * W
         self.B = B
@@ -84,8 +96,10 @@ class SequenSolver(nn.Module):
         self.engine = None
         self.batched_encoding = True      # the T (+1) frames of a call go through the encoder as ONE batch
 
+    def _build_encoder(self, encoder_config):
         cfg = dict(REFERENCE_ENCODER if encoder_config is None else encoder_config)
         self.encoder = Transolver_Structured_Mesh2D_Encoder.Model(**cfg)
+        H, W, M, C = self.H, self.W, self.M, self.C
         enc_h, enc_w, enc_m = self.encoder.H, self.encoder.W, self.encoder.blocks[-1].Attn.in_project_slice.out_features
         enc_heads, enc_c = self.encoder.blocks[-1].Attn.heads, self.encoder.blocks[-1].Attn.dim_head
         if (enc_h, enc_w) != (H, W):
@@ -94,40 +108,31 @@ class SequenSolver(nn.Module):
             raise ValueError(f"the encoder has {enc_heads} heads; SequenSolver reads its code as one head of M x C")
         if (enc_m, enc_c) != (M, C):
             raise ValueError(f"M x C = {M} x {C} does not match the encoder's code {enc_m} slices x {enc_c} channels")
-        if not 1 <= T <= ops.SEQ_ATTN_MAX_T:
-            raise NotImplementedError(f"the sequence attention kernel serves 1 <= T <= {ops.SEQ_ATTN_MAX_T}; got T = {T}")
+
+    def _refuse_dim(self):
         if self.dim > ops.SEQ_ATTN_MAX_DIM or self.dim % 4:
             raise NotImplementedError(f"dim = M*C = {self.dim}: LayerNorm and the sequence attention kernel serve "
                                       f"dim % 4 == 0 up to {ops.SEQ_ATTN_MAX_DIM}")
-        if transolver_path is not None:
-            sd = transolver_path
-            if isinstance(sd, (str, os.PathLike)):
-                sd = torch.load(sd, weights_only=True, map_location="cpu")
-            self.encoder.load_state_dict({k: torch.as_tensor(v) for k, v in sd.items()}, strict=False)
-        self.encoder.eval()
-        for param in self.encoder.parameters():
-            param.requires_grad = False
 
-        self.to_q = nn.Linear(self.dim, self.dim, bias=False)
-        self.to_k = nn.Linear(self.dim, self.dim, bias=False)
-        self.to_v = nn.Linear(self.dim, self.dim, bias=False)
+    def _build_attention(self, transolver_path, width, dropout):
+        """The encoder's checkpoint, loaded and frozen; q / k / v of `width`; the non-persistent `slice_weights` buffer,
+        which follows .cuda() / .to() and stays out of the state_dict, like the reference's plain tensor attribute."""
+        load_frozen(transolver_path, lambda: self.encoder, strict=False)
+        self.to_q = nn.Linear(width, width, bias=False)
+        self.to_k = nn.Linear(width, width, bias=False)
+        self.to_v = nn.Linear(width, width, bias=False)
         self.softmax_attention = nn.Softmax(dim=-1)
         self.dropout = nn.Dropout(dropout)
-
-        # follows .cuda() / .to() and stays out of the state_dict, like the reference's plain tensor attribute
-        self.register_buffer("slice_weights", torch.zeros(B, 1, self.N, self.M), persistent=False)
+        self.register_buffer("slice_weights", torch.zeros(self.B, 1, self.N, self.M), persistent=False)
         self.slice_weights_t = 0
-        self.slice_projection = nn.Linear(self.M, self.M)                           # never used (reference :93)
-        self.temporal_slice_projection = MLP(self.T, self.T * mlp_ratio, 1)         # never used (reference :95)
         self.code = None
-        self.learned_slice_weights = None      # what solve_with_slice_learner's LearnSlice predicted last
-        self.weight_projection = MLP(self.C + 2, WEIGHT_PROJECTION_HIDDEN, 1)
-        self.softmax_slice = nn.Softmax(dim=-1)
 
+    def _build_blocks(self, mlp_ratio, act):
         self.ln_1 = nn.LayerNorm(self.dim)
         self.ln_2 = nn.LayerNorm(self.dim)
         self.mlp = MLP(self.dim, self.dim * mlp_ratio, self.dim, n_layers=0, res=False, act=act)
 
+    def _build_readout(self):
         self.ln_3 = nn.LayerNorm(self.C)
         self.mlp2 = nn.Linear(self.C, 1)
 
@@ -139,12 +144,13 @@ class SequenSolver(nn.Module):
         return self
 
     def set_engine(self, engine):
-        """GEMM engine of the encoder and of this model's dense layers ("f32" | "split" | "bf16" | None = default); bf16
-        storage ('bf16s') is refused, as for the encoder family.  The two SequenSolver stages are exact fp32 on every engine."""
+        """GEMM engine of the encoder and of this model's dense layers and conv ("f32" | "split" | "bf16" | None =
+        default); bf16 storage ('bf16s') is refused, as for the encoder family.  The attention, z-score and slice-weight
+        stages are exact fp32 on every engine."""
         self.encoder.set_engine(engine)          # refuses 'bf16s'
         self.engine = None if engine is None else ops.resolve_engine(engine)
-        for m in (self.mlp, self.weight_projection, self.temporal_slice_projection):
-            m.engine = self.engine
+        for name in self.ENGINE_MODULES:
+            getattr(self, name).engine = self.engine
         return self
 
     def train(self, mode=True):
@@ -152,9 +158,9 @@ class SequenSolver(nn.Module):
         self.encoder.eval()                      # the encoder is frozen and stays in eval()
         return self
 
-    def _refuse(self, what="SequenSolver"):
+    def _refuse(self, what=None):
         if ops.resolve_engine(self.engine) == ops.ENGINE_BF16S:
-            raise NotImplementedError(f"bf16 storage (engine 'bf16s') is not implemented for {what}")
+            raise NotImplementedError(f"bf16 storage (engine 'bf16s') is not implemented for {what or self.WHAT}")
         if self.training and self.dropout.p > 0:
             raise NotImplementedError("dropout > 0 is not implemented in the HIP path; refusing to ignore it")
 
@@ -176,6 +182,16 @@ class SequenSolver(nn.Module):
                 tokens = torch.cat(codes, 2)
         return tokens, sw
 
+    def _encode_window(self, spatial_pos, fx, y=None):
+        """The T frames of fx [B, N, T] -> (tokens [B, Head, T, dim], slice weights of the last frame encoded).  With y
+        [B, N, 1] the target is encoded with them, last, so that the encoder's cached slice weights (and the ones
+        returned) are y's."""
+        frames = [fx[:, :, i:i + 1] for i in range(self.T)]
+        if y is None:
+            return self._encode_frames(spatial_pos, frames)
+        tokens, sw = self._encode_frames(spatial_pos, frames + [y])
+        return tokens[:, :, :self.T].contiguous(), sw
+
     def _blocks(self, tokens):
         mlp = self.mlp
         pre, post = mlp.linear_pre[0], mlp.linear_post
@@ -189,25 +205,73 @@ class SequenSolver(nn.Module):
         B = tokens.shape[0]
         return tokens[:, :, -1:, ].reshape(B, self.Head, self.M, self.C).contiguous()
 
+    def _window_count(self, seq, who):
+        n = seq.shape[-1] - self.T
+        if n < 1:
+            raise ValueError(f"{who} needs seq [B, N, T + n] with n >= 1; got {tuple(seq.shape)} at T = {self.T}")
+        return n
+
+    def _token_width(self):
+        """The widest per-token row of the blocks: the MLP's hidden layer."""
+        return int(self.mlp.linear_pre[0].weight.shape[0] / self.dim * self.dim)
+
+    def get_code(self, spatial_pos, fx, y):
+        self._refuse()
+        tokens, _ = self._encode_window(spatial_pos, fx)
+        return self._code(self._blocks(tokens))
+
+    def get_last_slice_weight(self, spatial_pos, fx):
+        with torch.no_grad():
+            self.encoder.encode(spatial_pos, fx[:, :, -1:])
+        return self.encoder.get_attention_slice()
+
+    def decode(self, code):
+        return Fn.deslice_weights(code, self.slice_weights)
+
+    def readout(self, code, slice_weights):
+        """mlp2(ln_3(code de-sliced with slice_weights)): code [B, 1, M, C], slice_weights [B, 1, N, M] -> [B, N, 1]."""
+        decoded = Fn.deslice_weights(code, slice_weights)
+        return Fn.head(Fn.layer_norm(decoded, self.ln_3.weight, self.ln_3.bias), self.mlp2.weight, self.mlp2.bias)
+
+    def freeze_attention(self):
+        frozen = (self.to_q, self.to_k, self.to_v, self.mlp, self.ln_1, self.ln_2)
+        for m in frozen + (self.softmax_attention,):
+            m.eval()
+        for m in frozen:
+            for param in m.parameters():
+                param.requires_grad = False
+
+
+class SequenSolver(_LatentSequence):
+    WHAT = "SequenSolver"
+    ENGINE_MODULES = ("mlp", "weight_projection", "temporal_slice_projection")
+
+    def __init__(self, transolver_path, T, W, H, M, C, B, mlp_ratio=4, layers=5, act='gelu', dropout=0., *,
+                 encoder_config=None):
+        super().__init__()
+        self._set_geometry(T, W, H, M, C, B, layers)
+        self._build_encoder(encoder_config)
+        if not 1 <= T <= ops.SEQ_ATTN_MAX_T:
+            raise NotImplementedError(f"the sequence attention kernel serves 1 <= T <= {ops.SEQ_ATTN_MAX_T}; got T = {T}")
+        self._refuse_dim()
+        self._build_attention(transolver_path, self.dim, dropout)
+        self.slice_projection = nn.Linear(self.M, self.M)                           # never used (reference :93)
+        self.temporal_slice_projection = MLP(self.T, self.T * mlp_ratio, 1)         # never used (reference :95)
+        self.learned_slice_weights = None      # what solve_with_slice_learner's LearnSlice predicted last
+        self.weight_projection = MLP(self.C + 2, WEIGHT_PROJECTION_HIDDEN, 1)
+        self.softmax_slice = nn.Softmax(dim=-1)
+        self._build_blocks(mlp_ratio, act)
+        self._build_readout()
+
     def forward(self, spatial_pos, fx, y, use_gt=True):
         """spatial_pos [B, N, 2] point coordinates, fx [B, N, T] the last T frames, y [B, N, 1] the next frame (read with
         use_gt=True only) -> [B, N, 1]."""
         self._refuse()
-        B = fx.shape[0]
-        frames = [fx[:, :, i:i + 1] for i in range(self.T)]
-        if use_gt:      # the target's slice weights: encoded with the T frames, last, so that they are the cached ones
-            tokens, sw = self._encode_frames(spatial_pos, frames + [y])
-            tokens = tokens[:, :, :self.T].contiguous()
-            self.slice_weights = sw
-        else:
-            tokens, _ = self._encode_frames(spatial_pos, frames)
-        tokens = self._blocks(tokens)
-        code = self._code(tokens)
-        self.code = code
-        if not use_gt:
-            self.slice_weights = self._predicted_slice_weights(code, spatial_pos)
-        decoded = self.decode(code)
-        return Fn.head(Fn.layer_norm(decoded, self.ln_3.weight, self.ln_3.bias), self.mlp2.weight, self.mlp2.bias)
+        # use_gt: the target's slice weights, encoded with the T frames, last, so that they are the cached ones
+        tokens, sw = self._encode_window(spatial_pos, fx, y if use_gt else None)
+        self.code = code = self._code(self._blocks(tokens))
+        self.slice_weights = sw if use_gt else self._predicted_slice_weights(code, spatial_pos)
+        return self.readout(code, self.slice_weights)
 
     def _predicted_slice_weights(self, code, spatial_pos):
         if spatial_pos.dim() != 3 or spatial_pos.shape[-1] != 2:
@@ -231,30 +295,24 @@ class SequenSolver(nn.Module):
         the point features (C + 2) and weight_projection's hidden layer, its widest per-token row the blocks' mlp_ratio*dim."""
         self._refuse()
         B, T = seq.shape[0], self.T
-        n = seq.shape[-1] - T
-        if n < 1:
-            raise ValueError(f"forward_windows needs seq [B, N, T + n] with n >= 1; got {tuple(seq.shape)} at T = {T}")
+        n = self._window_count(seq, "forward_windows")
         if use_gt:
             tokens, slices = encode_table(self, spatial_pos, seq, T + n, want_slices=True)
         else:
             tokens = encode_table(self, spatial_pos, seq, T + n - 1)
-        ratio = self.mlp.linear_pre[0].weight.shape[0] / self.dim
-        group = fold_calls(n, B, self.N, T, max(self.M, self.C + 2, WEIGHT_PROJECTION_HIDDEN), int(ratio * self.dim))
         outs = []
-        for k0 in range(0, n, group):
-            g = min(group, n - k0)
-            win = torch.cat([tokens[:, :, k:k + T] for k in range(k0, k0 + g)], 0)       # [g*B, Head, T, dim], call-major
-            code = self._code(self._blocks(win))
+        for k0, g in groups(n, self._calls_per_fold(n, B)):
+            code = self._code(self._blocks(windows(tokens, k0, g, T, 2)))               # on [g*B, Head, T, dim], call-major
             if use_gt:
                 sw = slices[(T + k0) * B:(T + k0 + g) * B]
             else:
                 sw = self._predicted_slice_weights(code, spatial_pos.repeat(g, 1, 1))
-            decoded = Fn.deslice_weights(code, sw)
-            out = Fn.head(Fn.layer_norm(decoded, self.ln_3.weight, self.ln_3.bias), self.mlp2.weight, self.mlp2.bias)
-            outs.append(out.reshape(g, B, self.N))
+            outs.append(self.readout(code, sw).reshape(g, B, self.N))
         self.code, self.slice_weights = code[-B:], sw[-B:]
-        out = outs[0] if len(outs) == 1 else torch.cat(outs, 0)
-        return out.permute(1, 2, 0)
+        return joined(outs).permute(1, 2, 0)
+
+    def _calls_per_fold(self, n, B):
+        return fold_calls(n, B, self.N, self.T, max(self.M, self.C + 2, WEIGHT_PROJECTION_HIDDEN), self._token_width())
 
     def code_windows(self, spatial_pos, seq):
         """Everything the slice trainers take from this frozen model for the n = seq.shape[-1] - T teacher-forced calls of
@@ -272,20 +330,15 @@ class SequenSolver(nn.Module):
         loops never write, are not touched."""
         self._refuse()
         B, T = seq.shape[0], self.T
-        n = seq.shape[-1] - T
-        if n < 1:
-            raise ValueError(f"code_windows needs seq [B, N, T + n] with n >= 1; got {tuple(seq.shape)} at T = {T}")
+        n = self._window_count(seq, "code_windows")
         with torch.no_grad(), ops.weights_frozen():
             tokens, slices = encode_table(self, spatial_pos, seq, T + n, want_slices=True)
-            ratio = self.mlp.linear_pre[0].weight.shape[0] / self.dim
-            group = fold_calls(n, B, self.N, T, max(self.M, self.C + 2, WEIGHT_PROJECTION_HIDDEN), int(ratio * self.dim))
             codes = []
-            for k0 in range(0, n, group):
-                g = min(group, n - k0)
-                win = torch.cat([tokens[:, :, k:k + T] for k in range(k0, k0 + g)], 0)   # [g*B, Head, T, dim], call-major
-                codes.append(self._code(self._blocks(win)).reshape(g, B, self.Head, self.M, self.C))
+            for k0, g in groups(n, self._calls_per_fold(n, B)):
+                code = self._code(self._blocks(windows(tokens, k0, g, T, 2)))           # on [g*B, Head, T, dim], call-major
+                codes.append(code.reshape(g, B, self.Head, self.M, self.C))
             self.encoder.set_attention_slice(slices[(T + n - 2) * B:(T + n - 1) * B].contiguous())
-        return (codes[0] if len(codes) == 1 else torch.cat(codes, 0)), slices
+        return joined(codes), slices
 
     def solve_with_slice_learner(self, slice_learner_path, spatial_pos, fx, y, unified_pos=0, use_vorticity=0,
                                  use_previous_slice=False, learn_from_vort=False, use_code_for_vorticity=False, *,
@@ -296,41 +349,20 @@ class SequenSolver(nn.Module):
         `slice_learner_path`: a checkpoint file, a state_dict or a LearnSlice instance.  `decode_with_learned=True`
         (extension) decodes with the learned weights instead.  spatial_pos is what the slice learner was trained on
         ([B, N, 2], or [B, N, 64] with unified_pos); any B."""
-        from .LearnSlice import LearnSlice
         self._refuse("solve_with_slice_learner (SequenSolver and LearnSlice keep fp32 activations)")
         if use_previous_slice or learn_from_vort:
             raise NotImplementedError("solve_with_slice_learner serves the default mode (LearnSlice.get_slice_weight); "
                                       "use_previous_slice needs LearnSlice.forward_previous_slice and learn_from_vort "
                                       "LearnSlice.forward_from_vorticity, which are not built")
-        learner = slice_learner_path
-        if not isinstance(learner, LearnSlice):      # a module built here is frozen, as the reference's; the caller's own is left as it is
-            sd = slice_learner_path
-            if isinstance(sd, (str, os.PathLike)):
-                sd = torch.load(sd, weights_only=True, map_location="cpu")
-            learner = LearnSlice(unified_pos=unified_pos, use_vorticity=use_vorticity,
-                                 use_code_for_vorticity=use_code_for_vorticity, C=self.C, M=self.M, T=self.T)
-            learner.load_state_dict({k: torch.as_tensor(v) for k, v in sd.items()}, strict=True)
-            learner = learner.to(fx.device).eval()
-            for param in learner.parameters():
-                param.requires_grad = False
-        frames = [fx[:, :, i:i + 1] for i in range(self.T)]
-        tokens, sw_gt = self._encode_frames(spatial_pos, frames + [y])       # y last: its slice weights are the cached ones
-        code = self._code(self._blocks(tokens[:, :, :self.T].contiguous()))
-        self.code = code
+        # a module built here is frozen, as the reference's; the caller's own is left as it is
+        learner = load_frozen(slice_learner_path, lambda: LearnSlice(
+            unified_pos=unified_pos, use_vorticity=use_vorticity, use_code_for_vorticity=use_code_for_vorticity,
+            C=self.C, M=self.M, T=self.T), strict=True, device=fx.device)
+        tokens, sw_gt = self._encode_window(spatial_pos, fx, y)              # y last: its slice weights are the cached ones
+        self.code = code = self._code(self._blocks(tokens))
         self.learned_slice_weights = learner.get_slice_weight(code, spatial_pos, fx, use_vorticity)
         self.slice_weights = self.learned_slice_weights if decode_with_learned else sw_gt
-        decoded = self.decode(code)
-        return Fn.head(Fn.layer_norm(decoded, self.ln_3.weight, self.ln_3.bias), self.mlp2.weight, self.mlp2.bias)
-
-    def get_code(self, spatial_pos, fx, y):
-        self._refuse()
-        tokens, _ = self._encode_frames(spatial_pos, [fx[:, :, i:i + 1] for i in range(self.T)])
-        return self._code(self._blocks(tokens))
-
-    def get_last_slice_weight(self, spatial_pos, fx):
-        with torch.no_grad():
-            self.encoder.encode(spatial_pos, fx[:, :, -1:])
-        return self.encoder.get_attention_slice()
+        return self.readout(code, self.slice_weights)
 
     def attention(self, tokens, residual=None):
         """Attention among the T tokens: tokens [B, Head, T, dim] -> the same shape.  `residual` (extension): added in
@@ -343,14 +375,3 @@ class SequenSolver(nn.Module):
         flat = (-1, shp[-2], shp[-1])
         res = None if residual is None else residual.reshape(flat)
         return Fn.seq_attention(q.reshape(flat), k.reshape(flat), v.reshape(flat), self.scale, res=res).reshape(shp)
-
-    def decode(self, code):
-        return Fn.deslice_weights(code, self.slice_weights)
-
-    def freeze_attention(self):
-        frozen = (self.to_q, self.to_k, self.to_v, self.mlp, self.ln_1, self.ln_2)
-        for m in frozen + (self.softmax_attention,):
-            m.eval()
-        for m in frozen:
-            for param in m.parameters():
-                param.requires_grad = False

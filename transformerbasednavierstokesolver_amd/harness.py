@@ -52,6 +52,7 @@ import torch
 
 from . import functional as Fn
 from . import ops
+from .folding import FOLD_MAX_BYTES, _fold_group, _slice_fold_group, groups, joined, model_engine, windows  # noqa: F401
 from .model.Transolver_Structured_Mesh_2D import Model
 from .utils.testloss import TestLoss
 
@@ -60,12 +61,6 @@ def build_model(cfg, state_dict=None, device="cuda", engine=None):
     """`engine`: GEMM engine of this model ("f32" | "split" | "bf16"; None = PA2D_GEMM / the split default)."""
     m = _build_model(cfg, state_dict, device)
     return m.set_engine(engine) if engine is not None else m
-
-
-def model_engine(model):
-    """The resolved GEMM engine id of a (possibly SOL-wrapped) Transolver."""
-    inner = getattr(model, "transolver_model", model)
-    return ops.resolve_engine(getattr(inner, "engine", None))
 
 
 def _build_model(cfg, state_dict, device):
@@ -109,36 +104,12 @@ def train_iteration(model, x, fx, yy, step=1, loss_fn=None, fold_time=False):
     return loss, full, pred
 
 
-# widest per-row tensor any kernel addresses through a 32-bit buffer descriptor must stay below 4 GiB
-FOLD_MAX_BYTES = 2 ** 32 - 4096
-
-
-def _fold_group(model, bsz, npoints, ncalls):
-    """How many teacher-forced calls fit in ONE folded model call: the widest activation row ([x_mid | fx_mid] =
-    2C, the preprocess hidden 2C, or the MLP hidden r*C floats) times the folded row count must stay under the
-    4 GiB extent of a buffer descriptor (libpa2d returns PA2D_ERR_UNSUPPORTED beyond it)."""
-    inner = getattr(model, "transolver_model", model)
-    C = inner.n_hidden
-    r = max((blk.mlp.linear_pre[0].weight.shape[0] for blk in inner.blocks), default=C) / C
-    width = int(max(2, r) * C)
-    row_bytes = 4 * width
-    eng = model_engine(model)
-    if eng == ops.ENGINE_SPLIT:      # split engine: the 2C-wide conv gradient travels as 3 bf16 planes
-        row_bytes = max(row_bytes, 6 * 2 * C)
-    elif eng == ops.ENGINE_BF16S:    # bf16 storage: block activations are 2 bytes wide, the fp32 input embedding (2C) is not
-        row_bytes = max(2 * width, 4 * 2 * C)
-    rows = FOLD_MAX_BYTES // row_bytes
-    return max(1, min(ncalls, rows // max(1, bsz * npoints)))
-
-
 def _train_iteration_folded(model, x, fx, yy, step, loss_fn):
     T, bsz, F = yy.shape[-1], x.shape[0], fx.shape[-1]
     nt = len(range(0, T, step))
     seq = torch.cat((fx, yy), dim=-1)                                     # frames the windows slide over
-    group = _fold_group(model, bsz, x.shape[1], nt)
     loss, outs = 0, []
-    for t0 in range(0, nt, group):                                        # normally ONE group
-        g = min(group, nt - t0)
+    for t0, g in groups(nt, _fold_group(model, bsz, x.shape[1], nt)):     # normally ONE group
         wins = torch.stack([seq[..., t * step:t * step + F] for t in range(t0, t0 + g)], 0)       # [g,B,N,F]
         im = model(x.repeat(g, 1, 1), fx=wins.reshape(g * bsz, *fx.shape[1:]))                    # [g*B,N,step]
         im = im.reshape(g, bsz, *im.shape[1:])
@@ -147,7 +118,7 @@ def _train_iteration_folded(model, x, fx, yy, step, loss_fn):
             y = yy[..., t * step:(t + 1) * step]
             loss = loss + loss_fn(im[k].reshape(bsz, -1), y.reshape(bsz, -1))
         outs.append(im)
-    im = torch.cat(outs, 0) if len(outs) > 1 else outs[0]
+    im = joined(outs)
     pred = im.permute(1, 2, 0, 3).reshape(bsz, im.shape[2], -1)
     with torch.no_grad():
         full = loss_fn(pred.reshape(bsz, -1), yy.reshape(bsz, -1))
@@ -598,8 +569,20 @@ def sequensolver_train_step(model, optimizer, scheduler, x, fx, yy, use_gt=True,
             full = loss_fn(pred.reshape(bsz, -1), yy.reshape(bsz, -1))
         optimizer.zero_grad()
         loss.backward()
-    _apply_step(optimizer, scheduler, (p for p in model.parameters() if p.requires_grad), max_grad_norm, grad_sync)
+    _apply_step(optimizer, scheduler, _trainable(model), max_grad_norm, grad_sync)
     return loss.detach(), full
+
+
+def _trainable(model):
+    """The parameters that an optimizer of `model` steps and a clip reads: the ones with requires_grad."""
+    return (p for p in model.parameters() if p.requires_grad)
+
+
+def _target_slices(sequen_solver, x, y):
+    """The frozen encoder's slice weights [B, 1, N, M] of the true frame y [B, N, 1] (left as its cached ones)."""
+    with torch.no_grad():
+        sequen_solver.encoder.encode(x, y)
+        return sequen_solver.encoder.get_attention_slice()
 
 
 def _fold_table(sequen_solver, x, fx, yy):
@@ -612,18 +595,6 @@ def _fold_table(sequen_solver, x, fx, yy):
     seq = torch.cat((fx, yy), dim=-1)
     codes, slices = sequen_solver.code_windows(x, seq)
     return seq, codes, slices
-
-
-def _slice_fold_group(model, ncalls, bsz, npoints):
-    """How many calls of a slice predictor fit in ONE folded forward: its widest per-point row (the previous-slice
-    predictor's 4 (M + M C) hidden layer; the conv predictors' preprocess hidden 2 n_hidden or first-layer input) times
-    the folded row count stays under the 4 GiB extent of a buffer descriptor (SequenSolver.fold_calls)."""
-    from .SequenSolver import fold_calls
-    if hasattr(model, "weight_projection_form_slice"):
-        width = model.weight_projection_form_slice.n_hidden
-    else:
-        width = max(2 * model.n_hidden, getattr(model, "concatenated", model.n_hidden))
-    return fold_calls(ncalls, bsz, npoints, 1, width, 1)
 
 
 def learnslice_train_step(model, optimizer, scheduler, sequen_solver, x, fx, yy, use_vorticity, max_grad_norm=None,
@@ -639,44 +610,46 @@ def learnslice_train_step(model, optimizer, scheduler, sequen_solver, x, fx, yy,
     encoded once); the optimizer still steps once per frame, on window k = cat(fx, yy)[..., k:k+T].
     Returns the list of the Tout detached step losses."""
     losses = []
-    params = lambda: (p for p in model.parameters() if p.requires_grad)
-    if fold_time:
-        T, B = fx.shape[-1], x.shape[0]
-        with ops.weights_frozen():
+
+    def step(code, window, target):
+        loss = Fn.slice_mse(model.get_slice_weight(code, x, window, use_vorticity=use_vorticity), target)
+        optimizer.zero_grad()
+        loss.backward()
+        _apply_step(optimizer, scheduler, _trainable(model), max_grad_norm, grad_sync)
+        losses.append(loss.detach())
+
+    with ops.weights_frozen():            # the sequence model's weights; LearnSlice's go through no packed GEMM
+        if fold_time:
+            T, B = fx.shape[-1], x.shape[0]
             seq, codes, slices = _fold_table(sequen_solver, x, fx, yy)
             for k in range(yy.shape[-1]):
-                target = slices[(T + k) * B:(T + k + 1) * B]
-                loss = Fn.slice_mse(model.get_slice_weight(codes[k], x, seq[..., k:k + T], use_vorticity=use_vorticity), target)
-                optimizer.zero_grad()
-                loss.backward()
-                _apply_step(optimizer, scheduler, params(), max_grad_norm, grad_sync)
-                losses.append(loss.detach())
-        return losses
-    with ops.weights_frozen():            # the sequence model's weights; LearnSlice's go through no packed GEMM
-        for t in range(yy.shape[-1]):
-            y = yy[..., t:t + 1]
-            with torch.no_grad():
-                sequen_solver.encoder.encode(x, y)
-                target = sequen_solver.encoder.get_attention_slice()
-                code = sequen_solver.get_code(x, fx, y)
-            loss = Fn.slice_mse(model.get_slice_weight(code, x, fx, use_vorticity=use_vorticity), target)
-            optimizer.zero_grad()
-            loss.backward()
-            _apply_step(optimizer, scheduler, (p for p in model.parameters() if p.requires_grad), max_grad_norm, grad_sync)
-            losses.append(loss.detach())
-            fx = torch.cat((fx[..., 1:], y), dim=-1)             # the ground truth enters the window
+                step(codes[k], seq[..., k:k + T], slices[(T + k) * B:(T + k + 1) * B])
+        else:
+            for t in range(yy.shape[-1]):
+                y = yy[..., t:t + 1]
+                target = _target_slices(sequen_solver, x, y)
+                with torch.no_grad():
+                    code = sequen_solver.get_code(x, fx, y)
+                step(code, fx, target)
+                fx = torch.cat((fx[..., 1:], y), dim=-1)             # the ground truth enters the window
     return losses
 
 
+def _conv_slices(model, x, fx, code, groups=None):
+    """The slice weights of a conv slice predictor.  The code-conditioned predictor (SliceLearner.VorticitySliceLearner
+    built with use_code_for_vorticity) reads the code; SliceLearner gets none.  `groups`: the batch is that many folded
+    calls, call-major (`forward_folded`: the z-scores stay per call)."""
+    if not hasattr(model, "use_code_for_vorticity"):
+        return model(x, fx)
+    code = code if model.use_code_for_vorticity else None
+    return model(x, fx, code) if groups is None else model.forward_folded(x, fx, code, groups=groups)
+
+
 def _predict_slices(model, sequen_solver, x, fx):
-    """(slice weights [B, 1, N, M] of a conv slice predictor, code [B, 1, M, C] of the frozen sequence model).  The
-    code-conditioned predictor (SliceLearner.VorticitySliceLearner built with use_code_for_vorticity) reads the code;
-    SliceLearner gets none."""
+    """(slice weights [B, 1, N, M] of a conv slice predictor, code [B, 1, M, C] of the frozen sequence model)."""
     with torch.no_grad():
         code = sequen_solver.get_code(x, fx, None)
-    if hasattr(model, "use_code_for_vorticity"):
-        return model(x, fx, code if model.use_code_for_vorticity else None), code
-    return model(x, fx), code
+    return _conv_slices(model, x, fx, code), code
 
 
 def _folded_terms(pred, target, ncalls):
@@ -701,35 +674,15 @@ def slice_predictor_train_step(model, optimizer, scheduler, sequen_solver, x, fx
     call and the predictor runs ONE forward on the Tout*B folded samples, call-major (cut where a folded tensor would pass
     the 4 GiB extent); the code-conditioned predictor's z-scores stay per call (`groups`).  The same terms, summed in call
     order.  Returns the detached summed loss."""
-    loss = 0
-    with ops.weights_frozen():
-        if fold_time:
-            T, B, n = fx.shape[-1], x.shape[0], yy.shape[-1]
-            seq, codes, slices = _fold_table(sequen_solver, x, fx, yy)
-            group = _slice_fold_group(model, n, B, x.shape[1])
-            for k0 in range(0, n, group):
-                g = min(group, n - k0)
-                wins = torch.cat([seq[..., k:k + T] for k in range(k0, k0 + g)], 0)            # [g*B, N, T], call-major
-                xs = x.repeat(g, *([1] * (x.dim() - 1)))
-                if hasattr(model, "use_code_for_vorticity"):
-                    code = codes[k0:k0 + g].reshape(g * B, *codes.shape[2:]) if model.use_code_for_vorticity else None
-                    pred = model.forward_folded(xs, wins, code, groups=g)
-                else:
-                    pred = model(xs, wins)
-                loss = loss + _folded_terms(pred, slices[(T + k0) * B:(T + k0 + g) * B], g)
-        else:
-            for t in range(yy.shape[-1]):
-                y = yy[..., t:t + 1]
-                with torch.no_grad():
-                    sequen_solver.encoder.encode(x, y)
-                    target = sequen_solver.encoder.get_attention_slice()
-                pred, _ = _predict_slices(model, sequen_solver, x, fx)
-                loss = loss + Fn.slice_mse(pred, target) / (pred.shape[0] * pred.shape[2])
-                fx = torch.cat((fx[..., 1:], y), dim=-1)             # the ground truth enters the window
-        optimizer.zero_grad()
-        loss.backward()
-    _apply_step(optimizer, scheduler, (p for p in model.parameters() if p.requires_grad), max_grad_norm, grad_sync)
-    return loss.detach()
+    def eager(fx, y):
+        return _predict_slices(model, sequen_solver, x, fx)[0]
+
+    def folded(seq, code, slices, k0, g):
+        wins = windows(seq, k0, g, fx.shape[-1])                                               # [g*B, N, T], call-major
+        return _conv_slices(model, x.repeat(g, *([1] * (x.dim() - 1))), wins, code, groups=g)
+
+    return _summed_slice_step(model, optimizer, scheduler, sequen_solver, x, fx, yy, max_grad_norm, grad_sync, fold_time,
+                              eager, folded)
 
 
 def previous_slice_train_step(model, optimizer, scheduler, sequen_solver, x, fx, yy, max_grad_norm=None, grad_sync=None,
@@ -743,30 +696,46 @@ def previous_slice_train_step(model, optimizer, scheduler, sequen_solver, x, fx,
     `fold_time=True`: targets, codes and previous slices come from ONE `sequen_solver.code_windows` call (previous slice of
     call k = frame T + k - 1 of its table) and the predictor runs ONE forward on the Tout*B folded samples, call-major; the
     same terms, summed in call order.  Returns the detached summed loss."""
+    T, B = fx.shape[-1], x.shape[0]
+
+    def eager(fx, y):
+        with torch.no_grad():
+            code = sequen_solver.get_code(x, fx, y)
+            prev = sequen_solver.get_last_slice_weight(x, fx)
+        return model(prev, code)
+
+    def folded(seq, code, slices, k0, g):
+        return model(slices[(T - 1 + k0) * B:(T - 1 + k0 + g) * B], code)
+
+    return _summed_slice_step(model, optimizer, scheduler, sequen_solver, x, fx, yy, max_grad_norm, grad_sync, fold_time,
+                              eager, folded)
+
+
+def _summed_slice_step(model, optimizer, scheduler, sequen_solver, x, fx, yy, max_grad_norm, grad_sync, fold_time, eager,
+                       folded):
+    """The frame of slice_predictor_train_step and previous_slice_train_step: the Tout F.mse_loss terms against the frozen
+    encoder's slice weights of each true frame, summed in call order, zero_grad, ONE backward, `_apply_step` on the
+    trainable parameters.  `eager(fx, y)`: the prediction of one call on the window fx, which then slides on with y;
+    `folded(seq, code, slices, k0, g)`: the prediction of calls k0 .. k0+g-1 on `_fold_table`'s seq and slices and their
+    codes [g*B, 1, M, C], call-major."""
     loss = 0
     with ops.weights_frozen():
         if fold_time:
             T, B, n = fx.shape[-1], x.shape[0], yy.shape[-1]
-            _, codes, slices = _fold_table(sequen_solver, x, fx, yy)
-            group = _slice_fold_group(model, n, B, x.shape[1])
-            for k0 in range(0, n, group):
-                g = min(group, n - k0)
-                pred = model(slices[(T - 1 + k0) * B:(T - 1 + k0 + g) * B], codes[k0:k0 + g].reshape(g * B, *codes.shape[2:]))
+            seq, codes, slices = _fold_table(sequen_solver, x, fx, yy)
+            for k0, g in groups(n, _slice_fold_group(model, n, B, x.shape[1])):
+                pred = folded(seq, codes[k0:k0 + g].reshape(g * B, *codes.shape[2:]), slices, k0, g)
                 loss = loss + _folded_terms(pred, slices[(T + k0) * B:(T + k0 + g) * B], g)
         else:
             for t in range(yy.shape[-1]):
                 y = yy[..., t:t + 1]
-                with torch.no_grad():
-                    sequen_solver.encoder.encode(x, y)
-                    target = sequen_solver.encoder.get_attention_slice()
-                    code = sequen_solver.get_code(x, fx, y)
-                    prev = sequen_solver.get_last_slice_weight(x, fx)
-                new_slice = model(prev, code)
-                loss = loss + Fn.slice_mse(new_slice, target) / (new_slice.shape[0] * new_slice.shape[2])
+                target = _target_slices(sequen_solver, x, y)
+                pred = eager(fx, y)
+                loss = loss + Fn.slice_mse(pred, target) / (pred.shape[0] * pred.shape[2])
                 fx = torch.cat((fx[..., 1:], y), dim=-1)             # the ground truth enters the window
         optimizer.zero_grad()
         loss.backward()
-    _apply_step(optimizer, scheduler, (p for p in model.parameters() if p.requires_grad), max_grad_norm, grad_sync)
+    _apply_step(optimizer, scheduler, _trainable(model), max_grad_norm, grad_sync)
     return loss.detach()
 
 
@@ -774,9 +743,7 @@ def _decode_step(sequen_solver, slice_weights, code):
     """The rollouts' feedback: decode `code` with `slice_weights` (left in sequen_solver.slice_weights) and apply
     mlp2(ln_3(.)) -> [B, N, 1]."""
     sequen_solver.slice_weights = slice_weights.contiguous()
-    decoded = sequen_solver.decode(code)
-    return Fn.head(Fn.layer_norm(decoded, sequen_solver.ln_3.weight, sequen_solver.ln_3.bias),
-                   sequen_solver.mlp2.weight, sequen_solver.mlp2.bias)
+    return sequen_solver.readout(code, sequen_solver.slice_weights)
 
 
 @torch.no_grad()
@@ -806,10 +773,7 @@ def slice_predictor_rollout(model, sequen_solver, x, fx, nsteps):
     with ops.weights_frozen():
         for _ in range(nsteps):
             sw, code = _predict_slices(model, sequen_solver, x, fx)
-            sequen_solver.slice_weights = sw.contiguous()
-            decoded = sequen_solver.decode(code)
-            pred = Fn.head(Fn.layer_norm(decoded, sequen_solver.ln_3.weight, sequen_solver.ln_3.bias),
-                           sequen_solver.mlp2.weight, sequen_solver.mlp2.bias)
+            pred = _decode_step(sequen_solver, sw, code)
             preds.append(pred)
             fx = torch.cat((fx[..., 1:], pred), dim=-1)
     return torch.cat(preds, -1)
@@ -1486,8 +1450,7 @@ def slice_learner_test_loss(kind, model, sequen_solver, x, fx, yy, use_vorticity
         code = prev = None
         for t in range(yy.shape[-1]):
             y = yy[..., t:t + 1]
-            sequen_solver.encoder.encode(x, y)
-            target = sequen_solver.encoder.get_attention_slice()
+            target = _target_slices(sequen_solver, x, y)
             if kind == "previous":
                 if code is None:
                     code = sequen_solver.get_code(x, fx, y)

@@ -208,14 +208,12 @@ def _slice_learner_rollout(model, slice_learner_path, pos, fx, yy):
     import torch
     from . import harness, ops
     from .LearnSlice import LearnSlice
+    from .SequenSolver import load_frozen
     if slice_learner_path is None:
         raise SystemExit("--driver sequensolver --eval 1 needs --slice_learner_path (a LearnSlice checkpoint)")
-    learner = slice_learner_path
-    if not isinstance(learner, LearnSlice):      # built once, not once per frame as the script does
-        sd = torch.load(slice_learner_path, map_location="cpu", weights_only=True)
-        learner = LearnSlice(unified_pos=1, use_vorticity=1, use_code_for_vorticity=False, C=model.C, M=model.M, T=model.T)
-        learner.load_state_dict(sd, strict=True)
-        learner = learner.to(fx.device).eval()
+    learner = load_frozen(slice_learner_path, lambda: LearnSlice(       # built once, not once per frame as the script does
+        unified_pos=1, use_vorticity=1, use_code_for_vorticity=False, C=model.C, M=model.M, T=model.T),
+        strict=True, device=fx.device, freeze=False)
     bsz, preds = fx.shape[0], []
     with torch.no_grad(), ops.weights_frozen():
         for t in range(yy.shape[-1]):

@@ -99,14 +99,9 @@ def build_learner(args):
 
 def build_sequen_solver(args, dev):
     """The frozen sequence model of the three scripts (:389-398)."""
-    import torch
-    from .SequenSolver import SequenSolver
-    solver = SequenSolver(args.encoder_path, T=T_IN, B=BATCH_SIZE, layers=LAYERS, **GEOMETRY)
-    solver.load_state_dict(torch.load(args.sequensolver_path, map_location="cpu", weights_only=True), strict=False)
-    solver = solver.to(dev).eval()
-    for param in solver.parameters():
-        param.requires_grad = False
-    return solver
+    from .SequenSolver import SequenSolver, load_frozen
+    return load_frozen(args.sequensolver_path, lambda: SequenSolver(args.encoder_path, T=T_IN, B=BATCH_SIZE, layers=LAYERS,
+                                                                    **GEOMETRY), strict=False, device=dev)
 
 
 def run(args):
