@@ -346,7 +346,7 @@ def test_train_sequence_hands_the_flags_to_the_loops(monkeypatch, tmp_path):
     """--driver sequensolver_merged end to end on the host, with the model, the device and the loop replaced by recorders."""
     import numpy as np
     import scipy.io as scio
-    from transformerbasednavierstokesolver_amd import SequenSolverMerged, harness, train, train_sequence as ts
+    from transformerbasednavierstokesolver_amd import SequenSolverMerged, cli, harness, train_sequence as ts
     u = np.random.default_rng(0).standard_normal((5, 64, 64, 20)).astype(np.float32)
     scio.savemat(str(tmp_path / "NavierStokes_V1e-5_N1200_T20.mat"), {"u": u})
     seen = {}
@@ -361,8 +361,8 @@ def test_train_sequence_hands_the_flags_to_the_loops(monkeypatch, tmp_path):
         return []
 
     monkeypatch.setattr(SequenSolverMerged, "SequenSolver", Model)
-    monkeypatch.setattr(train, "_device", lambda args: torch.device("cpu"))
-    monkeypatch.setattr(ts, "_optim", lambda model, *a, **k: (type("O", (), {"sync": None})(), None))
+    monkeypatch.setattr(cli, "device", lambda args: torch.device("cpu"))
+    monkeypatch.setattr(cli, "optim", lambda model, *a, **k: (type("O", (), {"sync": None})(), None))
     monkeypatch.setattr(harness, "fit_sequensolver", fit)
     ts.main(["--driver", "sequensolver_merged", "--eval", "0", "--sim_num", "3", "--ntest", "2", "--epochs", "4",
              "--data_path", str(tmp_path), "--transolver_path", "enc.pt", "--save_name", "run"])

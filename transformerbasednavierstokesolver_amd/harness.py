@@ -799,6 +799,21 @@ def sequensolver_rollout(model, x, fx, yy, use_gt=True):
     return pred, loss, loss_fn(pred.reshape(bsz, -1), yy.reshape(bsz, -1))
 
 
+@torch.no_grad()
+def learned_slice_rollout(model, learner, x, fx, yy, unified_pos=1, use_vorticity=1):
+    """SequenSolver.py:553-568: Tout = yy.shape[-1] prediction-feedback calls of `model.solve_with_slice_learner` with the
+    LearnSlice module `learner` (the caller's one instance: the script builds and loads it once per frame).  Returns the
+    full rel-L2 of the batch."""
+    bsz, preds = fx.shape[0], []
+    with ops.weights_frozen():
+        for t in range(yy.shape[-1]):
+            im = model.solve_with_slice_learner(learner, x, fx, yy[..., t:t + 1], unified_pos=unified_pos,
+                                                use_vorticity=use_vorticity)
+            preds.append(im)
+            fx = torch.cat((fx[..., 1:], im), dim=-1)
+    return TestLoss(size_average=False)(torch.cat(preds, -1).reshape(bsz, -1), yy.reshape(bsz, -1))
+
+
 # ------------------------------------------------------------------------------ epoch loops of the reference drivers
 def _device_of(model):
     return next(model.parameters()).device
@@ -862,6 +877,21 @@ def _fit(model, *, epochs, n_acc, batches, train_batch, test_pass, metrics, on_e
     return history
 
 
+def _evaluate(model, n_acc, test_pass, metrics):
+    """The test half of one `_fit` epoch alone: a zeroed float64 accumulator [n_acc] on the model's device, model.eval(),
+    `test_pass(acc)`, ONE acc.tolist(), `metrics(a)`.  What every evaluate_* returns."""
+    acc = torch.zeros(n_acc, dtype=torch.float64, device=_device_of(model))
+    model.eval()
+    test_pass(acc)
+    return metrics(acc.tolist())
+
+
+# the test half of each family's epoch dict: fit_X and evaluate_X both read it (`a`: the accumulator of X's test pass)
+_ns_test_metrics = lambda a, ntest, calls: dict(test_step=a[2] / ntest / calls, test_full=a[3] / ntest)
+_plas_test_metrics = lambda a, ntest, T: dict(test_step=a[1] / ntest / T, test_full=a[2] / ntest)
+_rel_err = lambda total, ntest: dict(rel_err=total / ntest)                     # darcy and the static drivers
+
+
 def _graphed_or_eager(graphed, batch_size, build, replay, eager):
     """run(*batch) of a loop with a graph mode.  A full batch (batch[0].shape[0] == batch_size) of a graphed loop goes to
     `replay(graph, *batch)`, where `graph = build(*batch)` is made of the first full batch; every other batch, and every
@@ -901,11 +931,8 @@ def _ns_test_pass(model, test, batch_size, T, step, loss_fn, acc, full=True):
 def evaluate_ns(model, test, batch_size, T=10, step=1, loss_fn=None):
     """The test pass alone (exp_ns.py:137-183 without the plots): {'test_step', 'test_full'} normalised like fit_ns."""
     loss_fn = loss_fn or TestLoss(size_average=False)
-    acc = torch.zeros(4, dtype=torch.float64, device=_device_of(model))
-    model.eval()
-    _ns_test_pass(model, test, batch_size, T, step, loss_fn, acc)
-    a = acc.tolist()
-    return dict(test_step=a[2] / len(test) / (T / step), test_full=a[3] / len(test))
+    return _evaluate(model, 4, lambda acc: _ns_test_pass(model, test, batch_size, T, step, loss_fn, acc),
+                     lambda a: _ns_test_metrics(a, len(test), T / step))
 
 
 @torch.no_grad()
@@ -931,11 +958,9 @@ def _darcy_setup(model, data, want_train=True):
 def evaluate_darcy(model, data, batch_size, loss_fn=None):
     """The test pass alone (exp_darcy.py:154-203 without the plots): {'rel_err'} = summed rel-L2 / ntest."""
     loss_fn = loss_fn or TestLoss(size_average=False)
-    dev, yn, _, test, positions = _darcy_setup(model, data, want_train=False)
-    acc = torch.zeros(3, dtype=torch.float64, device=dev)
-    model.eval()
-    _darcy_test_pass(model, test, batch_size, positions, yn, loss_fn, acc)
-    return dict(rel_err=acc.tolist()[2] / len(test))
+    _, yn, _, test, positions = _darcy_setup(model, data, want_train=False)
+    return _evaluate(model, 3, lambda acc: _darcy_test_pass(model, test, batch_size, positions, yn, loss_fn, acc),
+                     lambda a: _rel_err(a[2], len(test)))
 
 
 def fit_ns(model, optimizer, scheduler, train, test, *, epochs, batch_size, T=10, step=1, max_grad_norm=None, loss_fn=None,
@@ -979,7 +1004,7 @@ def fit_ns(model, optimizer, scheduler, train, test, *, epochs, batch_size, T=10
     return _fit(model, epochs=epochs, n_acc=4, batches=lambda ep: _epoch_batches(train, batch_size, ep, epoch_orders, generator),
                 train_batch=train_batch, test_pass=lambda acc: _ns_test_pass(model, test, batch_size, T, step, loss_fn, acc),
                 metrics=lambda a: dict(train_step=a[0] / ntrain / calls, train_full=a[1] / ntrain,
-                                           test_step=a[2] / ntest / calls, test_full=a[3] / ntest),
+                                       **_ns_test_metrics(a, ntest, calls)),
                 on_epoch=on_epoch, save_path=save_path, save_every=save_every)
 
 
@@ -1017,7 +1042,8 @@ def fit_unrolled(sol_model, optimizer, scheduler, train, test, *, epochs, batch_
 
     return _fit(sol_model, epochs=epochs, n_acc=4, batches=batches, train_batch=train_batch,
                 test_pass=lambda acc: _ns_test_pass(inner, test, batch_size, T, step, loss_fn, acc, full=False),
-                metrics=lambda a: dict(train_step=a[0], test_step=a[2] / ntest / calls, look_ahead=curriculum.look_ahead),
+                metrics=lambda a: dict(train_step=a[0], test_step=_ns_test_metrics(a, ntest, calls)["test_step"],
+                                       look_ahead=curriculum.look_ahead),
                 on_epoch=on_epoch, save_path=save_path, save_every=save_every, save_module=inner)
 
 
@@ -1065,7 +1091,7 @@ def fit_darcy(model, optimizer, scheduler, data, *, epochs, batch_size, max_grad
 
     return _fit(model, epochs=epochs, n_acc=3, batches=lambda ep: _epoch_batches(train, batch_size, ep, epoch_orders, generator),
                 train_batch=train_batch, test_pass=lambda acc: _darcy_test_pass(model, test, batch_size, positions, yn, test_loss, acc),
-                metrics=lambda a: dict(reg=a[1] / ntrain, train_loss=a[0] / ntrain, rel_err=a[2] / ntest),
+                metrics=lambda a: dict(reg=a[1] / ntrain, train_loss=a[0] / ntrain, **_rel_err(a[2], ntest)),
                 on_epoch=on_epoch, save_path=save_path, save_every=save_every)
 
 
@@ -1117,11 +1143,9 @@ def _static_setup(model, data, want_train=True):
 def evaluate_static(model, data, batch_size, loss_fn=None):
     """The test pass alone (the `eval` branch of the three scripts without the plots): {'rel_err'} = summed rel-L2 / ntest."""
     loss_fn = loss_fn or TestLoss(size_average=False)
-    dev, yn, _, test = _static_setup(model, data, want_train=False)
-    acc = torch.zeros(2, dtype=torch.float64, device=dev)
-    model.eval()
-    _static_test_pass(model, test, batch_size, yn, loss_fn, acc)
-    return dict(rel_err=acc.tolist()[1] / len(test))
+    _, yn, _, test = _static_setup(model, data, want_train=False)
+    return _evaluate(model, 2, lambda acc: _static_test_pass(model, test, batch_size, yn, loss_fn, acc),
+                     lambda a: _rel_err(a[1], len(test)))
 
 
 def fit_static(model, optimizer, scheduler, data, *, epochs, batch_size, max_grad_norm=None, loss_fn=None,
@@ -1164,7 +1188,7 @@ def fit_static(model, optimizer, scheduler, data, *, epochs, batch_size, max_gra
 
     return _fit(model, epochs=epochs, n_acc=2, batches=lambda ep: _epoch_batches(train, batch_size, ep, epoch_orders, generator),
                 train_batch=train_batch, test_pass=lambda acc: _static_test_pass(model, test, batch_size, yn, loss_fn, acc),
-                metrics=lambda a: dict(train_loss=a[0] / ntrain, rel_err=a[1] / ntest),
+                metrics=lambda a: dict(train_loss=a[0] / ntrain, **_rel_err(a[1], ntest)),
                 on_epoch=on_epoch, save_path=save_path, save_every=save_every,
                 per_epoch=scheduler.step if scheduler_per_epoch and scheduler is not None else None)
 
@@ -1215,12 +1239,9 @@ def _plas_setup(model, data, want_train=True):
 def evaluate_plas(model, data, batch_size, loss_fn=None):
     """The test pass alone (exp_plas.py:168-231 without the plots): {'test_step', 'test_full'} normalised like fit_plas."""
     loss_fn = loss_fn or TestLoss(size_average=False)
-    dev, _, test, positions, t = _plas_setup(model, data, want_train=False)
-    acc = torch.zeros(3, dtype=torch.float64, device=dev)
-    model.eval()
-    _plas_test_pass(model, test, batch_size, positions, t, loss_fn, acc)
-    a = acc.tolist()
-    return dict(test_step=a[1] / len(test) / t.numel(), test_full=a[2] / len(test))
+    _, _, test, positions, t = _plas_setup(model, data, want_train=False)
+    return _evaluate(model, 3, lambda acc: _plas_test_pass(model, test, batch_size, positions, t, loss_fn, acc),
+                     lambda a: _plas_test_metrics(a, len(test), t.numel()))
 
 
 def fit_plas(model, optimizer, scheduler, data, *, epochs, batch_size, max_grad_norm=None, loss_fn=None, epoch_orders=None,
@@ -1288,11 +1309,36 @@ def fit_plas(model, optimizer, scheduler, data, *, epochs, batch_size, max_grad_
 
     return _fit(model, epochs=epochs, n_acc=3, batches=batches, train_batch=train_batch,
                 test_pass=lambda acc: _plas_test_pass(model, test, batch_size, positions, t, loss_fn, acc),
-                metrics=lambda a: dict(train_step=a[0] / ntrain / T, test_step=a[1] / ntest / T, test_full=a[2] / ntest),
+                metrics=lambda a: dict(train_step=a[0] / ntrain / T, **_plas_test_metrics(a, ntest, T)),
                 on_epoch=on_epoch, save_path=save_path, save_every=save_every)
 
 
 # ------------------------------------------------------------------------------ latent-sequence family: epoch loops
+def _autoencoder_test(model, data):
+    """test_pass(acc, batch_size) of the auto-encoder, and positions(bsz): acc[1] += TestLoss(size_average=False) of
+    model(x, fx) against fx itself, over `data["test"]` under no_grad (auto_encoder.py:188-197)."""
+    from .data import ResidentDataset, grid_positions
+    dev = _device_of(model)
+    test = ResidentDataset(data["test"], device=dev)
+    positions = _positions_cache(grid_positions(data["h"]).to(dev))
+    loss_fn = TestLoss(size_average=False)
+
+    @torch.no_grad()
+    def test_pass(acc, batch_size):
+        for fx, in test.batches(batch_size):
+            bsz = fx.shape[0]
+            acc[1] += loss_fn(model(positions(bsz), fx=fx).reshape(bsz, -1), fx.reshape(bsz, -1))
+
+    return test_pass, positions
+
+
+def evaluate_autoencoder(model, data, batch_size, ntest):
+    """The test pass of fit_autoencoder alone (auto_encoder.py:135-158 without the plots): {'test_l2'} = summed loss / ntest,
+    where `ntest` counts TRAJECTORIES, not frames, as the script divides."""
+    test_pass, _ = _autoencoder_test(model, data)
+    return _evaluate(model, 2, lambda acc: test_pass(acc, batch_size), lambda a: dict(test_l2=a[1] / ntest))
+
+
 def fit_autoencoder(model, optimizer, scheduler, data, *, epochs, batch_size, ntrain, ntest, T=10, step=1, max_grad_norm=None,
                     epoch_orders=None, generator=None, save_path=None, save_name=None, save_every=100, grad_sync=None,
                     on_epoch=None):
@@ -1305,27 +1351,20 @@ def fit_autoencoder(model, optimizer, scheduler, data, *, epochs, batch_size, nt
     (the script's globals), not frames.  One host synchronisation per epoch.  The state_dict is written when
     ep % save_every == 0 (the script: 100) and after the last epoch, to `save_path`, or, as the script names it, to
     sequential_checkpoints/<save_name>.pt.  `epoch_orders`, `generator`, `grad_sync`, `on_epoch` as fit_ns."""
-    from .data import ResidentDataset, grid_positions
+    from .data import ResidentDataset
     if save_path is None and save_name is not None:
         save_path = os.path.join("sequential_checkpoints", save_name + ".pt")
-    dev = _device_of(model)
-    train, test = ResidentDataset(data["train"], device=dev), ResidentDataset(data["test"], device=dev)
-    positions = _positions_cache(grid_positions(data["h"]).to(dev))
-    loss_fn, calls = TestLoss(size_average=False), T / step
+    train = ResidentDataset(data["train"], device=_device_of(model))
+    test_pass, positions = _autoencoder_test(model, data)
+    calls = T / step
 
     def train_batch(batch, acc):
         fx, = batch
         acc[0] += autoencoder_train_step(model, optimizer, scheduler, positions(fx.shape[0]), fx, max_grad_norm=max_grad_norm,
                                          grad_sync=grad_sync)
 
-    @torch.no_grad()
-    def test_pass(acc):
-        for fx, in test.batches(batch_size):
-            bsz = fx.shape[0]
-            acc[1] += loss_fn(model(positions(bsz), fx=fx).reshape(bsz, -1), fx.reshape(bsz, -1))
-
     return _fit(model, epochs=epochs, n_acc=2, batches=lambda ep: _epoch_batches(train, batch_size, ep, epoch_orders, generator),
-                train_batch=train_batch, test_pass=test_pass,
+                train_batch=train_batch, test_pass=lambda acc: test_pass(acc, batch_size),
                 metrics=lambda a: dict(train_step=a[0] / ntrain / calls, test_step=a[1] / ntest / calls),
                 on_epoch=on_epoch, save_path=save_path, save_every=save_every)
 
@@ -1413,6 +1452,24 @@ def fit_sequensolver(model, optimizer, scheduler, pos, train, test, *, epochs, b
     if save_path is not None and save_every is None:
         _save_state(model, save_path)
     return history
+
+
+def evaluate_sequensolver(model, pos, test, ntest, batch_size=1, slice_learner=None):
+    """train(eval=True) of the two scripts without the prints and plots: {'test_full'} = the summed full rel-L2 of every
+    test batch's prediction-feedback rollout / `ntest` (the caller's count).  The merged model (SequenSolverMerged.py) is
+    given no `slice_learner` and runs `sequensolver_rollout(use_gt=False)`; the plain one (SequenSolver.py:541-570) is
+    given its LearnSlice module and runs `learned_slice_rollout`."""
+    positions = _positions_cache(pos.to(_device_of(model)))
+
+    def test_pass(acc):
+        for fx, yy in test.batches(batch_size):
+            x = positions(fx.shape[0])
+            if slice_learner is None:
+                acc[0] += sequensolver_rollout(model, x, fx, yy, use_gt=False)[2]
+            else:
+                acc[0] += learned_slice_rollout(model, slice_learner, x, fx, yy)
+
+    return _evaluate(model, 1, test_pass, lambda a: dict(test_full=a[0] / ntest))
 
 
 # ------------------------------------------------------------------------------ slice learners: epoch loops
@@ -1527,3 +1584,26 @@ def fit_slice_learner(model, optimizer, scheduler, sequen_solver, pos, train, te
     return _fit(model, epochs=epochs, n_acc=2, batches=lambda ep: _epoch_batches(train, batch_size, ep, epoch_orders, generator),
                 train_batch=train_batch, test_pass=test_pass, metrics=metrics, on_epoch=on_epoch, save_path=save_path,
                 save_every=save_every)
+
+
+def evaluate_slice_learner(kind, model, sequen_solver, pos, test, use_vorticity=0, batch_size=1):
+    """train(eval=True) of LearnSlice.py's three trainers on a loaded `model`, per test batch:
+      learnslice           {'test_slice'}: sum of `slice_learner_test_loss` / Tout, / len(test) (it has no rollout of its own);
+      vorticity, previous  {'test_full'}: sum of the full rel-L2 of the kind's prediction-feedback rollout
+                           (`slice_predictor_rollout` / `previous_slice_rollout`), / len(test)."""
+    if kind not in SLICE_LEARNER_KINDS:
+        raise ValueError(f"kind must be one of {SLICE_LEARNER_KINDS}; got {kind!r}")
+    positions = _positions_cache(pos.to(_device_of(model)))
+    loss_fn = TestLoss(size_average=False)
+    rollout = slice_predictor_rollout if kind == "vorticity" else previous_slice_rollout
+
+    def test_pass(acc):
+        for fx, yy in test.batches(batch_size):
+            bsz, x = fx.shape[0], positions(fx.shape[0])
+            if kind == "learnslice":
+                acc[0] += slice_learner_test_loss(kind, model, sequen_solver, x, fx, yy, use_vorticity) / yy.shape[-1]
+            else:
+                acc[0] += loss_fn(rollout(model, sequen_solver, x, fx, yy.shape[-1]).reshape(bsz, -1), yy.reshape(bsz, -1))
+
+    return _evaluate(model, 1, test_pass,
+                     lambda a: {"test_slice" if kind == "learnslice" else "test_full": a[0] / len(test)})

@@ -31,97 +31,42 @@ from __future__ import annotations
 
 import argparse
 import math
-import os
 import sys
+
+from . import cli
 
 DRIVERS = ("ns", "unrolled", "darcy", "airfoil", "pipe", "elas", "plas")
 STATIC_DRIVERS = ("airfoil", "pipe", "elas")
-# what differs between the three reference parsers / module globals
-_PER_DRIVER = {
+# what differs between the seven reference parsers / module globals.  exp_airfoil / exp_pipe / exp_elas / exp_plas: their
+# sample counts are locals of main(), here --ntrain / --ntest (--ntrain is exp_elas's and exp_darcy's only); downsample
+# None: the script has --downsamplex / --downsampley
+_FLAGS = {
     "ns": dict(epochs=30, gpu="0", downsample=1, save_name="ns_2d_UniPDE", ntrain=50, ntest=50),
     "unrolled": dict(epochs=5, gpu="0", downsample=1, save_name="ns_2d_UniPDE", ntrain=100, ntest=50),
     "darcy": dict(epochs=500, gpu="1", downsample=5, save_name="darcy_Transolver", ntrain=1000, ntest=200),
-}
-# exp_airfoil / exp_pipe / exp_elas / exp_plas: their sample counts are locals of main(), here --ntrain / --ntest
-_PER_BENCHMARK = {
-    "airfoil": dict(gpu="0", model="Transolver_2D", save_name="airfoil_Transolver", data_path="/data/fno/airfoil/naca",
+    "airfoil": dict(epochs=500, gpu="0", downsample=None, save_name="airfoil_Transolver", data_path="/data/fno/airfoil/naca",
                     ntrain=1000, ntest=200),
-    "pipe": dict(gpu="0", model="Transolver_2D", save_name="pipe_UniPDE", data_path="/data/fno/pipe", ntrain=1000, ntest=200),
-    "elas": dict(gpu="1", model="Transolver_1D", save_name="elas_Transolver", data_path="/data/fno", ntrain=1000, ntest=200),
-    "plas": dict(gpu="0", model="Transolver_2D", save_name="plas_Transolver", data_path="/data/fno/plas_N987_T20.mat",
+    "pipe": dict(epochs=500, gpu="0", downsample=None, save_name="pipe_UniPDE", data_path="/data/fno/pipe", ntrain=1000,
+                 ntest=200),
+    "elas": dict(epochs=500, gpu="1", downsample=5, model="Transolver_1D", save_name="elas_Transolver", ntrain=1000, ntest=200),
+    "plas": dict(epochs=500, gpu="0", downsample=None, save_name="plas_Transolver", data_path="/data/fno/plas_N987_T20.mat",
                  ntrain=900, ntest=80),
 }
+CHECKPOINTS = "./checkpoints"
 DARCY_SCHEDULE_EPOCHS = 500
 T_IN = T = 10
 STEP = 1
 MAX_LOOK_AHEAD = 10
-NS_FILE = "NavierStokes_V1e-5_N1200_T20"
 DARCY_FILES = ("piececonst_r421_N1024_smooth1.mat", "piececonst_r421_N1024_smooth2.mat")
 
 
-def _benchmark_parser(driver):
-    d = _PER_BENCHMARK[driver]
-    p = argparse.ArgumentParser("Training Transformer")
-    p.add_argument("--lr", type=float, default=1e-3)
-    p.add_argument("--epochs", type=int, default=500)
-    p.add_argument("--weight_decay", type=float, default=1e-5)
-    p.add_argument("--model", type=str, default=d["model"])
-    p.add_argument("--n-hidden", type=int, default=64, help="hidden dim")
-    p.add_argument("--n-layers", type=int, default=3, help="layers")
-    p.add_argument("--n-heads", type=int, default=4)
-    p.add_argument("--batch-size", type=int, default=8)
-    p.add_argument("--gpu", type=str, default=d["gpu"], help="GPU index to use")
-    p.add_argument("--max_grad_norm", type=float, default=None)
-    if driver == "elas":
-        p.add_argument("--downsample", type=int, default=5)
-    else:
-        p.add_argument("--downsamplex", type=int, default=1)
-        p.add_argument("--downsampley", type=int, default=1)
-    p.add_argument("--mlp_ratio", type=int, default=1)
-    p.add_argument("--dropout", type=float, default=0.0)
-    p.add_argument("--ntrain", type=int, default=d["ntrain"])
-    p.add_argument("--unified_pos", type=int, default=0)
-    p.add_argument("--ref", type=int, default=8)
-    p.add_argument("--slice_num", type=int, default=32)
-    p.add_argument("--eval", type=int, default=0)
-    p.add_argument("--save_name", type=str, default=d["save_name"])
-    p.add_argument("--data_path", type=str, default=d["data_path"])
-    # not in the reference (--ntrain is exp_elas's only)
-    p.add_argument("--driver", choices=DRIVERS, default=driver)
-    p.add_argument("--engine", type=str, default=None, help="GEMM engine: f32 | split | bf16 | bf16s")
-    p.add_argument("--ntest", type=int, default=d["ntest"])
-    return p
-
-
 def build_parser(driver):
-    if driver in _PER_BENCHMARK:
-        return _benchmark_parser(driver)
-    d = _PER_DRIVER[driver]
+    d = dict(_FLAGS[driver])
+    ntest = d.pop("ntest")
     p = argparse.ArgumentParser("Training Transolver" if driver == "darcy" else "Training Transformer")
-    p.add_argument("--lr", type=float, default=1e-3)
-    p.add_argument("--epochs", type=int, default=d["epochs"])
-    p.add_argument("--weight_decay", type=float, default=1e-5)
-    p.add_argument("--model", type=str, default="Transolver_2D")
-    p.add_argument("--n-hidden", type=int, default=64, help="hidden dim")
-    p.add_argument("--n-layers", type=int, default=3, help="layers")
-    p.add_argument("--n-heads", type=int, default=4)
-    p.add_argument("--batch-size", type=int, default=8)
-    p.add_argument("--gpu", type=str, default=d["gpu"], help="GPU index to use")
-    p.add_argument("--max_grad_norm", type=float, default=None)
-    p.add_argument("--downsample", type=int, default=d["downsample"])
-    p.add_argument("--mlp_ratio", type=int, default=1)
-    p.add_argument("--dropout", type=float, default=0.0)
-    p.add_argument("--ntrain", type=int, default=d["ntrain"])
-    p.add_argument("--unified_pos", type=int, default=0)
-    p.add_argument("--ref", type=int, default=8)
-    p.add_argument("--slice_num", type=int, default=32)
-    p.add_argument("--eval", type=int, default=0)
-    p.add_argument("--save_name", type=str, default=d["save_name"])
-    p.add_argument("--data_path", type=str, default="/data/fno")
-    # not in the reference
-    p.add_argument("--driver", choices=DRIVERS, default=driver)
-    p.add_argument("--engine", type=str, default=None, help="GEMM engine: f32 | split | bf16 | bf16s")
-    p.add_argument("--ntest", type=int, default=d["ntest"])
+    cli.add_core_flags(p, **d)
+    cli.add_driver_flags(p, DRIVERS, driver, engines="f32 | split | bf16 | bf16s")             # not in the reference
+    p.add_argument("--ntest", type=int, default=ntest)
     return p
 
 
@@ -134,94 +79,53 @@ def command_line_parser(driver):
 
 
 def parse_args(argv=None):
-    pre = argparse.ArgumentParser(add_help=False)
-    pre.add_argument("--driver", choices=DRIVERS, default="ns")
-    driver = pre.parse_known_args(argv)[0].driver
-    parser = command_line_parser(driver)
-    args = parser.parse_args(argv)
-    if driver == "unrolled" and args.graphed:
+    parser, args = cli.parse(argv, DRIVERS, command_line_parser, default="ns")
+    if args.driver == "unrolled" and args.graphed:
         parser.error("--graphed 1 is not available for --driver unrolled: its look-ahead curriculum changes the number of "
                      "chained model calls from epoch to epoch, so there is no one iteration to capture")
     return args
 
 
-def _find(data_path, names):
-    if os.path.isfile(data_path):
-        return data_path
-    for n in names:
-        if os.path.isfile(os.path.join(data_path, n)):
-            return os.path.join(data_path, n)
-    raise FileNotFoundError(f"none of {list(names)} under --data_path {data_path}")
-
-
-def _device(args):
-    import torch
-    idx = int(args.gpu)
-    if not torch.cuda.is_available() or idx >= torch.cuda.device_count():
-        raise SystemExit(f"--gpu {args.gpu}: no such GPU ({torch.cuda.device_count()} visible); this package has no CPU path")
-    torch.cuda.set_device(idx)
-    return torch.device("cuda", idx)
-
-
-def _model_kwargs(args, h, fun_dim):
-    return dict(space_dim=2, n_layers=args.n_layers, n_hidden=args.n_hidden, dropout=args.dropout, n_head=args.n_heads,
-                Time_Input=False, mlp_ratio=args.mlp_ratio, fun_dim=fun_dim, out_dim=1, slice_num=args.slice_num,
-                ref=args.ref, unified_pos=args.unified_pos, H=h, W=h)
-
-
-def _checkpoint(args):
-    return os.path.join("./checkpoints", args.save_name + ".pt")
-
-
-def _optim(args, model, steps_per_epoch, schedule_epochs, clip):
-    import torch
-    from .optim import FusedAdamW
-    opt = FusedAdamW(model.parameters(), lr=args.lr, weight_decay=args.weight_decay, max_grad_norm=clip)
-    sched = torch.optim.lr_scheduler.OneCycleLR(opt, max_lr=args.lr, epochs=schedule_epochs, steps_per_epoch=steps_per_epoch)
-    return opt, sched
+def _optim(args, model, epochs, clip):
+    return cli.optim(model, args.lr, args.weight_decay, epochs, math.ceil(args.ntrain / args.batch_size), clip)
 
 
 def run_ns(args, unrolled):
-    import torch
     from . import data, harness, model_dict
     from .model.SOL_Transolver_Structured_Mesh_2D import SOL_Transolver_Structured_Mesh_2D
     from .utils.testloss import FusedTestLoss
-    dev = _device(args)
-    r = args.downsample
-    split = data.load_ns_mat(_find(args.data_path, (NS_FILE + ".mat", os.path.join(NS_FILE, NS_FILE + ".mat"))),
-                             args.ntrain, args.ntest, T_IN, T, r)
+    dev = cli.device(args)
+    split = data.load_ns_mat(cli.ns_mat_file(args), args.ntrain, args.ntest, T_IN, T, args.downsample)
     h = split["h"]
     pos = data.grid_positions(h)
     train = data.ResidentDataset(pos.repeat(args.ntrain, 1, 1), split["train_a"].float(), split["train_u"].float(), device=dev)
     test = data.ResidentDataset(pos.repeat(args.ntest, 1, 1), split["test_a"].float(), split["test_u"].float(), device=dev)
-    kw = _model_kwargs(args, h, T_IN)
+    kw = cli.model_kwargs(args, T_IN, H=h, W=h)
     if unrolled:
         model = SOL_Transolver_Structured_Mesh_2D(**kw, step=STEP, look_ahead=1).to(dev)
         inner = model.transolver_model
     else:
         model = inner = model_dict.get_model(args).Model(**kw).to(dev)
-    if args.engine is not None:
-        inner.set_engine(args.engine)
-    print(args)
-    print(f"Total Trainable Params: {sum(p.numel() for p in model.parameters() if p.requires_grad)}")
+    cli.set_engine(args, inner)
+    cli.describe(args, model)
     loss_fn = FusedTestLoss(size_average=False)
+    save_path = cli.checkpoint(CHECKPOINTS, args)
     if args.eval:
-        inner.load_state_dict(torch.load(_checkpoint(args), map_location=dev, weights_only=True), strict=True)
+        cli.load_state(inner, save_path, dev, strict=True)
         m = harness.evaluate_ns(inner, test, args.batch_size, T, STEP, loss_fn)
         print(m["test_full"])
         return m
-    steps = math.ceil(args.ntrain / args.batch_size)
     if unrolled:
-        opt, sched = _optim(args, model, steps, args.epochs, None)          # this loop never clips
+        opt, sched = _optim(args, model, args.epochs, None)                 # this loop never clips
         return harness.fit_unrolled(
             model, opt, sched, train, test, epochs=args.epochs, batch_size=args.batch_size, T=T, step=STEP, look_ahead=1,
-            max_look_ahead=MAX_LOOK_AHEAD, loss_fn=loss_fn, save_path=_checkpoint(args), grad_sync=opt.sync,
+            max_look_ahead=MAX_LOOK_AHEAD, loss_fn=loss_fn, save_path=save_path, grad_sync=opt.sync,
             on_epoch=lambda ep, m: print("Epoch {} , train_step_loss:{:.5f} , test_step_loss:{:.5f} , look_ahead:{}".format(
                 ep, m["train_step"], m["test_step"], m["look_ahead"]), flush=True))
-    opt, sched = _optim(args, model, steps, args.epochs, args.max_grad_norm)
+    opt, sched = _optim(args, model, args.epochs, args.max_grad_norm)
     return harness.fit_ns(
         model, opt, sched, train, test, epochs=args.epochs, batch_size=args.batch_size, T=T, step=STEP, loss_fn=loss_fn,
-        save_path=_checkpoint(args), grad_sync=opt.sync, graphed=bool(args.graphed),
+        save_path=save_path, grad_sync=opt.sync, graphed=bool(args.graphed),
         on_epoch=lambda ep, m: print(
             "Epoch {} , train_step_loss:{:.5f} , train_full_loss:{:.5f} , test_step_loss:{:.5f} , test_full_loss:{:.5f}".format(
                 ep, m["train_step"], m["train_full"], m["test_step"], m["test_full"]), flush=True))
@@ -231,31 +135,28 @@ def run_darcy(args):
     import torch
     from . import data, harness, model_dict
     from .utils.testloss import FusedTestLoss, TestLoss
-    dev = _device(args)
-    d = data.load_darcy_mat(_find(args.data_path, DARCY_FILES[:1]), _find(args.data_path, DARCY_FILES[1:]), args.ntrain,
+    dev = cli.device(args)
+    d = data.load_darcy_mat(cli.find(args.data_path, DARCY_FILES[:1]), cli.find(args.data_path, DARCY_FILES[1:]), args.ntrain,
                             args.ntest, args.downsample)
-    model = model_dict.get_model(args).Model(**_model_kwargs(args, d["s"], 1)).to(dev)
-    if args.engine is not None:
-        model.set_engine(args.engine)
-    print(args)
-    print(f"Total Trainable Params: {sum(p.numel() for p in model.parameters() if p.requires_grad)}")
+    model = model_dict.get_model(args).Model(**cli.model_kwargs(args, 1, H=d["s"], W=d["s"])).to(dev)
+    cli.set_engine(args, model)
+    cli.describe(args, model)
     # a real .mat holds a float64 solution: the test metric is then evaluated in float64 by torch, as in the reference
     loss_fn = (FusedTestLoss if d["y_test"].dtype == torch.float32 else TestLoss)(size_average=False)
+    save_path = cli.checkpoint(CHECKPOINTS, args)
     if args.eval:
-        model.load_state_dict(torch.load(_checkpoint(args), map_location=dev, weights_only=True), strict=True)
+        cli.load_state(model, save_path, dev, strict=True)
         m = harness.evaluate_darcy(model, d, args.batch_size, loss_fn)
         print("rel_err:{}".format(m["rel_err"]))
         return m
-    opt, sched = _optim(args, model, math.ceil(args.ntrain / args.batch_size), max(DARCY_SCHEDULE_EPOCHS, args.epochs),
-                        args.max_grad_norm)
+    opt, sched = _optim(args, model, max(DARCY_SCHEDULE_EPOCHS, args.epochs), args.max_grad_norm)
 
     def line(ep, m):
         print("Epoch {} Reg : {:.5f} Train loss : {:.5f}".format(ep, m["reg"], m["train_loss"]))
         print("rel_err:{}".format(m["rel_err"]), flush=True)
 
     return harness.fit_darcy(model, opt, sched, d, epochs=args.epochs, batch_size=args.batch_size, loss_fn=loss_fn,
-                             save_path=_checkpoint(args), fused=True, grad_sync=opt.sync, on_epoch=line,
-                             graphed=bool(args.graphed))
+                             save_path=save_path, fused=True, grad_sync=opt.sync, on_epoch=line, graphed=bool(args.graphed))
 
 
 def _load_static(args):
@@ -269,70 +170,60 @@ def _load_static(args):
 
 def run_static(args):
     """exp_airfoil / exp_pipe / exp_elas: fun_dim = 0 (the placeholder path), one model(x, None) call per batch."""
-    import torch
     from . import harness, model_dict
-    from .optim import FusedAdamW
     from .utils.testloss import FusedTestLoss
-    dev = _device(args)
+    dev = cli.device(args)
     d = _load_static(args)
-    kw = dict(space_dim=2, n_layers=args.n_layers, n_hidden=args.n_hidden, dropout=args.dropout, n_head=args.n_heads,
-              Time_Input=False, mlp_ratio=args.mlp_ratio, fun_dim=0, out_dim=1, slice_num=args.slice_num, ref=args.ref,
-              unified_pos=args.unified_pos)
-    if args.driver != "elas":                       # the irregular-mesh model has no H / W
-        kw.update(H=d["s1"], W=d["s2"])
-    model = model_dict.get_model(args).Model(**kw).to(dev)
-    if args.engine is not None:
-        model.set_engine(args.engine)
-    print(args)
-    print(f"Total Trainable Params: {sum(p.numel() for p in model.parameters() if p.requires_grad)}")
+    per_epoch = args.driver == "elas"
+    mesh = {} if per_epoch else dict(H=d["s1"], W=d["s2"])                  # the irregular-mesh model has no H / W
+    model = model_dict.get_model(args).Model(**cli.model_kwargs(args, 0, **mesh)).to(dev)
+    cli.set_engine(args, model)
+    cli.describe(args, model)
     loss_fn = FusedTestLoss(size_average=False)
-    err_line = "rel_err : {}" if args.driver == "elas" else "rel_err:{}"
+    err_line = "rel_err : {}" if per_epoch else "rel_err:{}"
+    save_path = cli.checkpoint(CHECKPOINTS, args)
     if args.eval:
-        model.load_state_dict(torch.load(_checkpoint(args), map_location=dev, weights_only=True), strict=True)
+        cli.load_state(model, save_path, dev, strict=True)
         m = harness.evaluate_static(model, d, args.batch_size, loss_fn)
         print(err_line.format(m["rel_err"]))
         return m
-    per_epoch = args.driver == "elas"
     if per_epoch:       # exp_elas.py:102 reads an undefined global `epochs`; T_max = --epochs is the evident intent
-        opt = FusedAdamW(model.parameters(), lr=args.lr, weight_decay=args.weight_decay, max_grad_norm=args.max_grad_norm)
-        sched = torch.optim.lr_scheduler.CosineAnnealingLR(opt, T_max=args.epochs)
+        opt, sched = cli.optim(model, args.lr, args.weight_decay, args.epochs, None, args.max_grad_norm)
     else:
-        opt, sched = _optim(args, model, math.ceil(args.ntrain / args.batch_size), args.epochs, args.max_grad_norm)
+        opt, sched = _optim(args, model, args.epochs, args.max_grad_norm)
 
     def line(ep, m):
         print("Epoch {} Train loss : {:.5f}".format(ep, m["train_loss"]))
         print(err_line.format(m["rel_err"]), flush=True)
 
     return harness.fit_static(model, opt, sched, d, epochs=args.epochs, batch_size=args.batch_size, loss_fn=loss_fn,
-                              save_path=_checkpoint(args), scheduler_per_epoch=per_epoch, grad_sync=opt.sync, on_epoch=line,
+                              save_path=save_path, scheduler_per_epoch=per_epoch, grad_sync=opt.sync, on_epoch=line,
                               graphed=bool(args.graphed))
 
 
 def run_plas(args):
     """exp_plas: Time_Input, fun_dim = 1, out_dim = 4 on the 101 x 31 mesh; T = 20 calls and optimizer steps per batch."""
-    import torch
     from . import data, harness, model_dict
     from .utils.testloss import FusedTestLoss
-    dev = _device(args)
+    dev = cli.device(args)
     d = data.load_plas_mat(args.data_path, args.ntrain, args.ntest)
     model = model_dict.get_model(args).Model(
         space_dim=2, n_hidden=args.n_hidden, n_layers=args.n_layers, Time_Input=True, n_head=args.n_heads, fun_dim=1,
         out_dim=data.PLAS_DEFORMATION, mlp_ratio=args.mlp_ratio, slice_num=args.slice_num, unified_pos=args.unified_pos,
         H=d["s1"], W=d["s2"]).to(dev)
-    if args.engine is not None:
-        model.set_engine(args.engine)
-    print(args)
-    print(f"Total Trainable Params: {sum(p.numel() for p in model.parameters() if p.requires_grad)}")
+    cli.set_engine(args, model)
+    cli.describe(args, model)
     loss_fn = FusedTestLoss(size_average=False)
+    save_path = cli.checkpoint(CHECKPOINTS, args)
     if args.eval:
         # exp_plas.py:169 loads with strict=False; a checkpoint of this model has every key, so strict stays on
-        model.load_state_dict(torch.load(_checkpoint(args), map_location=dev, weights_only=True), strict=True)
+        cli.load_state(model, save_path, dev, strict=True)
         m = harness.evaluate_plas(model, d, args.batch_size, loss_fn)
         print("test_step_loss:{:.5f} , test_full_loss:{:.5f}".format(m["test_step"], m["test_full"]))
         return m
-    opt, sched = _optim(args, model, math.ceil(args.ntrain / args.batch_size), args.epochs, args.max_grad_norm)
+    opt, sched = _optim(args, model, args.epochs, args.max_grad_norm)
     return harness.fit_plas(
-        model, opt, sched, d, epochs=args.epochs, batch_size=args.batch_size, loss_fn=loss_fn, save_path=_checkpoint(args),
+        model, opt, sched, d, epochs=args.epochs, batch_size=args.batch_size, loss_fn=loss_fn, save_path=save_path,
         grad_sync=opt.sync, graphed=bool(args.graphed),
         on_epoch=lambda ep, m: print("Epoch {} , train_step_loss:{:.5f} , test_step_loss:{:.5f} , test_full_loss:{:.5f}".format(
             ep, m["train_step"], m["test_step"], m["test_full"]), flush=True))

@@ -33,13 +33,15 @@ import math
 import os
 import sys
 
+from . import cli
+
 DRIVERS = ("autoencoder", "sequensolver", "sequensolver_merged")
-NS_FILE = "NavierStokes_V1e-5_N1200_T20"
 T_IN = T_OUT = 10
 STEP = 1
 LR, WEIGHT_DECAY, BATCH_SIZE = 1e-3, 1e-5, 1                      # the sequence scripts' constants
 GEOMETRY = dict(H=64, W=64, M=16, C=32)
 LAYERS, SEQUENTIAL_HEAD = 8, 16
+CHECKPOINTS = "./sequential_checkpoints"
 ENCODER_CHECKPOINT = os.path.join("sequential_checkpoints", "encoder_ep20_head_1.pt")
 _SEQUENCE = {
     "sequensolver": dict(eval=1, epochs=10, save_name="tokenizer_ep10_sim10_2", sim_num=10, ntest=2),
@@ -52,25 +54,7 @@ def build_parser(driver):
     """The reference script's flag table, then the flags that are not in the reference."""
     p = argparse.ArgumentParser("Training Transformer")
     if driver == "autoencoder":
-        p.add_argument("--lr", type=float, default=1e-3)
-        p.add_argument("--epochs", type=int, default=30)
-        p.add_argument("--weight_decay", type=float, default=1e-5)
-        p.add_argument("--model", type=str, default="Transolver_2D")
-        p.add_argument("--n-hidden", type=int, default=64, help="hidden dim")
-        p.add_argument("--n-layers", type=int, default=3, help="layers")
-        p.add_argument("--n-heads", type=int, default=4)
-        p.add_argument("--batch-size", type=int, default=8)
-        p.add_argument("--gpu", type=str, default="0", help="GPU index to use")
-        p.add_argument("--max_grad_norm", type=float, default=None)
-        p.add_argument("--downsample", type=int, default=1)
-        p.add_argument("--mlp_ratio", type=int, default=1)
-        p.add_argument("--dropout", type=float, default=0.0)
-        p.add_argument("--unified_pos", type=int, default=0)
-        p.add_argument("--ref", type=int, default=8)
-        p.add_argument("--slice_num", type=int, default=32)
-        p.add_argument("--eval", type=int, default=0)
-        p.add_argument("--save_name", type=str, default="ns_2d_UniPDE")
-        p.add_argument("--data_path", type=str, default="/data/fno")
+        cli.add_core_flags(p, epochs=30, gpu="0", save_name="ns_2d_UniPDE", downsample=1)
         p.add_argument("--ntrain", type=int, default=100)          # the script's module globals
         p.add_argument("--ntest", type=int, default=20)
     else:
@@ -87,83 +71,56 @@ def build_parser(driver):
                        help="1: the Tout teacher-forced calls of an iteration as one folded call")
         if driver == "sequensolver":
             p.add_argument("--slice_learner_path", type=str, default=None, help="LearnSlice checkpoint of --eval 1")
-    p.add_argument("--driver", choices=DRIVERS, default=driver)
-    p.add_argument("--engine", type=str, default=None, help="GEMM engine: f32 | split | bf16")
+    cli.add_driver_flags(p, DRIVERS, driver)
     return p
 
 
 def parse_args(argv=None):
-    pre = argparse.ArgumentParser(add_help=False)
-    pre.add_argument("--driver", choices=DRIVERS, required=True)
-    driver = pre.parse_known_args(argv)[0].driver
-    return build_parser(driver).parse_args(argv)
-
-
-def _checkpoint(args):
-    return os.path.join("./sequential_checkpoints", args.save_name + ".pt")
-
-
-def _ns_mat(args):
-    import scipy.io as scio
-    from .train import _find
-    return scio.loadmat(_find(args.data_path, (NS_FILE + ".mat", os.path.join(NS_FILE, NS_FILE + ".mat"))))["u"]
-
-
-def _optim(model, lr, weight_decay, epochs, steps_per_epoch, clip=None):
-    import torch
-    from .optim import FusedAdamW
-    opt = FusedAdamW(model.parameters(), lr=lr, weight_decay=weight_decay, max_grad_norm=clip)
-    return opt, torch.optim.lr_scheduler.OneCycleLR(opt, max_lr=lr, epochs=epochs, steps_per_epoch=steps_per_epoch)
+    return cli.parse(argv, DRIVERS, build_parser, required=True)[1]
 
 
 def run_autoencoder(args):
-    import torch
     from . import data, harness
     from .model import Transolver_Structured_Mesh2D_Encoder
-    from .train import _device
-    dev = _device(args)
+    dev = cli.device(args)
     if args.downsample != 1:        # the script trains on data['u'][:ntrain, :, :, :] whatever --downsample says, at H = W = h
         raise SystemExit("--downsample other than 1: auto_encoder.py builds an h x h model and feeds it the full 64 x 64 frames")
-    d = data.split_ns_all_frames(_ns_mat(args), args.ntrain, args.ntest)
+    d = data.split_ns_all_frames(cli.ns_mat(args), args.ntrain, args.ntest)
     d = dict(d, train=d["train"].float(), test=d["test"].float())
-    h = d["h"]
-    model = Transolver_Structured_Mesh2D_Encoder.Model(
-        space_dim=2, n_layers=args.n_layers, n_hidden=args.n_hidden, dropout=args.dropout, n_head=args.n_heads,
-        Time_Input=False, mlp_ratio=args.mlp_ratio, fun_dim=1, out_dim=1, slice_num=args.slice_num, ref=args.ref,
-        unified_pos=args.unified_pos, H=h, W=h).to(dev)
-    if args.engine is not None:
-        model.set_engine(args.engine)
-    print(args)
-    print(f"Total Trainable Params: {sum(p.numel() for p in model.parameters() if p.requires_grad)}")
+    model = Transolver_Structured_Mesh2D_Encoder.Model(**cli.model_kwargs(args, 1, H=d["h"], W=d["h"])).to(dev)
+    cli.set_engine(args, model)
+    cli.describe(args, model)
+    save_path = cli.checkpoint(CHECKPOINTS, args)
     if args.eval:
-        model.load_state_dict(torch.load(_checkpoint(args), map_location=dev, weights_only=True), strict=False)
-        model.eval()
-        loss_fn = harness.TestLoss(size_average=False)
-        pos = data.grid_positions(h).to(dev)
-        total = torch.zeros((), dtype=torch.float64, device=dev)
-        with torch.no_grad():
-            for fx, in data.ResidentDataset(d["test"], device=dev).batches(args.batch_size):
-                bsz = fx.shape[0]
-                total += loss_fn(model(pos.expand(bsz, -1, -1).contiguous(), fx=fx).reshape(bsz, -1), fx.reshape(bsz, -1))
-        m = dict(test_l2=float(total) / args.ntest)
+        cli.load_state(model, save_path, dev, strict=False)
+        m = harness.evaluate_autoencoder(model, d, args.batch_size, args.ntest)
         print(m["test_l2"])
         return m
-    steps = math.ceil(d["train"].shape[0] / args.batch_size)
-    opt, sched = _optim(model, args.lr, args.weight_decay, args.epochs, steps)
+    opt, sched = cli.optim(model, args.lr, args.weight_decay, args.epochs, math.ceil(d["train"].shape[0] / args.batch_size))
     return harness.fit_autoencoder(
         model, opt, sched, d, epochs=args.epochs, batch_size=args.batch_size, ntrain=args.ntrain, ntest=args.ntest, T=T_OUT,
-        step=STEP, max_grad_norm=args.max_grad_norm, save_path=_checkpoint(args), grad_sync=opt.sync,
+        step=STEP, max_grad_norm=args.max_grad_norm, save_path=save_path, grad_sync=opt.sync,
         on_epoch=lambda ep, m: print(f"Epoch {ep} , train_step_loss:{m['train_step']} , test_step_loss:{m['test_step']}",
                                      flush=True))
 
 
+def load_slice_learner(args, model, dev):
+    """The LearnSlice module of the plain script's evaluation (SequenSolver.py:541-570: unified_pos = 1, use_vorticity = 1),
+    loaded ONCE from --slice_learner_path; the script builds and loads it once per frame."""
+    from .LearnSlice import LearnSlice
+    from .SequenSolver import load_frozen
+    if args.slice_learner_path is None:
+        raise SystemExit("--driver sequensolver --eval 1 needs --slice_learner_path (a LearnSlice checkpoint)")
+    return load_frozen(args.slice_learner_path, lambda: LearnSlice(
+        unified_pos=1, use_vorticity=1, use_code_for_vorticity=False, C=model.C, M=model.M, T=model.T),
+        strict=True, device=dev, freeze=False)
+
+
 def run_sequensolver(args):
-    import torch
     from . import data, harness
-    from .train import _device
     merged = args.driver == "sequensolver_merged"
-    dev = _device(args)
-    split = data.split_ns_trajectories(_ns_mat(args), args.sim_num, args.ntest, T_IN, T_OUT)
+    dev = cli.device(args)
+    split = data.split_ns_trajectories(cli.ns_mat(args), args.sim_num, args.ntest, T_IN, T_OUT)
     pos = data.unified_positions(GEOMETRY["H"], GEOMETRY["W"]).to(dev)            # both scripts set unified_pos = 1
     train = data.ResidentDataset(split["train_a"].float(), split["train_u"].float(), device=dev)
     test = data.ResidentDataset(split["test_a"].float(), split["test_u"].float(), device=dev)
@@ -174,23 +131,16 @@ def run_sequensolver(args):
         from .SequenSolver import SequenSolver
         model = SequenSolver(args.transolver_path, T=T_IN, B=BATCH_SIZE, layers=LAYERS, **GEOMETRY)
     model = model.to(dev)
-    if args.engine is not None:
-        model.set_engine(args.engine)
-    print(args)
+    cli.set_engine(args, model)
+    cli.describe(args)
+    save_path = cli.checkpoint(CHECKPOINTS, args)
     if args.eval:
-        model.load_state_dict(torch.load(_checkpoint(args), map_location=dev, weights_only=True), strict=False)
-        model.eval()
-        total = torch.zeros((), dtype=torch.float64, device=dev)
-        for fx, yy in test.batches(BATCH_SIZE):
-            if merged:
-                _, _, full = harness.sequensolver_rollout(model, pos, fx, yy, use_gt=False)
-            else:
-                full = _slice_learner_rollout(model, args.slice_learner_path, pos, fx, yy)
-            total += full
-        m = dict(test_full=float(total) / args.ntest)
+        cli.load_state(model, save_path, dev, strict=False)
+        m = harness.evaluate_sequensolver(model, pos, test, args.ntest, BATCH_SIZE,
+                                          slice_learner=None if merged else load_slice_learner(args, model, dev))
         print(m["test_full"])
         return m
-    opt, sched = _optim(model, LR, WEIGHT_DECAY, args.epochs, math.ceil(args.sim_num / BATCH_SIZE))
+    opt, sched = cli.optim(model, LR, WEIGHT_DECAY, args.epochs, math.ceil(args.sim_num / BATCH_SIZE))
 
     def line(ep, m):
         print("Epoch {} , train_step_loss:{:.5f} , train_full_loss:{:.5f} , test_step_loss:{:.5f} , test_full_loss:{:.5f}".format(
@@ -200,29 +150,7 @@ def run_sequensolver(args):
 
     return harness.fit_sequensolver(model, opt, sched, pos, train, test, epochs=args.epochs, batch_size=BATCH_SIZE,
                                     variant="merged" if merged else "plain", Tin=T_IN, fold_time=bool(args.fold_time),
-                                    save_path=_checkpoint(args), grad_sync=opt.sync, on_epoch=line)
-
-
-def _slice_learner_rollout(model, slice_learner_path, pos, fx, yy):
-    """SequenSolver.py:553-568: Tout prediction-feedback calls of solve_with_slice_learner; the full rel-L2 of the batch."""
-    import torch
-    from . import harness, ops
-    from .LearnSlice import LearnSlice
-    from .SequenSolver import load_frozen
-    if slice_learner_path is None:
-        raise SystemExit("--driver sequensolver --eval 1 needs --slice_learner_path (a LearnSlice checkpoint)")
-    learner = load_frozen(slice_learner_path, lambda: LearnSlice(       # built once, not once per frame as the script does
-        unified_pos=1, use_vorticity=1, use_code_for_vorticity=False, C=model.C, M=model.M, T=model.T),
-        strict=True, device=fx.device, freeze=False)
-    bsz, preds = fx.shape[0], []
-    with torch.no_grad(), ops.weights_frozen():
-        for t in range(yy.shape[-1]):
-            im = model.solve_with_slice_learner(learner, pos.expand(bsz, -1, -1).contiguous(), fx, yy[..., t:t + 1],
-                                                unified_pos=1, use_vorticity=1)
-            preds.append(im)
-            fx = torch.cat((fx[..., 1:], im), dim=-1)
-    pred = torch.cat(preds, -1)
-    return harness.TestLoss(size_average=False)(pred.reshape(bsz, -1), yy.reshape(bsz, -1))
+                                    save_path=save_path, grad_sync=opt.sync, on_epoch=line)
 
 
 def main(argv=None):

@@ -32,7 +32,8 @@ import math
 import os
 import sys
 
-from .train_sequence import BATCH_SIZE, ENCODER_CHECKPOINT, GEOMETRY, LAYERS, LR, T_IN, T_OUT, WEIGHT_DECAY
+from . import cli
+from .train_sequence import BATCH_SIZE, CHECKPOINTS, ENCODER_CHECKPOINT, GEOMETRY, LAYERS, LR, T_IN, T_OUT, WEIGHT_DECAY
 
 DRIVERS = ("learnslice", "vorticity", "previous")
 SEQUENSOLVER_CHECKPOINT = os.path.join("sequential_checkpoints", "tokenizer_ep10_sim10_2.pt")
@@ -67,20 +68,12 @@ def build_parser(driver):
     p.add_argument("--fold_time", type=int, default=FOLD_TIME_DEFAULT[driver],
                    help="1: codes, targets and previous slices of an iteration from one code_windows call")
     p.add_argument("--gpu", type=str, default="0", help="GPU index to use")
-    p.add_argument("--driver", choices=DRIVERS, default=driver)
-    p.add_argument("--engine", type=str, default=None, help="GEMM engine: f32 | split | bf16")
+    cli.add_driver_flags(p, DRIVERS, driver)
     return p
 
 
 def parse_args(argv=None):
-    pre = argparse.ArgumentParser(add_help=False)
-    pre.add_argument("--driver", choices=DRIVERS, required=True)
-    driver = pre.parse_known_args(argv)[0].driver
-    return build_parser(driver).parse_args(argv)
-
-
-def _checkpoint(args):
-    return os.path.join("./sequential_checkpoints", args.save_name + ".pt")
+    return cli.parse(argv, DRIVERS, build_parser, required=True)[1]
 
 
 def build_learner(args):
@@ -105,47 +98,29 @@ def build_sequen_solver(args, dev):
 
 
 def run(args):
-    import torch
     from . import data, harness
-    from .train import _device
-    from .train_sequence import _ns_mat, _optim
-    dev = _device(args)
-    split = data.split_ns_trajectories(_ns_mat(args), args.ntrain, args.ntest, T_IN, T_OUT)
+    dev = cli.device(args)
+    split = data.split_ns_trajectories(cli.ns_mat(args), args.ntrain, args.ntest, T_IN, T_OUT)
     H, W = GEOMETRY["H"], GEOMETRY["W"]
     pos = (data.unified_positions(H, W) if args.unified_pos else data.grid_positions(H, W)).to(dev)
     train = data.ResidentDataset(split["train_a"].float(), split["train_u"].float(), device=dev)
     test = data.ResidentDataset(split["test_a"].float(), split["test_u"].float(), device=dev)
     solver = build_sequen_solver(args, dev)
     model = build_learner(args).to(dev)
-    if args.engine is not None:
-        solver.set_engine(args.engine)
-        if hasattr(model, "set_engine"):
-            model.set_engine(args.engine)
-    print(args)
+    cli.set_engine(args, solver, *([model] if hasattr(model, "set_engine") else []))
+    cli.describe(args)
     kind = args.driver
+    save_path = cli.checkpoint(CHECKPOINTS, args)
     if args.eval:
-        model.load_state_dict(torch.load(_checkpoint(args), map_location=dev, weights_only=True), strict=False)
-        model.eval()
-        loss_fn = harness.TestLoss(size_average=False)
-        total = torch.zeros(2, dtype=torch.float64, device=dev)
-        for fx, yy in test.batches(BATCH_SIZE):
-            bsz = fx.shape[0]
-            x = pos.expand(bsz, -1, -1).contiguous()
-            if kind == "learnslice":
-                total[0] += harness.slice_learner_test_loss(kind, model, solver, x, fx, yy, args.use_vorticity) / yy.shape[-1]
-                continue
-            rollout = harness.slice_predictor_rollout if kind == "vorticity" else harness.previous_slice_rollout
-            pred = rollout(model, solver, x, fx, yy.shape[-1])
-            total[1] += loss_fn(pred.reshape(bsz, -1), yy.reshape(bsz, -1))
-        a = total.tolist()
-        m = dict(test_slice=a[0] / len(test)) if kind == "learnslice" else dict(test_full=a[1] / len(test))
+        cli.load_state(model, save_path, dev, strict=False)
+        m = harness.evaluate_slice_learner(kind, model, solver, pos, test, args.use_vorticity, BATCH_SIZE)
         print(m)
         return m
     steps = math.ceil(args.ntrain / BATCH_SIZE) * (T_OUT if kind == "learnslice" else 1)
-    opt, sched = _optim(model, args.lr, args.weight_decay, args.epochs, steps)
+    opt, sched = cli.optim(model, args.lr, args.weight_decay, args.epochs, steps)
     return harness.fit_slice_learner(
         model, opt, sched, solver, pos, train, test, epochs=args.epochs, batch_size=BATCH_SIZE, kind=kind,
-        fold_time=bool(args.fold_time), use_vorticity=args.use_vorticity, save_path=_checkpoint(args), grad_sync=opt.sync,
+        fold_time=bool(args.fold_time), use_vorticity=args.use_vorticity, save_path=save_path, grad_sync=opt.sync,
         on_epoch=lambda ep, m: print(f"loss epoch {ep}: {m['train']} , overall test loss {m['test']}", flush=True))
 
 
