@@ -29,6 +29,8 @@ static Pa2dEnv read_env() {
     v.conv_mfma16 = num("PA2D_CONV_MFMA", 16) == 32 ? 0 : 1;
     v.conv_ahead = num("PA2D_CONV_AHEAD", 1) == 0 ? 0 : 1;
     v.mc_mfma16 = num("PA2D_MC_MFMA", 16) == 32 ? 0 : 1;
+    v.mc_dma = num("PA2D_MC_DMA", 1) == 0 ? 0 : 1;
+    v.mc_chain = num("PA2D_MC_CHAIN", 1) == 0 ? 0 : 1;
     v.split_big = num("PA2D_SPLIT_BIG", 1);
     v.slice_map = is("PA2D_SLICE_MAP", "l") ? 0 : 1;
     v.default_engine = is("PA2D_GEMM", "f") ? 0 : (is("PA2D_GEMM", "b") ? 2 : 1);

@@ -329,7 +329,12 @@ __global__ __launch_bounds__(256, 2) void gemm_mc_planes_kernel(const MCPlanesPa
 // rows and the same X rows (at different tap shifts) sit behind one L2.
 // MF16 (NT = 3; PA2D_MC_MFMA=32 turns it off): v_mfma_f32_16x16x32_bf16 on 32-row K-steps read from two of THREE 16-row LDS slots (144 KB);
 // same tile, plane images, transposed reads and bytes per MAC (see the branch below).
-template <int NT, int KS, bool MF16 = false>
+// DMA (MF16 only; PA2D_MC_DMA=0 turns it off): the slots are filled by buffer_load_dwordx4 ... lds, global -> LDS with no
+// staging registers and no ds_write.  CHAIN (on top of DMA; PA2D_MC_CHAIN): the six terms of an accumulator issue back to back.
+#ifndef MB_MID
+#define MB_MID 5      // DMA: the dOut tile in front of whose MFMAs the slot-freeing barrier of a step sits (7 = where register staging has it)
+#endif
+template <int NT, int KS, bool MF16 = false, bool DMA = false, bool CHAIN = false>
 __global__ __launch_bounds__(512, 1) void gemm_mc_planes_big_kernel(const MCPlanesParams p, const int per_xcd) {
     constexpr int PIMG = 8192;                       // one plane image of one K-step: 16 rows x 512 B (256 bf16 columns)
     constexpr int STAGE = 2 * NT * KS * PIMG;        // dOut planes then X planes
@@ -355,7 +360,14 @@ __global__ __launch_bounds__(512, 1) void gemm_mc_planes_big_kernel(const MCPlan
     // staging assignment: the 512 threads cover ONE plane image of ONE 16-row K-step (16 rows x 32 pieces of 16 bytes);
     // piece s of a thread = (operand, plane, k-step) of the same (row, column group c, piece) -> the metadata is per
     // thread, not per piece (a second register set for a 2-stage-deep prefetch was tried: 256 VGPRs + 160 spilled)
-    const int row16 = tid >> 5, cgrp = (tid & 31) >> 2, piece = tid & 3;
+    // DMA: one wave-instruction writes 64 x 16 bytes CONTIGUOUSLY (wave w = rows 2w, 2w+1 of an image, thread t at byte 16 t),
+    // so the row swizzle moves to the global side: thread t fetches the chunk that belongs at linear position t & 31 of its
+    // row, i.e. chunk (t & 31) ^ swizzle(row) -- the image the transposed reads see is byte for byte the same
+    static_assert(!DMA || MF16, "LDS-DMA staging is written for the 16x16x32 pipeline");
+    static_assert(!CHAIN || DMA, "the chained issue order needs the registers that DMA staging frees");
+    const int row16 = tid >> 5;
+    const int lchunk = DMA ? (tid & 31) ^ (((row16 & 3) << 2) | ((row16 >> 2) & 3)) : (tid & 31);
+    const int cgrp = lchunk >> 2, piece = lchunk & 3;
     const bool colok_a = ti * 256 + cgrp * 32 < p.Mi;
     const unsigned goff_a = (unsigned)((((ti * 256) >> 5) + cgrp) * NT * 64 + piece * 16);
     const int jc = tj * 256 + cgrp * 32;             // X: column group = one tap, one 32-channel chunk
@@ -392,7 +404,50 @@ __global__ __launch_bounds__(512, 1) void gemm_mc_planes_big_kernel(const MCPlan
         _Pragma("unroll") for (int s = 0; s < NP; ++s)                                                    \
             *reinterpret_cast<u32x4*>(smem + (buf_) * STAGE + s * PIMG + lds_off) = RG[s];                \
     }
-    u32x4 rg0[NP];
+    // stage c_ straight into slot buf_ (KS = 1).  Same offsets and the same range check as MB_LOAD: rows outside the image,
+    // past c_end or past Mk arrive as zeros; the wave's LDS base goes through M0, the lanes follow at 16 bytes each
+#define MB_DMA(c_, buf_)                                                                                  \
+    {                                                                                                     \
+        const int m_ = (c_) * 16 + row16;                                                                 \
+        const bool okr_ = m_ < p.Mk && (c_) < c_end;                                                      \
+        bool okb_ = okr_ && colok_b;                                                                      \
+        int mm_ = m_;                                                                                     \
+        if (p.taps != 1) {                                                                                \
+            okb_ = okb_ && (unsigned)(ly + tap_dy) < (unsigned)p.H && (unsigned)(lx + tap_dx) < (unsigned)p.W; \
+            mm_ = m_ + tap_shift;                                                                         \
+            lx += 16;                                                                                     \
+            while (lx >= p.W) { lx -= p.W; ++ly; }                                                        \
+            while (ly >= p.H) ly -= p.H;                                                                  \
+        }                                                                                                 \
+        const unsigned oa_ = (okr_ && colok_a) ? (unsigned)m_ * pitch_a + goff_a : OOB_OFF;               \
+        const unsigned ob_ = okb_ ? (unsigned)mm_ * pitch_b + goff_b : OOB_OFF;                           \
+        const unsigned va_[NT] = {oa_, oa_ == OOB_OFF ? OOB_OFF : oa_ + 64u, oa_ == OOB_OFF ? OOB_OFF : oa_ + 128u}; \
+        const unsigned vb_[NT] = {ob_, ob_ == OOB_OFF ? OOB_OFF : ob_ + 64u, ob_ == OOB_OFF ? OOB_OFF : ob_ + 128u}; \
+        unsigned keep_;                                                                                   \
+        asm volatile(MB_DMA_ASM                                                                           \
+                     : "=&s"(keep_)                                                                       \
+                     : "s"(lds_base + (unsigned)(buf_) * (unsigned)STAGE), "s"(dma_ra), "s"(dma_rb),      \
+                       "v"(va_[0]), "v"(va_[1]), "v"(va_[2]), "v"(vb_[0]), "v"(vb_[1]), "v"(vb_[2])       \
+                     : "memory", "scc");                                                                  \
+    }
+    // The six images of a slot are 8 KB apart: M0 steps through them.  The compiler neither counts these loads nor knows that
+    // they write LDS (told so, through the builtin, it drains them with vmcnt(0) in front of the next fragment read): MB_DMA_WAIT
+    // in front of a barrier is the wait.  M0 is the compiler's: saved and restored inside the statement.
+#define MB_DMA_ASM                                                                                        \
+    "s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t"                                      \
+    "buffer_load_dwordx4 %4, %2, 0 offen lds\n\ts_add_u32 m0, m0, 0x2000\n\ts_nop 0\n\t"                  \
+    "buffer_load_dwordx4 %5, %2, 0 offen lds\n\ts_add_u32 m0, m0, 0x2000\n\ts_nop 0\n\t"                  \
+    "buffer_load_dwordx4 %6, %2, 0 offen lds\n\ts_add_u32 m0, m0, 0x2000\n\ts_nop 0\n\t"                  \
+    "buffer_load_dwordx4 %7, %3, 0 offen lds\n\ts_add_u32 m0, m0, 0x2000\n\ts_nop 0\n\t"                  \
+    "buffer_load_dwordx4 %8, %3, 0 offen lds\n\ts_add_u32 m0, m0, 0x2000\n\ts_nop 0\n\t"                  \
+    "buffer_load_dwordx4 %9, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
+#define MB_DMA_WAIT() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
+    static_assert(!DMA || (NT == 3 && PIMG == 0x2000), "MB_DMA_ASM is written out for six 8 KB images");
+    typedef __attribute__((address_space(3))) unsigned char lds_char;
+    const unsigned lds_base = (unsigned)(uintptr_t)(lds_char*)smem + (unsigned)__builtin_amdgcn_readfirstlane(wave) * 1024u;
+    const u32x4 dma_ra = {(unsigned)(uintptr_t)p.PA, (unsigned)((uintptr_t)p.PA >> 32) & 0xFFFFu, p.a_bytes, 0x00020000u};
+    const u32x4 dma_rb = {(unsigned)(uintptr_t)p.PB, (unsigned)((uintptr_t)p.PB >> 32) & 0xFFFFu, p.b_bytes, 0x00020000u};
+    u32x4 rg0[DMA ? 1 : NP];
     // pixel coordinates of this thread's row of the NEXT K-step to be loaded: two integer divisions once, not per K-step
     // (the loads walk the rows in order, 16 per K-step; PMC before: 2.4 vector instructions per MFMA, most of them these)
     int ly = 0, lx = 0;
@@ -429,14 +484,31 @@ __global__ __launch_bounds__(512, 1) void gemm_mc_planes_big_kernel(const MCPlan
             fa[r] = 512u * row + 16u * ((unsigned)(wm * 16 + (pq >> 1)) ^ swz) + 8u * (pq & 1);
             fb[r] = 512u * row + 16u * ((unsigned)(wn * 8 + (pq >> 1)) ^ swz) + 8u * (pq & 1);
         }
-#define MB16_MMA(ib_, AF) _Pragma("unroll") for (int j = 0; j < 4; ++j) split_terms(AF, xf[j], acc[ib_][j]);
+        // CHAIN: left alone the compiler interleaves the four accumulators of a row block term by term; a pin behind each
+        // accumulator keeps its six terms together (same per-accumulator order: the outputs do not change by a bit)
+#define MB16_MMA(ib_, AF)                                                                                 \
+    _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                       \
+        split_terms(AF, xf[j], acc[ib_][j]);                                                              \
+        if constexpr (CHAIN) MB16_CHAIN_PIN(j)                                                            \
+    }
+#define MB16_CHAIN_PIN(j_) __builtin_amdgcn_sched_barrier(0);
         const int nst = c_end - c_begin, steps = (nst + 1) >> 1;
+        // DMA pipeline of step k (no register set; M = MB_MID): tile 0 | DMA stage 2k+2 to R | tiles 1..M-1, fragments of tiles
+        //   M..7 | barrier | DMA stage 2k+3 to P | MFMAs of tiles M..7 | vmcnt(0) | barrier: every wave has its own pieces of both
+        //   slots in LDS before the barrier that publishes them, and no fragment read of R or P lies between a DMA and that
+        //   barrier.  M = 5: 1.07 ms where M = 7 runs 1.21 and register staging 1.19.
         if (nst > 0) {
-            MB_LOAD(c_begin, rg0)
-            MB_STORE(0, rg0)
-            MB_LOAD(c_begin + 1, rg0)
-            MB_STORE(1, rg0)
-            if (steps > 1) MB_LOAD(c_begin + 2, rg0)
+            if constexpr (DMA) {
+                MB_DMA(c_begin, 0)
+                MB_DMA(c_begin + 1, 1)
+                MB_DMA_WAIT();
+            } else {
+                MB_LOAD(c_begin, rg0)
+                MB_STORE(0, rg0)
+                MB_LOAD(c_begin + 1, rg0)
+                MB_STORE(1, rg0)
+                if (steps > 1) MB_LOAD(c_begin + 2, rg0)
+            }
         }
         __syncthreads();
         int sp = 0, sq = 1, sr = 2;
@@ -452,6 +524,30 @@ __global__ __launch_bounds__(512, 1) void gemm_mc_planes_big_kernel(const MCPlan
                 for (int pl = 0; pl < NT; ++pl) xf[j][pl] = MC16_FRAG(ub, j, pl);
             // dOut fragments one 16-row tile ahead of their MFMAs.  Stores and loads past the last step are harmless (free
             // slots, out-of-range offsets) and keep the loop body free of branches.
+            if constexpr (DMA) {
+                // the DMA into P has no registers to land in while P is still read: it starts at the barrier that frees P and
+                // must be in LDS at the end of the step.  So the barrier moves up to tile MB_MID, and the fragments of the
+                // tiles from there on are read before it, together with tile MB_MID's
+                bf16x8 af[8][NT];
+#pragma unroll
+                for (int pl = 0; pl < NT; ++pl) af[0][pl] = MC16_FRAG(ua, 0, pl);
+#pragma unroll
+                for (int ib = 0; ib < 8; ++ib) {
+#pragma unroll
+                    for (int t = 1; t < 8; ++t)
+                        if (ib + 1 == (t < MB_MID ? t : MB_MID)) {
+#pragma unroll
+                            for (int pl = 0; pl < NT; ++pl) af[t][pl] = MC16_FRAG(ua, t, pl);
+                        }
+                    if (ib == 1) MB_DMA(c_begin + 2 * k + 2, sr)
+                    if (ib == MB_MID) {      // every LDS read of the step is done: P is free
+                        __syncthreads();
+                        MB_DMA(c_begin + 2 * k + 3, sp)
+                    }
+                    MB16_MMA(ib, af[ib])
+                }
+                MB_DMA_WAIT();
+            } else {
             bf16x8 afc[NT], afn[NT];
 #pragma unroll
             for (int pl = 0; pl < NT; ++pl) afc[pl] = MC16_FRAG(ua, 0, pl);
@@ -474,6 +570,7 @@ __global__ __launch_bounds__(512, 1) void gemm_mc_planes_big_kernel(const MCPlan
 #pragma unroll
                 for (int pl = 0; pl < NT; ++pl) afc[pl] = afn[pl];
             }
+            }
             __syncthreads();
             const int t = sp;
             sp = sr;
@@ -481,6 +578,7 @@ __global__ __launch_bounds__(512, 1) void gemm_mc_planes_big_kernel(const MCPlan
             sq = t;
         }
 #undef MB16_MMA
+#undef MB16_CHAIN_PIN
         // accumulator quad r = 0..3 of lane l: dW row (dOut channel) ti*256 + wm*128 + ib*16 + (l & 15), columns
         // tj*256 + wn*64 + j*16 + 4*(l >> 4) + r (Nj % 32 == 0: a quad is inside or outside as a whole)
         float* out = p.slab + (size_t)split * p.Mi * p.Nj;
@@ -559,6 +657,9 @@ __global__ __launch_bounds__(512, 1) void gemm_mc_planes_big_kernel(const MCPlan
 #undef MB_COMPUTE
 #undef MB_LOAD
 #undef MB_STORE
+#undef MB_DMA
+#undef MB_DMA_ASM
+#undef MB_DMA_WAIT
 
     float* out = p.slab + (size_t)split * p.Mi * p.Nj;
     const int col0 = tj * 256 + wn * 64 + (lane & 31);
@@ -590,7 +691,10 @@ int launch_wgrad_planes(const MCDesc& d, const MCChoice& c, unsigned a_bytes, un
         p.chA = d.Mi / 32; p.chB = d.Cin / 32;
         const int wgs = ceil_div(p.Mi, 256) * ceil_div(p.Nj, 256) * c.pl.splits;
         int rc;
-        if (mf16) rc = launch_big(&gemm_mc_planes_big_kernel<3, 1, true>, 3 * 2 * 3 * 1 * 8192, p, wgs, st);      // three 16-row slots
+        const int dma = mf16 ? (pa2d_env().mc_dma ? (pa2d_env().mc_chain ? 2 : 1) : 0) : 0;
+        if (dma == 2) rc = launch_big(&gemm_mc_planes_big_kernel<3, 1, true, true, true>, 3 * 2 * 3 * 1 * 8192, p, wgs, st);
+        else if (dma == 1) rc = launch_big(&gemm_mc_planes_big_kernel<3, 1, true, true>, 3 * 2 * 3 * 1 * 8192, p, wgs, st);
+        else if (mf16) rc = launch_big(&gemm_mc_planes_big_kernel<3, 1, true>, 3 * 2 * 3 * 1 * 8192, p, wgs, st);      // three 16-row slots
         else if (NT == 3) rc = launch_big(&gemm_mc_planes_big_kernel<3, 1>, 2 * 2 * 3 * 1 * 8192, p, wgs, st);
         else rc = launch_big(&gemm_mc_planes_big_kernel<1, 4>, 2 * 2 * 1 * 4 * 8192, p, wgs, st);      // four 16-row K-steps per stage
         return rc;

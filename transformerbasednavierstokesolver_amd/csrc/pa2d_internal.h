@@ -141,6 +141,8 @@ struct Pa2dEnv {
     int conv_mfma16;      // PA2D_CONV_MFMA=32 -> 0 (halo conv consumers back on v_mfma_f32_32x32x16_bf16)
     int conv_ahead;       // PA2D_CONV_AHEAD=0 -> 0 (16x16x32 halo conv consumers back on the loop without hand-placed fragment reads)
     int mc_mfma16;        // PA2D_MC_MFMA=32 -> 0 (split-engine weight gradients back on v_mfma_f32_32x32x16_bf16 and 16-row K-steps)
+    int mc_dma;           // PA2D_MC_DMA=0 -> 0 (256 x 256 conv weight gradient back on register staging: global -> VGPR -> ds_write)
+    int mc_chain;         // PA2D_MC_CHAIN=0 -> 0 (with mc_dma: back to the compiler's term-major order over the four accumulators of a row block)
     int lin_small_split;  // PA2D_LIN_SMALL_SPLIT=off -> 0 (small split-engine linears back on the exact-fp32 kernels)
     int lin_rowpanel;     // PA2D_LIN_ROWPANEL=off -> 0 (row-stationary linears back on the panel / per-tile kernels)
     int split_big;        // PA2D_SPLIT_BIG=0 -> 0
