@@ -655,6 +655,40 @@ int pa2d_head_fwd_bf16(const void* xn, const float* w, const float* b, float* y,
 int pa2d_head_bwd_bf16(const float* dy, const void* xn, const float* w, void* dxn, float* dw, float* db, void* ws,
                        size_t ws_bytes, int rows, int C, int out_dim, int accumulate, pa2d_stream_t stream);
 
+/* ---- the step tail of the velocity-field trainers (ns_velocity.py, ns_velocity_unrolling.py, ns_unrolling2_with_t.py): one
+ * prediction is k = `step` columns of a [B, N, T] trajectory.  fp32, no float atomics; partial sums are added in a fixed
+ * order (two calls give the same bits); caller-owned workspace / record, explicit stream, no static state; operands need
+ * 4-byte alignment only (PA2D_ERR_ARG otherwise).  k outside [1, PA2D_WINDOW_MAX_K], F < k, F > PA2D_WINDOW_MAX_F or
+ * B > 65535 return PA2D_ERR_UNSUPPORTED before any pointer is looked at; B = 0 or N = 0 touches nothing.
+ * rel_l2_window: per sample ||pred - y|| / ||y|| of pred [B, N, k] (contiguous) against a column window of a wider
+ * tensor read in place: target element (b, n, j) is y[b * y_batch_stride + n * y_row_stride + j], j < k (strides in
+ * elements).  fwd writes dnorm, ynorm, ratio [B]; ws: at least 2 * B * PA2D_WINDOW_SPLIT floats.  bwd: dpred[b] =
+ * gout[b] (pred_b - y_b) / (dnorm_b ynorm_b), the zero sub-gradient where dnorm_b == 0; no gradient goes to y. */
+#define PA2D_WINDOW_SPLIT 64
+#define PA2D_WINDOW_MAX_K 8
+#define PA2D_WINDOW_MAX_F 64
+int pa2d_rel_l2_window_fwd(const float* pred, const float* y, long long y_row_stride, long long y_batch_stride,
+                           float* dnorm, float* ynorm, float* ratio, void* ws, size_t ws_bytes, int B, int N, int k,
+                           pa2d_stream_t stream);
+int pa2d_rel_l2_window_bwd(const float* pred, const float* y, long long y_row_stride, long long y_batch_stride,
+                           const float* dnorm, const float* ynorm, const float* gout, float* dpred, int B, int N, int k,
+                           pa2d_stream_t stream);
+/* One launch per step of a no-grad prediction-feedback rollout, given pred [B, N, k]: (1) the input window [B, N, F] is
+ * shifted by k columns IN PLACE and pred appended (window[..., :F-k] = window[..., k:], window[..., F-k:] = pred; a tile of
+ * rows is read completely before any of its rows is written, tiles own disjoint rows); (2) traj != NULL: pred is written
+ * into columns [c, c + k) of traj [B, N, T], every other column is left alone (c < 0 or c + k > T: PA2D_ERR_ARG);
+ * (3) y != NULL (addressed as for rel_l2_window): this step's partial sums of (pred - y)^2 and y^2 per sample go into
+ * slot s of record [S, B, PA2D_WINDOW_SPLIT, 2] (s outside [0, S) or record NULL: PA2D_ERR_ARG).
+ * pa2d_rollout_score, once after the last step, adds the record in a fixed order (double): step_ratio [S, B] =
+ * ||pred_s - y_s|| / ||y_s|| and full_ratio [B] = sqrt(sum_s d_s) / sqrt(sum_s y_s), which is the relative L2 of the
+ * concatenated prediction against the whole target because the steps' columns partition it.  N must be the N of the
+ * tail calls (it fixes how many slots of a sample are in use). */
+int pa2d_rollout_tail(const float* pred, float* window, float* traj, long long T, long long c, const float* y,
+                      long long y_row_stride, long long y_batch_stride, float* record, int s, int S, int B, int N, int k,
+                      int F, pa2d_stream_t stream);
+int pa2d_rollout_score(const float* record, float* step_ratio, float* full_ratio, int S, int B, int N,
+                       pa2d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

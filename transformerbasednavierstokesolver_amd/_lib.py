@@ -168,6 +168,16 @@ SIGNATURES.update({
     "pa2d_conv3x3x2_bwd_bf16": (_i, [_f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _sz, _i, _i, _i, _i, _i, _st, _st, _st]),
 })
 
+SIGNATURES.update({      # the velocity-field trainers' step tail (csrc/pa2d_window.hip)
+    "pa2d_rel_l2_window_fwd": (_i, [_f, _f, _ll, _ll, _f, _f, _f, _f, _sz, _i, _i, _i, _st]),
+    "pa2d_rel_l2_window_bwd": (_i, [_f, _f, _ll, _ll, _f, _f, _f, _f, _i, _i, _i, _st]),
+    "pa2d_rollout_tail": (_i, [_f, _f, _f, _ll, _ll, _f, _ll, _ll, _f, _i, _i, _i, _i, _i, _i, _st]),
+    "pa2d_rollout_score": (_i, [_f, _f, _f, _i, _i, _i, _st]),
+})
+WINDOW_SPLIT = 64            # PA2D_WINDOW_SPLIT
+WINDOW_MAX_K = 8             # PA2D_WINDOW_MAX_K
+WINDOW_MAX_F = 64            # PA2D_WINDOW_MAX_F
+
 ERRORS = {1001: "PA2D_ERR_ARG (alignment/shape contract)", 1002: "PA2D_ERR_UNSUPPORTED (size outside kernel grid)",
           1003: "PA2D_ERR_WORKSPACE (workspace too small)"}
 

@@ -282,3 +282,32 @@ def load_plas_mat(path, ntrain=900, ntest=80):
     """exp_plas.py:105: plas_N987_T20.mat ('input', 'output'), see `plas_from_mat`."""
     import scipy.io as scio
     return plas_from_mat(scio.loadmat(path), ntrain, ntest)
+
+
+# ------------------------------------------------------------------------------ ns_velocity.py and its two siblings
+VELOCITY_SIDE = 64      # ns_velocity.py:64: the crop size comes from this constant, not from the array
+
+
+def split_velocity(arr, ntrain, ntest, T_in=10, T=10, r=1):
+    """ns_velocity.py:63-97 (the same lines in ns_velocity_unrolling.py and ns_unrolling2_with_t.py) on the loaded array
+    [S, H, W, >= T_in + T], whose columns interleave (vel_x, vel_y) per frame: h = int((64 - 1) / r + 1), spatial stride r,
+    the [:h, :h] crop, points flattened row-major; the first `ntrain` samples train, the LAST `ntest` test; inputs are
+    columns [0, T_in), targets [T_in, T_in + T).  Returns (h, train, test): ResidentDatasets of (pos, a, u) on the CPU,
+    pos = grid_positions(h) repeated per sample."""
+    arr = np.asarray(arr)
+    h = int(((VELOCITY_SIDE - 1) / r) + 1)
+
+    def cut(block, c0, c1):
+        x = block[:, ::r, ::r, c0:c1][:, :h, :h, :]
+        return torch.from_numpy(np.ascontiguousarray(x.reshape(x.shape[0], -1, x.shape[-1])))
+
+    pos = grid_positions(h)
+    sets = []
+    for block, n in ((arr[:ntrain], ntrain), (arr[-ntest:], ntest)):
+        sets.append(ResidentDataset(pos.repeat(n, 1, 1), cut(block, 0, T_in), cut(block, T_in, T_in + T)))
+    return h, sets[0], sets[1]
+
+
+def load_velocity_npy(path, ntrain, ntest, T_in=10, T=10, r=1):
+    """`split_velocity` of the `.npy` file at `path` (the scripts' ns_50_20.npy / ns_20_20.npy)."""
+    return split_velocity(np.load(path), ntrain, ntest, T_in, T, r)

@@ -977,3 +977,29 @@ def prev_slice_entry(sw, wsw, tb, act, fused=True, engine=None):
     if tb.shape[-1] % 4:
         raise NotImplementedError(f"prev_slice_entry needs a hidden width that is a multiple of 4; got {tb.shape[-1]}")
     return activation(embed_bias(linear(sw, wsw, None, None, engine=engine), None, tb), act)
+
+
+class RelL2WindowFn(Function):
+    """Per-sample ||pred - yy[..., col0:col0+k]|| / ||yy[..., col0:col0+k]|| of pred [B, N, k] with the column window of
+    the wider target read in place (ops.rel_l2_window_fwd / _bwd): the loss of the velocity-field trainers, whose
+    prediction is a (vel_x, vel_y) pair.  Gradient w.r.t. pred only."""
+
+    @staticmethod
+    def forward(ctx, pred, yy, col0):
+        p3, yy = pred.detach().contiguous(), yy.detach()
+        dn, yn, ratio = ops.rel_l2_window_fwd(p3, yy, col0)
+        ctx.saved, ctx.col0 = (p3, yy, dn, yn), col0
+        return ratio
+
+    @staticmethod
+    def backward(ctx, gratio):
+        p3, yy, dn, yn = ctx.saved
+        return ops.rel_l2_window_bwd(p3, yy, ctx.col0, dn, yn, gratio.contiguous()), None, None
+
+
+def rel_l2_window(pred, yy, col0, k):
+    """ratio [B] of pred [B, N, k] against the columns [col0, col0 + k) of yy [B, N, W] (fp32 GPU tensors; yy may be a view
+    with unit stride along its last axis).  `k` must be pred's last dimension."""
+    if pred.dim() != 3 or pred.shape[-1] != k:
+        raise ValueError(f"rel_l2_window needs pred [B, N, {k}]; got {tuple(pred.shape)}")
+    return RelL2WindowFn.apply(pred, yy, col0)

@@ -36,6 +36,11 @@ made (tests/golden/G14-G16, tools/make_golden_drivers.py):
   learnslice_train_step         LearnSlice.py:477-526 (slice weights from the frozen model's code: one optimizer step per frame)
   slice_predictor_train_step    LearnSlice.py:929-962 and :861-913 (the conv slice predictors: Tout summed terms and one step;
   / slice_predictor_rollout     the prediction-feedback evaluation)
+  fit_velocity                  ns_velocity.py:192-273, ns_velocity_unrolling.py:202-313, ns_unrolling2_with_t.py:200-313: the
+  / fit_velocity_unrolled       epoch loops on PhiFlow velocity data (one prediction = a (vel_x, vel_y) pair, step = 2), with
+  / fit_unrolled_t              graphed=True one whole-iteration hipGraph per look-ahead value (end of this file)
+  scored_rollout                their prediction-feedback test pass with one fused launch after each model call (window shift,
+  / GraphedScoredRollout        kept prediction, the step's score) and one after the last; the whole of it in ONE hipGraph
 
 Every *_train_step, the body of fit_unrolled and GraphedTrainStep end in `_apply_step`: [grad_sync], [clip], optimizer.step(),
 [scheduler.step()].  zero_grad and backward stay in each function, because their place differs and is kept as the drivers have
@@ -1607,3 +1612,398 @@ def evaluate_slice_learner(kind, model, sequen_solver, pos, test, use_vorticity=
 
     return _evaluate(model, 1, test_pass,
                      lambda a: {"test_slice" if kind == "learnslice" else "test_full": a[0] / len(test)})
+
+
+# ------------------------------------------------------------------------------ velocity-field trainers
+# ns_velocity.py, ns_velocity_unrolling.py, ns_unrolling2_with_t.py: the exp_ns / SOL-wrapper loops on PhiFlow velocity data,
+# where one prediction is a (vel_x, vel_y) pair: out_dim = step = 2, so a step's target yy[..., t:t+step] is a
+# two-dimensional strided view.  Shared by the three loops below:
+#   * `_step_loss`: the per-call loss; with step > 1, fp32 GPU tensors and the p = 2 batch-sum `rel` it is
+#     functional.rel_l2_window (the target read in place), otherwise `loss_fn` on the reshaped copies, as the scripts do;
+#   * `scored_rollout` / `GraphedScoredRollout`: the prediction-feedback test pass with ONE launch after each model call
+#     (window shift, prediction kept, step scored) and one after the last, no host synchronisation;
+#   * `_ScopedCallStep`: a whole iteration (chained calls, windows, summed loss, backward, staged AdamW) in one hipGraph.
+def _batch_sum_rel(loss_fn):
+    """True where `loss_fn` is the scripts' loss: a `TestLoss` (or FusedTestLoss) with p = 2 that sums over the batch."""
+    return isinstance(loss_fn, TestLoss) and loss_fn.p == 2 and loss_fn.reduction and not loss_fn.size_average
+
+
+def _on_window_kernels(loss_fn, *tensors):
+    return _batch_sum_rel(loss_fn) and all(t.is_cuda and t.dtype == torch.float32 for t in tensors)
+
+
+def _step_loss(loss_fn, im, yy, col, calls=None):
+    """The loss of one model call against the columns [col, col + k) of yy, k = im.shape[-1]; the value (detached, a device
+    tensor) is appended to `calls` where that is a list."""
+    bsz, k = im.shape[0], im.shape[-1]
+    if k > 1 and k <= ops.WINDOW_MAX_K and _on_window_kernels(loss_fn, im, yy) and not yy.requires_grad:
+        v = Fn.rel_l2_window(im, yy, col, k).sum()
+    else:
+        v = loss_fn(im.reshape(bsz, -1), yy[..., col:col + k].reshape(bsz, -1))
+    if calls is not None:
+        calls.append(v.detach())
+    return v
+
+
+def _full_loss(loss_fn, preds, yy, calls=None):
+    bsz = yy.shape[0]
+    with torch.no_grad():
+        v = loss_fn(torch.cat(preds, -1).reshape(bsz, -1), yy.reshape(bsz, -1))
+    if calls is not None:
+        calls.append(v)
+    return v
+
+
+def scored_rollout_supported(model, x, fx, yy, step, loss_fn=None):
+    """True where `scored_rollout` serves the prediction-feedback test pass: the model on the GPU, fp32 tensors, a window of
+    at most ops.WINDOW_MAX_F columns, 1 <= step <= ops.WINDOW_MAX_K dividing T, and (where given) the p = 2 batch-sum `rel`."""
+    return ((loss_fn is None or _batch_sum_rel(loss_fn)) and _device_of(model).type == "cuda"
+            and all(t.is_cuda and t.dtype == torch.float32 for t in (x, fx, yy)) and fx.dim() == 3 and yy.dim() == 3
+            and 1 <= step <= min(ops.WINDOW_MAX_K, fx.shape[-1]) and fx.shape[-1] <= ops.WINDOW_MAX_F
+            and yy.shape[-1] % step == 0 and yy.shape[-1] > 0)
+
+
+def _scored_steps(model, x, win, yy, step, record, traj):
+    """The T / step model calls of a scored rollout on the window `win` (shifted in place), each followed by one
+    pa2d_rollout_tail launch; then the one pa2d_rollout_score launch."""
+    for s in range(yy.shape[-1] // step):
+        im = model(x, fx=win)
+        if im.shape[-1] != step:
+            raise ValueError(f"scored_rollout: the model predicts {im.shape[-1]} columns per call, step is {step}")
+        ops.rollout_tail(im.contiguous(), win, traj, s * step, yy, s * step, record, s)
+    return ops.rollout_score(record, win.shape[1])
+
+
+@torch.no_grad()
+def scored_rollout(model, x, fx, yy, step, keep_pred=False):
+    """The prediction-feedback rollout of the test passes (ns_velocity.py:238-254) with its scores, on the GPU: T / step
+    model calls under `ops.weights_frozen()`, each followed by ONE launch that shifts the input window, appends the
+    prediction, keeps it (keep_pred) and adds the step's partial sums to a record; one more launch reduces the record.
+    Returns (step_ratio [S, B], full_ratio [B], pred [B, N, T] or None), device tensors, no host synchronisation:
+    step_ratio[s, b] = ||pred_s - y_s|| / ||y_s||, full_ratio[b] = the relative L2 of the whole predicted trajectory (the
+    steps' columns partition it, so the concatenated prediction is not needed for it).  `fx` is left as it is."""
+    if not scored_rollout_supported(model, x, fx, yy, step):
+        raise ValueError("scored_rollout needs a model on the GPU, fp32 GPU tensors x, fx [B, N, F <= "
+                         f"{ops.WINDOW_MAX_F}], yy [B, N, T] and 1 <= step <= {ops.WINDOW_MAX_K} dividing T")
+    B, N, _ = fx.shape
+    win = fx.clone(memory_format=torch.contiguous_format)
+    record = ops.rollout_record(yy.shape[-1] // step, B, fx)
+    traj = torch.empty(B, N, yy.shape[-1], dtype=torch.float32, device=fx.device) if keep_pred else None
+    with ops.weights_frozen():
+        step_ratio, full_ratio = _scored_steps(model, x, win, yy, step, record, traj)
+    return step_ratio, full_ratio, traj
+
+
+class GraphedScoredRollout:
+    """The WHOLE scored rollout (every model call, every tail launch and the score) in ONE hipGraph with static buffers
+    (x, the initial window, the target, the window the steps shift, the record, the trajectory).  `run(x, fx, yy)` copies
+    a batch in, refreshes the weight packs the captured launches point at (GraphedRollout's scheme, with its check that
+    parameter storage has not moved) and replays once.  It returns `scored_rollout`'s triple, bit for bit (the same
+    kernels in the same order on the same values); the tensors are the graph's own and hold until the next run."""
+
+    def __init__(self, model, x, fx, yy, step, keep_pred=False, warmup=2, fused_tail=None):
+        if not scored_rollout_supported(model, x, fx, yy, step):
+            raise ValueError("GraphedScoredRollout: what scored_rollout needs")
+        with _fused_tail_set(model, fused_tail):
+            self._capture(model, x, fx, yy, step, keep_pred, warmup)
+
+    def _capture(self, model, x, fx, yy, step, keep_pred, warmup):
+        self.model, self.step = model, step
+        self.x, self.fx, self.yy = x.clone(), fx.clone(memory_format=torch.contiguous_format), yy.clone()
+        B, N, _ = fx.shape
+        self.win = torch.empty_like(self.fx)
+        self.record = ops.rollout_record(yy.shape[-1] // step, B, fx)
+        self.traj = torch.empty(B, N, yy.shape[-1], dtype=torch.float32, device=fx.device) if keep_pred else None
+        self.graph = torch.cuda.CUDAGraph()
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with ops.weights_frozen() as self.packs:
+            with torch.cuda.stream(side), torch.no_grad():
+                for _ in range(warmup):
+                    self._body()
+            torch.cuda.current_stream().wait_stream(side)
+            with torch.no_grad(), torch.cuda.graph(self.graph):
+                self.out = self._body()
+        self._param_ptrs = [p.data_ptr() for p in model.parameters()]
+
+    def _body(self):
+        self.win.copy_(self.fx)
+        return _scored_steps(self.model, self.x, self.win, self.yy, self.step, self.record, self.traj)
+
+    @torch.no_grad()
+    def run(self, x, fx, yy):
+        if [p.data_ptr() for p in self.model.parameters()] != self._param_ptrs:
+            raise RuntimeError("parameter storage moved since this rollout graph was captured (e.g. FusedAdamW / "
+                               "FlatGradSync built afterwards, or .to()); build the optimizer first or re-capture")
+        for buf, t in zip((self.x, self.fx, self.yy), (x, fx, yy)):
+            if t is not None:
+                buf.copy_(t)
+        self.packs.refresh()
+        self.graph.replay()
+        return self.out[0], self.out[1], self.traj
+
+
+class _ScopedCallStep(GraphedCallStep):
+    """GraphedCallStep for an iteration of SEVERAL model calls: zero-grad, the body and the backward sit in one
+    `ops.weights_frozen()` scope inside the capture (each layer's weights are packed once per replay, as in
+    GraphedTrainStep and in the eager iterations below); the staged optimizer step follows outside the scope."""
+
+    def _iteration(self):
+        with ops.weights_frozen():
+            self.opt.zero_grad()
+            parts = self.body(self.model, *self.static)
+            parts[0].backward()
+        self.opt.step_staged()
+        return tuple(p.detach() for p in parts)
+
+
+class StepCurriculum:
+    """look_ahead += 1 whenever `ep % period == 0 and ep >= period and look_ahead <= max_look_ahead`
+    (ns_velocity_unrolling.py:210-214 with period 40, ns_unrolling2_with_t.py:208-212 with period 10): the look-ahead can
+    reach max_look_ahead + 1."""
+
+    def __init__(self, period, look_ahead=1, max_look_ahead=4):
+        self.period, self.look_ahead, self.max_look_ahead = period, look_ahead, max_look_ahead
+
+    def update(self, ep):
+        if ep % self.period == 0 and ep >= self.period and self.look_ahead <= self.max_look_ahead:
+            self.look_ahead += 1
+        return self.look_ahead
+
+
+def velocity_iteration(model, x, fx, yy, step=2, loss_fn=None, calls=None):
+    """Forward part of one ns_velocity.py:204-225 mini-batch (exp_ns's teacher-forced iteration with step columns per
+    call).  Returns (loss [graph attached], full loss)."""
+    loss_fn = loss_fn or TestLoss(size_average=False)
+    loss, preds = 0, []
+    for t in range(0, yy.shape[-1], step):
+        im = model(x, fx=fx)
+        loss = loss + _step_loss(loss_fn, im, yy, t, calls)
+        preds.append(im.detach())
+        fx = torch.cat((fx[..., step:], yy[..., t:t + step]), dim=-1)
+    return loss, _full_loss(loss_fn, preds, yy, calls)
+
+
+def unrolled_window_iteration(sol_model, x, fx, yy, look_ahead, step=2, loss_fn=None, calls=None):
+    """One mini-batch of ns_velocity_unrolling.py:220-227: ONE window, `look_ahead` chained calls through the SOL wrapper,
+    scored against yy[..., offset - step:offset], offset = step * look_ahead.  Returns the loss (graph attached)."""
+    loss_fn = loss_fn or TestLoss(size_average=False)
+    sol_model.n = look_ahead
+    offset = step * look_ahead
+    return _step_loss(loss_fn, sol_model(x, fx), yy, offset - step, calls)
+
+
+def unrolled_t_iteration(sol_model, x, fx, yy, look_ahead, step=2, loss_fn=None, calls=None):
+    """One mini-batch of ns_unrolling2_with_t.py:219-229: every window t in range(0, T - offset + step, step) is scored
+    against yy[..., t + offset - step:t + offset] after `look_ahead` chained calls, and the window then advances by `step`
+    GROUND-TRUTH columns.  Returns the summed loss (graph attached)."""
+    loss_fn = loss_fn or TestLoss(size_average=False)
+    sol_model.n = look_ahead
+    offset = step * look_ahead
+    loss = 0
+    for t in range(0, yy.shape[-1] - offset + step, step):
+        loss = loss + _step_loss(loss_fn, sol_model(x, fx), yy, t + offset - step, calls)
+        fx = torch.cat((fx[..., step:], yy[..., t:t + step]), dim=-1)
+    return loss
+
+
+def _eager_iteration(module, optimizer, scheduler, forward, max_grad_norm, grad_sync):
+    """forward() -> loss parts (the first is differentiated) inside one `ops.weights_frozen()` scope with zero_grad and
+    backward; then `_apply_step`."""
+    with ops.weights_frozen():
+        parts = forward()
+        optimizer.zero_grad(set_to_none=False)
+        parts[0].backward()
+    _apply_step(optimizer, scheduler, module.parameters(), max_grad_norm, grad_sync)
+    return tuple(p.detach() for p in parts)
+
+
+def _velocity_runner(module, optimizer, scheduler, batch_size, graphed, max_grad_norm, grad_sync, calls, forward, nparts):
+    """run(key, x, fx, yy) -> the `nparts` detached loss parts of one iteration `forward(key, x, fx, yy, calls)`.  Eager:
+    the iteration as the scripts run it.  graphed: a full batch replays the `_ScopedCallStep` of `key` (the look-ahead),
+    captured when the curriculum first reaches that key; the short last batch runs eagerly.  A replay's per-call loss
+    values are copied to `calls` (the graph's own tensors are overwritten by the next replay)."""
+    graphs = {}
+
+    def run(key, x, fx, yy):
+        if not (graphed and x.shape[0] == batch_size):
+            return _eager_iteration(module, optimizer, scheduler, lambda: forward(key, x, fx, yy, calls), max_grad_norm,
+                                    grad_sync)
+        if key not in graphs:
+            def body(_, sx, sfx, syy):
+                vals = []
+                return forward(key, sx, sfx, syy, vals) + tuple(vals)
+            graphs[key] = _ScopedCallStep(module, optimizer, scheduler, (x.clone(), fx.clone(), yy.clone()), body)
+        out = graphs[key](x, fx, yy)
+        if calls is not None:
+            calls.extend(v.clone() for v in out[nparts:])
+        return out[:nparts]
+
+    return run
+
+
+@torch.no_grad()
+def _velocity_test_pass(model, test, batch_size, T, step, loss_fn, acc, full=True, calls=None, graphed=False, _graphs=None):
+    """The prediction-feedback test pass of the three scripts (ns_velocity.py:238-254): acc[2] += the summed step losses,
+    acc[3] += the loss of the whole trajectory (full).  On `scored_rollout` where `scored_rollout_supported` says so (with
+    graphed: full batches replay one GraphedScoredRollout, kept in `_graphs`), otherwise the torch loop."""
+    for x, fx, yy in test.batches(batch_size):
+        yy = yy[..., :T]
+        bsz = x.shape[0]
+        if scored_rollout_supported(model, x, fx, yy, step, loss_fn):
+            if graphed and bsz == batch_size:
+                if "rollout" not in _graphs:
+                    _graphs["rollout"] = GraphedScoredRollout(model, x, fx, yy, step)
+                step_ratio, full_ratio, _ = _graphs["rollout"].run(x, fx, yy)
+            else:
+                step_ratio, full_ratio, _ = scored_rollout(model, x, fx, yy, step)
+            per_step = step_ratio.sum(1)
+            acc[2] += per_step.sum()
+            if calls is not None:
+                calls.extend(per_step.unbind(0))
+            if full:
+                total = full_ratio.sum()
+                acc[3] += total
+                if calls is not None:
+                    calls.append(total)
+            continue
+        loss, preds = 0, []
+        with ops.weights_frozen():
+            for t in range(0, T, step):
+                im = model(x, fx=fx)
+                loss = loss + _step_loss(loss_fn, im, yy, t, calls)
+                preds.append(im)
+                fx = torch.cat((fx[..., step:], im), dim=-1)
+        acc[2] += loss
+        if full:
+            acc[3] += _full_loss(loss_fn, preds, yy, calls)
+
+
+def evaluate_velocity(model, test, batch_size, T=10, step=2, loss_fn=None, full=True, calls=None, graphed=False):
+    """The test pass alone: {'test_step'} (and {'test_full'} with full) normalised like the loops' metrics."""
+    loss_fn = loss_fn or TestLoss(size_average=False)
+    graphs = {}
+    m = _evaluate(model, 4, lambda acc: _velocity_test_pass(model, test, batch_size, T, step, loss_fn, acc, full, calls,
+                                                            graphed, graphs),
+                  lambda a: _ns_test_metrics(a, len(test), T / step))
+    return m if full else dict(test_step=m["test_step"])
+
+
+def _velocity_setup(who, module, optimizer, max_grad_norm, graphed):
+    if graphed:
+        _refuse_graphed_dropout(module, who)
+        _graphed_refusals(who, optimizer, max_grad_norm)
+        _capturable_model(module, who)
+
+
+def fit_velocity(model, optimizer, scheduler, train, test, *, epochs, batch_size, T=10, step=2, max_grad_norm=None,
+                 loss_fn=None, epoch_orders=None, generator=None, save_path=None, save_every=100, graphed=False,
+                 grad_sync=None, on_epoch=None, calls=None):
+    """The epoch loop of ns_velocity.main() (ns_velocity.py:192-273): exp_ns's loop on velocity data, `step` = 2 columns
+    (vel_x, vel_y) per model call.  `train` / `test`: data.ResidentDataset of (x [n, N, 2], fx [n, N, T_in], yy [n, N, >= T])
+    on the model's device (any device: a CPU module goes through the same loop).
+
+    Per batch the teacher-forced iteration (T / step calls, summed loss, the loss of the whole trajectory, zero_grad,
+    backward, [grad_sync], [clip], optimizer.step(), scheduler.step()); per epoch the prediction-feedback test pass
+    (`scored_rollout` on the GPU).  Metrics, unrounded, as the script prints them: train_step = sum / ntrain / (T / step),
+    train_full = sum / ntrain, test_step = sum / ntest / (T / step), test_full = sum / ntest.  One host synchronisation
+    per epoch.  The whole model's state_dict is saved when ep % save_every == 0 and after the last epoch.
+    `calls`: a list that receives every loss value (device tensors) in the script's call order.
+    `graphed=True` (CUDA, optim.FusedAdamW, one rank, no dropout, clip inside the optimizer): full batches replay ONE
+    hipGraph of the whole iteration with its optimizer step and the test pass one GraphedScoredRollout, bit for bit the
+    eager results; the short last batch runs eagerly."""
+    _velocity_setup("fit_velocity", model, optimizer, max_grad_norm, graphed)
+    loss_fn = loss_fn or TestLoss(size_average=False)
+    ntrain, ntest, ncalls = len(train), len(test), T / step
+
+    def forward(key, x, fx, yy, vals):
+        return velocity_iteration(model, x, fx, yy, step, loss_fn, vals)
+    run = _velocity_runner(model, optimizer, scheduler, batch_size, graphed, max_grad_norm, grad_sync, calls, forward, 2)
+    graphs = {}
+
+    def train_batch(batch, acc):
+        x, fx, yy = batch
+        loss, full = run(0, x, fx, yy[..., :T])
+        acc[0] += loss
+        acc[1] += full
+
+    return _fit(model, epochs=epochs, n_acc=4, batches=lambda ep: _epoch_batches(train, batch_size, ep, epoch_orders, generator),
+                train_batch=train_batch,
+                test_pass=lambda acc: _velocity_test_pass(model, test, batch_size, T, step, loss_fn, acc, True, calls, graphed,
+                                                          graphs),
+                metrics=lambda a: dict(train_step=a[0] / ntrain / ncalls, train_full=a[1] / ntrain,
+                                       **_ns_test_metrics(a, ntest, ncalls)),
+                on_epoch=on_epoch, save_path=save_path, save_every=save_every)
+
+
+def _fit_sol(who, sol_model, optimizer, scheduler, train, test, curriculum, iteration, accumulate, *, epochs,
+             batch_size, T, step, loss_fn, epoch_orders, generator, save_path, save_every, graphed, grad_sync, on_epoch, calls):
+    """What fit_velocity_unrolled and fit_unrolled_t share: the curriculum stepped before an epoch's first batch, the
+    per-look-ahead iteration (eager, or one graph per look-ahead value), the test pass on the INNER model with the step
+    loss only, the inner model saved."""
+    _velocity_setup(who, sol_model, optimizer, None, graphed)
+    loss_fn = loss_fn or TestLoss(size_average=False)
+    ntest, ncalls = len(test), T / step
+    inner = sol_model.transolver_model
+    sol_model.n = curriculum.look_ahead
+
+    def forward(la, x, fx, yy, vals):
+        return (iteration(sol_model, x, fx, yy, la, step, loss_fn, vals),)
+    run = _velocity_runner(sol_model, optimizer, scheduler, batch_size, graphed, None, grad_sync, calls, forward, 1)
+    graphs = {}
+
+    def batches(ep):
+        sol_model.n = curriculum.update(ep)      # before the epoch's first batch; it then holds for the epoch
+        return _epoch_batches(train, batch_size, ep, epoch_orders, generator)
+
+    def train_batch(batch, acc):
+        x, fx, yy = batch
+        (loss,) = run(curriculum.look_ahead, x, fx, yy[..., :T])
+        if accumulate:
+            acc[0] += loss
+        else:
+            acc[0] = loss
+
+    return _fit(sol_model, epochs=epochs, n_acc=4, batches=batches, train_batch=train_batch,
+                test_pass=lambda acc: _velocity_test_pass(inner, test, batch_size, T, step, loss_fn, acc, False, calls, graphed,
+                                                          graphs),
+                metrics=lambda a: dict(train_step=a[0], test_step=_ns_test_metrics(a, ntest, ncalls)["test_step"],
+                                       look_ahead=curriculum.look_ahead),
+                on_epoch=on_epoch, save_path=save_path, save_every=save_every, save_module=inner)
+
+
+def fit_velocity_unrolled(sol_model, optimizer, scheduler, train, test, *, epochs, batch_size, T=20, step=2, look_ahead=1,
+                          max_look_ahead=8, period=40, loss_fn=None, epoch_orders=None, generator=None, save_path=None,
+                          save_every=100, graphed=False, grad_sync=None, on_epoch=None, calls=None):
+    """The epoch loop of ns_velocity_unrolling.main() (ns_velocity_unrolling.py:202-313) on the SOL wrapper.  Per batch ONE
+    window: `look_ahead` chained calls scored against yy[..., offset - step:offset], zero_grad, backward, [grad_sync],
+    step, scheduler.step(); it never clips.  look_ahead += 1 when ep % period == 0 and ep >= period and look_ahead <=
+    max_look_ahead (`StepCurriculum`; the defaults are the script's module constants).  The test pass runs the inner
+    `transolver_model` with prediction feedback and keeps the step loss.
+
+    Returns one dict per epoch: test_step = sum / ntest / (T / step), as printed; train_step = the loss of the epoch's
+    LAST batch (the script assigns, it does not add, and never prints it), kept on the device and read with the epoch's one
+    synchronisation (the script's per-batch `loss.item()` is gone); look_ahead.  Saves the inner model's state_dict.
+    `calls`, `graphed`: as fit_velocity, with one graph per look-ahead value, built when the curriculum first reaches it."""
+    return _fit_sol("fit_velocity_unrolled", sol_model, optimizer, scheduler, train, test,
+                    StepCurriculum(period, look_ahead, max_look_ahead), unrolled_window_iteration, False,
+                    epochs=epochs, batch_size=batch_size, T=T, step=step, loss_fn=loss_fn, epoch_orders=epoch_orders,
+                    generator=generator, save_path=save_path, save_every=save_every, graphed=graphed, grad_sync=grad_sync,
+                    on_epoch=on_epoch, calls=calls)
+
+
+def fit_unrolled_t(sol_model, optimizer, scheduler, train, test, *, epochs, batch_size, T=10, step=2, look_ahead=1,
+                   max_look_ahead=4, period=10, loss_fn=None, epoch_orders=None, generator=None, save_path=None,
+                   save_every=100, graphed=False, grad_sync=None, on_epoch=None, calls=None):
+    """The epoch loop of ns_unrolling2_with_t.main() (ns_unrolling2_with_t.py:200-313) on the SOL wrapper: per batch every
+    window t in range(0, T - offset + step, step), `look_ahead` chained calls scored against yy[..., t + offset - step:
+    t + offset], the window then advanced by `step` ground-truth columns; one backward over the summed loss.  look_ahead
+    += 1 when ep % period == 0 and ep >= period and look_ahead <= max_look_ahead.
+
+    Returns one dict per epoch: train_step = the RAW epoch sum (what the script prints), test_step = sum / ntest /
+    (T / step), look_ahead.  Everything else as fit_velocity_unrolled."""
+    return _fit_sol("fit_unrolled_t", sol_model, optimizer, scheduler, train, test,
+                    StepCurriculum(period, look_ahead, max_look_ahead), unrolled_t_iteration, True,
+                    epochs=epochs, batch_size=batch_size, T=T, step=step, loss_fn=loss_fn, epoch_orders=epoch_orders,
+                    generator=generator, save_path=save_path, save_every=save_every, graphed=graphed, grad_sync=grad_sync,
+                    on_epoch=on_epoch, calls=calls)

@@ -1405,3 +1405,89 @@ def prev_slice_entry_bwd(dh0, sw, wsw, tb, act):
     _lib.check(_L().pa2d_prev_slice_entry_bwd(_p(dh0), _p(sw), _p(wsw), _p(tb), _p(dwsw), _p(dtb), ws.data_ptr(), nb, B, N,
                                               M, H, ACT_IDS[act], _stream()), "prev_slice_entry_bwd")
     return dwsw, dtb
+
+
+# ---------------------------------------------------------------------------------------------- velocity-field step tail
+WINDOW_SPLIT, WINDOW_MAX_K, WINDOW_MAX_F = _lib.WINDOW_SPLIT, _lib.WINDOW_MAX_K, _lib.WINDOW_MAX_F
+
+
+def _column_window(pred, yy, col0, what):
+    """(B, N, k, pointer of yy[0, 0, col0], row stride, batch stride) for pred [B, N, k] and the columns [col0, col0 + k) of
+    yy [B, N, W]: any fp32 GPU view with unit stride along its last axis (yy[..., :T] of a longer tensor included)."""
+    _chk(pred)
+    if pred.dim() != 3 or yy.dim() != 3 or tuple(yy.shape[:2]) != tuple(pred.shape[:2]):
+        raise ValueError(f"{what} needs pred [B, N, k] and a target [B, N, W]; got {tuple(pred.shape)}, {tuple(yy.shape)}")
+    if not yy.is_cuda or yy.dtype != torch.float32 or (yy.shape[-1] > 1 and yy.stride(-1) != 1):
+        raise ValueError(f"{what} needs an fp32 GPU target with unit stride along its last axis")
+    B, N, k = pred.shape
+    if not 0 <= col0 <= yy.shape[-1] - k:
+        raise ValueError(f"{what}: columns [{col0}, {col0 + k}) are outside a target of {yy.shape[-1]} columns")
+    if not 1 <= k <= WINDOW_MAX_K:
+        raise ValueError(f"{what} handles 1 <= k <= {WINDOW_MAX_K} columns per prediction; got {k}")
+    return B, N, k, _p(yy, col0), yy.stride(1), yy.stride(0)
+
+
+def rel_l2_window_fwd(pred, yy, col0):
+    """Per-sample ||pred - yy[..., col0:col0+k]|| / ||yy[..., col0:col0+k]|| with the target read where it lies.
+    Returns (dnorm, ynorm, ratio), each [B]."""
+    B, N, k, yp, rs, bs = _column_window(pred, yy, col0, "rel_l2_window")
+    dn = torch.empty(B, dtype=torch.float32, device=pred.device)
+    yn, ratio = torch.empty_like(dn), torch.empty_like(dn)
+    nb = 4 * 2 * B * WINDOW_SPLIT
+    ws = _ws(nb, pred)
+    _lib.check(_L().pa2d_rel_l2_window_fwd(_p(pred), yp, rs, bs, _p(dn), _p(yn), _p(ratio), ws.data_ptr(), nb, B, N, k,
+                                           _stream()), "rel_l2_window_fwd")
+    return dn, yn, ratio
+
+
+def rel_l2_window_bwd(pred, yy, col0, dn, yn, gout):
+    """gout: per-sample upstream gradient [B].  Returns d pred [B, N, k]."""
+    B, N, k, yp, rs, bs = _column_window(pred, yy, col0, "rel_l2_window")
+    _chk(dn, yn, gout)
+    if gout.numel() != B or dn.numel() != B or yn.numel() != B:
+        raise ValueError("dn, yn and gout must hold one value per sample")
+    dpred = torch.empty_like(pred)
+    _lib.check(_L().pa2d_rel_l2_window_bwd(_p(pred), yp, rs, bs, _p(dn), _p(yn), _p(gout), _p(dpred), B, N, k, _stream()),
+               "rel_l2_window_bwd")
+    return dpred
+
+
+def rollout_record(nsteps, B, like):
+    """The record [S, B, WINDOW_SPLIT, 2] that `rollout_tail` fills step by step and `rollout_score` reduces."""
+    return torch.empty(nsteps, B, WINDOW_SPLIT, 2, dtype=torch.float32, device=like.device)
+
+
+def rollout_tail(pred, window, traj=None, col=0, yy=None, ycol=0, record=None, s=0):
+    """One launch after a model call of a no-grad rollout: `window` [B, N, F] is shifted by k columns in place and `pred`
+    [B, N, k] appended; traj [B, N, T] (optional) receives pred in columns [col, col + k); with a target yy [B, N, W]
+    (optional; columns [ycol, ycol + k) are this step's) the step's partial sums go into slot `s` of `record`."""
+    _chk(pred, window, traj, record)
+    if window.dim() != 3 or pred.dim() != 3 or tuple(window.shape[:2]) != tuple(pred.shape[:2]):
+        raise ValueError(f"rollout_tail needs pred [B, N, k] and a window [B, N, F]; got {tuple(pred.shape)}, "
+                         f"{tuple(window.shape)}")
+    (B, N, k), F = pred.shape, window.shape[-1]
+    if not 1 <= k <= min(F, WINDOW_MAX_K) or F > WINDOW_MAX_F:
+        raise ValueError(f"rollout_tail handles 1 <= k <= min(F, {WINDOW_MAX_K}) and F <= {WINDOW_MAX_F}; got k = {k}, F = {F}")
+    T = 0
+    if traj is not None:
+        if traj.dim() != 3 or tuple(traj.shape[:2]) != (B, N) or not 0 <= col <= traj.shape[-1] - k:
+            raise ValueError(f"rollout_tail: columns [{col}, {col + k}) do not lie in a trajectory buffer {tuple(traj.shape)}")
+        T = traj.shape[-1]
+    yp = rs = bs = S = 0
+    if yy is not None:
+        _, _, _, yp, rs, bs = _column_window(pred, yy, ycol, "rollout_tail")
+        if record is None or record.dim() != 4 or tuple(record.shape[1:]) != (B, WINDOW_SPLIT, 2) or not 0 <= s < record.shape[0]:
+            raise ValueError("rollout_tail: a target needs a record [S, B, WINDOW_SPLIT, 2] and a step index inside it")
+        S = record.shape[0]
+    _lib.check(_L().pa2d_rollout_tail(_p(pred), _p(window), _p(traj), T, col, yp, rs, bs, _p(record), s, S, B, N, k, F,
+                                      _stream()), "rollout_tail")
+
+
+def rollout_score(record, N):
+    """(step_ratio [S, B], full_ratio [B]) of a record that S `rollout_tail` calls on [B, N, .] tensors filled."""
+    _chk(record)
+    S, B = record.shape[:2]
+    step_ratio = torch.empty(S, B, dtype=torch.float32, device=record.device)
+    full_ratio = torch.empty(B, dtype=torch.float32, device=record.device)
+    _lib.check(_L().pa2d_rollout_score(_p(record), _p(step_ratio), _p(full_ratio), S, B, N, _stream()), "rollout_score")
+    return step_ratio, full_ratio

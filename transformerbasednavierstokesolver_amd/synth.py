@@ -307,3 +307,25 @@ def plas_output_sample(index, seed, s1=101, s2=31, T=20):
     du = a * t * np.sin(np.pi * i + ph) * (1 - j)
     dv = b * t * np.cos(np.pi * j) * i
     return np.stack([50.0 * i + du, 15.0 * j + dv, du, dv], axis=-1).astype(np.float32)
+
+
+def velocity_fields(S, H=64, W=64, frames=20, seed=0):
+    """[S, H, W, 2 * frames] fp32: a seeded, divergence-free (vel_x, vel_y) sequence standing in for the PhiFlow arrays of
+    ns_velocity.py (ns_50_20.npy: frame t is the column pair (2 t, 2 t + 1), vel_x first).  The vorticity w of
+    `synth_ns_fields` gives the stream function psi with -lap psi = w (spectral, the mean mode dropped) and the velocity
+    (d psi / dy, -d psi / dx), whose spectral divergence is zero mode by mode; unit std overall."""
+    w = synth_ns_fields(S, H, W, frames, seed).astype(np.float64)
+    ky = 2.0 * np.pi * np.fft.fftfreq(H, d=1.0 / H)[:, None]
+    kx = 2.0 * np.pi * np.fft.fftfreq(W, d=1.0 / W)[None, :]
+    k2 = ky ** 2 + kx ** 2
+    k2[0, 0] = 1.0
+    psi = np.fft.fft2(w, axes=(1, 2)) / k2[None, :, :, None]
+    psi[:, 0, 0, :] = 0.0
+    if H % 2 == 0:                       # the Nyquist rows / columns have no real derivative: dropped
+        psi[:, H // 2, :, :] = 0.0
+    if W % 2 == 0:
+        psi[:, :, W // 2, :] = 0.0
+    vx =np.real(np.fft.ifft2(1j * ky[None, :, :, None] * psi, axes=(1, 2)))
+    vy = np.real(np.fft.ifft2(-1j * kx[None, :, :, None] * psi, axes=(1, 2)))
+    out = np.stack((vx, vy), axis=-1).reshape(S, H, W, 2 * frames)
+    return (out / out.std()).astype(np.float32)
