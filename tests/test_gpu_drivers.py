@@ -133,6 +133,45 @@ def test_fit_ns_graphed_is_bit_identical_to_eager():
     assert any(not torch.equal(p0[k].cpu(), torch.from_numpy(dr.weights(case)[k])) for k in p0)     # it did train
 
 
+def _counted(monkeypatch, module, name):
+    hits = []
+    real = getattr(module, name)
+    monkeypatch.setattr(module, name, lambda *a, **k: (hits.append(1), real(*a, **k))[1])
+    return hits
+
+
+def test_the_fused_switch_keeps_the_exp_ns_loops_off_the_window_kernels(monkeypatch):
+    """harness's `fused` switch from both sides, at step = 2 where the two routes differ: 8 x 8 points, C = 32, 4 heads,
+    M = 8, 2 layers, out_dim = 2; 3 training and 3 test samples at batch 2 (a short last batch each), T = 4, one epoch.
+    fit_ns and evaluate_ns never reach functional.rel_l2_window, ops.rollout_tail or ops.rollout_score; fit_velocity on the
+    same data runs every training loss on the first (2 batches x 2 calls) and its test pass on the other two (2 batches x
+    2 tails, 2 scores)."""
+    import velocity_restatement as vr
+    from transformerbasednavierstokesolver_amd import data, functional, harness, ops
+    from transformerbasednavierstokesolver_amd.optim import FusedAdamW
+    from transformerbasednavierstokesolver_amd.utils.testloss import FusedTestLoss
+    train_set, test_set = (data.ResidentDataset(*[t[:3] for t in ds.tensors]) for ds in vr.datasets("velocity", DEV))
+    window, tails, scores = (_counted(monkeypatch, functional, "rel_l2_window"), _counted(monkeypatch, ops, "rollout_tail"),
+                             _counted(monkeypatch, ops, "rollout_score"))
+
+    def run(fit):
+        model = harness.build_model(vr.model_config("velocity"), vr.weights("velocity"), DEV)
+        opt = FusedAdamW(model.parameters(), lr=5e-4, weight_decay=1e-5)
+        sched = torch.optim.lr_scheduler.OneCycleLR(opt, max_lr=5e-4, epochs=1, steps_per_epoch=2)
+        hist = fit(model, opt, sched, train_set, test_set, epochs=1, batch_size=2, T=4, step=2,
+                   loss_fn=FusedTestLoss(size_average=False), epoch_orders=[[2, 0, 1]], grad_sync=opt.sync)
+        assert len(hist) == 1 and all(np.isfinite(v) and v > 0 for v in hist[0].values()), hist
+        return model, hist[0]
+
+    model, last = run(harness.fit_ns)
+    ev = harness.evaluate_ns(model, test_set, 2, T=4, step=2, loss_fn=FusedTestLoss(size_average=False))
+    # the epoch's test pass again, on the same weights (the bound of the Darcy test above)
+    assert sorted(ev) == ["test_full", "test_step"] and all(abs(ev[k] - last[k]) <= 1e-6 * last[k] for k in ev), (ev, last)
+    assert (len(window), len(tails), len(scores)) == (0, 0, 0)
+    run(harness.fit_velocity)
+    assert (len(window), len(tails), len(scores)) == (2 * 2, 2 * 2, 2)
+
+
 def test_train_command_line_end_to_end(tmp_path):
     """`python -m ...train --driver ns` as a fresh child process on a .mat in a temporary directory; a second child reads
     the checkpoint with --eval 1 and prints the metric of the last epoch's test pass."""

@@ -206,6 +206,51 @@ def test_graphed_loops_refuse_what_they_would_not_apply():
         harness.fit_velocity(model, opt, sched, train_set, test_set, epochs=1, batch_size=4, graphed=True)
 
 
+def test_graphed_or_eager_keeps_one_graph_per_key():
+    """On stubs: a full batch with key k builds once per distinct k and replays after that; a short batch goes to `eager`
+    even when a graph for its key exists; with graphed=False `build` is never called; no key is the one key None.  A key
+    that is given reaches build, replay and eager as their last argument."""
+    full, short = torch.zeros(4, 1), torch.zeros(3, 1)
+    for graphed in (True, False):
+        log, keys = [], []
+        run = harness._graphed_or_eager(graphed, 4,
+                                        lambda x, tag, *k: keys.append(k) or log.append(("build", tag)) or ("graph", tag),
+                                        lambda graph, x, tag, *k: keys.append(k) or log.append(("replay", graph, tag)) or "replayed",
+                                        lambda x, tag, *k: keys.append(k) or log.append(("eager", x.shape[0], tag)) or "eager")
+        got = [run(full, "a", key=1), run(full, "b", key=1), run(full, "c", key=2), run(short, "d", key=1),
+               run(full, "e", key=1), run(full, "f"), run(full, "g"), run(short, "h")]
+        if not graphed:
+            assert got == ["eager"] * 8 and [e[0] for e in log] == ["eager"] * 8
+            assert keys == [(1,), (1,), (2,), (1,), (1,), (), (), ()]
+            continue
+        assert keys == [(1,), (1,), (1,), (2,), (2,), (1,), (1,), (), (), (), ()]
+        assert got == ["replayed", "replayed", "replayed", "eager", "replayed", "replayed", "replayed", "eager"]
+        assert log == [("build", "a"), ("replay", ("graph", "a"), "a"), ("replay", ("graph", "a"), "b"),
+                       ("build", "c"), ("replay", ("graph", "c"), "c"), ("eager", 3, "d"), ("replay", ("graph", "a"), "e"),
+                       ("build", "f"), ("replay", ("graph", "f"), "f"), ("replay", ("graph", "f"), "g"), ("eager", 3, "h")]
+
+
+def test_velocity_runner_hands_the_key_to_the_eager_iteration():
+    """The short batch of a graphed SOL loop runs eagerly at ITS look-ahead, with the loop's own zero_grad argument."""
+    seen = []
+    model = torch.nn.Linear(1, 1)
+
+    class Opt:
+        def zero_grad(self, **kw):
+            seen.append(("zero_grad", kw))
+
+        def step(self):
+            seen.append("step")
+
+    def forward(key, x, fx, yy, vals):
+        seen.append(("forward", key, x.shape[0]))
+        return (model(x).sum(),)
+
+    run = harness._velocity_runner(model, Opt(), None, 4, True, None, None, None, forward, 1, dict(set_to_none=False))
+    (loss,) = run(3, torch.ones(2, 1), None, None)
+    assert seen == [("forward", 3, 2), ("zero_grad", dict(set_to_none=False)), "step"] and not loss.requires_grad
+
+
 def test_scored_rollout_refuses_a_cpu_module():
     case = "velocity"
     model = dr.OracleModel(vr.model_config(case), vr.weights(case))

@@ -61,31 +61,23 @@ def build(case, dev, look_ahead):
         it = harness.unrolled_window_iteration if case == "velocity_unrolled" else harness.unrolled_t_iteration
         forward = lambda key, a, b, c, vals: (it(module, a, b, c, key, STEP, loss_fn, vals),)
         nparts = 1
-    runs = {mode: harness._velocity_runner(module, opt, sched, BATCH, mode == "graphed", None, None, None, forward, nparts)
+    runs = {mode: harness._velocity_runner(module, opt, sched, BATCH, mode == "graphed", None, None, None, forward, nparts,
+                                           dict(set_to_none=False))
             for mode in ("eager", "graphed")}
     key = 0 if case == "velocity" else look_ahead
     train = {mode: (lambda run=run: run(key, x, fx, yy)) for mode, run in runs.items()}
-
-    full = case == "velocity"
-
-    def torch_loop():
-        acc = torch.zeros(4, dtype=torch.float64, device=dev)
-        harness._velocity_test_pass(inner, _OneBatch(x, fx, yy), BATCH, T, STEP, lambda a, b: loss_fn(a, b), acc, full)
-        return acc
-
-    def scored():
-        acc = torch.zeros(4, dtype=torch.float64, device=dev)
-        harness._velocity_test_pass(inner, _OneBatch(x, fx, yy), BATCH, T, STEP, loss_fn, acc, full)
-        return acc
-
     graphs = {}
 
-    def graphed():
-        acc = torch.zeros(4, dtype=torch.float64, device=dev)
-        harness._velocity_test_pass(inner, _OneBatch(x, fx, yy), BATCH, T, STEP, loss_fn, acc, full, None, True, graphs)
-        return acc
+    def test_pass(fused, graphed):
+        def run():
+            acc = torch.zeros(4, dtype=torch.float64, device=dev)
+            harness._rollout_test_pass(inner, _OneBatch(x, fx, yy), BATCH, T, STEP, loss_fn, acc, case == "velocity", fused,
+                                       None, graphed, graphs)
+            return acc
+        return run
 
-    return module, opt, train, dict(torch_loop=torch_loop, scored=scored, graphed=graphed)
+    return module, opt, train, dict(torch_loop=test_pass(False, False), scored=test_pass(True, False),
+                                    graphed=test_pass(True, True))
 
 
 class _OneBatch:

@@ -42,12 +42,16 @@ made (tests/golden/G14-G16, tools/make_golden_drivers.py):
   scored_rollout                their prediction-feedback test pass with one fused launch after each model call (window shift,
   / GraphedScoredRollout        kept prediction, the step's score) and one after the last; the whole of it in ONE hipGraph
 
-Every *_train_step, the body of fit_unrolled and GraphedTrainStep end in `_apply_step`: [grad_sync], [clip], optimizer.step(),
+Every *_train_step, the SOL loops and GraphedTrainStep end in `_apply_step`: [grad_sync], [clip], optimizer.step(),
 [scheduler.step()].  zero_grad and backward stay in each function, because their place differs and is kept as the drivers have
 it: the Darcy, static and plasticity steps zero with set_to_none=False outside any `ops.weights_frozen()` scope (before the
-model call; plas after it), the others zero after the forward and inside the scope (train_step with its `set_to_none`
-argument, the rest with the optimizer's default); the sequence-model and slice steps clip the trainable parameters only, the
-others all of them.
+model call; plas after it), the others zero after the forward and inside the scope (the NS time-stepping family through the one
+`_eager_iteration`: train_step with its `set_to_none` argument, fit_unrolled with the optimizer's default, the velocity loops
+with set_to_none=False; the rest with the optimizer's default); the sequence-model and slice steps clip the trainable
+parameters only, the others all of them.  The NS time-stepping drivers (exp_ns, ns_vorticity_unrolling and the three velocity
+scripts) are one family: one teacher-forced loop, one prediction-feedback test pass, one windowed SOL loop and one SOL epoch
+loop, switched by `fused` (see `_step_loss`); the four Graphed* classes capture through `_warm_capture` and guard their
+parameter pointers with `_ParamPointers`.
 """
 from __future__ import annotations
 
@@ -91,22 +95,60 @@ def train_iteration(model, x, fx, yy, step=1, loss_fn=None, fold_time=False):
     With training-mode dropout the folded call draws ONE larger mask per layer for all its windows where the loop draws one
     per call: both are valid dropout, from different stretches of the generator, so the two routes are not bit-equal then."""
     loss_fn = loss_fn or TestLoss(size_average=False)
-    T = yy.shape[-1]
     bsz = x.shape[0]
     if fold_time:
         return _train_iteration_folded(model, x, fx, yy, step, loss_fn)
-    loss = 0
-    preds = []
-    for t in range(0, T, step):
-        y = yy[..., t:t + step]
-        im = model(x, fx=fx)
-        loss = loss + loss_fn(im.reshape(bsz, -1), y.reshape(bsz, -1))
-        preds.append(im)
-        fx = torch.cat((fx[..., step:], y), dim=-1)          # teacher forcing with ground truth
+    loss, preds = _teacher_forced(model, x, fx, yy, step, loss_fn, False)
     pred = torch.cat(preds, -1)
     with torch.no_grad():
         full = loss_fn(pred.reshape(bsz, -1), yy.reshape(bsz, -1))
     return loss, full, pred
+
+
+def _batch_sum_rel(loss_fn):
+    """True where `loss_fn` is the scripts' loss: a `TestLoss` (or FusedTestLoss) with p = 2 that sums over the batch."""
+    return isinstance(loss_fn, TestLoss) and loss_fn.p == 2 and loss_fn.reduction and not loss_fn.size_average
+
+
+def _step_loss(loss_fn, im, yy, col, fused, calls=None):
+    """The loss of one model call against the columns [col, col + k) of yy, k = im.shape[-1]; the value (detached, a device
+    tensor) is appended to `calls` where that is a list.  `fused` is THE switch for "on the window kernels" of the NS
+    time-stepping family: False (exp_ns, ns_vorticity_unrolling: fit_ns, evaluate_ns, train_step, GraphedTrainStep,
+    fit_unrolled) is always `loss_fn` on the reshaped copies, as the scripts have it; True (the velocity loops) is
+    functional.rel_l2_window, the target read in place, where k > 1 with fp32 GPU tensors and the p = 2 batch-sum `rel`, and
+    the same `loss_fn` call otherwise.  At k = 1 the two are the same code; at k > 1 they differ in the last bits.
+    The target columns are counted by the prediction's width k, where the scripts count by `step`: the same wherever the
+    model's out_dim equals step, as in every script and fixture (with another out_dim the scripts' own reshape fails)."""
+    bsz, k = im.shape[0], im.shape[-1]
+    if (fused and 1 < k <= ops.WINDOW_MAX_K and _batch_sum_rel(loss_fn) and not yy.requires_grad
+            and all(t.is_cuda and t.dtype == torch.float32 for t in (im, yy))):
+        v = Fn.rel_l2_window(im, yy, col, k).sum()
+    else:
+        v = loss_fn(im.reshape(bsz, -1), yy[..., col:col + k].reshape(bsz, -1))
+    if calls is not None:
+        calls.append(v.detach())
+    return v
+
+
+def _full_loss(loss_fn, preds, yy, calls=None):
+    bsz = yy.shape[0]
+    with torch.no_grad():
+        v = loss_fn(torch.cat(preds, -1).reshape(bsz, -1), yy.reshape(bsz, -1))
+    if calls is not None:
+        calls.append(v)
+    return v
+
+
+def _teacher_forced(model, x, fx, yy, step, loss_fn, fused, calls=None):
+    """The teacher-forced loop of exp_ns.py:199-211 and ns_velocity.py:204-225: T / step model calls, the input window of
+    each built from GROUND TRUTH columns only.  Returns (summed per-call loss, the per-call predictions), graphs attached."""
+    loss, preds = 0, []
+    for t in range(0, yy.shape[-1], step):
+        im = model(x, fx=fx)
+        loss = loss + _step_loss(loss_fn, im, yy, t, fused, calls)
+        preds.append(im)
+        fx = torch.cat((fx[..., step:], yy[..., t:t + step]), dim=-1)
+    return loss, preds
 
 
 def _train_iteration_folded(model, x, fx, yy, step, loss_fn):
@@ -149,12 +191,21 @@ def train_step(model, optimizer, scheduler, x, fx, yy, step=1, max_grad_norm=Non
     the optimizer step (all-reduce SUM of the flat gradient bucket).  With `optim.FusedAdamW` pass
     `grad_sync=optimizer.sync` (same bucket) and put the clip threshold in the optimizer instead of
     `max_grad_norm`."""
-    with ops.weights_frozen():       # no parameter moves between the first model call and the end of backward
-        loss, full, _ = train_iteration(model, x, fx, yy, step, loss_fn, fold_time)
-        optimizer.zero_grad(set_to_none=set_to_none)
-        loss.backward()
-    _apply_step(optimizer, scheduler, model.parameters(), max_grad_norm, grad_sync)
-    return loss.detach(), full
+    return _eager_iteration(model, optimizer, scheduler, lambda: train_iteration(model, x, fx, yy, step, loss_fn, fold_time)[:2],
+                            max_grad_norm, grad_sync, dict(set_to_none=set_to_none))
+
+
+def _eager_iteration(module, optimizer, scheduler, forward, max_grad_norm, grad_sync, zero_grad_kw):
+    """The eager iteration of train_step, fit_unrolled and the velocity loops: forward() -> loss parts (the first is
+    differentiated), optimizer.zero_grad(**zero_grad_kw) and the backward inside ONE `ops.weights_frozen()` scope (no
+    parameter moves between the first model call and the end of backward); then `_apply_step` on the module's parameters.
+    Returns the detached parts."""
+    with ops.weights_frozen():
+        parts = forward()
+        optimizer.zero_grad(**zero_grad_kw)
+        parts[0].backward()
+    _apply_step(optimizer, scheduler, module.parameters(), max_grad_norm, grad_sync)
+    return tuple(p.detach() for p in parts)
 
 
 class _fused_tail_set:
@@ -188,7 +239,68 @@ def rollout(model, x, fx, nsteps, step=1, fused_tail=None):
     return torch.cat(frames, -1)
 
 
-class GraphedRollout:
+def _warm_capture(body, warmup, between=None, before_run=None):
+    """The capture of every Graphed* class: `warmup` runs of body() on a side stream that waits for the current one (they
+    set kernel attributes and warm the allocator), the current stream waits for the side stream, `between()` where given
+    (state that the warm-up moved is put back), then ONE more run inside torch.cuda.graph.  `before_run()`, where given,
+    runs ahead of every one of those runs and outside the capture (the optimizer's host half).  Returns (graph, what the
+    captured run returned)."""
+    current, side = torch.cuda.current_stream(), torch.cuda.Stream()
+    side.wait_stream(current)
+    with torch.cuda.stream(side):
+        for _ in range(warmup):
+            if before_run is not None:
+                before_run()
+            body()
+    current.wait_stream(side)
+    if between is not None:
+        between()
+    if before_run is not None:
+        before_run()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        out = body()
+    return graph, out
+
+
+class _ParamPointers:
+    """Captured launches hold raw parameter pointers: anything that re-seats parameter storage afterwards (an optimizer
+    that flattens the parameters, .to(), load with assign=True) invalidates the graph.  Records the pointers of `model`'s
+    parameters; check() raises RuntimeError "parameter storage moved since this `what` was captured`advice`"."""
+
+    def __init__(self, model, what, advice):
+        self.model, self.what, self.advice = model, what, advice
+        self.ptrs = [p.data_ptr() for p in model.parameters()]
+
+    def check(self):
+        if [p.data_ptr() for p in self.model.parameters()] != self.ptrs:
+            raise RuntimeError(f"parameter storage moved since this {self.what} was captured{self.advice}")
+
+
+class _RolloutGraph:
+    """What GraphedRollout and GraphedScoredRollout share: warm-up and capture under no_grad, with the model's fused block
+    tail set as asked, inside one `ops.weights_frozen()` scope that is kept: the conv weight packs are made during the
+    warm-up and only REFERENCED by the captured launches, and `_ready()` refreshes them in place before a replay, so later
+    weight updates (training between rollouts) are seen."""
+
+    def _capture(self, model, body, warmup, fused_tail, between=None):
+        self.model = model
+        with _fused_tail_set(model, fused_tail), ops.weights_frozen() as self.packs, torch.no_grad():
+            self.graph, out = _warm_capture(body, warmup, between)
+        self._ptrs = _ParamPointers(model, "rollout graph", " (e.g. FusedAdamW / FlatGradSync built afterwards, or .to()); "
+                                    "build the optimizer first or re-capture")
+        return out
+
+    def _ready(self, buffers, batch):
+        """Before a replay: the pointer check, the batch copied into the static buffers (None keeps one), the packs."""
+        self._ptrs.check()
+        for buf, t in zip(buffers, batch):
+            if t is not None:
+                buf.copy_(t)
+        self.packs.refresh()
+
+
+class GraphedRollout(_RolloutGraph):
     """One autoregressive step (model call + window shift) captured in a hipGraph and replayed.
 
     Static buffers: `x`, the input window `fx` [B,N,fun_dim] and the output `im`.  The window shift
@@ -198,30 +310,9 @@ class GraphedRollout:
     captured step keeps that route; the model's own flag is restored when the constructor returns)."""
 
     def __init__(self, model, x, fx, step=1, warmup=2, fused_tail=None):
-        with _fused_tail_set(model, fused_tail):
-            self._capture(model, x, fx, step, warmup)
-
-    def _capture(self, model, x, fx, step, warmup):
-        self.model, self.step = model, step
-        self.x = x.clone()
-        self.fx = fx.clone()
-        self.graph = torch.cuda.CUDAGraph()
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        # the conv weight packs are made during the warm-up and only REFERENCED by the captured step; run()
-        # refreshes them in place before replaying, so later weight updates (training between rollouts) are seen
-        with ops.weights_frozen() as self.packs:
-            with torch.cuda.stream(side), torch.no_grad():
-                for _ in range(warmup):
-                    self._step_eager()
-            torch.cuda.current_stream().wait_stream(side)
-            self.fx.copy_(fx)
-            with torch.no_grad(), torch.cuda.graph(self.graph):
-                self._step_eager()
+        self.step, self.x, self.fx = step, x.clone(), fx.clone()
+        self._capture(model, self._step_eager, warmup, fused_tail, between=lambda: self.fx.copy_(fx))
         self.fx.copy_(fx)
-        # the captured launches hold raw parameter pointers: anything that re-seats parameter storage afterwards
-        # (an optimizer that flattens the parameters, .to(), load with assign=True) invalidates the graph
-        self._param_ptrs = [p.data_ptr() for p in model.parameters()]
 
     def _step_eager(self):
         self.im = self.model(self.x, fx=self.fx)
@@ -232,11 +323,7 @@ class GraphedRollout:
 
     @torch.no_grad()
     def run(self, fx0, nsteps):
-        if [p.data_ptr() for p in self.model.parameters()] != self._param_ptrs:
-            raise RuntimeError("parameter storage moved since this rollout graph was captured (e.g. FusedAdamW / "
-                               "FlatGradSync built afterwards, or .to()); build the optimizer first or re-capture")
-        self.fx.copy_(fx0)
-        self.packs.refresh()
+        self._ready((self.fx,), (fx0,))
         frames = []
         for _ in range(nsteps):
             self.graph.replay()
@@ -279,17 +366,11 @@ class GraphedTrainStep:
         self.model, self.opt, self.sched, self.step_size, self.loss_fn = model, optimizer, scheduler, step, loss_fn
         self.x, self.fx, self.yy = x.clone(), fx.clone(), yy.clone()
         snap = [p.detach().clone() for p in model.parameters()]
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(warmup):           # sets kernel attributes, warms the allocator
-                self._fwd_bwd()
-        torch.cuda.current_stream().wait_stream(side)
-        for p, q in zip(model.parameters(), snap):     # warm-up must not move the weights
-            p.data.copy_(q)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            self.loss, self.full = self._fwd_bwd()
+
+        def restore():                                     # warm-up must not move the weights
+            for p, q in zip(model.parameters(), snap):
+                p.data.copy_(q)
+        self.graph, (self.loss, self.full) = _warm_capture(self._fwd_bwd, warmup, between=restore)
 
     def _fwd_bwd(self):
         with ops.weights_frozen():      # inside the capture: each layer's weights are packed once per replay
@@ -352,22 +433,15 @@ class GraphedCallStep:
         opt = optimizer
         snap = [t.clone() for t in (opt.flat_p, opt.exp_avg, opt.exp_avg_sq)]
         steps = opt.steps
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(warmup):           # sets kernel attributes, warms the allocator, marks the touched parameters
-                opt.stage_step()
-                self._iteration()
-        torch.cuda.current_stream().wait_stream(side)
-        self._restore(snap, steps)
-        self.ranges = opt.sync.active_ranges()
-        self.graph = torch.cuda.CUDAGraph()
-        opt.stage_step()                      # a valid row for the capture's own (never executed) launches to point at
-        with torch.cuda.graph(self.graph):
-            self.out = self._iteration()
+
+        def between():                        # the warm-up has marked the touched parameters
+            self._restore(snap, steps)
+            self.ranges = opt.sync.active_ranges()
+        # stage_step before every run: also a valid row for the capture's own (never executed) launches to point at
+        self.graph, self.out = _warm_capture(self._iteration, warmup, between=between, before_run=opt.stage_step)
         self._restore(snap, steps)
         opt.sync.release_untouched()          # what step() leaves behind; a replay changes no Python state
-        self._param_ptrs = [p.data_ptr() for p in model.parameters()]
+        self._ptrs = _ParamPointers(model, "iteration", "; re-capture")
 
     def _restore(self, snap, steps):
         opt = self.opt
@@ -387,8 +461,7 @@ class GraphedCallStep:
         if self.opt.sync.active_ranges() != self.ranges:
             raise RuntimeError("the set of parameters with a gradient changed since this iteration was captured (its "
                                "AdamW launches cover the ranges of then); re-capture")
-        if [p.data_ptr() for p in self.model.parameters()] != self._param_ptrs:
-            raise RuntimeError("parameter storage moved since this iteration was captured; re-capture")
+        self._ptrs.check()
         with torch.no_grad():
             for buf, t in zip(self.static, batch):
                 if t is not None:
@@ -433,21 +506,42 @@ def _plas_body(loss_fn):
 
 
 # ------------------------------------------------------------------------------ unrolled look-ahead training
-def unrolled_train_iteration(sol_model, x, fx, yy, look_ahead, step=1, loss_fn=None):
-    """One mini-batch of ns_vorticity_unrolling.py:225-244.  `sol_model.n` chained calls per window;
-    the window then advances by `look_ahead` GROUND-TRUTH frames.  Returns the loss (graph attached)."""
+def _windowed_iteration(sol_model, x, fx, yy, look_ahead, step, starts, loss_fn, fused, calls=None):
+    """The windowed loop of the three SOL scripts: at every window start t of `starts` (the script's own range), `look_ahead`
+    chained calls through the SOL wrapper, scored against yy[..., t + offset - step:t + offset], offset = step * look_ahead;
+    the window then advances by `starts.step` GROUND-TRUTH columns.  `starts` None: the single window at 0, which never
+    advances and whose loss is returned as it is.  Returns the summed loss (graph attached)."""
     loss_fn = loss_fn or TestLoss(size_average=False)
     sol_model.n = look_ahead
     offset = step * look_ahead
-    T = yy.shape[-1]
-    bsz = x.shape[0]
+    if starts is None:
+        return _step_loss(loss_fn, sol_model(x, fx), yy, offset - step, fused, calls)
     loss = 0
-    for t in range(0, T - look_ahead + 1, look_ahead):
-        y = yy[..., t + offset - step:t + offset]
-        im = sol_model(x, fx)
-        loss = loss + loss_fn(im.reshape(bsz, -1), y.reshape(bsz, -1))
-        fx = torch.cat((fx[..., look_ahead:], yy[..., t:t + look_ahead]), dim=-1)
+    for t in starts:
+        loss = loss + _step_loss(loss_fn, sol_model(x, fx), yy, t + offset - step, fused, calls)
+        fx = torch.cat((fx[..., starts.step:], yy[..., t:t + starts.step]), dim=-1)
     return loss
+
+
+def unrolled_train_iteration(sol_model, x, fx, yy, look_ahead, step=1, loss_fn=None):
+    """One mini-batch of ns_vorticity_unrolling.py:225-244.  `sol_model.n` chained calls per window;
+    the window then advances by `look_ahead` GROUND-TRUTH frames.  Returns the loss (graph attached)."""
+    return _windowed_iteration(sol_model, x, fx, yy, look_ahead, step, range(0, yy.shape[-1] - look_ahead + 1, look_ahead),
+                               loss_fn, False)
+
+
+def unrolled_window_iteration(sol_model, x, fx, yy, look_ahead, step=2, loss_fn=None, calls=None):
+    """One mini-batch of ns_velocity_unrolling.py:220-227: ONE window, `look_ahead` chained calls through the SOL wrapper,
+    scored against yy[..., offset - step:offset], offset = step * look_ahead.  Returns the loss (graph attached)."""
+    return _windowed_iteration(sol_model, x, fx, yy, look_ahead, step, None, loss_fn, True, calls)
+
+
+def unrolled_t_iteration(sol_model, x, fx, yy, look_ahead, step=2, loss_fn=None, calls=None):
+    """One mini-batch of ns_unrolling2_with_t.py:219-229: every window t in range(0, T - offset + step, step) is scored
+    against yy[..., t + offset - step:t + offset] after `look_ahead` chained calls, and the window then advances by `step`
+    GROUND-TRUTH columns.  Returns the summed loss (graph attached)."""
+    return _windowed_iteration(sol_model, x, fx, yy, look_ahead, step, range(0, yy.shape[-1] - step * look_ahead + step, step),
+                               loss_fn, True, calls)
 
 
 class LookAheadCurriculum:
@@ -898,45 +992,65 @@ _rel_err = lambda total, ntest: dict(rel_err=total / ntest)                     
 
 
 def _graphed_or_eager(graphed, batch_size, build, replay, eager):
-    """run(*batch) of a loop with a graph mode.  A full batch (batch[0].shape[0] == batch_size) of a graphed loop goes to
-    `replay(graph, *batch)`, where `graph = build(*batch)` is made of the first full batch; every other batch, and every
-    batch of an eager loop, goes to `eager(*batch)`."""
-    graph = None
+    """run(*batch, key=None) of a loop with a graph mode.  A full batch (batch[0].shape[0] == batch_size) of a graphed loop
+    goes to `replay(graph, *batch)`, where `graph = build(*batch)` is made of the first full batch with that `key` (one
+    graph per key: the look-ahead of the SOL loops; the other loops have the one key None); every other batch, and every
+    batch of an eager loop, goes to `eager(*batch)`.  A key that is given is handed on to the three as their last argument."""
+    graphs = {}
 
-    def run(*batch):
-        nonlocal graph
+    def run(*batch, key=None):
+        args = batch if key is None else batch + (key,)
         if not (graphed and batch[0].shape[0] == batch_size):
-            return eager(*batch)
-        if graph is None:
-            graph = build(*batch)
-        return replay(graph, *batch)
+            return eager(*args)
+        if key not in graphs:
+            graphs[key] = build(*args)
+        return replay(graphs[key], *args)
 
     return run
 
 
 @torch.no_grad()
-def _ns_test_pass(model, test, batch_size, T, step, loss_fn, acc, full=True):
-    """exp_ns.py:225-241: prediction-feedback rollout of every test batch; acc[2] += step loss, acc[3] += full loss."""
+def _rollout_test_pass(model, test, batch_size, T, step, loss_fn, acc, full, fused, calls=None, graphed=False, graphs=None):
+    """The prediction-feedback test pass of the NS scripts (exp_ns.py:225-241, ns_vorticity_unrolling.py:264-286,
+    ns_velocity.py:238-254): acc[2] += the summed step losses, acc[3] += the loss of the whole trajectory (full); every
+    value also goes to `calls` where that is a list.  With `fused` (the velocity loops) and where
+    `scored_rollout_supported` says so it runs on `scored_rollout` (graphed: full batches replay one GraphedScoredRollout,
+    kept in the caller's dict `graphs`); otherwise the torch loop, whose step losses follow `_step_loss(fused)`."""
     for x, fx, yy in test.batches(batch_size):
         yy = yy[..., :T]
-        bsz = x.shape[0]
+        if fused and scored_rollout_supported(model, x, fx, yy, step, loss_fn):
+            if graphed and x.shape[0] == batch_size:
+                if "rollout" not in graphs:
+                    graphs["rollout"] = GraphedScoredRollout(model, x, fx, yy, step)
+                step_ratio, full_ratio, _ = graphs["rollout"].run(x, fx, yy)
+            else:
+                step_ratio, full_ratio, _ = scored_rollout(model, x, fx, yy, step)
+            per_step = step_ratio.sum(1)
+            acc[2] += per_step.sum()
+            if calls is not None:
+                calls.extend(per_step.unbind(0))
+            if full:
+                total = full_ratio.sum()
+                acc[3] += total
+                if calls is not None:
+                    calls.append(total)
+            continue
         loss, preds = 0, []
         with ops.weights_frozen():
             for t in range(0, T, step):
-                y = yy[..., t:t + step]
                 im = model(x, fx=fx)
-                loss = loss + loss_fn(im.reshape(bsz, -1), y.reshape(bsz, -1))
+                loss = loss + _step_loss(loss_fn, im, yy, t, fused, calls)
                 preds.append(im)
                 fx = torch.cat((fx[..., step:], im), dim=-1)
         acc[2] += loss
         if full:
-            acc[3] += loss_fn(torch.cat(preds, -1).reshape(bsz, -1), yy.reshape(bsz, -1))
+            acc[3] += _full_loss(loss_fn, preds, yy, calls)
 
 
 def evaluate_ns(model, test, batch_size, T=10, step=1, loss_fn=None):
     """The test pass alone (exp_ns.py:137-183 without the plots): {'test_step', 'test_full'} normalised like fit_ns."""
     loss_fn = loss_fn or TestLoss(size_average=False)
-    return _evaluate(model, 4, lambda acc: _ns_test_pass(model, test, batch_size, T, step, loss_fn, acc),
+    return _evaluate(model, 4, lambda acc: _rollout_test_pass(model, test, batch_size, T, step, loss_fn, acc, True, False),
                      lambda a: _ns_test_metrics(a, len(test), T / step))
 
 
@@ -992,13 +1106,23 @@ def fit_ns(model, optimizer, scheduler, train, test, *, epochs, batch_size, T=10
     if graphed:
         _graphed_refusals("fit_ns", optimizer, max_grad_norm, one_rank=False)
     loss_fn = loss_fn or TestLoss(size_average=False)
-    ntrain, ntest, calls = len(train), len(test), T / step
     run = _graphed_or_eager(
         graphed, batch_size,
         lambda x, fx, yy: GraphedTrainStep(model, optimizer, scheduler, x, fx, yy, step=step, loss_fn=loss_fn),
         lambda graph, x, fx, yy: graph(x, fx, yy),
         lambda x, fx, yy: train_step(model, optimizer, scheduler, x, fx, yy, step=step, max_grad_norm=max_grad_norm,
                                      grad_sync=grad_sync, loss_fn=loss_fn))
+    return _fit_teacher_forced(model, train, test, run, False, None, False, epochs=epochs, batch_size=batch_size, T=T,
+                               step=step, loss_fn=loss_fn, epoch_orders=epoch_orders, generator=generator,
+                               save_path=save_path, save_every=save_every, on_epoch=on_epoch)
+
+
+def _fit_teacher_forced(model, train, test, run, fused, calls, graphed, *, epochs, batch_size, T, step, loss_fn, epoch_orders,
+                        generator, save_path, save_every, on_epoch):
+    """The frame of fit_ns and fit_velocity, which differ in `fused`, in the graph class behind `run` and in whether
+    `calls` is threaded through: run(x, fx, yy[..., :T]) -> (step loss, full loss) per batch, the prediction-feedback test
+    pass (with `graphed`: on one GraphedScoredRollout), the four metrics of exp_ns.py:243-246."""
+    ntrain, ntest, ncalls, graphs = len(train), len(test), T / step, {}
 
     def train_batch(batch, acc):
         x, fx, yy = batch
@@ -1007,9 +1131,11 @@ def fit_ns(model, optimizer, scheduler, train, test, *, epochs, batch_size, T=10
         acc[1] += full
 
     return _fit(model, epochs=epochs, n_acc=4, batches=lambda ep: _epoch_batches(train, batch_size, ep, epoch_orders, generator),
-                train_batch=train_batch, test_pass=lambda acc: _ns_test_pass(model, test, batch_size, T, step, loss_fn, acc),
-                metrics=lambda a: dict(train_step=a[0] / ntrain / calls, train_full=a[1] / ntrain,
-                                       **_ns_test_metrics(a, ntest, calls)),
+                train_batch=train_batch,
+                test_pass=lambda acc: _rollout_test_pass(model, test, batch_size, T, step, loss_fn, acc, True, fused, calls,
+                                                         graphed, graphs),
+                metrics=lambda a: dict(train_step=a[0] / ntrain / ncalls, train_full=a[1] / ntrain,
+                                       **_ns_test_metrics(a, ntest, ncalls)),
                 on_epoch=on_epoch, save_path=save_path, save_every=save_every)
 
 
@@ -1026,30 +1152,12 @@ def fit_unrolled(sol_model, optimizer, scheduler, train, test, *, epochs, batch_
     Returns one dict per epoch: train_step = the RAW epoch sum (what :257 prints), test_step = sum / ntest / (T / step),
     look_ahead = the epoch's look-ahead.  One host synchronisation per epoch.  Saves
     `sol_model.transolver_model.state_dict()` (ep % save_every == 0 and after the last epoch).  No graph mode."""
-    loss_fn = loss_fn or TestLoss(size_average=False)
-    ntest, calls = len(test), T / step
-    curriculum = LookAheadCurriculum(epochs, look_ahead, max_look_ahead)
-    inner = sol_model.transolver_model
-    sol_model.n = look_ahead
-
-    def batches(ep):
-        curriculum.update(ep)                # before the epoch's first batch; curriculum.look_ahead then holds for the epoch
-        return _epoch_batches(train, batch_size, ep, epoch_orders, generator)
-
-    def train_batch(batch, acc):
-        x, fx, yy = batch
-        with ops.weights_frozen():
-            loss = unrolled_train_iteration(sol_model, x, fx, yy[..., :T], curriculum.look_ahead, step, loss_fn)
-            optimizer.zero_grad()
-            loss.backward()
-        _apply_step(optimizer, scheduler, (), None, grad_sync)           # this loop never clips
-        acc[0] += loss.detach()
-
-    return _fit(sol_model, epochs=epochs, n_acc=4, batches=batches, train_batch=train_batch,
-                test_pass=lambda acc: _ns_test_pass(inner, test, batch_size, T, step, loss_fn, acc, full=False),
-                metrics=lambda a: dict(train_step=a[0], test_step=_ns_test_metrics(a, ntest, calls)["test_step"],
-                                       look_ahead=curriculum.look_ahead),
-                on_epoch=on_epoch, save_path=save_path, save_every=save_every, save_module=inner)
+    return _fit_sol("fit_unrolled", sol_model, optimizer, scheduler, train, test,
+                    LookAheadCurriculum(epochs, look_ahead, max_look_ahead),
+                    lambda sol, x, fx, yy, la, step, loss_fn, vals: unrolled_train_iteration(sol, x, fx, yy, la, step, loss_fn),
+                    accumulate=True, fused=False, zero_grad_kw={}, epochs=epochs, batch_size=batch_size, T=T, step=step,
+                    loss_fn=loss_fn, epoch_orders=epoch_orders, generator=generator, save_path=save_path,
+                    save_every=save_every, graphed=False, grad_sync=grad_sync, on_epoch=on_epoch, calls=None)
 
 
 def fit_darcy(model, optimizer, scheduler, data, *, epochs, batch_size, max_grad_norm=None, loss_fn=None,
@@ -1617,43 +1725,16 @@ def evaluate_slice_learner(kind, model, sequen_solver, pos, test, use_vorticity=
 # ------------------------------------------------------------------------------ velocity-field trainers
 # ns_velocity.py, ns_velocity_unrolling.py, ns_unrolling2_with_t.py: the exp_ns / SOL-wrapper loops on PhiFlow velocity data,
 # where one prediction is a (vel_x, vel_y) pair: out_dim = step = 2, so a step's target yy[..., t:t+step] is a
-# two-dimensional strided view.  Shared by the three loops below:
-#   * `_step_loss`: the per-call loss; with step > 1, fp32 GPU tensors and the p = 2 batch-sum `rel` it is
+# two-dimensional strided view.  They are ONE family with exp_ns / ns_vorticity_unrolling and run the same functions:
+# `_teacher_forced` (train_iteration, velocity_iteration), `_rollout_test_pass`, `_windowed_iteration` (the three
+# unrolled_* iterations), `_fit_sol` (fit_unrolled, fit_velocity_unrolled, fit_unrolled_t), `_fit_teacher_forced` (fit_ns,
+# fit_velocity), `_eager_iteration` and `_graphed_or_eager`.  The velocity loops pass fused=True, the older ones False:
+#   * `_step_loss(fused=True)`: the per-call loss; with step > 1, fp32 GPU tensors and the p = 2 batch-sum `rel` it is
 #     functional.rel_l2_window (the target read in place), otherwise `loss_fn` on the reshaped copies, as the scripts do;
 #   * `scored_rollout` / `GraphedScoredRollout`: the prediction-feedback test pass with ONE launch after each model call
 #     (window shift, prediction kept, step scored) and one after the last, no host synchronisation;
-#   * `_ScopedCallStep`: a whole iteration (chained calls, windows, summed loss, backward, staged AdamW) in one hipGraph.
-def _batch_sum_rel(loss_fn):
-    """True where `loss_fn` is the scripts' loss: a `TestLoss` (or FusedTestLoss) with p = 2 that sums over the batch."""
-    return isinstance(loss_fn, TestLoss) and loss_fn.p == 2 and loss_fn.reduction and not loss_fn.size_average
-
-
-def _on_window_kernels(loss_fn, *tensors):
-    return _batch_sum_rel(loss_fn) and all(t.is_cuda and t.dtype == torch.float32 for t in tensors)
-
-
-def _step_loss(loss_fn, im, yy, col, calls=None):
-    """The loss of one model call against the columns [col, col + k) of yy, k = im.shape[-1]; the value (detached, a device
-    tensor) is appended to `calls` where that is a list."""
-    bsz, k = im.shape[0], im.shape[-1]
-    if k > 1 and k <= ops.WINDOW_MAX_K and _on_window_kernels(loss_fn, im, yy) and not yy.requires_grad:
-        v = Fn.rel_l2_window(im, yy, col, k).sum()
-    else:
-        v = loss_fn(im.reshape(bsz, -1), yy[..., col:col + k].reshape(bsz, -1))
-    if calls is not None:
-        calls.append(v.detach())
-    return v
-
-
-def _full_loss(loss_fn, preds, yy, calls=None):
-    bsz = yy.shape[0]
-    with torch.no_grad():
-        v = loss_fn(torch.cat(preds, -1).reshape(bsz, -1), yy.reshape(bsz, -1))
-    if calls is not None:
-        calls.append(v)
-    return v
-
-
+#   * `_ScopedCallStep`: a whole iteration (chained calls, windows, summed loss, backward, staged AdamW) in one hipGraph,
+#     one per look-ahead value (the key of `_graphed_or_eager`).
 def scored_rollout_supported(model, x, fx, yy, step, loss_fn=None):
     """True where `scored_rollout` serves the prediction-feedback test pass: the model on the GPU, fp32 tensors, a window of
     at most ops.WINDOW_MAX_F columns, 1 <= step <= ops.WINDOW_MAX_K dividing T, and (where given) the p = 2 batch-sum `rel`."""
@@ -1694,7 +1775,7 @@ def scored_rollout(model, x, fx, yy, step, keep_pred=False):
     return step_ratio, full_ratio, traj
 
 
-class GraphedScoredRollout:
+class GraphedScoredRollout(_RolloutGraph):
     """The WHOLE scored rollout (every model call, every tail launch and the score) in ONE hipGraph with static buffers
     (x, the initial window, the target, the window the steps shift, the record, the trajectory).  `run(x, fx, yy)` copies
     a batch in, refreshes the weight packs the captured launches point at (GraphedRollout's scheme, with its check that
@@ -1704,27 +1785,13 @@ class GraphedScoredRollout:
     def __init__(self, model, x, fx, yy, step, keep_pred=False, warmup=2, fused_tail=None):
         if not scored_rollout_supported(model, x, fx, yy, step):
             raise ValueError("GraphedScoredRollout: what scored_rollout needs")
-        with _fused_tail_set(model, fused_tail):
-            self._capture(model, x, fx, yy, step, keep_pred, warmup)
-
-    def _capture(self, model, x, fx, yy, step, keep_pred, warmup):
-        self.model, self.step = model, step
+        self.step = step
         self.x, self.fx, self.yy = x.clone(), fx.clone(memory_format=torch.contiguous_format), yy.clone()
         B, N, _ = fx.shape
         self.win = torch.empty_like(self.fx)
         self.record = ops.rollout_record(yy.shape[-1] // step, B, fx)
         self.traj = torch.empty(B, N, yy.shape[-1], dtype=torch.float32, device=fx.device) if keep_pred else None
-        self.graph = torch.cuda.CUDAGraph()
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with ops.weights_frozen() as self.packs:
-            with torch.cuda.stream(side), torch.no_grad():
-                for _ in range(warmup):
-                    self._body()
-            torch.cuda.current_stream().wait_stream(side)
-            with torch.no_grad(), torch.cuda.graph(self.graph):
-                self.out = self._body()
-        self._param_ptrs = [p.data_ptr() for p in model.parameters()]
+        self.out = self._capture(model, self._body, warmup, fused_tail)
 
     def _body(self):
         self.win.copy_(self.fx)
@@ -1732,13 +1799,7 @@ class GraphedScoredRollout:
 
     @torch.no_grad()
     def run(self, x, fx, yy):
-        if [p.data_ptr() for p in self.model.parameters()] != self._param_ptrs:
-            raise RuntimeError("parameter storage moved since this rollout graph was captured (e.g. FusedAdamW / "
-                               "FlatGradSync built afterwards, or .to()); build the optimizer first or re-capture")
-        for buf, t in zip((self.x, self.fx, self.yy), (x, fx, yy)):
-            if t is not None:
-                buf.copy_(t)
-        self.packs.refresh()
+        self._ready((self.x, self.fx, self.yy), (x, fx, yy))
         self.graph.replay()
         return self.out[0], self.out[1], self.traj
 
@@ -1775,116 +1836,41 @@ def velocity_iteration(model, x, fx, yy, step=2, loss_fn=None, calls=None):
     """Forward part of one ns_velocity.py:204-225 mini-batch (exp_ns's teacher-forced iteration with step columns per
     call).  Returns (loss [graph attached], full loss)."""
     loss_fn = loss_fn or TestLoss(size_average=False)
-    loss, preds = 0, []
-    for t in range(0, yy.shape[-1], step):
-        im = model(x, fx=fx)
-        loss = loss + _step_loss(loss_fn, im, yy, t, calls)
-        preds.append(im.detach())
-        fx = torch.cat((fx[..., step:], yy[..., t:t + step]), dim=-1)
+    loss, preds = _teacher_forced(model, x, fx, yy, step, loss_fn, True, calls)
     return loss, _full_loss(loss_fn, preds, yy, calls)
 
 
-def unrolled_window_iteration(sol_model, x, fx, yy, look_ahead, step=2, loss_fn=None, calls=None):
-    """One mini-batch of ns_velocity_unrolling.py:220-227: ONE window, `look_ahead` chained calls through the SOL wrapper,
-    scored against yy[..., offset - step:offset], offset = step * look_ahead.  Returns the loss (graph attached)."""
-    loss_fn = loss_fn or TestLoss(size_average=False)
-    sol_model.n = look_ahead
-    offset = step * look_ahead
-    return _step_loss(loss_fn, sol_model(x, fx), yy, offset - step, calls)
-
-
-def unrolled_t_iteration(sol_model, x, fx, yy, look_ahead, step=2, loss_fn=None, calls=None):
-    """One mini-batch of ns_unrolling2_with_t.py:219-229: every window t in range(0, T - offset + step, step) is scored
-    against yy[..., t + offset - step:t + offset] after `look_ahead` chained calls, and the window then advances by `step`
-    GROUND-TRUTH columns.  Returns the summed loss (graph attached)."""
-    loss_fn = loss_fn or TestLoss(size_average=False)
-    sol_model.n = look_ahead
-    offset = step * look_ahead
-    loss = 0
-    for t in range(0, yy.shape[-1] - offset + step, step):
-        loss = loss + _step_loss(loss_fn, sol_model(x, fx), yy, t + offset - step, calls)
-        fx = torch.cat((fx[..., step:], yy[..., t:t + step]), dim=-1)
-    return loss
-
-
-def _eager_iteration(module, optimizer, scheduler, forward, max_grad_norm, grad_sync):
-    """forward() -> loss parts (the first is differentiated) inside one `ops.weights_frozen()` scope with zero_grad and
-    backward; then `_apply_step`."""
-    with ops.weights_frozen():
-        parts = forward()
-        optimizer.zero_grad(set_to_none=False)
-        parts[0].backward()
-    _apply_step(optimizer, scheduler, module.parameters(), max_grad_norm, grad_sync)
-    return tuple(p.detach() for p in parts)
-
-
-def _velocity_runner(module, optimizer, scheduler, batch_size, graphed, max_grad_norm, grad_sync, calls, forward, nparts):
+def _velocity_runner(module, optimizer, scheduler, batch_size, graphed, max_grad_norm, grad_sync, calls, forward, nparts,
+                     zero_grad_kw):
     """run(key, x, fx, yy) -> the `nparts` detached loss parts of one iteration `forward(key, x, fx, yy, calls)`.  Eager:
     the iteration as the scripts run it.  graphed: a full batch replays the `_ScopedCallStep` of `key` (the look-ahead),
     captured when the curriculum first reaches that key; the short last batch runs eagerly.  A replay's per-call loss
     values are copied to `calls` (the graph's own tensors are overwritten by the next replay)."""
-    graphs = {}
+    def build(x, fx, yy, key):
+        def body(_, sx, sfx, syy):
+            vals = []                        # a fresh list per run: the body runs in every warm-up and again in the capture
+            return forward(key, sx, sfx, syy, vals) + tuple(vals)
+        return _ScopedCallStep(module, optimizer, scheduler, (x.clone(), fx.clone(), yy.clone()), body)
 
-    def run(key, x, fx, yy):
-        if not (graphed and x.shape[0] == batch_size):
-            return _eager_iteration(module, optimizer, scheduler, lambda: forward(key, x, fx, yy, calls), max_grad_norm,
-                                    grad_sync)
-        if key not in graphs:
-            def body(_, sx, sfx, syy):
-                vals = []
-                return forward(key, sx, sfx, syy, vals) + tuple(vals)
-            graphs[key] = _ScopedCallStep(module, optimizer, scheduler, (x.clone(), fx.clone(), yy.clone()), body)
-        out = graphs[key](x, fx, yy)
+    def replay(graph, x, fx, yy, key):
+        out = graph(x, fx, yy)
         if calls is not None:
             calls.extend(v.clone() for v in out[nparts:])
         return out[:nparts]
 
-    return run
-
-
-@torch.no_grad()
-def _velocity_test_pass(model, test, batch_size, T, step, loss_fn, acc, full=True, calls=None, graphed=False, _graphs=None):
-    """The prediction-feedback test pass of the three scripts (ns_velocity.py:238-254): acc[2] += the summed step losses,
-    acc[3] += the loss of the whole trajectory (full).  On `scored_rollout` where `scored_rollout_supported` says so (with
-    graphed: full batches replay one GraphedScoredRollout, kept in `_graphs`), otherwise the torch loop."""
-    for x, fx, yy in test.batches(batch_size):
-        yy = yy[..., :T]
-        bsz = x.shape[0]
-        if scored_rollout_supported(model, x, fx, yy, step, loss_fn):
-            if graphed and bsz == batch_size:
-                if "rollout" not in _graphs:
-                    _graphs["rollout"] = GraphedScoredRollout(model, x, fx, yy, step)
-                step_ratio, full_ratio, _ = _graphs["rollout"].run(x, fx, yy)
-            else:
-                step_ratio, full_ratio, _ = scored_rollout(model, x, fx, yy, step)
-            per_step = step_ratio.sum(1)
-            acc[2] += per_step.sum()
-            if calls is not None:
-                calls.extend(per_step.unbind(0))
-            if full:
-                total = full_ratio.sum()
-                acc[3] += total
-                if calls is not None:
-                    calls.append(total)
-            continue
-        loss, preds = 0, []
-        with ops.weights_frozen():
-            for t in range(0, T, step):
-                im = model(x, fx=fx)
-                loss = loss + _step_loss(loss_fn, im, yy, t, calls)
-                preds.append(im)
-                fx = torch.cat((fx[..., step:], im), dim=-1)
-        acc[2] += loss
-        if full:
-            acc[3] += _full_loss(loss_fn, preds, yy, calls)
+    run = _graphed_or_eager(
+        graphed, batch_size, build, replay,
+        lambda x, fx, yy, key: _eager_iteration(module, optimizer, scheduler, lambda: forward(key, x, fx, yy, calls),
+                                                max_grad_norm, grad_sync, zero_grad_kw))
+    return lambda key, x, fx, yy: run(x, fx, yy, key=key)
 
 
 def evaluate_velocity(model, test, batch_size, T=10, step=2, loss_fn=None, full=True, calls=None, graphed=False):
     """The test pass alone: {'test_step'} (and {'test_full'} with full) normalised like the loops' metrics."""
     loss_fn = loss_fn or TestLoss(size_average=False)
     graphs = {}
-    m = _evaluate(model, 4, lambda acc: _velocity_test_pass(model, test, batch_size, T, step, loss_fn, acc, full, calls,
-                                                            graphed, graphs),
+    m = _evaluate(model, 4, lambda acc: _rollout_test_pass(model, test, batch_size, T, step, loss_fn, acc, full, True, calls,
+                                                           graphed, graphs),
                   lambda a: _ns_test_metrics(a, len(test), T / step))
     return m if full else dict(test_step=m["test_step"])
 
@@ -1914,33 +1900,23 @@ def fit_velocity(model, optimizer, scheduler, train, test, *, epochs, batch_size
     eager results; the short last batch runs eagerly."""
     _velocity_setup("fit_velocity", model, optimizer, max_grad_norm, graphed)
     loss_fn = loss_fn or TestLoss(size_average=False)
-    ntrain, ntest, ncalls = len(train), len(test), T / step
 
     def forward(key, x, fx, yy, vals):
         return velocity_iteration(model, x, fx, yy, step, loss_fn, vals)
-    run = _velocity_runner(model, optimizer, scheduler, batch_size, graphed, max_grad_norm, grad_sync, calls, forward, 2)
-    graphs = {}
-
-    def train_batch(batch, acc):
-        x, fx, yy = batch
-        loss, full = run(0, x, fx, yy[..., :T])
-        acc[0] += loss
-        acc[1] += full
-
-    return _fit(model, epochs=epochs, n_acc=4, batches=lambda ep: _epoch_batches(train, batch_size, ep, epoch_orders, generator),
-                train_batch=train_batch,
-                test_pass=lambda acc: _velocity_test_pass(model, test, batch_size, T, step, loss_fn, acc, True, calls, graphed,
-                                                          graphs),
-                metrics=lambda a: dict(train_step=a[0] / ntrain / ncalls, train_full=a[1] / ntrain,
-                                       **_ns_test_metrics(a, ntest, ncalls)),
-                on_epoch=on_epoch, save_path=save_path, save_every=save_every)
+    run = _velocity_runner(model, optimizer, scheduler, batch_size, graphed, max_grad_norm, grad_sync, calls, forward, 2,
+                           dict(set_to_none=False))
+    return _fit_teacher_forced(model, train, test, lambda x, fx, yy: run(0, x, fx, yy), True, calls, graphed, epochs=epochs,
+                               batch_size=batch_size, T=T, step=step, loss_fn=loss_fn, epoch_orders=epoch_orders,
+                               generator=generator, save_path=save_path, save_every=save_every, on_epoch=on_epoch)
 
 
-def _fit_sol(who, sol_model, optimizer, scheduler, train, test, curriculum, iteration, accumulate, *, epochs,
-             batch_size, T, step, loss_fn, epoch_orders, generator, save_path, save_every, graphed, grad_sync, on_epoch, calls):
-    """What fit_velocity_unrolled and fit_unrolled_t share: the curriculum stepped before an epoch's first batch, the
-    per-look-ahead iteration (eager, or one graph per look-ahead value), the test pass on the INNER model with the step
-    loss only, the inner model saved."""
+def _fit_sol(who, sol_model, optimizer, scheduler, train, test, curriculum, iteration, *, accumulate, fused, zero_grad_kw,
+             epochs, batch_size, T, step, loss_fn, epoch_orders, generator, save_path, save_every, graphed, grad_sync, on_epoch,
+             calls):
+    """The epoch loop of the three SOL scripts (fit_unrolled, fit_velocity_unrolled, fit_unrolled_t): the curriculum stepped
+    before an epoch's first batch, the per-look-ahead `iteration` (eager, or one graph per look-ahead value) with a step that
+    never clips, the loss of a batch added to the epoch's (`accumulate`) or put in its place, the test pass on the INNER
+    model with the step loss only (`fused`: on the scored rollout), the inner model saved."""
     _velocity_setup(who, sol_model, optimizer, None, graphed)
     loss_fn = loss_fn or TestLoss(size_average=False)
     ntest, ncalls = len(test), T / step
@@ -1949,7 +1925,8 @@ def _fit_sol(who, sol_model, optimizer, scheduler, train, test, curriculum, iter
 
     def forward(la, x, fx, yy, vals):
         return (iteration(sol_model, x, fx, yy, la, step, loss_fn, vals),)
-    run = _velocity_runner(sol_model, optimizer, scheduler, batch_size, graphed, None, grad_sync, calls, forward, 1)
+    run = _velocity_runner(sol_model, optimizer, scheduler, batch_size, graphed, None, grad_sync, calls, forward, 1,
+                           zero_grad_kw)
     graphs = {}
 
     def batches(ep):
@@ -1965,8 +1942,8 @@ def _fit_sol(who, sol_model, optimizer, scheduler, train, test, curriculum, iter
             acc[0] = loss
 
     return _fit(sol_model, epochs=epochs, n_acc=4, batches=batches, train_batch=train_batch,
-                test_pass=lambda acc: _velocity_test_pass(inner, test, batch_size, T, step, loss_fn, acc, False, calls, graphed,
-                                                          graphs),
+                test_pass=lambda acc: _rollout_test_pass(inner, test, batch_size, T, step, loss_fn, acc, False, fused, calls,
+                                                         graphed, graphs),
                 metrics=lambda a: dict(train_step=a[0], test_step=_ns_test_metrics(a, ntest, ncalls)["test_step"],
                                        look_ahead=curriculum.look_ahead),
                 on_epoch=on_epoch, save_path=save_path, save_every=save_every, save_module=inner)
@@ -1986,10 +1963,10 @@ def fit_velocity_unrolled(sol_model, optimizer, scheduler, train, test, *, epoch
     synchronisation (the script's per-batch `loss.item()` is gone); look_ahead.  Saves the inner model's state_dict.
     `calls`, `graphed`: as fit_velocity, with one graph per look-ahead value, built when the curriculum first reaches it."""
     return _fit_sol("fit_velocity_unrolled", sol_model, optimizer, scheduler, train, test,
-                    StepCurriculum(period, look_ahead, max_look_ahead), unrolled_window_iteration, False,
-                    epochs=epochs, batch_size=batch_size, T=T, step=step, loss_fn=loss_fn, epoch_orders=epoch_orders,
-                    generator=generator, save_path=save_path, save_every=save_every, graphed=graphed, grad_sync=grad_sync,
-                    on_epoch=on_epoch, calls=calls)
+                    StepCurriculum(period, look_ahead, max_look_ahead), unrolled_window_iteration, accumulate=False,
+                    fused=True, zero_grad_kw=dict(set_to_none=False), epochs=epochs, batch_size=batch_size, T=T, step=step,
+                    loss_fn=loss_fn, epoch_orders=epoch_orders, generator=generator, save_path=save_path,
+                    save_every=save_every, graphed=graphed, grad_sync=grad_sync, on_epoch=on_epoch, calls=calls)
 
 
 def fit_unrolled_t(sol_model, optimizer, scheduler, train, test, *, epochs, batch_size, T=10, step=2, look_ahead=1,
@@ -2003,7 +1980,7 @@ def fit_unrolled_t(sol_model, optimizer, scheduler, train, test, *, epochs, batc
     Returns one dict per epoch: train_step = the RAW epoch sum (what the script prints), test_step = sum / ntest /
     (T / step), look_ahead.  Everything else as fit_velocity_unrolled."""
     return _fit_sol("fit_unrolled_t", sol_model, optimizer, scheduler, train, test,
-                    StepCurriculum(period, look_ahead, max_look_ahead), unrolled_t_iteration, True,
-                    epochs=epochs, batch_size=batch_size, T=T, step=step, loss_fn=loss_fn, epoch_orders=epoch_orders,
-                    generator=generator, save_path=save_path, save_every=save_every, graphed=graphed, grad_sync=grad_sync,
-                    on_epoch=on_epoch, calls=calls)
+                    StepCurriculum(period, look_ahead, max_look_ahead), unrolled_t_iteration, accumulate=True,
+                    fused=True, zero_grad_kw=dict(set_to_none=False), epochs=epochs, batch_size=batch_size, T=T, step=step,
+                    loss_fn=loss_fn, epoch_orders=epoch_orders, generator=generator, save_path=save_path,
+                    save_every=save_every, graphed=graphed, grad_sync=grad_sync, on_epoch=on_epoch, calls=calls)
